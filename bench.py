@@ -9,10 +9,13 @@ A step = one pass of the hot path (ImVoxelNet.simple_test: ResNet-50 + FPN -> un
 batch of synthetic KITTI-shaped input already resident in HBM.  Workload = BASELINE.json configs[1]:
 1 view 3x384x1280, 216x248x12 voxels, batch 4 per GPU, fp32 (the reference's arithmetic type).
 
-Prints ONE JSON line (rank 0) with `roofline` (the implicit-GEMM kernel over its launches on the 3-D neck -- executed
-FLOPs, the neck runs in the Winograd F(6x6,3x3) form -- measured live with HIP events on the launch stream inside the timed
-region), `roofline_winograd_transforms` (the HBM-bound transform kernels around those launches) and, at N == 1, `cpu_baseline` (the oracle's torch-fp32/C port of
-the same path timed on this box's host cores on one image).
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the `--steps` steps and prints the headline figure
+(`value` images/s, `ms_per_step`, `dtype`, ...).  `--full` adds everything else: `roofline` (the implicit-GEMM kernel over its
+launches on the 3-D neck -- executed FLOPs, the neck runs in the Winograd F(6x6,3x3) form -- measured live with HIP events on the
+launch stream inside the timed region), `roofline_winograd_transforms` (the HBM-bound transform kernels around those launches),
+the start-up ceilings, the exact fp32-MFMA pass, the other BASELINE workloads and, at N == 1, `cpu_baseline` (the oracle's
+torch-fp32/C port of the same path timed on the host cores on one image).
+`--dump-outputs DIR` writes the detections of the last timed step as DIR/<name>.npy (inputs are seeded: identical run to run).
 """
 import argparse
 import json
@@ -31,6 +34,34 @@ import torch.distributed as dist  # noqa: E402
 PEAK_F32_MFMA_TFLOPS = 157.3   # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32 dense peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0  # MI355X_MICROARCH.md: v_mfma_f32_32x32x16_bf16 dense peak (no sparsity)
 BATCH_PER_GPU = 4
+DUMP_MAX_ELEMS = 1 << 20       # per array written by --dump-outputs (8 MB at float64)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: write {name: tensor / array} as path/<name>.npy -- floating types as float32 (float64 kept), integer and
+    bool types as float64 (exact).  An array of more than DUMP_MAX_ELEMS elements is replaced by the same fixed, seeded sample of
+    its flat entries in every run (path/<name>.npy holds the sample, path/<name>.sample_index.npy the flat indices)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        a = a.detach().cpu() if isinstance(a, torch.Tensor) else torch.as_tensor(a)
+        a = a.to(torch.float64) if (not a.is_floating_point() or a.dtype == torch.float64) else a.to(torch.float32)
+        a = a.numpy()
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).integers(0, a.size, DUMP_MAX_ELEMS))
+            np.save(os.path.join(path, name + '.sample_index.npy'), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
+def detections_arrays(results):
+    """The per-sample detections a caller of simple_test receives: boxes_3d / scores_3d / labels_3d of sample b."""
+    out = {}
+    for b, r in enumerate(results):
+        boxes, scores, labels = (r['boxes_3d'], r['scores_3d'], r['labels_3d']) if isinstance(r, dict) else r
+        out[f'boxes_3d_{b}'] = boxes.tensor if hasattr(boxes, 'tensor') else boxes
+        out[f'scores_3d_{b}'], out[f'labels_3d_{b}'] = scores, labels
+    return out
 
 
 def measured_ceilings(dev, bf16=False):
@@ -109,6 +140,8 @@ def bench_lift(args, ia, kc, dev):
     e1.record()
     torch.cuda.synchronize()
     ms = e0.elapsed_time(e1) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {'volume': vol, 'valid': valid})
     n = nv[0] * nv[1] * nv[2]
     by = B * (V * Cf * fh * fw * esz + Cf * n * esz + n)
     print(json.dumps({'metric': f'scenes/sec, unprojection only ({args.config}: {V} views {Cf}x{fh}x{fw} -> {"x".join(map(str, nv))})',
@@ -203,9 +236,10 @@ def bench_other(args, ia, kc, dev, rank, world, emit=True):
     # default: the public call.  model.simple_test runs trunk + unprojection + neck (+ the anchor head and tail for nuScenes)
     # through the native model handle; stage times come from its coarse trace (neck stages individually, trunk as one span)
     public = args.api == 'simple_test' and getattr(model, '_native', None) is not None and not view_sharded
-    traced_run = os.environ.get('IVX_BENCH_TRACE', '1') != '0'
+    traced_run = args.full and os.environ.get('IVX_BENCH_TRACE', '1') != '0'
     if public:
-        step(0)                                  # one composed step: the neck's direct / executed FLOP counts
+        if args.full:
+            step(0)                              # one composed step: the neck's direct / executed FLOP counts
 
         def step(i, traced=False):               # noqa: F811
             res = model.simple_test(img, metas, gather=multi)
@@ -227,8 +261,16 @@ def bench_other(args, ia, kc, dev, rank, world, emit=True):
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, detections_arrays(last))
     rccl_ranks, rank_ms = None, None
-    if multi:
+    if multi and not args.full:
+        t = torch.tensor([dt], device=dev, dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        dt = float(t.item())
+        if rank != 0:
+            return
+    elif multi:
         # self-check of the N > 1 line, as on the KITTI line: every rank's own step time and the rank count an actual all-reduce sees
         tl = torch.tensor([dt], device=dev, dtype=torch.float64)
         allt = torch.empty((dist.get_world_size(),), device=dev, dtype=torch.float64)
@@ -243,7 +285,7 @@ def bench_other(args, ia, kc, dev, rank, world, emit=True):
         if rank != 0:
             return
     trunk_note = ''
-    if public and not traced_run:                # throughput only
+    if not args.full or (public and not traced_run):     # throughput only (the stage figures need --full)
         neck_ms, t2d, t2d_ms, t2d_flops, nt = 1e9, [], 0.0, 0.0, 0
     elif public and multi:                       # (the gathered step holds a collective: no extra single-rank steps)
         neck_ms, t2d, t2d_ms, t2d_flops, nt = 1e9, [], 0.0, 0.0, 0
@@ -316,7 +358,7 @@ def bench_other(args, ia, kc, dev, rank, world, emit=True):
                       'trunk_fp8': fp8_note, 'api': 'simple_test (native handle)' if public else 'composed',
                       'wino_operands': 'fp16 pairs' if (FusedConv.wino_operands == 4 and args.storage != 'bf16') else 'storage type',
                       'detections_last_step': int(sum(len(r[1]) for r in last))},
-           'roofline': neck_roof,
+           'roofline': neck_roof if args.full else None,
            'roofline_trunk_2d': None if not t2d else trunk_roof}
     if emit:
         print(json.dumps(rec))
@@ -457,7 +499,15 @@ def main():
                     help="2-D trunk (ResNet-50 + FPN): 'f16pair' (default) = activations chained as fp16 (hi, lo) pair tensors with device-side "
                          "power-of-two scales (ivx_conv_fwd_pio: three fp16 MFMA products per multiply-add, fp32 accumulation, no conversion "
                          "passes); 'f32' = fp32 MFMA")
+    ap.add_argument('--full', action='store_true',
+                    help='also measure and check everything beyond the headline figure: start-up ceilings, stage events and the roofline entries, '
+                         'the exact fp32-MFMA pass, the other BASELINE workloads, the CPU baselines (default: set up, warm up, time the steps, print the line)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64; '
+                         'arrays above %d elements as a fixed, seeded sample)' % DUMP_MAX_ELEMS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     # One process per GPU.  Under torch.distributed.run (the reference's launcher is tools/dist_test.sh:9-10,
     # `torch.distributed.launch --nproc_per_node=$GPUS`) RANK / WORLD_SIZE are set; a bare `python bench.py --gpus N`
@@ -520,7 +570,7 @@ def main():
     bf16 = args.storage == 'bf16'
     pair = args.wino_operands == 'f16pair' and not bf16
     FusedConv.wino_operands = 4 if pair else 0
-    ceil = measured_ceilings(dev, bf16 or pair) if os.environ.get('IVX_BENCH_UBENCH', '1') != '0' else {}
+    ceil = measured_ceilings(dev, bf16 or pair) if args.full and os.environ.get('IVX_BENCH_UBENCH', '1') != '0' else {}
     model.prepare(dev, dtype=torch.bfloat16 if bf16 else torch.float32)
     # the pair form issues fp16 MFMAs (same rate as bf16): priced against the dense 16-bit MFMA peak, counting every product it issues
     peak = PEAK_BF16_MFMA_TFLOPS if (bf16 or pair) else PEAK_F32_MFMA_TFLOPS
@@ -541,13 +591,13 @@ def main():
 
     native_trace = False
     if args.api == 'simple_test':
-        native_trace = model._native is not None and os.environ.get('IVX_BENCH_TRACE', '1') != '0'   # stage events are recorded inside the native handle
+        native_trace = args.full and model._native is not None and os.environ.get('IVX_BENCH_TRACE', '1') != '0'   # stage events are recorded inside the native handle
         if native_trace:
             model._native.trace(1)     # coarse: neck stages, unprojection, tail individually; the 2-D trunk as one span
 
         def step(i):
             """The drop-in call, as tools/benchmark.py:74 times it: returns the list of result dicts on the host."""
-            FusedConv.trace, ops.stage_trace = traces[i], lifts[i]
+            FusedConv.trace, ops.stage_trace = (traces[i], lifts[i]) if args.full else (None, None)
             try:
                 return model.simple_test(img, metas, gather=multi)
             finally:
@@ -557,7 +607,7 @@ def main():
             return int(sum(len(r['scores_3d']) for r in out)) if out is not None else 0
     else:
         def step(i):
-            FusedConv.trace, ops.stage_trace = traces[i], lifts[i]
+            FusedConv.trace, ops.stage_trace = (traces[i], lifts[i]) if args.full else (None, None)
             p0 = model.features_2d_cl(img)
             proj, new_origin, crop = model._camera_setup(metas, 4, p0.device)   # host camera set-up + 3 small H2D copies
             vol, _ = ops.backproject_mean(p0, proj, new_origin, crop, model.voxel_size, model.n_voxels)
@@ -594,6 +644,32 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, detections_arrays(last) if args.api == 'simple_test' else {'packed_detections': last})
+    dtype = ('f32 (fp16 (hi, lo) pair MFMA operands: %s)' % ' and '.join(
+        (['the Winograd-domain neck GEMMs'] if pair else []) + (['the chained 2-D trunk'] if (FusedConv.trunk_operands == 4 and not bf16) else [])))\
+        if (pair or (FusedConv.trunk_operands == 4 and not bf16)) else args.storage
+
+    def headline(dt):
+        return {'metric': 'images/sec/node (KITTI 3x384x1280, 216x248x12 vox)',
+                'value': round(B * world * args.steps / dt, 3), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
+                'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True,
+                'scaling': 'weak', 'vs_baseline': None, 'dtype': dtype, 'data': 'synthetic'}
+    if not args.full:                  # the headline figure only; everything else is behind --full
+        if multi:
+            t = torch.tensor([dt], device=dev, dtype=torch.float64)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            dt = float(t.item())
+        if rank == 0:
+            rec = headline(dt)
+            rec['config'] = {'workload': 'kitti_mono_1x3x384x1280_vox216x248x12_resnet50_fpn64_kittineck_anchor3dhead',
+                             'batch_per_gpu': B, 'global_batch': B * world, 'parallelism': f'dp{world}',
+                             'api': 'ImVoxelNet.simple_test(img, img_metas)' if args.api == 'simple_test' else 'composed stages',
+                             'detections_last_step': n_det(last)}
+            print(json.dumps(rec))
+        if multi:
+            dist.destroy_process_group()
+        return
     recs_timed, n_post = None, 0
     if native_trace and not trace_timed_all:
         recs_timed = model._native.trace_records()          # stage-2 records of the timed steps
@@ -763,15 +839,7 @@ def main():
                   'note': 'floors: products issued / %.0f TFLOP/s (dense 16-bit MFMA; the pair form issues 3 per multiply-add) and algorithmic bytes / 8 TB/s; '
                           'frac = the larger floor / the measured step' % peak_step}
     if rank == 0:
-        total_images = B * world * args.steps
-        rec = {
-            'metric': 'images/sec/node (KITTI 3x384x1280, 216x248x12 vox)',
-            'value': round(total_images / dt, 3), 'unit': 'images/s', 'n_gpus': world, 'steps': args.steps,
-            'warmup': args.warmup, 'ms_per_step': round(dt / args.steps * 1e3, 3), 'higher_is_better': True,
-            'scaling': 'weak', 'vs_baseline': None,
-            'dtype': ('f32 (fp16 (hi, lo) pair MFMA operands: %s)' % ' and '.join(
-                (['the Winograd-domain neck GEMMs'] if pair else []) + (['the chained 2-D trunk'] if (FusedConv.trunk_operands == 4 and not bf16) else [])))
-            if (pair or (FusedConv.trunk_operands == 4 and not bf16)) else args.storage, 'data': 'synthetic',
+        rec = dict(headline(dt), **{
             'config': {'workload': 'kitti_mono_1x3x384x1280_vox216x248x12_resnet50_fpn64_kittineck_anchor3dhead',
                        'batch_per_gpu': B, 'global_batch': B * world, 'parallelism': f'dp{world}', 'hip_graph': False,
                        'api': 'ImVoxelNet.simple_test(img, img_metas)' if args.api == 'simple_test' else 'composed stages',
@@ -840,7 +908,7 @@ def main():
                                   'ms_per_step': round(t2d_ms, 3), 'executed_gflop_per_step': round(t2d_flops / 1e9, 1),
                                   'algorithmic_GB_per_step': round(t2d_bytes / 1e9, 3) if t2d_bytes > 0 else None,
                                   'hbm_GBps_algorithmic': round(t2d_bytes / (t2d_ms * 1e-3) / 1e9, 1) if (t2d_bytes > 0 and t2d_ms > 0) else None},
-        }
+        })
         if untraced:
             for k in ('roofline', 'roofline_winograd_transforms', 'roofline_unprojection', 'roofline_trunk_2d'):
                 rec[k] = None
@@ -853,7 +921,7 @@ def main():
             import subprocess
             rec['extra_configs'] = []
             for cname, views in (('nuscenes', 0), ('scannet_fast', 20), ('scannet_v1', 50), ('sunrgbd_fast', 0)):
-                cmd = [sys.executable, os.path.abspath(__file__), '--config', cname, '--steps', '5', '--warmup', '2', '--batch', str(BATCH_PER_GPU)]
+                cmd = [sys.executable, os.path.abspath(__file__), '--full', '--config', cname, '--steps', '5', '--warmup', '2', '--batch', str(BATCH_PER_GPU)]
                 if views:
                     cmd += ['--views', str(views)]
                 if not pair:

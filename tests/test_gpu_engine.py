@@ -429,7 +429,7 @@ def test_bench_rccl_path_at_world_size_1(ia):
     import json
     env = dict(os.environ, IVX_BENCH_FORCE_DIST='1', HSA_ENABLE_IPC_MODE_LEGACY='0')
     cmd = [sys.executable, '-m', 'torch.distributed.run', '--nnodes=1', '--nproc-per-node', '1', '--master-addr', '127.0.0.1', '--master-port', '29533',
-           os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline']
+           os.path.join(ROOT, 'bench.py'), '--full', '--gpus', '1', '--steps', '3', '--warmup', '1', '--no-cpu-baseline']
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]
@@ -439,6 +439,29 @@ def test_bench_rccl_path_at_world_size_1(ia):
     # default operands: fp16 pairs priced against the 16-bit MFMA peak (every product counted); in fp32 multiply-adds the GEMMs must beat
     # what the fp32 MFMA form could ever reach
     assert rec['roofline']['frac'] > 0.2 and rec['roofline']['fp32_equivalent_tflops'] > 160 and rec['measured_ceilings']['hbm_copy_gbps'] > 3000
+
+
+def test_bench_plain_line_and_dump_outputs(ia, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times exactly K steps and prints the headline figure only (the stage figures,
+    ceilings and CPU legs are behind --full); --dump-outputs writes the last timed step's detections, identical from run to run."""
+    import json
+    recs = []
+    for d in ('a', 'b'):
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--dump-outputs', str(tmp_path / d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    assert rec['steps'] == 3 and rec['warmup'] == 1 and rec['unit'] == 'images/s' and rec['higher_is_better'] is True and rec['dtype']
+    assert rec['ms_per_step'] > 0 and abs(rec['value'] - 4 * 1e3 / rec['ms_per_step']) <= 0.01 * rec['value']
+    assert not any(k in rec for k in ('roofline', 'measured_ceilings', 'exact_fp32_mfma', 'extra_configs', 'cpu_baseline'))
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(f'{k}_{b}.npy' for k in ('boxes_3d', 'scores_3d', 'labels_3d') for b in range(4))
+    assert sum(len(np.load(tmp_path / 'a' / f'scores_3d_{b}.npy')) for b in range(4)) == rec['config']['detections_last_step'] > 0
+    for n in names:
+        a, b = np.load(tmp_path / 'a' / n), np.load(tmp_path / 'b' / n)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), n
 
 
 def test_rccl_two_gpus_gather_and_slab_exchange(ia):

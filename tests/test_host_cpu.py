@@ -1712,3 +1712,34 @@ def test_fp8_noise_budget_quantisers():
     rms = ref.pow(2).mean().sqrt()
     r1, r4 = float((one - ref).pow(2).mean().sqrt() / rms), float((built - ref).pow(2).mean().sqrt() / rms)
     assert 0.01 < r1 < 0.04 and 1.5 * r1 < r4 < 2.6 * r1        # four independent sources of about the same size add in quadrature
+
+
+def test_bench_dump_outputs_format(tmp_path):
+    """bench.py --dump-outputs: every array as <name>.npy in float32 / float64 (integers and masks exact as float64), an array above
+    DUMP_MAX_ELEMS as the same seeded sample of its flat entries in every run (with its flat indices beside it)."""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('ivx_bench', os.path.join(ROOT, 'bench.py'))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    class Boxes:
+        def __init__(self, t):
+            self.tensor = t
+    g = torch.Generator().manual_seed(3)
+    res = [dict(boxes_3d=Boxes(torch.randn(5, 7, generator=g)), scores_3d=torch.rand(5, generator=g), labels_3d=torch.arange(5)),
+           (torch.randn(0, 7), torch.rand(0), torch.zeros(0, dtype=torch.int64))]
+    big = torch.randn(bench.DUMP_MAX_ELEMS + 17, generator=g).to(torch.bfloat16)
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), dict(bench.detections_arrays(res), volume=big, valid=torch.ones(3, dtype=torch.bool),
+                                                   wide=torch.zeros(2, dtype=torch.float64)))
+    names = sorted(os.listdir(tmp_path / 'a'))
+    assert names == sorted(['boxes_3d_0.npy', 'scores_3d_0.npy', 'labels_3d_0.npy', 'boxes_3d_1.npy', 'scores_3d_1.npy', 'labels_3d_1.npy',
+                            'volume.npy', 'volume.sample_index.npy', 'valid.npy', 'wide.npy'])
+    a = {n: np.load(tmp_path / 'a' / n) for n in names}
+    assert a['boxes_3d_0.npy'].dtype == np.float32 and np.array_equal(a['boxes_3d_0.npy'], res[0]['boxes_3d'].tensor.numpy())
+    assert a['labels_3d_0.npy'].dtype == np.float64 and np.array_equal(a['labels_3d_0.npy'], np.arange(5))
+    assert a['boxes_3d_1.npy'].shape == (0, 7) and a['valid.npy'].dtype == np.float64 and a['wide.npy'].dtype == np.float64
+    idx = a['volume.sample_index.npy'].astype(np.int64)
+    assert a['volume.npy'].dtype == np.float32 and a['volume.npy'].shape == (bench.DUMP_MAX_ELEMS,) and idx.max() < big.numel()
+    assert np.array_equal(a['volume.npy'], big.float().numpy()[idx])
+    assert all(np.array_equal(a[n], np.load(tmp_path / 'b' / n)) for n in names)

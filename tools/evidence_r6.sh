@@ -8,35 +8,35 @@ mkdir -p $ROOT/$OUT
 cd $ROOT
 if [ "$EVIDENCE_PROFILES_ONLY" != "1" ]; then
 nproc > $OUT/host.txt; lscpu | grep -E "Model name|Socket|Core|Thread" >> $OUT/host.txt
-python bench.py --steps 20 --warmup 5 2>$OUT/bench.err | tail -1 > $OUT/bench_default.json
+python bench.py --full --steps 20 --warmup 5 2>$OUT/bench.err | tail -1 > $OUT/bench_default.json
 NOX="env IVX_BENCH_EXTRA=0"
-$NOX python bench.py --steps 10 --warmup 3 --wino-operands f32 --trunk-operands f32 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_f32_operands.json
-$NOX python bench.py --steps 10 --warmup 3 --trunk-operands f32 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_trunk_f32.json
-$NOX python bench.py --steps 10 --warmup 3 --api composed --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_composed.json
-$NOX python bench.py --steps 10 --warmup 3 --storage bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_bf16.json
+$NOX python bench.py --full --steps 10 --warmup 3 --wino-operands f32 --trunk-operands f32 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_f32_operands.json
+$NOX python bench.py --full --steps 10 --warmup 3 --trunk-operands f32 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_trunk_f32.json
+$NOX python bench.py --full --steps 10 --warmup 3 --api composed --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_composed.json
+$NOX python bench.py --full --steps 10 --warmup 3 --storage bf16 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_bf16.json
 # A/B of this round's one-launch kernels inside the whole step
-IVX_FUSE_BOTTLENECK=0 $NOX python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_no_fused_bottleneck.json
-IVX_FUSE_STEM=0 $NOX python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_no_fused_stem.json
-IVX_FUSE_STEM=0 IVX_FUSE_BOTTLENECK=0 $NOX python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_no_fusion.json
+IVX_FUSE_BOTTLENECK=0 $NOX python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_no_fused_bottleneck.json
+IVX_FUSE_STEM=0 $NOX python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_no_fused_stem.json
+IVX_FUSE_STEM=0 IVX_FUSE_BOTTLENECK=0 $NOX python bench.py --full --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_no_fusion.json
 IVX_BENCH_FORCE_DIST=1 $NOX python -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29533 \
-    bench.py --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_dist1.json
-for c in nuscenes sunrgbd_fast scannet_fast scannet_v1; do python bench.py --config $c --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other.jsonl; done
-python bench.py --config scannet_fast --views 20 --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other.jsonl
-for c in nuscenes scannet_v1; do IVX_FUSE_STEM=0 IVX_FUSE_BOTTLENECK=0 python bench.py --config $c --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other_no_fusion.jsonl; done
-for c in nuscenes sunrgbd_fast scannet_fast scannet_v1; do python bench.py --config $c --steps 10 --warmup 3 --wino-operands f32 --trunk-operands f32 2>/dev/null | tail -1 >> $OUT/other_f32_operands.jsonl; done
-python bench.py --config scannet_v1 --steps 10 --warmup 3 --storage bf16 2>/dev/null | tail -1 >> $OUT/other_bf16.jsonl
-python bench.py --config scannet_v1 --steps 10 --warmup 3 --storage bf16 --trunk-fp8 2>/dev/null | tail -1 >> $OUT/other_bf16.jsonl
-python bench.py --config scannet_v1 --steps 10 --warmup 3 --storage bf16 --trunk-fp8 --fp8-variant full 2>/dev/null | tail -1 >> $OUT/other_bf16.jsonl
+    bench.py --full --gpus 1 --steps 5 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_dist1.json
+for c in nuscenes sunrgbd_fast scannet_fast scannet_v1; do python bench.py --full --config $c --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other.jsonl; done
+python bench.py --full --config scannet_fast --views 20 --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other.jsonl
+for c in nuscenes scannet_v1; do IVX_FUSE_STEM=0 IVX_FUSE_BOTTLENECK=0 python bench.py --full --config $c --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other_no_fusion.jsonl; done
+for c in nuscenes sunrgbd_fast scannet_fast scannet_v1; do python bench.py --full --config $c --steps 10 --warmup 3 --wino-operands f32 --trunk-operands f32 2>/dev/null | tail -1 >> $OUT/other_f32_operands.jsonl; done
+python bench.py --full --config scannet_v1 --steps 10 --warmup 3 --storage bf16 2>/dev/null | tail -1 >> $OUT/other_bf16.jsonl
+python bench.py --full --config scannet_v1 --steps 10 --warmup 3 --storage bf16 --trunk-fp8 2>/dev/null | tail -1 >> $OUT/other_bf16.jsonl
+python bench.py --full --config scannet_v1 --steps 10 --warmup 3 --storage bf16 --trunk-fp8 --fp8-variant full 2>/dev/null | tail -1 >> $OUT/other_bf16.jsonl
 # A/B of the split-operand form of the non-Winograd 3x3x3 neck layers + K split of the narrow head convs (round 6, last change) inside the whole step
-for c in nuscenes sunrgbd_fast scannet_fast scannet_v1; do IVX_CONV_PAIR=0 IVX_CONV_SKINNY=0 python bench.py --config $c --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other_no_split_form.jsonl; done
+for c in nuscenes sunrgbd_fast scannet_fast scannet_v1; do IVX_CONV_PAIR=0 IVX_CONV_SKINNY=0 python bench.py --full --config $c --steps 10 --warmup 3 2>/dev/null | tail -1 >> $OUT/other_no_split_form.jsonl; done
 for c in scannet_v1 scannet_fast sunrgbd_fast nuscenes; do python tools/neck_layers.py --config $c --min-pos 256 > $OUT/neck_layers_$c.md 2>/dev/null; done
 # the round-5 placement of the stage events (an event pair around every launch group of the timed steps)
-IVX_BENCH_TRACE_TIMED=1 $NOX python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_events_in_timed_region.json
+IVX_BENCH_TRACE_TIMED=1 $NOX python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > $OUT/bench_events_in_timed_region.json
 fi   # EVIDENCE_PROFILES_ONLY
 # kernel traces (IVX_BENCH_TRACE_TIMED=1: the profiled process runs exactly warmup + steps model steps, no traced steps after the timed region)
 trace() {   # name, steps-profiled, bench args...
   name=$1; nst=$2; shift 2
-  (cd /tmp && IVX_BENCH_ALT=0 IVX_BENCH_EXTRA=0 IVX_BENCH_TRACE_TIMED=1 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/trace_$name -o t -- python $ROOT/bench.py --no-cpu-baseline "$@" > $ROOT/$OUT/trace_$name.log 2>&1)
+  (cd "$TMPDIR" && IVX_BENCH_ALT=0 IVX_BENCH_EXTRA=0 IVX_BENCH_TRACE_TIMED=1 rocprofv3 --kernel-trace --stats -d $ROOT/$OUT/trace_$name -o t -- python $ROOT/bench.py --full --no-cpu-baseline "$@" > $ROOT/$OUT/trace_$name.log 2>&1)
   grep '^{"metric' $OUT/trace_$name.log | tail -1 > $OUT/bench_profiled_$name.json
   DB=$(find $OUT/trace_$name -name "*.db" | head -1)
   [ -n "$DB" ] && python tools/rocpd_summary.py $DB $nst > $OUT/kernel_trace_$name.md

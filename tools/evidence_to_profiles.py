@@ -36,7 +36,7 @@ def main():
         if os.path.exists(os.path.join(E, src)):
             with open(os.path.join(P, f'{pre}_{dst}'), 'w') as f:
                 f.writelines(l for l in open(os.path.join(E, src)) if 'amdgpu.ids' not in l)
-    rows = [('default: `python bench.py --steps 20 --warmup 5` (simple_test -> ivx_model_detect; neck GEMMs and 2-D trunk on fp16 pair operands)', 'bench_default.json'),
+    rows = [('default: `python bench.py --full --steps 20 --warmup 5` (simple_test -> ivx_model_detect; neck GEMMs and 2-D trunk on fp16 pair operands)', 'bench_default.json'),
             ('`--trunk-operands f32` (round 3: the 2-D trunk on fp32 MFMA, the neck GEMMs on pairs)', 'bench_trunk_f32.json'),
             ('`--wino-operands f32 --trunk-operands f32` (fp32 MFMA everywhere: the round-2 arithmetic)', 'bench_f32_operands.json'),
             ('--api composed (layer by layer over the op-level ABI)', 'bench_composed.json'),
