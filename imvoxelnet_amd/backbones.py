@@ -55,14 +55,15 @@ class _Bottleneck(nn.Module):
         mid = stream_dtype if c3_only else sd          # storage type of conv1's output and of conv2's input / filters
         self.f1 = FusedConv(self.conv1.weight, bn=self.bn1.tensors(), relu=True, dims=2, dtype=xd, out_dtype=mid, chain=chain).to(device)
         if self.dcn:
-            if sd != torch.float32:
-                raise NotImplementedError('the DCNv2 stages are built for float32 storage only')
+            if sd not in (torch.float32, torch.bfloat16):
+                raise NotImplementedError('the DCNv2 stages are built for float32 / bfloat16 storage only')
             co = self.conv2.conv_offset
             # 27 raw channels + one zero channel (csrc/model.cpp cout_zero): Cout % 4 == 0, so the layer can read pair tensors; the column
-            # kernel takes the map's channel count as its row stride
+            # kernel takes the map's channel count as its row stride.  bf16 storage: bf16 input and filters, fp32 offsets / masks out (the
+            # column kernel samples at fp32 positions; csrc/model.cpp out_f32), bf16 columns into the bf16 1x1 over K = 9 * C
             w_off = torch.cat([co.weight.detach().float(), torch.zeros_like(co.weight.detach()[:1]).float()], 0)
             b_off = torch.cat([co.bias.detach().float(), torch.zeros(1, dtype=torch.float32, device=co.bias.device)], 0)
-            self.f_off = FusedConv(w_off, b_off, stride=self.stride, padding=1, dims=2, chain=chain).to(device)
+            self.f_off = FusedConv(w_off, b_off, stride=self.stride, padding=1, dims=2, chain=chain, out_dtype=torch.float32).to(device)
             w = self.conv2.weight.detach()                               # [Cout, C, 3, 3] -> 1x1 over K = (tap, c)
             w_col = w.permute(0, 2, 3, 1).reshape(w.shape[0], -1, 1, 1)
             self.f2 = FusedConv(w_col, bn=self.bn2.tensors(), relu=True, dims=2, chain=chain).to(device)

@@ -13,8 +13,21 @@ void ivx_set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ivx_version(void) { return 410; /* 0.4.1: ivx_bottleneck_fwd_pio, ivx_stem_pool_fwd_pair, the SURVEY 8(b) export names, include/imvoxel_lab.h; 0.4.0: ivx_pair_io / ivx_conv_fwd_pio (chained fp16-pair activations), ivx_model_cfg.trunk_operands; 0.3.1: ivx_conv_desc.wino_operands, IVX_BF16_PAIR / IVX_F16_PAIR, ivx_model_cfg.wino_operands (0.3.0: head / DCNv2 / LayoutHead fields, ivx_model_detect) */ }
+extern "C" int ivx_version(void) { return 420; /* 0.4.2: ivx_dcn_im2col_fwd_bf16, ivx_global_avgpool_fwd_bf16 (bf16 storage with DCNv2 stages / the LayoutHead); 0.4.1: ivx_bottleneck_fwd_pio, ivx_stem_pool_fwd_pair, the SURVEY 8(b) export names, include/imvoxel_lab.h; 0.4.0: ivx_pair_io / ivx_conv_fwd_pio (chained fp16-pair activations), ivx_model_cfg.trunk_operands; 0.3.1: ivx_conv_desc.wino_operands, IVX_BF16_PAIR / IVX_F16_PAIR, ivx_model_cfg.wino_operands (0.3.0: head / DCNv2 / LayoutHead fields, ivx_model_detect) */ }
 extern "C" const char *ivx_last_error(void) { return g_err; }
+
+// bf16 entry points that model.cpp calls on a bf16 handle with DCNv2 stages / a LayoutHead.  The product library defines them in dcn.hip and
+// pool_layout.hip (the strong symbols win at link time); a build of model.cpp without those sources (a host-memory restatement of the op-level
+// entry points) links against these and reports the mode as unsupported instead of failing to link.
+extern "C" __attribute__((weak)) int ivx_dcn_im2col_fwd_bf16(const void *, const float *, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t, int32_t,
+                                                             int32_t, int32_t, int32_t, void *, ivx_stream_t) {
+  ivx_set_error("ivx_dcn_im2col_fwd_bf16: bf16 storage is not available in this build");
+  return IVX_ERR_UNSUPPORTED;
+}
+extern "C" __attribute__((weak)) int ivx_global_avgpool_fwd_bf16(const void *, int32_t, int64_t, int32_t, float *, ivx_stream_t) {
+  ivx_set_error("ivx_global_avgpool_fwd_bf16: bf16 storage is not available in this build");
+  return IVX_ERR_UNSUPPORTED;
+}
 
 // SURVEY.md section 8(b) names (include/imvoxel.h, last section): the same entry points under the survey's spelling
 extern "C" int ivx_anchor_head_decode(const ivx_anchor_head_desc *d, const float *head_out, const float *anchors, void *workspace, int64_t workspace_bytes,

@@ -186,3 +186,83 @@ extern "C" int ivx_dcn_im2col_fwd_pair(const void *x, const float *x_scale, cons
   return IVX_OK;
 }
 
+
+// The same columns on bf16 storage (ivx_model_cfg.storage = IVX_BF16): x a bf16 NHWC map, offsets / masks fp32 (conv_offset writes fp32
+// on a bf16 handle), col a bf16 tensor [B,1,Ho,Wo,kh*kw*C] in the (tap, c) order of ivx_dcn_im2col_fwd -- the contraction is the bf16 1x1
+// conv over K = 9 * C with the filters packed as for fp32.  Blend and mask multiply in fp32 with the expression of dcn_im2col_kernel, one
+// rounding to bf16 (round to nearest even; NaN stays NaN).  Structure of dcn_im2col_pair_kernel: one thread walks the taps of 8 channels of
+// one pixel (corner reads of neighbouring taps hit L1), 16-byte corner loads and column stores, XCD-contiguous workgroup order.
+__global__ __launch_bounds__(256) void dcn_im2col_bf16_kernel(const __bf16 *x, const float *om, int B, int H, int W, int C, int kh, int kw,
+                                                              int stride, int pad, int dil, int Ho, int Wo, int OMC, __bf16 *col, int xcd_order) {
+  typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+  const int C8 = C >> 3;
+  const int KK = kh * kw;
+  const size_t total = (size_t)B * Ho * Wo * C8;
+  size_t first = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (xcd_order) {     // one pass, grid rounded up to 8 * per blocks: XCD x takes the x-th contiguous eighth (see dcn_im2col_pair_kernel)
+    const size_t per = gridDim.x >> 3;
+    first = ((size_t)(blockIdx.x & 7) * per + (blockIdx.x >> 3)) * blockDim.x + threadIdx.x;
+  }
+  for (size_t idx = first; idx < total; idx += (size_t)gridDim.x * blockDim.x) {
+    const int n = (int)(idx % C8) * 8;
+    size_t t = idx / C8;            // t = output pixel m
+    const size_t m = t;
+    const int wo = (int)(t % Wo);
+    t /= Wo;
+    const int ho = (int)(t % Ho);
+    const int b = (int)(t / Ho);
+    const float *o = om + m * OMC;
+    const __bf16 *xb = x + (size_t)b * H * W * C + n;
+    __bf16 *op = col + m * (size_t)(KK * C) + n;
+    for (int k = 0; k < KK; ++k) {
+      const float dh = o[2 * k], dw = o[2 * k + 1];
+      const float mk = 1.0f / (1.0f + expf(-o[2 * KK + k]));
+      const int i = k / kw, j = k - i * kw;
+      const float h_im = (float)(ho * stride - pad + i * dil) + dh;
+      const float w_im = (float)(wo * stride - pad + j * dil) + dw;
+      float val[8];
+#pragma unroll
+      for (int q = 0; q < 8; ++q) val[q] = 0.f;
+      if (h_im > -1.f && w_im > -1.f && h_im < (float)H && w_im < (float)W) {
+        const int h_low = (int)floorf(h_im), w_low = (int)floorf(w_im);
+        const int h_high = h_low + 1, w_high = w_low + 1;
+        const float lh = h_im - h_low, lw = w_im - w_low, hh = 1.f - lh, hw = 1.f - lw;
+        const bf16x8 z = {};
+        auto at = [&](bool ok, int hy, int wx) { return ok ? *reinterpret_cast<const bf16x8 *>(xb + ((size_t)hy * W + wx) * C) : z; };
+        const bf16x8 v1 = at(h_low >= 0 && w_low >= 0, h_low, w_low);
+        const bf16x8 v2 = at(h_low >= 0 && w_high <= W - 1, h_low, w_high);
+        const bf16x8 v3 = at(h_high <= H - 1 && w_low >= 0, h_high, w_low);
+        const bf16x8 v4 = at(h_high <= H - 1 && w_high <= W - 1, h_high, w_high);
+        const float w1 = hh * hw, w2 = hh * lw, w3 = lh * hw, w4 = lh * lw;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) val[q] = (w1 * (float)v1[q] + w2 * (float)v2[q] + w3 * (float)v3[q] + w4 * (float)v4[q]) * mk;
+      }
+      bf16x8 r;
+#pragma unroll
+      for (int q = 0; q < 8; ++q) r[q] = (__bf16)val[q];
+      *reinterpret_cast<bf16x8 *>(op + (size_t)k * C) = r;
+    }
+  }
+}
+
+extern "C" int ivx_dcn_im2col_fwd_bf16(const void *x, const float *offset_mask, int32_t B, int32_t H, int32_t W, int32_t C, int32_t kh,
+                                       int32_t kw, int32_t stride, int32_t pad, int32_t dil, int32_t om_channels, void *col,
+                                       ivx_stream_t stream) {
+  IVX_REQUIRE(x && offset_mask && col, "ivx_dcn_im2col_fwd_bf16: null argument");
+  IVX_REQUIRE(B > 0 && H > 0 && W > 0 && C > 0 && C % 8 == 0, "ivx_dcn_im2col_fwd_bf16: bad dims (C %% 8 must be 0, got C = %d)", C);
+  IVX_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)col & 15) == 0, "ivx_dcn_im2col_fwd_bf16: x and col must be 16-byte aligned");
+  IVX_REQUIRE(kh > 0 && kw > 0 && stride > 0 && pad >= 0 && dil > 0, "ivx_dcn_im2col_fwd_bf16: bad window");
+  IVX_REQUIRE(om_channels >= 3 * kh * kw, "ivx_dcn_im2col_fwd_bf16: offset/mask map needs 3*kh*kw channels (deform_groups = 1)");
+  const int Ho = (H + 2 * pad - (dil * (kh - 1) + 1)) / stride + 1;
+  const int Wo = (W + 2 * pad - (dil * (kw - 1) + 1)) / stride + 1;
+  IVX_REQUIRE(Ho > 0 && Wo > 0, "ivx_dcn_im2col_fwd_bf16: empty output");
+  const size_t total = (size_t)B * Ho * Wo * (C / 8);
+  size_t blocks = (total + 255) / 256;
+  int xcd_order = 0;
+  if (blocks <= 256 * 64 - 8) { blocks = (blocks + 7) / 8 * 8; xcd_order = 1; }      // one pass: XCD x takes the x-th eighth of the pixels
+  else blocks = 256 * 64;
+  hipLaunchKernelGGL(dcn_im2col_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)x, offset_mask, B, H, W,
+                     C, kh, kw, stride, pad, dil, Ho, Wo, om_channels, (__bf16 *)col, xcd_order);
+  IVX_CHECK_LAUNCH("ivx_dcn_im2col_fwd_bf16");
+  return IVX_OK;
+}

@@ -117,7 +117,8 @@ struct ConvLayer {
   std::map<int, float *> u;           // tile * 8 + operand type -> transformed filters
   // fp16-pair form (cfg.trunk_operands = IVX_F16_PAIR; ivx_conv_fwd_pio): pair filters, scale / s_w, and the terms of the output bound
   bool stem_s2d = false;              // bf16 storage: the 7x7 stride-2 stem as a 4x4 stride-1 conv over 2x2 space-to-depth blocks (weights re-indexed at pack time)
-  bool out_f32 = false;               // bf16 storage: this layer writes fp32 (the head convs: the tails decode fp32 scores / deltas)
+  bool out_f32 = false;               // bf16 storage: this layer writes fp32 (the head convs: the tails decode fp32 scores / deltas; conv_offset)
+  bool f32 = false;                   // bf16 storage: an fp32 layer (fp32 filters, input and output: the LayoutHead MLPs, as heads_layout.py)
   // e4m3 interior of the bottlenecks (ivx_model_calibrate_fp8 on a bf16 handle): 1 conv1 (bf16 in, e4m3 out), 2 conv2 (e4m3 in / filters /
   // out), 3 conv3 (e4m3 in / filters, bf16 out + bf16 shortcut); 0: not part of it
   int fp8_role = 0;
@@ -323,6 +324,7 @@ void build_trunk(ivx_model *m) {
         ConvLayer co = conv2d(pre + "conv2.conv_offset", planes, 28, 3, stride, 1, false, pre + "conv2.conv_offset.weight",
                               pre + "conv2.conv_offset.bias", "");
         co.cout_zero = 1;                                   // 27 raw channels + one zero channel
+        co.out_f32 = true;                                  // bf16 storage: fp32 offsets / masks (the column kernels read fp32)
         const int off = add_conv(m, co, y);
         Step dc; dc.kind = ST_DCN_COL; dc.in = y; dc.res = off; dc.out = new_tensor(m); dc.aux = stride;
         m->steps.push_back(dc);
@@ -357,6 +359,7 @@ void build_trunk(ivx_model *m) {
         const std::string pre = "head_2d." + name + "." + std::to_string(idx[q]) + ".";
         ConvLayer L = conv2d(pre, ci, co[q], 1, 1, 0, q < 2, pre + "weight", pre + "bias", "");
         L.linear = true;
+        L.f32 = L.out_f32 = true;                         // bf16 storage: fp32 layers on the fp32 pooled C5 (heads_layout.py prepare)
         t = add_conv(m, L, t);
         ci = co[q];
       }
@@ -598,7 +601,7 @@ const HostTensor *find_w(const ivx_model *m, const std::string &key) {
 // Deploy form of one layer: imvoxelnet_amd/conv.py FusedConv.__init__ in C++ (same fp32 operations in the same order).
 int pack_layer(ivx_model *m, ConvLayer &L, hipStream_t st, std::string *missing) {
   const int kd = L.k[0], kh = L.k[1], kw = L.k[2], taps = kd * kh * kw;
-  const bool bf16 = m->cfg.storage == IVX_BF16;      // bf16 storage (conv.py FusedConv with dtype bfloat16): 8-channel chunks, 64-channel K chunks
+  const bool bf16 = m->cfg.storage == IVX_BF16 && !L.f32;   // bf16 storage (conv.py FusedConv with dtype bfloat16): 8-channel chunks, 64-channel K chunks
   L.cin_pad = bf16 ? (L.cin + 7) / 8 * 8 : (L.cin + 3) / 4 * 4;
   L.layout = (L.cin_pad % (bf16 ? 64 : 32) == 0) ? 1 : 0;
   // staging buffers live in the handle and are reused by every layer (fresh 100 MB vectors per layer cost seconds of first-touch
@@ -833,7 +836,7 @@ int plan_conv(ivx_model *m, ConvLayer &L, const TInfo &in, const Step &st, const
   d.res_after_act = st.res_after_act;
   d.out_mode = L.conv_t ? 1 : 0;
   M_REQUIRE(in.C == L.cin_pad, "layer %s: input has %d channels, expected %d", L.name.c_str(), in.C, L.cin_pad);
-  if (m->cfg.storage == IVX_BF16) {   // bf16 storage: the direct kernel on bf16 operands, fp32 accumulate; the head convs write fp32
+  if (m->cfg.storage == IVX_BF16 && !L.f32) {   // bf16 storage: the direct kernel on bf16 operands, fp32 accumulate; the head convs write fp32
     d.in_dtype = IVX_BF16;
     d.out_dtype = L.out_f32 ? IVX_F32 : IVX_BF16;
     if (m->fp8_on && L.fp8_eff) {     // e4m3 interior of a bottleneck: tensor scales are folded into scale_q / shift_q
@@ -1068,7 +1071,7 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
       continue;
     }
     if (s.kind != ST_CONV && s.kind != ST_MAXPOOL && s.kind != ST_IMG2CL && s.kind != ST_DCN_COL) { o.fmt = 0; o.slot = -1; }   // (`o = in` above copies the input's)
-    o.esz = (s.kind == ST_CONV && m->layers[s.layer].out_f32) ? 4 : esz;
+    o.esz = ((s.kind == ST_CONV && m->layers[s.layer].out_f32) || s.kind == ST_AVGPOOL) ? 4 : esz;   // (the pooled C5 is fp32 in every storage)
     if (s.kind == ST_CONV && m->fp8_on && (m->layers[s.layer].fp8_eff == 1 || m->layers[s.layer].fp8_eff == 2)) o.esz = 1;
     o.bytes = align256(o.elems() * o.esz);
     o.first = i;
@@ -1626,10 +1629,12 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
       }
       case ST_DCN_COL: {
         const TInfo &om = pl.t[s.res];
-        M_TRY(trace_begin(m, i, 0, 0, 0.0, 4.0 * pl.t[s.out].elems(), "dcn columns", st));
+        M_TRY(trace_begin(m, i, 0, 0, 0.0, (double)pl.t[s.out].esz * pl.t[s.out].elems(), "dcn columns", st));
         if (pl.ps[i].pio)            // inside the pair chain: pair map in, pair columns out (same scale)
           M_TRY(ivx_dcn_im2col_fwd_pair(ptr(s.in), scalep(s.in), (const float *)ptr(s.res), in.B, in.H, in.W, in.C, 3, 3, s.aux, 1, 1, om.C,
                                         ptr(s.out), scalep(s.out), slotp(s.out), st));
+        else if (m->cfg.storage == IVX_BF16)     // bf16 map + fp32 offsets / masks -> bf16 columns
+          M_TRY(ivx_dcn_im2col_fwd_bf16(ptr(s.in), (const float *)ptr(s.res), in.B, in.H, in.W, in.C, 3, 3, s.aux, 1, 1, om.C, ptr(s.out), st));
         else
           M_TRY(ivx_dcn_im2col_fwd((const float *)ptr(s.in), (const float *)ptr(s.res), in.B, in.H, in.W, in.C, 3, 3, s.aux, 1, 1, om.C,
                                    (float *)ptr(s.out), st));
@@ -1637,7 +1642,10 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
         break;
       }
       case ST_AVGPOOL:
-        M_TRY(ivx_global_avgpool_fwd((const float *)ptr(s.in), in.B, (int64_t)in.D * in.H * in.W, in.C, (float *)ptr(s.out), st));
+        if (m->cfg.storage == IVX_BF16)          // bf16 C5 -> fp32 mean (same summation order)
+          M_TRY(ivx_global_avgpool_fwd_bf16(ptr(s.in), in.B, (int64_t)in.D * in.H * in.W, in.C, (float *)ptr(s.out), st));
+        else
+          M_TRY(ivx_global_avgpool_fwd((const float *)ptr(s.in), in.B, (int64_t)in.D * in.H * in.W, in.C, (float *)ptr(s.out), st));
         break;
       case ST_LAYOUT: {
         // LayoutHead._forward_single (layout_head.py:52-74) + the projection from the PREDICTED angles (detectors/imvoxelnet.py:59-61,
@@ -1733,8 +1741,6 @@ extern "C" int ivx_create(const ivx_model_cfg *cfg, ivx_model **out) {
   M_REQUIRE(cfg->trunk_operands == IVX_F32 || cfg->trunk_operands == IVX_F16_PAIR, "ivx_create: trunk_operands IVX_F32 | IVX_F16_PAIR");
   M_REQUIRE(cfg->storage == IVX_F32 || cfg->storage == IVX_BF16, "ivx_create: storage IVX_F32 | IVX_BF16");
   if (cfg->storage == IVX_BF16) {
-    M_REQUIRE(!cfg->layout_head && !cfg->dcn_stages[0] && !cfg->dcn_stages[1] && !cfg->dcn_stages[2] && !cfg->dcn_stages[3],
-              "ivx_create: bf16 storage is not built for the DCNv2 stages / the LayoutHead");
     M_REQUIRE(cfg->fpn_channels % 8 == 0 && cfg->neck_out_channels % 8 == 0, "ivx_create: bf16 storage needs channel counts that are multiples of 8");
   }
   M_REQUIRE(cfg->winograd_tile == 0 || cfg->winograd_tile == 2 || cfg->winograd_tile == 4 || cfg->winograd_tile == 6, "ivx_create: winograd_tile 0 | 2 | 4 | 6");
@@ -1946,6 +1952,10 @@ extern "C" int ivx_model_calibrate_fp8_ex(ivx_model *m, const float *img, int32_
   M_TRY(check_img(m, BV, 1, H, W, "ivx_model_calibrate_fp8"));
   M_REQUIRE(img && margin > 0.f && first_stage >= 0 && first_stage <= 4, "ivx_model_calibrate_fp8: bad argument");
   M_REQUIRE(m->cfg.storage == IVX_BF16 && m->cfg.with_trunk, "ivx_model_calibrate_fp8: needs a handle with storage = IVX_BF16 and the 2-D trunk");
+  if (m->cfg.layout_head || m->cfg.dcn_stages[0] || m->cfg.dcn_stages[1] || m->cfg.dcn_stages[2] || m->cfg.dcn_stages[3]) {
+    ivx_set_error("ivx_model_calibrate_fp8: the e4m3 trunk is not built for DCNv2 stages or a LayoutHead (bf16 storage only)");
+    return IVX_ERR_UNSUPPORTED;
+  }
   hipStream_t st = (hipStream_t)stream;
   m->fp8_on = false;                         // a second calibration starts from the bf16 trunk again
   for (ConvLayer &L : m->layers) {

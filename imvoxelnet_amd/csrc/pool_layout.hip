@@ -357,6 +357,29 @@ extern "C" int ivx_global_avgpool_fwd(const float *in, int32_t B, int64_t S, int
   return IVX_OK;
 }
 
+// The same mean of a bf16 map (LayoutHead on bf16 storage: C5 is bf16, the pooled vector and the MLPs are fp32).  Same threads, same
+// summation order as global_avgpool_kernel: bf16 -> fp32 is exact, so the result equals ivx_global_avgpool_fwd(in.float()) bit for bit.
+__global__ __launch_bounds__(256) void global_avgpool_bf16_kernel(const __bf16 *in, int S, int C, float *out) {
+  __shared__ float part[4][64];
+  const int b = blockIdx.y;
+  const int c = blockIdx.x * 64 + (threadIdx.x & 63);
+  const int ph = threadIdx.x >> 6;
+  float acc = 0.f;
+  if (c < C)
+    for (int s = ph; s < S; s += 4) acc += (float)in[((size_t)b * S + s) * C + c];
+  part[ph][threadIdx.x & 63] = acc;
+  __syncthreads();
+  if (ph == 0 && c < C) out[(size_t)b * C + c] = (((part[0][threadIdx.x] + part[1][threadIdx.x]) + part[2][threadIdx.x]) + part[3][threadIdx.x]) / (float)S;
+}
+
+extern "C" int ivx_global_avgpool_fwd_bf16(const void *in, int32_t B, int64_t S, int32_t C, float *out, ivx_stream_t stream) {
+  IVX_REQUIRE(in && out, "ivx_global_avgpool_fwd_bf16: null argument");
+  IVX_REQUIRE(B > 0 && B <= 65535 && S > 0 && S < (1LL << 31) && C > 0, "ivx_global_avgpool_fwd_bf16: bad dims");
+  hipLaunchKernelGGL(global_avgpool_bf16_kernel, dim3((C + 63) / 64, B), dim3(256), 0, (hipStream_t)stream, (const __bf16 *)in, (int)S, C, out);
+  IVX_CHECK_LAUNCH("ivx_global_avgpool_fwd_bf16");
+  return IVX_OK;
+}
+
 // fp32 -> (hi, lo) pairs in the IVX_BF16_PAIR / IVX_F16_PAIR order (include/imvoxel.h): per 16 values [hi x16 | lo x16].  One lane
 // converts 8 values: 32 contiguous bytes in, 16 bytes of hi and 16 bytes of lo out; a pair of lanes fills one 64-byte group.
 typedef float pf32x4 __attribute__((ext_vector_type(4)));

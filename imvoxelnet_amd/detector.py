@@ -67,7 +67,9 @@ class ImVoxelNet(nn.Module):
         the layer-by-layer composition below stays available (extract_feat, forward_cl, the other configurations).
         dtype: storage type of activations and weights between layers.  float32 (default) is the reference's precision
         and the one every parity claim is made for; bfloat16 is an optional reduced-precision mode (fp32 accumulate,
-        fp32 epilogues, fp32 head output and detection tail) built for the single-view anchor-head configs."""
+        fp32 epilogues, fp32 head output and detection tail) for every config: with DCNv2 stages the offsets / masks are fp32
+        and the deformable columns bf16, with a LayoutHead the pooled C5 and its MLPs are fp32.  The native handle covers it
+        wherever it covers fp32 (engine.eligible)."""
         from .conv import storage_dtype
         with storage_dtype(dtype):
             for m in (self.backbone, self.neck, self.neck_3d, self.bbox_head):
@@ -84,10 +86,8 @@ class ImVoxelNet(nn.Module):
         if self._native is not None:
             self._native.close()
         self._native = None
-        # fp32, or the bf16 storage mode (ivx_model_cfg.storage; not with DCNv2 stages / a LayoutHead, which are fp32-only everywhere)
-        bf16_ok = dtype == torch.bfloat16 and self.head_2d is None and not any(
-            getattr(blk, 'dcn', False) for i in range(4) for blk in getattr(self.backbone, f'layer{i + 1}', []))
-        if native and (dtype == torch.float32 or bf16_ok) and engine.eligible(self):
+        # fp32, or the bf16 storage mode (ivx_model_cfg.storage), DCNv2 stages and a LayoutHead included
+        if native and dtype in (torch.float32, torch.bfloat16) and engine.eligible(self):
             self._native = engine.NativeModel(self, device)
         return self
 
@@ -109,8 +109,9 @@ class ImVoxelNet(nn.Module):
         from .conv import FusedConv, storage_dtype, FP8
         if self._prepared_device is None or self.storage_dtype != torch.bfloat16:
             raise RuntimeError('calibrate_fp8 needs prepare(device, dtype=torch.bfloat16) first')
-        if self.head_2d is not None or not hasattr(self.backbone, 'forward_image'):
-            raise NotImplementedError('the fp8 trunk is built for the plain ResNet + FPN configurations without a LayoutHead')
+        dcn = any(getattr(blk, 'dcn', False) for i in range(4) for blk in getattr(self.backbone, f'layer{i + 1}', []))
+        if self.head_2d is not None or dcn or not hasattr(self.backbone, 'forward_image'):
+            raise NotImplementedError('the fp8 trunk is built for the plain ResNet + FPN configurations without DCNv2 stages or a LayoutHead')
         dev = self._prepared_device
         x = img.reshape([-1] + list(img.shape)[-3:]).contiguous().to(dev)
         with storage_dtype(torch.bfloat16):          # a fresh bf16 trunk (a second calibration starts from bf16 again)

@@ -75,7 +75,7 @@ def model_cfg(model, with_trunk=True, winograd=None, winograd_tile=None):
     fam = family(model)
     if fam is None:
         raise NotImplementedError('the native model handle covers ResNet-50 (+ DCNv2 stages) + FPN with a Kitti / NuScenes neck + Anchor3DHead, or '
-                                  'with FastIndoorImVoxelNeck / ImVoxelNeck + an anchor-free head without towers (+ LayoutHead), fp32')
+                                  'with FastIndoorImVoxelNeck / ImVoxelNeck + an anchor-free head without towers (+ LayoutHead), fp32 or bf16 storage')
     head, n3, bb = model.bbox_head, model.neck_3d, model.backbone
     cfg = ModelCfg()
     cfg.with_trunk = int(bool(with_trunk))

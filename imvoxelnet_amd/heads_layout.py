@@ -59,7 +59,8 @@ class LayoutHead(nn.Module):
         """c5 [B,1,h,w,C] channels-last -> (angles: list of [2] CPU tensors, layouts: list of [7] CPU tensors)."""
         if self._device is None:
             self.prepare(c5.device)
-        x = ops.global_avgpool(c5 if c5.dtype == torch.float32 else c5.float())
+        x = ops.global_avgpool(c5)           # fp32 mean of an fp32 or bf16 C5 (the native handle runs the same kernel); fp32 MLPs
+
         a = l_ = x
         for f in self.f_angle:
             a = f(a)

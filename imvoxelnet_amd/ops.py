@@ -672,27 +672,32 @@ def bottleneck_proj_fwd_pio(x, f1, f2, bank):
 
 
 def global_avgpool(x):
-    """[B,D,H,W,C] channels-last -> [B,1,1,1,C]: mean over every spatial position."""
-    _chk(x, 'x')
+    """[B,D,H,W,C] channels-last fp32 or bf16 -> [B,1,1,1,C] fp32: mean over every spatial position (a bf16 map through
+    ivx_global_avgpool_fwd_bf16: the same bits as the fp32 pool of x.float())."""
+    bf16 = isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16
+    _chk(x, 'x', torch.bfloat16 if bf16 else torch.float32)
     B, Cn = x.shape[0], x.shape[-1]
     S = x.numel() // (B * Cn)
     out = torch.empty((B, 1, 1, 1, Cn), device=x.device, dtype=torch.float32)
-    check(_lib.lib().ivx_global_avgpool_fwd(_ptr(x), B, S, Cn, _ptr(out), _stream()), 'ivx_global_avgpool_fwd')
+    fn, name = (_lib.lib().ivx_global_avgpool_fwd_bf16, 'ivx_global_avgpool_fwd_bf16') if bf16 else (_lib.lib().ivx_global_avgpool_fwd, 'ivx_global_avgpool_fwd')
+    check(fn(_ptr(x), B, S, Cn, _ptr(out), _stream()), name)
     return out
 
 
 def dcn_im2col(x, offset_mask, kernel=3, stride=1, pad=1, dil=1):
-    """x [B,1,H,W,C], offset_mask [B,1,Ho,Wo,>=3*k*k] -> modulated deformable columns [B,1,Ho,Wo,k*k*C]."""
-    _chk(x, 'x')
+    """x [B,1,H,W,C], offset_mask [B,1,Ho,Wo,>=3*k*k] fp32 -> modulated deformable columns [B,1,Ho,Wo,k*k*C] in x's dtype:
+    fp32 (ivx_dcn_im2col_fwd) or, on bf16 storage, bf16 (ivx_dcn_im2col_fwd_bf16: fp32 blend, one rounding; C % 8 == 0)."""
+    bf16 = isinstance(x, torch.Tensor) and x.dtype == torch.bfloat16
+    _chk(x, 'x', torch.bfloat16 if bf16 else torch.float32)
     _chk(offset_mask, 'offset_mask')
     B, D, H, W, Cn = x.shape
     Ho = (H + 2 * pad - (dil * (kernel - 1) + 1)) // stride + 1
     Wo = (W + 2 * pad - (dil * (kernel - 1) + 1)) // stride + 1
     if D != 1 or tuple(offset_mask.shape[:4]) != (B, 1, Ho, Wo):
         raise ValueError('offset/mask map does not match the output size')
-    col = torch.empty((B, 1, Ho, Wo, kernel * kernel * Cn), device=x.device, dtype=torch.float32)
-    check(_lib.lib().ivx_dcn_im2col_fwd(_ptr(x), _ptr(offset_mask), B, H, W, Cn, kernel, kernel, stride, pad, dil,
-                                        offset_mask.shape[4], _ptr(col), _stream()), 'ivx_dcn_im2col_fwd')
+    col = torch.empty((B, 1, Ho, Wo, kernel * kernel * Cn), device=x.device, dtype=x.dtype)
+    fn, name = (_lib.lib().ivx_dcn_im2col_fwd_bf16, 'ivx_dcn_im2col_fwd_bf16') if bf16 else (_lib.lib().ivx_dcn_im2col_fwd, 'ivx_dcn_im2col_fwd')
+    check(fn(_ptr(x), _ptr(offset_mask), B, H, W, Cn, kernel, kernel, stride, pad, dil, offset_mask.shape[4], _ptr(col), _stream()), name)
     return col
 
 

@@ -37,8 +37,9 @@ extern "C" {
 
 typedef void *ivx_stream_t; /* hipStream_t */
 
-/* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header) and the message of
- * the last failing call on this thread (never NULL). */
+/* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header; 420 = 0.4.2: bf16 storage with
+ * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16) and the message of the last failing call on
+ * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
 
@@ -319,6 +320,13 @@ int ivx_dcn_im2col_fwd(const float *x, const float *offset_mask, int32_t B, int3
 int ivx_dcn_im2col_fwd_pair(const void *x, const float *x_scale, const float *offset_mask, int32_t B, int32_t H, int32_t W, int32_t C,
                             int32_t kh, int32_t kw, int32_t stride, int32_t pad, int32_t dil, int32_t om_channels, void *col,
                             float *col_scale, uint32_t *col_amax, ivx_stream_t stream);
+/* The same on bf16 storage (0.4.2): x a bf16 map [B,H,W,C], offset_mask fp32 as above (the conv_offset layer writes fp32 on a bf16 handle),
+ * col a bf16 tensor [B,Ho,Wo,kh*kw*C] in the (tap, c) order of ivx_dcn_im2col_fwd.  Blend and mask multiply in fp32 as in
+ * ivx_dcn_im2col_fwd, one rounding to bf16 (nearest even) per column element.  C % 8 == 0; x and col 16-byte aligned (else
+ * IVX_ERR_INVALID_ARG).  The contraction is ivx_conv_fwd on bf16 operands with Cin = kh*kw*C. */
+int ivx_dcn_im2col_fwd_bf16(const void *x, const float *offset_mask, int32_t B, int32_t H, int32_t W, int32_t C, int32_t kh,
+                            int32_t kw, int32_t stride, int32_t pad, int32_t dil, int32_t om_channels, void *col,
+                            ivx_stream_t stream);
 
 /* nn.MaxPool2d(kernel, stride, padding) on NHWC (ResNet stem: 3, 2, 1). */
 int ivx_maxpool2d_fwd(const float *in, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k,
@@ -508,6 +516,9 @@ int ivx_aligned_3d_nms_ws(const float *boxes, const float *scores, const int64_t
 /* Global average pool of a channels-last map: in [B,S,C] -> out [B,C]; `x.mean(dim=(2,3))` of LayoutHead.forward
  * (mmdet3d/models/dense_heads/layout_head.py:42, SUN RGB-D Total configs).                                        */
 int ivx_global_avgpool_fwd(const float *in, int32_t B, int64_t S, int32_t C, float *out, ivx_stream_t stream);
+/* The same pool of a bf16 map (0.4.2; LayoutHead on bf16 storage): fp32 out, the summation order of ivx_global_avgpool_fwd, so the result
+ * equals ivx_global_avgpool_fwd of the map converted to fp32 bit for bit. */
+int ivx_global_avgpool_fwd_bf16(const void *in, int32_t B, int64_t S, int32_t C, float *out, ivx_stream_t stream);
 
 /* Fused multi-class BEV NMS -- replaces box3d_multiclass_nms (mmdet3d/core/post_processing/box3d_nms.py:8-88), i.e.
  * the host loop over classes around nms_gpu / nms_normal_gpu with its per-class D2H, for n <= 65536 candidates and
@@ -631,8 +642,11 @@ typedef struct ivx_model_cfg {
                                       stored as bf16 (v_mfma_f32_32x32x16_bf16, fp32 accumulation and epilogues, the 7x7 stem as a 4x4 convolution
                                       over 2x2 space-to-depth blocks of the image), head outputs and the detection tails fp32.  The image input and
                                       the detection outputs keep their types; the tensors of the sub-path entry points (ivx_backbone_fpn_fwd's
-                                      fpn0, ivx_neck3d_*_fwd's volume / levels, ivx_model_forward_levels' levels) are bf16.  Not with DCNv2 stages
-                                      or a LayoutHead; the Winograd and pair forms are fp32-storage forms and are not used */
+                                      fpn0, ivx_neck3d_*_fwd's volume / levels, ivx_model_forward_levels' levels) are bf16.  (0.4.2) With DCNv2
+                                      stages conv_offset writes fp32 offsets / masks and the columns are bf16 (ivx_dcn_im2col_fwd_bf16);
+                                      with a LayoutHead C5 is pooled to fp32 (ivx_global_avgpool_fwd_bf16) and the six MLP linears stay
+                                      fp32 layers (fp32 filters, fp32 in and out).  ivx_model_calibrate_fp8 refuses both forms.  The
+                                      Winograd and pair forms are fp32-storage forms and are not used */
 } ivx_model_cfg;
 
 int ivx_create(const ivx_model_cfg *cfg, ivx_model **out);
@@ -698,7 +712,7 @@ int ivx_model_detect(ivx_model *m, const float *img, int32_t B, int32_t V, int32
                      void *workspace, int64_t workspace_bytes, float *out_boxes, float *out_scores, int64_t *out_labels, int32_t *out_count,
                      uint8_t *out_valid, float *out_angles /*host*/, float *out_layout /*host*/, ivx_stream_t stream);
 /* BASELINE config 5's named mode inside the handle: "bf16 with fp8 2-D conv MFMA".  On a handle with storage = IVX_BF16 and the trunk
- * (no DCNv2 stages): runs ONE bf16 pass of ResNet-50 + FPN over the given images (img [BV,3,H,W] fp32; synchronises the stream once),
+ * (no DCNv2 stages and no LayoutHead: IVX_ERR_UNSUPPORTED): runs ONE bf16 pass of ResNet-50 + FPN over the given images (img [BV,3,H,W] fp32; synchronises the stream once),
  * records max |output| of conv1 and conv2 of every bottleneck, and from then on stores the INSIDE of every bottleneck as OCP e4m3:
  * conv1 reads the bf16 residual stream and writes e4m3 (per-tensor scale amax * margin / 448), conv2 and conv3 run on
  * v_mfma_f32_32x32x16_fp8_fp8 (e4m3 activations, e4m3 filters with one scale per output channel), conv3 adds the bf16 shortcut and writes
