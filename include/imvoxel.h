@@ -177,7 +177,10 @@ int ivx_pair_pack_filters(const float *w, int32_t Cout, int32_t taps, int32_t Ci
                           float *scale_out, float *wbound, float *sbound);
 /* The head of such a chain.  ivx_nchw_to_nhwc that also accumulates max |in| into amax (the image);  nn.MaxPool2d on an fp32 map
  * (the stem's output) that writes an IVX_F16_PAIR tensor with the scale of the bound amax_in * wbound + sbound (the stem as a function
- * of the image: a maximum over a window cannot exceed it), leaves that scale in *out_scale and max |out| in amax_out.  C % 16 == 0. */
+ * of the image: a maximum over a window cannot exceed it), leaves that scale in *out_scale and max |out| in amax_out.  C % 16 == 0.
+ * ivx_nchw_to_nhwc_amax takes the maximum over the elements that are not NaN, and an Inf counts: the bound built from it has to hold
+ * every finite value of the chain, an Inf selects the fixed scale and the saturating split, and a NaN stays a NaN under any scale, so it
+ * needs none (ivx_amax_f32 below differs on purpose: there a NaN counts as Inf). */
 int ivx_nchw_to_nhwc_amax(const float *in, int32_t B, int32_t C, int64_t S, int32_t Cpad, float *out, uint32_t *amax, ivx_stream_t stream);
 int ivx_maxpool2d_fwd_pair(const float *in, int32_t B, int32_t H, int32_t W, int32_t C, int32_t k, int32_t s, int32_t p, void *out,
                            const uint32_t *amax_in, float wbound, float sbound, float *out_scale, uint32_t *amax_out, ivx_stream_t stream);
@@ -718,7 +721,9 @@ int ivx_model_detect(ivx_model *m, const float *img, int32_t B, int32_t V, int32
  * v_mfma_f32_32x32x16_fp8_fp8 (e4m3 activations, e4m3 filters with one scale per output channel), conv3 adds the bf16 shortcut and writes
  * bf16 -- the residual stream itself is never re-quantised (ImVoxelNet.calibrate_fp8(residual='bf16') of the Python host; both hosts
  * run the same kernels).  Plans are rebuilt on the next forward.  workspace as for ivx_backbone_fpn_fwd.  ivx_amax_bf16: the max |x|
- * reduction it uses (out: device float, zeroed by the caller). */
+ * reduction it uses (out: device float, zeroed by the caller; left as it is for n = 0).  The maximum is over the elements that are not
+ * NaN, and an Inf counts: the e4m3 scale amax * margin / 448 has to be a finite number that holds the finite values of the tensor, which a
+ * NaN counted as Inf would destroy for every element. */
 int ivx_model_calibrate_fp8(ivx_model *m, const float *img, int32_t BV, int32_t H, int32_t W, float margin, void *workspace,
                             int64_t workspace_bytes, ivx_stream_t stream);
 /* The same with the variant chosen: ResNet stages below first_stage (0 .. 4) keep plain bf16 bottlenecks; conv2_bf16 != 0: conv1 / conv2 stay bf16
