@@ -80,7 +80,35 @@ class TraceRec(C.Structure):
                 ('bytes', C.c_double), ('name', C.c_char * 48)]
 
 
-EXPORTS = ['ivx_bottleneck_proj_supported', 'ivx_bottleneck_proj_pack', 'ivx_bottleneck_proj_fwd_pio', 'ivx_anchor_head_decode', 'ivx_fcos3d_head_decode', 'ivx_nms_rotated_bev', 'ivx_nms_aligned3d', 'ivx_bottleneck_supported', 'ivx_bottleneck_fwd_pio', 'ivx_amax_f32', 'ivx_stem_pool_filter_bytes', 'ivx_stem_pool_pack_filters', 'ivx_stem_pool_out_dims', 'ivx_stem_pool_fwd_pair', 'ivx_conv_winograd_set_variant', 'ivx_ubench_mfma', 'ivx_ubench_copy', 'ivx_version', 'ivx_last_error', 'ivx_conv_out_dims', 'ivx_conv_fwd', 'ivx_conv_fwd_naive', 'ivx_conv_set_tile_override', 'ivx_conv_set_epilogue_mode', 'ivx_conv_set_plan_mode', 'ivx_topk_set_mode', 'ivx_conv_workspace_bytes', 'ivx_conv_fwd_ws', 'ivx_conv_set_halo_mode', 'ivx_bf16_pair_split', 'ivx_f16_pair_split', 'ivx_conv_pair_supported', 'ivx_conv_pio_workspace_bytes', 'ivx_conv_fwd_pio', 'ivx_conv_fwd_pio_naive', 'ivx_pair_pack_filters', 'ivx_nchw_to_nhwc_amax', 'ivx_maxpool2d_fwd_pair', 'ivx_f16_pair_merge', 'ivx_model_calibrate_fp8', 'ivx_model_calibrate_fp8_ex', 'ivx_amax_bf16', 'ivx_conv_winograd_output_blocks', 'ivx_conv_winograd_issued_fraction', 'ivx_conv_winograd_output_amax', 'ivx_conv_winograd_input_amax', 'ivx_conv_winograd_fused_supported', 'ivx_conv_winograd_fused_blocks', 'ivx_conv_winograd_gemm_output_amax',
+class PlanInfo(C.Structure):
+    """ivx_plan_info (include/imvoxel_lab.h): the byte layout of a cached plan of the model handle."""
+    _fields_ = [(n, C.c_int64) for n in ('cam_bytes', 'arena', 'ws_off', 'ws_bytes', 'ws2_off', 'ws2_bytes', 'total', 'scal_off', 'scal_bytes')] + \
+               [(n, C.c_int32) for n in ('slot_bytes', 'n_sides', 's0', 's1', 'n_steps', 'n_tensors')]
+
+
+class PlanStep(C.Structure):
+    """ivx_plan_step."""
+    _fields_ = [(n, C.c_int32) for n in ('kind', 'in_', 'res', 'out', 'out2', 'fuse_out', 'fuse', 'side', 'join', 'tile', 'pio', 'amax_n', 'amax_in_n',
+                                         'n_extra_in', 'n_extra_out')] + \
+               [('extra_in', C.c_int32 * 12), ('extra_out', C.c_int32 * 4)] + \
+               [(n, C.c_int64) for n in ('split', 'ws', 'amax_out', 'amax_in')] + [('name', C.c_char * 48)]
+
+
+class PlanTensor(C.Structure):
+    """ivx_plan_tensor."""
+    _fields_ = [(n, C.c_int64) for n in ('off', 'bytes', 'used', 'slot')] + \
+               [(n, C.c_int32) for n in ('first', 'last', 'fmt', 'esz', 'caller_owned', 'boundary')]
+
+
+def declare_plan_view(L):
+    """Argument types of the read-only plan view, on libimvoxel_hip.so or on the CPU restatement of the same ABI (tests)."""
+    key = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
+    L.ivx_model_plan_info.argtypes = key + [C.POINTER(PlanInfo)]
+    L.ivx_model_plan_step.argtypes = key + [C.c_int32, C.POINTER(PlanStep)]
+    L.ivx_model_plan_tensor.argtypes = key + [C.c_int32, C.POINTER(PlanTensor)]
+
+
+EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor', 'ivx_bottleneck_proj_supported', 'ivx_bottleneck_proj_pack', 'ivx_bottleneck_proj_fwd_pio', 'ivx_anchor_head_decode', 'ivx_fcos3d_head_decode', 'ivx_nms_rotated_bev', 'ivx_nms_aligned3d', 'ivx_bottleneck_supported', 'ivx_bottleneck_fwd_pio', 'ivx_amax_f32', 'ivx_stem_pool_filter_bytes', 'ivx_stem_pool_pack_filters', 'ivx_stem_pool_out_dims', 'ivx_stem_pool_fwd_pair', 'ivx_conv_winograd_set_variant', 'ivx_ubench_mfma', 'ivx_ubench_copy', 'ivx_version', 'ivx_last_error', 'ivx_conv_out_dims', 'ivx_conv_fwd', 'ivx_conv_fwd_naive', 'ivx_conv_set_tile_override', 'ivx_conv_set_epilogue_mode', 'ivx_conv_set_plan_mode', 'ivx_topk_set_mode', 'ivx_conv_workspace_bytes', 'ivx_conv_fwd_ws', 'ivx_conv_set_halo_mode', 'ivx_bf16_pair_split', 'ivx_f16_pair_split', 'ivx_conv_pair_supported', 'ivx_conv_pio_workspace_bytes', 'ivx_conv_fwd_pio', 'ivx_conv_fwd_pio_naive', 'ivx_pair_pack_filters', 'ivx_nchw_to_nhwc_amax', 'ivx_maxpool2d_fwd_pair', 'ivx_f16_pair_merge', 'ivx_model_calibrate_fp8', 'ivx_model_calibrate_fp8_ex', 'ivx_amax_bf16', 'ivx_conv_winograd_output_blocks', 'ivx_conv_winograd_issued_fraction', 'ivx_conv_winograd_output_amax', 'ivx_conv_winograd_input_amax', 'ivx_conv_winograd_fused_supported', 'ivx_conv_winograd_fused_blocks', 'ivx_conv_winograd_gemm_output_amax',
            'ivx_conv_winograd_supported', 'ivx_conv_winograd_weight_elems', 'ivx_conv_winograd_weights', 'ivx_conv_winograd_workspace_bytes',
            'ivx_conv_winograd_input', 'ivx_conv_winograd_gemm', 'ivx_conv_winograd_output', 'ivx_conv_winograd_fwd',
            'ivx_maxpool2d_fwd', 'ivx_maxpool2d_fwd_bf16', 'ivx_maxpool2d_fwd_fp8', 'ivx_global_avgpool_fwd', 'ivx_global_avgpool_fwd_bf16', 'ivx_upsample_trilinear2x_fwd', 'ivx_dcn_im2col_fwd', 'ivx_dcn_im2col_fwd_bf16', 'ivx_dcn_im2col_fwd_pair', 'ivx_nchw_to_nhwc', 'ivx_image_s2d_bf16', 'ivx_nhwc_to_nchw', 'ivx_backproject_mean_fwd', 'ivx_backproject_mean_fwd_amax', 'ivx_backproject_amax_blocks', 'ivx_backproject_mean_fwd_bf16', 'ivx_upsample_trilinear2x_fwd_bf16', 'ivx_backproject_sum_fwd', 'ivx_volume_normalize_fwd',
@@ -239,6 +267,7 @@ def lib():
     L.ivx_model_trace_count.argtypes = [vp]
     L.ivx_model_trace_count.restype = i32
     L.ivx_model_trace_read.argtypes = [vp, i32, C.POINTER(TraceRec)]
+    declare_plan_view(L)
     # ctypes' default restype (c_int) is the int status every other entry point returns; the 64-bit queries must have been
     # declared explicitly above (a missing one would silently truncate)
     wide = [n for n in EXPORTS if n.endswith(('_workspace_bytes', '_weight_elems')) and getattr(L, n).restype is not C.c_int64]

@@ -20,6 +20,7 @@
 #include <vector>
 
 #include "../../include/imvoxel.h"
+#include "../../include/imvoxel_lab.h"
 
 void ivx_set_error(const char *fmt, ...);
 
@@ -198,8 +199,9 @@ struct Plan {
   ivx_indoor_tail_desc itail;          // indoor families with a head
   int max_det = 0;                     // rows per sample of the detection outputs
   int64_t scal_off = 0, scal_bytes = 0;   // scalar blocks of the pair-chained tensors (zeroed at the start of every forward)
-  int64_t ws2_off = 0;                    // second split-K workspace (launches on the side stream), 0: none
+  int64_t ws2_off = 0, ws2_bytes = 0;     // second split-K workspace (launches on the side stream; ws2_off 0: none): the largest need of a side launch
   int n_sides = 0;
+  int s0 = 0, s1 = 0;                     // the step range the plan covers (ivx_model_plan_info)
 };
 
 }  // namespace
@@ -925,6 +927,7 @@ int plan_conv(ivx_model *m, ConvLayer &L, const TInfo &in, const Step &st, const
 int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_views, Plan *pl, hipStream_t stream) {
   pl->t.assign(m->n_tensors, TInfo());
   pl->ps.assign(m->steps.size(), PlanStep());
+  pl->s0 = r.s0; pl->s1 = r.s1;
   for (auto &kv : inputs) { pl->t[kv.first] = kv.second; pl->t[kv.first].first = -2; }
   const ivx_model_cfg &c = m->cfg;
   // fp16-pair chaining of the 2-D trunk (cfg.trunk_operands): a tensor is stored as pairs when its producer can write them (the
@@ -1031,6 +1034,7 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
         const int R = c.head_type == IVX_HEAD_SCANNET ? 6 : 7;
         const int64_t fw = ivx_fcos_head_workspace_bytes(in.B, n, c.head_nms_pre);
         M_REQUIRE(fw >= 0, "indoor head level %d: more than 65536 candidates per level (nms_pre %d)", s.aux, c.head_nms_pre);
+        pl->ps[i].ws = fw;
         pl->ws_bytes = std::max(pl->ws_bytes, fw);
         pl->itail.k[s.aux] = k;
         TInfo cb; cb.B = in.B; cb.D = cb.H = 1; cb.W = k; cb.C = R; cb.raw = true; cb.bytes = align256((int64_t)in.B * k * R * 4); cb.first = i;
@@ -1050,6 +1054,7 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
         pl->max_det = d.max_num;
         const int64_t tw = ivx_indoor_tail_workspace_bytes(&d);
         M_REQUIRE(tw >= 0, "indoor tail: %s", ivx_last_error());
+        pl->ps[i].ws = tw;
         pl->ws_bytes = std::max(pl->ws_bytes, tw);
         break;
       }
@@ -1066,6 +1071,7 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
       d.score_thr = c.score_thr; d.nms_thr = c.nms_thr; d.dir_offset = c.dir_offset; d.dir_limit_offset = c.dir_limit_offset;
       pl->tail_ws = ivx_anchor_head_workspace_bytes(&d);
       M_REQUIRE(pl->tail_ws >= 0, "anchor tail: %s", ivx_last_error());
+      pl->ps[i].ws = pl->tail_ws;
       pl->ws_bytes = std::max(pl->ws_bytes, pl->tail_ws);
       pl->max_det = c.max_num;
       continue;
@@ -1271,7 +1277,13 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
   pl->ws_off = pl->arena;
   pl->ws_bytes = align256(pl->ws_bytes);
   pl->total = pl->arena + pl->ws_bytes;
-  if (pl->n_sides > 0) { pl->ws2_off = pl->total; pl->total += pl->ws_bytes; }      // the side stream's own split-K workspace
+  if (pl->n_sides > 0) {      // the side stream's own split-K workspace: only the shortcut convs run there, so it holds the largest of THEIR needs
+    for (int i = r.s0; i < r.s1; ++i)
+      if (pl->ps[i].side > 0) pl->ws2_bytes = std::max(pl->ws2_bytes, pl->ps[i].ws);
+    pl->ws2_bytes = align256(pl->ws2_bytes);
+    pl->ws2_off = pl->total;
+    pl->total += pl->ws2_bytes;
+  }
   return IVX_OK;
 }
 
@@ -1532,6 +1544,7 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
         // the shortcut conv of a block runs on the side stream next to conv1 / conv2 (with per-launch tracing everything stays on `st`)
         hipStream_t cst = st;
         void *cws = ws;
+        int64_t cws_bytes = pl.ws_bytes;
         if (ps.side > 0 && !(m->trace_on && m->trace_level != 3) && pl.ws2_off > 0) {
           if (!m->side) {
             M_HIP(hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking), "hipStreamCreateWithFlags");
@@ -1546,6 +1559,7 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
           M_HIP(hipStreamWaitEvent(m->side, m->ev_fork, 0), "hipStreamWaitEvent");
           cst = m->side;
           cws = base + pl.ws2_off;
+          cws_bytes = pl.ws2_bytes;
           forked[ps.side - 1] = 1;
         }
         if (ps.join > 0 && forked[ps.join - 1]) {
@@ -1582,7 +1596,7 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
           io.out_scale = scalep(s.out);
           io.amax_in = slotp(s.in); io.amax_res = slotp(s.res); io.amax_out = slotp(s.out);
           io.wbound = L.wbound; io.sbound = L.sbound;
-          M_TRY(ivx_conv_fwd_pio(&ps.d, &io, ptr(s.in), L.wpair, L.scale_p, L.shift, res, ptr(s.out), cws, pl.ws_bytes, cst));
+          M_TRY(ivx_conv_fwd_pio(&ps.d, &io, ptr(s.in), L.wpair, L.scale_p, L.shift, res, ptr(s.out), cws, cws_bytes, cst));
         } else if (ps.tile) {
           M_TRY(ivx_conv_winograd_input_amax(&ps.d, ps.tile, ptr(s.in), ws, pl.ws_bytes, ps.amax_in >= 0 ? (const float *)(base + ps.amax_in) : nullptr,
                                              ps.amax_in_n, st));
@@ -1590,12 +1604,12 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
           M_TRY(ivx_conv_winograd_output_amax(&ps.d, ps.tile, L.scale, L.shift, res, ptr(s.out), ws, pl.ws_bytes,
                                               ps.amax_out >= 0 ? (float *)(base + ps.amax_out) : nullptr, st));
         } else if (m->fp8_on && L.fp8_eff) {
-          M_TRY(ivx_conv_fwd_ws(&ps.d, ptr(s.in), L.fp8_eff >= 2 ? L.wq : L.w, L.scale_q, L.shift_q, res, ptr(s.out), cws, pl.ws_bytes, cst));
+          M_TRY(ivx_conv_fwd_ws(&ps.d, ptr(s.in), L.fp8_eff >= 2 ? L.wq : L.w, L.scale_q, L.shift_q, res, ptr(s.out), cws, cws_bytes, cst));
         } else if (ps.split) {     // (hi, lo) bf16 copy of the input at the start of the workspace, then the three-product kernel
           M_TRY(ivx_bf16_pair_split((const float *)ptr(s.in), in.elems(), cws, cst));
-          M_TRY(ivx_conv_fwd_ws(&ps.d, cws, L.wsplit, L.scale, L.shift, res, ptr(s.out), (char *)cws + ps.split, pl.ws_bytes - ps.split, cst));
+          M_TRY(ivx_conv_fwd_ws(&ps.d, cws, L.wsplit, L.scale, L.shift, res, ptr(s.out), (char *)cws + ps.split, cws_bytes - ps.split, cst));
         } else {
-          M_TRY(ivx_conv_fwd_ws(&ps.d, ptr(s.in), L.w, L.scale, L.shift, res, ptr(s.out), cws, pl.ws_bytes, cst));
+          M_TRY(ivx_conv_fwd_ws(&ps.d, ptr(s.in), L.w, L.scale, L.shift, res, ptr(s.out), cws, cws_bytes, cst));
           if (m->calib_dev && (L.fp8_eff == 1 || L.fp8_eff == 2))       // calibration pass: max |output| of the tensors that will be e4m3
             M_TRY(ivx_amax_bf16(ptr(s.out), o.elems(), m->calib_dev + s.layer, st));
         }
@@ -2309,6 +2323,65 @@ extern "C" int ivx_model_trace_read(ivx_model *m, int32_t i, ivx_trace_rec *rec)
   M_HIP(hipEventElapsedTime(&start, m->trace[0].e0, r.e0), "hipEventElapsedTime");
   rec->step = r.step; rec->stage = r.stage; rec->is3d = r.is3d; rec->ms = ms; rec->start_ms = start; rec->flops = r.flops; rec->bytes = r.bytes;
   snprintf(rec->name, sizeof(rec->name), "%s", r.name.c_str());
+  return IVX_OK;
+}
+
+// ---- read-only view of a cached plan (include/imvoxel_lab.h): plain records for the plan checker of tests/.  Never plans.
+static int plan_lookup(ivx_model *m, const char *what, int B, int V, int H, int W, const char *who, const Plan **pl) {
+  M_REQUIRE(m && what, "%s: null argument", who);
+  auto it = m->plans.find(plan_key(what, B, V, H, W));
+  M_REQUIRE(it != m->plans.end(), "%s: no cached plan \"%s\" for (%d, %d, %d, %d); call the matching *_workspace_bytes first", who, what, B, V, H, W);
+  *pl = it->second.get();
+  return IVX_OK;
+}
+
+extern "C" int ivx_model_plan_info(ivx_model *m, const char *what, int32_t B, int32_t V, int32_t H, int32_t W, ivx_plan_info *info) {
+  const Plan *pl;
+  M_TRY(plan_lookup(m, what, B, V, H, W, "ivx_model_plan_info", &pl));
+  M_REQUIRE(info, "ivx_model_plan_info: null argument");
+  memset(info, 0, sizeof(*info));
+  info->cam_bytes = pl->cam_bytes; info->arena = pl->arena; info->ws_off = pl->ws_off; info->ws_bytes = pl->ws_bytes;
+  info->ws2_off = pl->ws2_off; info->ws2_bytes = pl->ws2_bytes; info->total = pl->total;
+  info->scal_off = pl->scal_off; info->scal_bytes = pl->scal_bytes; info->slot_bytes = 512;
+  info->n_sides = pl->n_sides; info->s0 = pl->s0; info->s1 = pl->s1;
+  info->n_steps = (int32_t)m->steps.size(); info->n_tensors = m->n_tensors;
+  return IVX_OK;
+}
+
+extern "C" int ivx_model_plan_step(ivx_model *m, const char *what, int32_t B, int32_t V, int32_t H, int32_t W, int32_t step, ivx_plan_step *rec) {
+  const Plan *pl;
+  M_TRY(plan_lookup(m, what, B, V, H, W, "ivx_model_plan_step", &pl));
+  M_REQUIRE(rec && step >= pl->s0 && step < pl->s1, "ivx_model_plan_step: step %d is outside the plan's range [%d, %d)", step, pl->s0, pl->s1);
+  const Step &s = m->steps[step];
+  const PlanStep &ps = pl->ps[step];
+  memset(rec, 0, sizeof(*rec));
+  rec->kind = (int32_t)s.kind;
+  rec->in = s.in; rec->res = s.res; rec->out = s.out; rec->out2 = s.out2; rec->fuse_out = ps.fuse_out;
+  rec->fuse = ps.fuse; rec->side = ps.side; rec->join = ps.join; rec->tile = ps.tile; rec->pio = ps.pio;
+  rec->amax_n = ps.amax_n; rec->amax_in_n = ps.amax_in_n;
+  rec->split = ps.split; rec->ws = ps.ws; rec->amax_out = ps.amax_out; rec->amax_in = ps.amax_in;
+  if (s.kind == ST_INDOOR_TAIL)             // run_steps hands it every level's boxes and scores; the counts travel with them
+    for (size_t l = 0; l < m->t_cb.size() && rec->n_extra_in + 3 <= 12; ++l)
+      for (int t : {m->t_cb[l], m->t_cs[l], m->t_cc[l]}) rec->extra_in[rec->n_extra_in++] = t;
+  if (s.kind == ST_FCOS) rec->extra_out[rec->n_extra_out++] = m->t_cc[s.aux];
+  if (s.kind == ST_CONV) snprintf(rec->name, sizeof(rec->name), "%s", m->layers[s.layer].name.c_str());
+  return IVX_OK;
+}
+
+extern "C" int ivx_model_plan_tensor(ivx_model *m, const char *what, int32_t B, int32_t V, int32_t H, int32_t W, int32_t tensor, ivx_plan_tensor *rec) {
+  const Plan *pl;
+  M_TRY(plan_lookup(m, what, B, V, H, W, "ivx_model_plan_tensor", &pl));
+  M_REQUIRE(rec && tensor >= 0 && tensor < m->n_tensors, "ivx_model_plan_tensor: bad tensor id %d", tensor);
+  const TInfo &t = pl->t[tensor];
+  memset(rec, 0, sizeof(*rec));
+  rec->off = t.off; rec->bytes = t.bytes;
+  rec->used = tensor == m->t_valid ? t.elems() : t.elems() * (t.raw ? 4 : t.esz);      // (the valid mask is bytes; candidate buffers are 32-bit words)
+  rec->slot = t.slot >= 0 ? pl->scal_off + t.slot * 512 : -1;
+  rec->first = t.first; rec->last = t.last; rec->fmt = t.fmt; rec->esz = t.esz;
+  rec->caller_owned = t.first == -2 ? 1 : 0;
+  std::vector<int> keep = {m->t_fpn0, m->t_volume, m->t_valid, m->t_neck, m->t_head, m->t_angle, m->t_layout};
+  keep.insert(keep.end(), m->t_levels.begin(), m->t_levels.end());
+  rec->boundary = std::find(keep.begin(), keep.end(), (int)tensor) != keep.end() ? 1 : 0;
   return IVX_OK;
 }
 

@@ -39,6 +39,55 @@ int ivx_topk_set_mode(int32_t single_workgroup);
 int ivx_ubench_mfma(int32_t dtype, void *scratch, int64_t scratch_bytes, double *tflops, ivx_stream_t stream);
 int ivx_ubench_copy(const void *src, void *dst, int64_t bytes, double *gbps, ivx_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------
+ * Read-only view of a cached plan of the model handle (tests/test_host_plan.py checks its invariants: liveness, aliasing, the side
+ * stream's sites, the workspaces).  `what` names the plan: "forward" (the forward and forward_levels entry points, key B, V, H, W),
+ * "detect" (the detect entry point, same key), "trunk" (the backbone + FPN entry point, key BV, 1, H, W) or "neck" (the 3-D neck entry
+ * points, key B, 1, 0, 0).  Nothing here creates a plan: the matching workspace-size query (or a forward) must have run before, else
+ * IVX_ERR_INVALID_ARG.  Host code only; the same functions exist in the CPU restatement of the ABI.
+ *
+ * Steps and tensors are numbered as in the handle's graph (the whole model); a plan covers the steps [s0, s1).  What a step does:
+ *   fuse 0  runs by itself: reads in, res and extra_in, writes out, out2 and extra_out;
+ *   fuse 1  one-launch identity bottleneck: runs the steps i .. i + 2 (the two behind it carry fuse 2) and writes fuse_out;
+ *   fuse 5  one-launch projection bottleneck: runs the steps i - 1 .. i + 2 (the shortcut conv in front and the two behind carry fuse 2),
+ *           writes fuse_out;
+ *   fuse 3  image layout change of the one-launch stem: only reads `in` (the maximum of the image goes to out's scalar block);
+ *   fuse 4  max-pool step of the one-launch stem: runs the steps i - 2 .. i (fuse 3, fuse 2, itself) from the caller's image, writes out;
+ *   fuse 2  covered by a neighbour, launches nothing.
+ * side / join: site number (1 .. n_sides) on the shortcut conv that goes to the side stream and on the step that waits for it. */
+typedef struct ivx_plan_info {
+  int64_t cam_bytes, arena, ws_off, ws_bytes, ws2_off, ws2_bytes, total, scal_off, scal_bytes;
+  int32_t slot_bytes;                 /* bytes of one tensor's scalar block inside [scal_off, scal_off + scal_bytes) */
+  int32_t n_sides, s0, s1, n_steps, n_tensors;
+} ivx_plan_info;
+
+typedef struct ivx_plan_step {
+  int32_t kind;                       /* 0 image layout, 1 image space-to-depth, 2 conv, 3 max-pool, 4 unprojection, 5 anchor tail, 6 upsample,
+                                         7 DCN columns, 8 average pool, 9 LayoutHead, 10 anchor-free candidates, 11 anchor-free tail */
+  int32_t in, res, out, out2, fuse_out;   /* tensor ids, -1: none */
+  int32_t fuse, side, join, tile, pio;
+  int32_t amax_n, amax_in_n;
+  int32_t n_extra_in, n_extra_out;    /* tensors read / written besides the five above (the anchor-free tail reads every level's candidates) */
+  int32_t extra_in[12], extra_out[4];
+  int64_t split, ws;                  /* ws: workspace bytes of this step's launches */
+  int64_t amax_out, amax_in;          /* arena offsets of per-workgroup maxima (4 * amax_n bytes), -1: none */
+  char name[48];                      /* layer name of a conv step, else "" */
+} ivx_plan_step;
+
+typedef struct ivx_plan_tensor {
+  int64_t off, bytes;                 /* arena placement; off -1: not placed (caller-owned input, or outside the plan) */
+  int64_t used;                       /* bytes the tensor's elements take (bytes is this, rounded up to 256) */
+  int64_t slot;                       /* arena offset of the scalar block, -1: none */
+  int32_t first, last;                /* the planner's live interval in steps (last == s1: kept to the end) */
+  int32_t fmt, esz;
+  int32_t caller_owned;               /* 1: an input of the plan, never placed in the arena */
+  int32_t boundary;                   /* 1: FPN level 0, volume, valid mask, neck output, head output, levels, angle, layout */
+} ivx_plan_tensor;
+
+int ivx_model_plan_info(ivx_model *m, const char *what, int32_t B, int32_t V, int32_t H, int32_t W, ivx_plan_info *info);
+int ivx_model_plan_step(ivx_model *m, const char *what, int32_t B, int32_t V, int32_t H, int32_t W, int32_t step, ivx_plan_step *rec);
+int ivx_model_plan_tensor(ivx_model *m, const char *what, int32_t B, int32_t V, int32_t H, int32_t W, int32_t tensor, ivx_plan_tensor *rec);
+
 #ifdef __cplusplus
 }
 #endif

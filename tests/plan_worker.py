@@ -1,0 +1,327 @@
+"""Worker of tests/test_host_plan.py and tests/test_gpu_plan_switches.py (also imported by them for the in-process checks).
+
+The planner reads IVX_SIDE_STREAM, IVX_FUSE_BOTTLENECK and IVX_FUSE_STEM once per process, so the other setting of a switch needs a fresh
+process: the calling test starts this script with the switch in the environment.  Two jobs, on libimvoxel_hip.so (--lib hip) or on the CPU
+restatement of the same ABI (--lib cpu):
+
+  plans  build one handle per family, plan one shape each through the *_workspace_bytes queries, read the plans back through the view of
+         include/imvoxel_lab.h and run tests/plan_check.py on them; one JSON line with what was seen (sites, fuse values) and any defect.
+  run    build a seeded model, run four steps alternating two seeded inputs (A, B, A, B) through ivx_model_detect and save, per step, every
+         boundary tensor of the plan (FPN level 0, volume, valid mask, neck output or levels, head output) read out of the arena plus the
+         detections to an .npz; --phases runs the four steps once per trace level in the SAME process (prefix t<level>_)."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(HERE)
+for p in (ROOT, HERE):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+FAMILIES = ('kitti', 'nuscenes', 'nuscenes_dcn', 'scannet_fast', 'sunrgbd_fast', 'scannet_v1', 'sunrgbd_total')
+# BASELINE shapes (B, V, H, W) per family: KITTI batch 4, nuScenes 6 cameras, ScanNet 50 (and 20) views, SUN RGB-D one view
+FULL_SHAPES = {'kitti': [(4, 1, 384, 1280)], 'nuscenes': [(1, 6, 928, 1600)], 'nuscenes_dcn': [(1, 6, 928, 1600)],
+               'scannet_fast': [(1, 50, 480, 640), (1, 20, 480, 640)], 'sunrgbd_fast': [(1, 1, 480, 640)], 'scannet_v1': [(1, 50, 480, 640)],
+               'sunrgbd_total': [(1, 1, 480, 640)]}
+IVX_F16_PAIR = 4
+
+
+def load_lib(which):
+    from imvoxelnet_amd import _lib
+    if which == 'hip':
+        L = _lib.lib()
+    else:
+        import importlib.util
+        spec = importlib.util.spec_from_file_location('ivx_cpu_abi_build', os.path.join(ROOT, 'oracle', 'cpu_abi', 'build.py'))
+        mod = importlib.util.module_from_spec(spec)
+        spec.loader.exec_module(mod)
+        L = C.CDLL(mod.build()[0])
+    L.ivx_last_error.restype = C.c_char_p
+    for f in ('ivx_model_workspace_bytes', 'ivx_neck3d_workspace_bytes', 'ivx_model_detect_workspace_bytes', 'ivx_backbone_fpn_workspace_bytes'):
+        getattr(L, f).restype = C.c_int64
+    _lib.declare_plan_view(L)
+    return L
+
+
+def family_model(family, n_voxels=None, seed=0, small_channels=False):
+    """(module, test_cfg) of a family with seeded random weights; n_voxels overrides the volume (the weights do not depend on it)."""
+    import torch
+    import imvoxelnet_amd as ia
+    from imvoxelnet_amd import workloads as kc
+    if family == 'kitti':
+        cfg, tcfg = (kc.kitti_model_cfg(in_ch=64, out_ch=64) if small_channels else kc.kitti_model_cfg()), dict(kc.KITTI_TEST_CFG, score_thr=0.05)
+    elif family in ('nuscenes', 'nuscenes_dcn'):
+        cfg, tcfg = kc.nuscenes_model_cfg(dcn=family == 'nuscenes_dcn'), dict(kc.NUSCENES_TEST_CFG)
+    elif family == 'scannet_fast':
+        cfg, tcfg = kc.scannet_fast_model_cfg(), dict(kc.SCANNET_FAST_TEST_CFG)
+    elif family in ('sunrgbd_fast', 'sunrgbd_total'):
+        cfg, tcfg = kc.sunrgbd_fast_model_cfg(), dict(kc.SUNRGBD_FAST_TEST_CFG)
+        if family == 'sunrgbd_total':
+            cfg['head_2d'] = dict(type='LayoutHead', n_channels=2048, linear_size=256, dropout=0.0)
+    elif family == 'scannet_v1':
+        cfg, tcfg = kc.scannet_v1_model_cfg(), dict(kc.SCANNET_V1_TEST_CFG)
+    else:
+        raise KeyError(family)
+    if n_voxels is not None:
+        cfg['n_voxels'] = tuple(n_voxels)
+        if family == 'kitti':
+            nv, ox = n_voxels, 0.5 + n_voxels[0] * .32 / 2
+            cfg['bbox_head']['anchor_generator']['ranges'] = [[ox - nv[0] * .16, -nv[1] * .16, -1.78, ox + nv[0] * .16 - .32, nv[1] * .16 - .32, -1.78]]
+        if family.startswith('nuscenes'):
+            nv = n_voxels
+            cfg['bbox_head']['anchor_generator']['ranges'] = [[-nv[0] * .16, -nv[1] * .16, -1.0, nv[0] * .16 - .64, nv[1] * .16 - .64, -1.0]]
+    torch.manual_seed(1234 + seed)                      # (the LayoutHead's Linear layers initialise from the global generator)
+    model = ia.build_detector(cfg, test_cfg=tcfg)
+    ia.randomize_(model, seed)
+    with torch.no_grad():
+        g = torch.Generator().manual_seed(5 + seed)
+        h = model.bbox_head
+        if hasattr(h, 'conv_cls'):
+            h.conv_cls.weight.normal_(0, 0.05, generator=g)
+            h.conv_cls.bias.fill_(-1.5)
+            h.conv_reg.weight.normal_(0, 0.002, generator=g)
+        else:
+            h.cls_conv.weight.normal_(0, 0.01, generator=g)
+            h.cls_conv.bias.fill_(-1.0)
+            h.centerness_conv.weight.normal_(0, 0.005, generator=g)
+            h.reg_conv.weight.normal_(0, 0.002, generator=g)
+    return model
+
+
+class Handle:
+    """ivx_model handle of a module on library L, in an explicit operand / storage mode (the configuration struct is built on the host)."""
+
+    def __init__(self, L, model, storage=0, trunk_operands=IVX_F16_PAIR, wino_operands=IVX_F16_PAIR, stream=None):
+        from imvoxelnet_amd import engine
+        self.L, self.model, self.stream = L, model, stream
+        cfg = engine.model_cfg(model, with_trunk=True)
+        cfg.storage, cfg.trunk_operands, cfg.wino_operands = storage, trunk_operands, wino_operands
+        self.cfg = cfg
+        self.h = C.c_void_p()
+        self.ok(L.ivx_create(C.byref(cfg), C.byref(self.h)), 'ivx_create')
+        for key, t in model.state_dict().items():
+            if t.dtype.is_floating_point:
+                a = t.detach().to('cpu').float().contiguous()
+                self.ok(L.ivx_weights_load(self.h, key.encode(), C.c_void_p(a.data_ptr()), (C.c_int64 * max(a.dim(), 1))(*a.shape), a.dim()), key)
+        self.ok(L.ivx_weights_finalize(self.h, stream), 'ivx_weights_finalize')
+
+    def ok(self, rc, what):
+        if rc != 0:
+            raise RuntimeError(f'{what}: {self.L.ivx_last_error().decode()}')
+
+    def close(self):
+        if self.h:
+            self.L.ivx_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def total(self, what, B, V, H, W):
+        """Plan `what` through its workspace query; returns (bytes, plan key)."""
+        L, h = self.L, self.h
+        if what == 'forward':
+            n, key = L.ivx_model_workspace_bytes(h, B, V, H, W), (B, V, H, W)
+        elif what == 'detect':
+            n, key = L.ivx_model_detect_workspace_bytes(h, B, V, H, W), (B, V, H, W)
+        elif what == 'trunk':
+            n, key = L.ivx_backbone_fpn_workspace_bytes(h, B * V, H, W), (B * V, 1, H, W)
+        else:
+            n, key = L.ivx_neck3d_workspace_bytes(h, B), (B, 1, 0, 0)
+        if n < 0:
+            raise RuntimeError(f'{what} {(B, V, H, W)}: {L.ivx_last_error().decode()}')
+        return int(n), key
+
+    def plan(self, what, B, V, H, W):
+        from plan_check import read_plan
+        n, key = self.total(what, B, V, H, W)
+        return read_plan(self.L, self.h, what, *key), n
+
+
+def plans_of(family):
+    """The plans a family's entry points use (the LayoutHead predicts one camera: its handle runs through the detect entry point)."""
+    return ('forward', 'detect', 'trunk', 'neck')
+
+
+# ------------------------------------------------------------------------------------------------- job: plans
+def job_plans(args):
+    from plan_check import check_plan, PlanDefect
+    L = load_lib(args.lib)
+    out = {'plans': [], 'defects': []}
+    for fam in FAMILIES:
+        model = family_model(fam)
+        hd = Handle(L, model)
+        try:
+            B, V, H, W = (1, 1, 128, 224) if fam == 'sunrgbd_total' else (2, 2, 128, 224)
+            for what in plans_of(fam):
+                p, n = hd.plan(what, B, V, H, W)
+                try:
+                    st = check_plan(p, n)
+                except PlanDefect as e:
+                    out['defects'].append(f'{fam} {what} {(B, V, H, W)}: {e}')
+                    continue
+                out['plans'].append(dict(family=fam, what=what, **st))
+        finally:
+            hd.close()
+    print(json.dumps(out))
+
+
+# ------------------------------------------------------------------------------------------------- job: run
+def run_config(name):
+    """(family, n_voxels, small channels, B, V, (H, W), storage, trunk_operands, fp8) of a run configuration."""
+    return {
+        'kitti_small': ('kitti', (24, 28, 12), True, 2, 1, (128, 224), 0, IVX_F16_PAIR, False),
+        'kitti_small_f32': ('kitti', (24, 28, 12), True, 2, 1, (128, 224), 0, 0, False),
+        'nuscenes_dcn': ('nuscenes_dcn', (24, 24, 12), False, 1, 6, (96, 160), 0, IVX_F16_PAIR, False),
+        'scannet_v1_bf16': ('scannet_v1', (32, 32, 16), False, 1, 4, (96, 128), 1, IVX_F16_PAIR, False),
+        'scannet_v1_fp8': ('scannet_v1', (32, 32, 16), False, 1, 6, (96, 128), 1, IVX_F16_PAIR, True),
+        'scannet_fast': ('scannet_fast', (24, 24, 8), False, 1, 3, (96, 128), 0, IVX_F16_PAIR, False),
+        'kitti_full': ('kitti', None, False, 4, 1, (384, 1280), 0, IVX_F16_PAIR, False),
+    }[name]
+
+
+def metas_for(family, B, V, hw):
+    import numpy as np
+    import imvoxelnet_amd as ia
+    from imvoxelnet_amd import workloads as kc
+    H, W = hw
+    out = []
+    for b in range(B):
+        if family == 'kitti':
+            if hw == (384, 1280):
+                m = kc.kitti_meta(t=(0.02 * b, 0.01 * b, 0.0), box_type=ia.LiDARInstance3DBoxes)
+            else:                                       # the small volume (24 x 28 x 12 voxels in front of the camera) seen by a short lens
+                K = np.array([[36. * W / 160, 0, W / 2, 0], [0, 36. * W / 160, H / 2 - 10, 0], [0, 0, 1, 0], [0, 0, 0, 1]], np.float32)
+                E = np.array([[0, -1, 0, 0.03 * b], [0, 0, -1, 0.2], [1, 0, 0, 0.1], [0, 0, 0, 1]], np.float32)
+                m = dict(img_shape=(H, W, 3), ori_shape=(H // 2, W // 2, 3), box_type_3d=ia.LiDARInstance3DBoxes,
+                         lidar2img=dict(intrinsic=K, extrinsic=[E], origin=np.array([0.5 + 24 * .16, 0, -1.0], np.float32)))
+        elif family.startswith('nuscenes'):
+            m = kc.nuscenes_meta(img_hw=hw, box_type=ia.LiDARInstance3DBoxes)
+            m['lidar2img']['extrinsic'] = [np.ascontiguousarray(np.diag([H / 928.0, H / 928.0, 1, 1]).astype(np.float32) @ e) for e in m['lidar2img']['extrinsic']]
+        else:
+            m = kc.indoor_meta(V, img_hw=hw, origin=(0, 3, -1) if family.startswith('sunrgbd') else (0, 0, .5), box_type=ia.DepthInstance3DBoxes)
+            m['lidar2img']['intrinsic'] = m['lidar2img']['intrinsic'].copy()
+            m['lidar2img']['intrinsic'][:2] *= H / 480.0
+        out.append(m)
+    return out
+
+
+def detect_once(hd, img, metas, dev, ws_cache):
+    """One ivx_model_detect on device `dev` ('cpu' for the CPU restatement): {name: numpy array} of the plan's boundary tensors and detections."""
+    import numpy as np
+    import torch
+    from imvoxelnet_amd._lib import SampleMeta
+    from plan_check import read_plan
+    L, h = hd.L, hd.h
+    B, V, _, H, W = img.shape
+    sm, keep = (SampleMeta * B)(), []
+    for b, meta in enumerate(metas):
+        K = np.zeros((4, 4), np.float32)
+        Ki = np.asarray(meta['lidar2img']['intrinsic'], np.float32)
+        K[:Ki.shape[0], :Ki.shape[1]] = Ki
+        sm[b].intrinsic[:] = K.reshape(-1).tolist()
+        if not hd.cfg.layout_head:
+            E = np.zeros((V, 4, 4), np.float32)
+            for v, e in enumerate(meta['lidar2img']['extrinsic']):
+                e = np.asarray(e, np.float32)
+                E[v, :e.shape[0], :e.shape[1]] = e
+            keep.append(E)
+            sm[b].extrinsics = E.ctypes.data
+        sm[b].origin[:] = [float(v) for v in np.asarray(meta['lidar2img']['origin'], np.float32)]
+        sm[b].img_h, sm[b].img_w, sm[b].ori_h = int(meta['img_shape'][0]), int(meta['img_shape'][1]), int(meta['ori_shape'][0])
+    n, key = hd.total('detect', B, V, H, W)
+    M = L.ivx_model_max_detections(h, B, V, H, W)
+    assert M > 0, L.ivx_last_error()
+    if ws_cache.get('n') != n:
+        ws_cache['n'], ws_cache['raw'] = n, torch.zeros((n + 256,), dtype=torch.uint8, device=dev)
+        ws_cache['plan'] = read_plan(L, h, 'detect', *key)
+    raw = ws_cache['raw']
+    shift = -raw.data_ptr() % 256
+    ws = raw[shift:shift + n]
+    boxes, scores = torch.zeros((B, M, 7), device=dev), torch.zeros((B, M), device=dev)
+    labels, count = torch.zeros((B, M), dtype=torch.int64, device=dev), torch.zeros((B,), dtype=torch.int32, device=dev)
+    p = lambda t: C.c_void_p(t.data_ptr())      # noqa: E731
+    hd.ok(L.ivx_model_detect(h, p(img), B, V, H, W, C.cast(sm, C.c_void_p), p(ws), C.c_int64(n), p(boxes), p(scores), p(labels), p(count),
+                             None, None, None, hd.stream), 'ivx_model_detect')
+    if dev != 'cpu':
+        torch.cuda.synchronize()
+    out = {}
+    plan = ws_cache['plan']
+    for t, ti in plan['tensors'].items():
+        if ti['boundary'] and ti['off'] >= 0 and not ti['caller_owned'] and ti['first'] >= plan['info']['s0']:
+            out[f'tensor{t}'] = ws[ti['off']:ti['off'] + ti['used']].cpu().numpy().copy()
+    lift = [s for s in plan['steps'].values() if s['kind'] == 4][0]
+    out['fpn0'] = out[f"tensor{lift['in']}"].view(np.uint16 if hd.cfg.storage == 1 else np.float32)
+    cnt = count.cpu().numpy()
+    out['count'] = cnt
+    for b in range(B):
+        k = int(cnt[b])
+        out[f'boxes{b}'], out[f'scores{b}'], out[f'labels{b}'] = boxes[b, :k].cpu().numpy(), scores[b, :k].cpu().numpy(), labels[b, :k].cpu().numpy()
+    return out
+
+
+def job_run(args):
+    import numpy as np
+    import torch
+    L = load_lib(args.lib)
+    dev = 'cuda' if args.lib == 'hip' else 'cpu'
+    fam, nv, small, B, V, hw, storage, trunk, fp8 = run_config(args.config)
+    model = family_model(fam, n_voxels=nv, seed=3, small_channels=small)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream) if dev == 'cuda' else None
+    hd = Handle(L, model, storage=storage, trunk_operands=trunk, stream=stream)
+    imgs = [torch.randn(B, V, 3, *hw, generator=torch.Generator().manual_seed(11 + k)).to(dev).contiguous() for k in range(2)]
+    metas = metas_for(fam, B, V, hw)
+    if fp8:                                             # the 'conv3' variant: e4m3 conv3 of ResNet stages 3 and 4 (first_stage 2, conv2 stays bf16)
+        x = imgs[0].reshape(B * V, 3, *hw)
+        n = L.ivx_backbone_fpn_workspace_bytes(hd.h, B * V, *hw)
+        raw = torch.zeros((n + 256,), dtype=torch.uint8, device=dev)
+        ws = raw[-raw.data_ptr() % 256:]
+        hd.ok(L.ivx_model_calibrate_fp8_ex(hd.h, C.c_void_p(x.data_ptr()), B * V, hw[0], hw[1], C.c_float(1.0), 2, 1, C.c_void_p(ws.data_ptr()),
+                                           C.c_int64(n), stream), 'ivx_model_calibrate_fp8_ex')
+    arrays, cache = {}, {}
+    for level in [int(v) for v in args.phases.split(',')]:
+        hd.ok(L.ivx_model_trace(hd.h, level), 'ivx_model_trace')
+        for step in range(4):
+            for k, a in detect_once(hd, imgs[step % 2], metas, dev, cache).items():
+                arrays[f't{level}_s{step}_{k}'] = a
+    info = cache['plan']['info']
+    steps = cache['plan']['steps'].values()
+    arrays['n_sides'] = np.int64(info['n_sides'])
+    arrays['fuse'] = np.array(sorted({s['fuse'] for s in steps}), np.int64)
+    hd.close()
+    np.savez(args.out, **arrays)
+    print(json.dumps(dict(config=args.config, n_sides=int(info['n_sides']), arrays=len(arrays), total=info['total'])))
+
+
+def compare_runs(a, b, prefix_a, prefix_b=None):
+    """Every saved array of run `a` equals run `b` bit for bit, step for step, and inside each run step 3 repeats step 1 and step 4 step 2.
+    Returns the number of arrays per step."""
+    prefix_b = prefix_b or prefix_a
+    names = sorted(k[len(prefix_a) + 4:] for k in a.files if k.startswith(prefix_a + '_s0_'))
+    assert names and 'fpn0' in names and 'count' in names
+    for step in range(4):
+        for nm in names:
+            x, y = a[f'{prefix_a}_s{step}_{nm}'], b[f'{prefix_b}_s{step}_{nm}']
+            assert x.shape == y.shape and x.tobytes() == y.tobytes(), f'step {step + 1}: {nm} differs between the two runs'
+    for run, pre in ((a, prefix_a), (b, prefix_b)):
+        for step in (2, 3):
+            for nm in names:
+                assert run[f'{pre}_s{step}_{nm}'].tobytes() == run[f'{pre}_s{step - 2}_{nm}'].tobytes(), \
+                    f'{nm}: step {step + 1} does not repeat step {step - 1} (something is carried over between calls)'
+    assert any(a[f'{prefix_a}_s0_{nm}'].tobytes() != a[f'{prefix_a}_s1_{nm}'].tobytes() for nm in names), 'the two inputs give the same outputs'
+    return len(names)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('job', choices=['plans', 'run'])
+    ap.add_argument('--lib', choices=['cpu', 'hip'], default='cpu')
+    ap.add_argument('--config', default='kitti_small')
+    ap.add_argument('--phases', default='0', help='comma-separated trace levels; the four steps run once per level')
+    ap.add_argument('--out', default=None)
+    args = ap.parse_args()
+    {'plans': job_plans, 'run': job_run}[args.job](args)
+
+
+if __name__ == '__main__':
+    main()
