@@ -24,6 +24,7 @@ SOURCES = [
     ('pool_layout.hip', []),
     ('backproject.hip', ['-ffp-contract=off']),
     ('anchor_tail.hip', ['-ffp-contract=off']),
+    ('preprocess.hip', ['-ffp-contract=off']),
     ('dcn.hip', []),
     ('ubench.hip', []),
     ('api_common.cpp', []),

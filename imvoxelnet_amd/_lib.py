@@ -100,6 +100,12 @@ class PlanTensor(C.Structure):
                [(n, C.c_int32) for n in ('first', 'last', 'fmt', 'esz', 'caller_owned', 'boundary')]
 
 
+class ImagePrepDesc(C.Structure):
+    """ivx_image_prep_desc: uint8 HWC frames -> Resize -> Normalize -> Pad (ivx_image_prep_u8)."""
+    _fields_ = [(n, C.c_int32) for n in ('src_h', 'src_w', 'src_row_bytes', 'dst_h', 'dst_w', 'pad_h', 'pad_w', 'to_rgb')] + \
+               [('mean', C.c_float * 3), ('std', C.c_float * 3)]
+
+
 def declare_plan_view(L):
     """Argument types of the read-only plan view, on libimvoxel_hip.so or on the CPU restatement of the same ABI (tests)."""
     key = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -122,6 +128,7 @@ EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor'
            'ivx_model_trace', 'ivx_model_trace_count', 'ivx_model_trace_read',
            'ivx_model_detect_workspace_bytes', 'ivx_model_max_detections', 'ivx_model_detect', 'ivx_layout_head_decode', 'ivx_layout_extrinsics',
            'ivx_indoor_tail_workspace_bytes', 'ivx_indoor_tail_get_bboxes',
+           'ivx_rescale_size', 'ivx_image_prep_u8',
            'ivx_kitti_image_box_overlap', 'ivx_kitti_compute_statistics', 'ivx_kitti_collect_scores', 'ivx_kitti_fused_statistics']
 
 
@@ -199,6 +206,8 @@ def lib():
     L.ivx_dcn_im2col_fwd_pair.argtypes = [vp, vp, vp] + [i32] * 10 + [vp, vp, vp, vp]
     L.ivx_nchw_to_nhwc.argtypes = [vp, i32, i32, i64, i32, vp, vp]
     L.ivx_nhwc_to_nchw.argtypes = [vp, i32, i64, i32, vp, vp]
+    L.ivx_rescale_size.argtypes = [i32, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]
+    L.ivx_image_prep_u8.argtypes = [C.POINTER(ImagePrepDesc), vp, i64, i32, vp, vp]
     L.ivx_backproject_mean_fwd.argtypes = [vp, i32, i32, i32, i32, i32, vp, vp, vp, C.POINTER(f32), i32, i32, i32,
                                            vp, vp, vp]
     L.ivx_backproject_sum_fwd.argtypes = L.ivx_backproject_mean_fwd.argtypes

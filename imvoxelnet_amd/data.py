@@ -1,5 +1,6 @@
 """Input side of the path: checkpoint loading, the test-time image pipeline and the
-on-disk calibration -> `lidar2img` adapters.  Host-side numpy/torch; nothing here touches the kernels.
+on-disk calibration -> `lidar2img` adapters.  Host-side numpy/torch, except prepare_images_device, which runs the image pipeline
+of prepare_image on the device (ops.image_prep_u8) and is held to prepare_image bit for bit.
 
 Reference: configs/imvoxelnet/imvoxelnet_kitti.py:66,94-105 (Resize keep_ratio -> Normalize -> Pad(size_divisor=32)),
 mmdet3d/datasets/{kitti,nuscenes,scannet,sunrgbd}_monocular_dataset.py (lidar2img), pipelines/multi_view.py:45-53
@@ -126,6 +127,81 @@ def prepare_image(img_bgr_u8, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor
     pw = (nw + size_divisor - 1) // size_divisor * size_divisor
     img = F.pad(img, (0, pw - nw, 0, ph - nh))
     return img[0], dict(img_shape=(nh, nw, 3), ori_shape=ori_shape, pad_shape=(ph, pw, 3))
+
+
+def _pipeline_shapes(ori_hw, img_scale, size_divisor, keep_ratio):
+    """(resized (h, w), own padded (h, w)) of one frame, as prepare_image computes them."""
+    if keep_ratio:
+        nh, nw = rescale_size(ori_hw, img_scale)
+    else:
+        nw, nh = img_scale
+    return (nh, nw), ((nh + size_divisor - 1) // size_divisor * size_divisor, (nw + size_divisor - 1) // size_divisor * size_divisor)
+
+
+def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor=32, keep_ratio=True, device='cuda'):
+    """prepare_image for a whole batch on the device (ops.image_prep_u8, csrc/preprocess.hip): the uint8 frames cross to the
+    device as they are (a quarter of the bytes of the fp32 tensor) and ONE launch per group of same-sized frames resizes, normalises
+    and pads them -- bit-identical to prepare_image per frame.
+    frames: a list of (H,W,3) uint8 BGR arrays / tensors; one [N,H,W,3] uint8 array or tensor (host or device); or a list of B
+    lists of V frames (multi-view samples).  Frames are grouped by source shape; a group of host frames is stacked and copied in one
+    host-to-device copy, device tensors are used where they are.  Every group is written into its slices of one output tensor
+    whose plane is the LARGEST pad shape of the batch (zero filled below / right of each image, what mmdet's collate does); a
+    group whose frames are not adjacent in the batch takes one launch per run of adjacent frames.
+    Returns (img [N,3,Hp,Wp] or [B,V,3,Hp,Wp] fp32 on `device`, list of per-sample dicts img_shape / ori_shape / pad_shape equal to
+    prepare_image's; for a multi-view sample the dict of its LAST view, as MultiViewPipeline)."""
+    from . import ops
+    device = torch.device(device)
+    views = None
+    if isinstance(frames, (np.ndarray, torch.Tensor)):
+        if frames.ndim != 4:
+            raise TypeError(f'a stacked batch must be [N,H,W,3] uint8, got {tuple(frames.shape)}')
+        flat = list(frames)
+        stacked = frames
+    else:
+        frames, stacked = list(frames), None
+        if frames and isinstance(frames[0], (list, tuple)):
+            views = len(frames[0])
+            if any(len(s) != views for s in frames) or views == 0:
+                raise ValueError('every multi-view sample must hold the same number of views')
+            flat = [f for s in frames for f in s]
+        else:
+            flat = frames
+    if not flat:
+        raise ValueError('no frames')
+    for f in flat:
+        if f.ndim != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
+            raise TypeError(f'frames must be (H,W,3) uint8, got {tuple(f.shape)} {f.dtype}')
+    groups = {}                                                  # source (h, w) -> indices, in batch order
+    for i, f in enumerate(flat):
+        groups.setdefault((int(f.shape[0]), int(f.shape[1])), []).append(i)
+    shapes = {hw: _pipeline_shapes(hw, img_scale, size_divisor, keep_ratio) for hw in groups}
+    Hp, Wp = max(s[1][0] for s in shapes.values()), max(s[1][1] for s in shapes.values())
+    out = torch.empty((len(flat), 3, Hp, Wp), device=device, dtype=torch.float32)
+    mean, std, to_rgb = img_norm_cfg['mean'], img_norm_cfg['std'], img_norm_cfg.get('to_rgb', True)
+    for hw, idx in groups.items():
+        if stacked is not None:                                  # one group by construction
+            src = torch.from_numpy(np.ascontiguousarray(stacked)) if isinstance(stacked, np.ndarray) else stacked
+        elif all(isinstance(flat[i], np.ndarray) for i in idx):
+            src = torch.from_numpy(np.stack([flat[i] for i in idx]))
+        else:
+            fs = [torch.from_numpy(flat[i]) if isinstance(flat[i], np.ndarray) else flat[i] for i in idx]
+            src = torch.stack([f.to(device) for f in fs] if any(f.is_cuda for f in fs) else fs)
+        src = src.to(device)                                     # the one host-to-device copy of the group (no-op for device tensors)
+        a = 0
+        while a < len(idx):                                      # runs of adjacent frames: one launch each (one per group when sorted)
+            b = a + 1
+            while b < len(idx) and idx[b] == idx[b - 1] + 1:
+                b += 1
+            ops.image_prep_u8(src[a:b], shapes[hw][0], (Hp, Wp), mean, std, to_rgb, out=out[idx[a]:idx[a] + b - a])
+            a = b
+    metas = []
+    for f in flat:
+        hw = (int(f.shape[0]), int(f.shape[1]))
+        (nh, nw), (ph, pw) = shapes[hw]
+        metas.append(dict(img_shape=(nh, nw, 3), ori_shape=(hw[0], hw[1], 3), pad_shape=(ph, pw, 3)))
+    if views is not None:
+        return out.view(len(flat) // views, views, 3, Hp, Wp), metas[views - 1::views]
+    return out, metas
 
 
 # ------------------------------------------------------------------ multi-view pipeline

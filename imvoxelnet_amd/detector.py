@@ -326,6 +326,19 @@ class ImVoxelNet(nn.Module):
                 results[i]['layout'] = layouts[i]
         return results
 
+    def simple_test_u8(self, frames, img_metas, img_scale, **pipeline_kw):
+        """simple_test from uint8 camera frames: the test pipeline (Resize -> Normalize -> Pad) runs on the device
+        (data.prepare_images_device: a list of N frames -- one single-view sample each --, one [N,H,W,3] batch, or B lists of V
+        views) and fills img_shape / ori_shape / pad_shape into a copy of every meta; the caller supplies lidar2img (and box_type_3d)
+        as for simple_test.  pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device of prepare_images_device."""
+        from .data import prepare_images_device
+        img, shapes = prepare_images_device(frames, img_scale, **pipeline_kw)
+        if len(shapes) != len(img_metas):
+            raise ValueError(f'{len(img_metas)} img_metas for {len(shapes)} samples')
+        if img.dim() == 4:
+            img = img.unsqueeze(1)
+        return self.simple_test(img, [dict(m, **s) for m, s in zip(img_metas, shapes)])
+
     @staticmethod
     def _results_one_copy(boxes, scores, labels, count, img_metas, with_yaw=True, indoor=False):
         """bbox3d2result (core/bbox/transforms.py:49-67) for the fixed-size padded device tensors of the anchor tail: ONE

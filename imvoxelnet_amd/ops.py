@@ -50,6 +50,36 @@ def image_s2d_bf16(img):
     return out
 
 
+def image_prep_u8(src, size_hw, pad_hw, mean, std, to_rgb=True, out=None):
+    """uint8 frames [n,H,W,3] (HWC, BGR as a decoder leaves them) -> Resize to size_hw -> Normalize -> zero Pad to pad_hw:
+    [n,3,pad_h,pad_w] fp32 in one launch (ivx_image_prep_u8), bit-identical to data.prepare_image per frame.  The pixels of a row
+    must be dense (strides (.., 3, 1)); a row stride above 3 * W (a decoder pitch) and any frame stride are passed through.
+    mean / std in output-channel order; out: a contiguous fp32 [n,3,pad_h,pad_w] view to write into (a slice of a batch tensor)."""
+    if not isinstance(src, torch.Tensor):
+        raise TypeError('src must be a torch.Tensor')
+    if not src.is_cuda:
+        raise RuntimeError('src must be a device (HIP) tensor; the MI355X path has no CPU fallback')
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise TypeError(f'src must be uint8 [n,H,W,3], got {src.dtype} {tuple(src.shape)}')
+    n, H, W, _ = src.shape
+    if n < 1:
+        raise ValueError('src holds no frame')
+    row = src.stride(1) if H > 1 else 3 * W                  # (the stride of an extent-1 axis is arbitrary)
+    if src.stride(3) != 1 or (W > 1 and src.stride(2) != 3) or row < 3 * W or (n > 1 and src.stride(0) < H * row):
+        raise ValueError(f'src rows must be dense HWC (strides (>= H * row, >= 3 * W, 3, 1)), got {tuple(src.stride())}')
+    (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
+    if out is None:
+        out = torch.empty((n, 3, ph, pw), device=src.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != (n, 3, ph, pw) or out.device != src.device:
+            raise ValueError(f'out must be [{n},3,{ph},{pw}] on {src.device}, got {tuple(out.shape)} on {out.device}')
+    d = _lib.ImagePrepDesc(H, W, row, nh, nw, ph, pw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
+                           (C.c_float * 3)(*[float(v) for v in std]))
+    check(_lib.lib().ivx_image_prep_u8(C.byref(d), _ptr(src), src.stride(0), n, _ptr(out), _stream()), 'ivx_image_prep_u8')
+    return out
+
+
 def to_channels_last(x, pad_to=None):
     """[B,C,*spatial] (reference layout) -> [B,D,H,W,Cpad] channels-last (D=1 for 2-D input)."""
     _chk(x, 'x')

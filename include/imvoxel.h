@@ -38,7 +38,7 @@ extern "C" {
 typedef void *ivx_stream_t; /* hipStream_t */
 
 /* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header; 420 = 0.4.2: bf16 storage with
- * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16) and the message of the last failing call on
+ * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size) and the message of the last failing call on
  * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -355,6 +355,43 @@ int ivx_nchw_to_nhwc(const float *in, int32_t B, int32_t C, int64_t S, int32_t C
  * (mmdet ResNet.conv1) becomes a 4x4 stride-1 pad-1 convolution over it (weights re-indexed kh = 2*th + a, kw = 2*tw + e). */
 int ivx_image_s2d_bf16(const float *img, int32_t B, int32_t H, int32_t W, void *out, ivx_stream_t stream);
 int ivx_nhwc_to_nchw(const float *in, int32_t B, int64_t S, int32_t C, float *out, ivx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Device-side image pipeline (0.4.3) -- the Resize(keep_ratio) -> Normalize -> Pad(32) steps of the reference test pipelines
+ * (configs/imvoxelnet/imvoxelnet_kitti.py:94-105) from uint8 HWC BGR frames to the fp32 NCHW input of the model, in one launch
+ * (csrc/preprocess.hip).  The result is bit-identical to data.prepare_image of the Python package, zero pad region included:
+ *   resize     the integer restatement of cv2.resize(INTER_LINEAR) on uint8 held by data.imresize_cv2_linear / data._linear_tables:
+ *              fx = float32((d + 0.5) * (double(src) / double(dst)) - 0.5) with the product and the difference in double, floor, both
+ *              borders clamped, 11-bit weights rounded half to even; int32 horizontal pass S[sx] * a0 + S[sx1] * a1; vertical pass
+ *              (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2, clamped to 0..255.  dst == src is a copy; src == 2 * dst on
+ *              BOTH axes takes the INTER_AREA shortcut (a + b + c + d + 2) >> 2.  Up-scaling goes through the same formulas.
+ *              Parity with cv2 ITSELF is UNPINNED: the restatement is checked against hand-derived vectors, not against OpenCV.
+ *   normalise  optional swap of channels 0 and 2 (BGR -> RGB), then (float(v) - mean[c]) / std[c] in fp32 with an IEEE divide;
+ *              mean / std in OUTPUT-channel order (IMG_NORM_CFG).
+ *   pad        out is [n, 3, pad_h, pad_w]; y >= dst_h or x >= dst_w is written as +0.0f by the same launch (no memset needed).  pad_h /
+ *              pad_w may exceed the image's own padded size (the common plane of a batch of mixed sizes).
+ * Limits: every extent (src, dst, pad) <= IVX_IMAGE_PREP_MAX_DIM, n <= 2^20.  Any pad_w and any 4-byte aligned `out` are accepted: the
+ * 16-byte store path needs pad_w % 4 == 0 and a 16-byte aligned out, everything else takes scalar stores (same bits). */
+#define IVX_IMAGE_PREP_MAX_DIM 32768
+typedef struct ivx_image_prep_desc {
+  int32_t src_h, src_w;      /* source frame, HWC uint8, 3 channels */
+  int32_t src_row_bytes;     /* >= 3 * src_w (decoder pitch) */
+  int32_t dst_h, dst_w;      /* resized size = img_shape */
+  int32_t pad_h, pad_w;      /* output plane = pad_shape, >= dst */
+  int32_t to_rgb;            /* swap channels 0 and 2 before normalising */
+  float mean[3], std[3];     /* output-channel order */
+} ivx_image_prep_desc;
+
+/* mmcv.rescale_size for a (long, short) scale: the Resize(keep_ratio=True) size. Host only.  Equals data.rescale_size: double
+ * arithmetic, f = min(max_long / max(h, w), max_short / min(h, w)), size = int(h * f + 0.5); the two scale values in either order. */
+int ivx_rescale_size(int32_t src_h, int32_t src_w, int32_t scale_a, int32_t scale_b,
+                     int32_t *dst_h, int32_t *dst_w);
+
+/* n frames of one geometry, src + i * src_image_bytes; out [n,3,pad_h,pad_w] fp32; caller-owned buffers, no sync.
+ * IVX_ERR_INVALID_ARG (before any launch): null pointers, non-positive sizes, pad < dst, src_row_bytes < 3 * src_w, a std entry that is
+ * zero or not finite, n <= 0, src_image_bytes < src_h * src_row_bytes with n > 1, an extent or n above the limits. */
+int ivx_image_prep_u8(const ivx_image_prep_desc *d, const void *src, int64_t src_image_bytes,
+                      int32_t n, float *out, ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused image-to-voxel unprojection -- replaces the per-sample Python loop
