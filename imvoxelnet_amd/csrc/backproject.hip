@@ -32,8 +32,10 @@ struct BpParams {
   const float *new_origin;  // [B, 3]
   const int *crop_hw;       // [B, 2]
   float *volume;            // [B, N, C]
-  uint8_t *valid;           // [B, N]
-  int *count;               // [B, N]  (sum mode: number of views that saw the voxel)
+  uint8_t *valid;           // [B, N]  (accumulate mode: written with mean_out, may be NULL)
+  int *count;               // [B, N]  (sum / accumulate mode: number of views that saw the voxel)
+  void *mean_out;           // accumulate mode: [B, N, C] in the feature type, the mean of the running sum, or NULL
+  int first;                // accumulate mode: != 0 starts the running (sum, count) from zero without reading them
   float vs0, vs1, vs2;
   int V, FH, FW, C;
   int X, Y, Z;
@@ -44,13 +46,20 @@ struct BpParams {
   int nblk, q;  // multi-view kernel: voxel blocks per sample and per XCD (grid.x = 8 * q, see the kernel's block order); q = 0: plain order (A/B)
 };
 
-// MEAN = true: the reference's view mean + valid mask.  MEAN = false (view-sharded multi-GPU mode): the raw sum over
+// MODE BP_MEAN: the reference's view mean + valid mask.  BP_SUM (view-sharded multi-GPU mode): the raw sum over
 // this rank's views and the per-voxel view count, to be all-reduced and normalised by volume_normalize_kernel.
+// BP_ACCUM (streaming scenes): the accumulator and the counter of a voxel start from the stored fp32 sum / count (from zero with
+// p.first, the state is then not read), this call's views are added in view order, and the new sum / count are stored back; with
+// p.mean_out the same pass also stores the mean (type T) and the valid mask.  The additions are the same __fadd_rn chain in the same
+// order as one BP_MEAN launch over all the views, so views that arrive in order give that launch's bits however they are chunked.
+// One lane group owns a voxel in every mode: no atomics.  VEC 4 only for BP_SUM / BP_ACCUM.
 // T = float (the reference's precision) or __bf16 (optional storage mode: features / volume stored as bf16, the view sum
 // and the division in fp32, one rounding at the store; VEC 4 only).
-template <int VEC, bool MEAN = true, typename T = float>
+enum { BP_SUM = 0, BP_MEAN = 1, BP_ACCUM = 2 };
+template <int VEC, int MODE = BP_MEAN, typename T = float>
 __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p) {
   typedef T tv4 __attribute__((ext_vector_type(4)));
+  constexpr bool MEAN = MODE == BP_MEAN;
   const int b = blockIdx.y;
   const int lpv = 1 << p.lpv_log2;
   const int lane = threadIdx.x & 63;
@@ -88,6 +97,21 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
   int cnt = 0;
+  if constexpr (MODE == BP_ACCUM) {
+    if (active && !p.first) {              // the running state of this voxel (16-byte loads, coalesced as the stores below)
+      const float *run = p.volume + ((size_t)b * p.N + n) * p.C;
+#pragma unroll
+      for (int q = 0; q < MAXCH; ++q) {
+        const int ch = g + q * lpv;
+        if (ch < p.nchunk) {
+          const f32x4 x = *reinterpret_cast<const f32x4 *>(run + ch * 4);
+#pragma unroll
+          for (int e = 0; e < VEC; ++e) acc[q][e] = x[e];
+        }
+      }
+      cnt = p.count[(size_t)b * p.N + n];
+    }
+  }
 
   for (int v0 = 0; v0 < p.V; v0 += lpv) {
     // lane g projects view v0 + g
@@ -138,6 +162,30 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
 
   if (!active) return;
   const float dn = (float)cnt;
+  if constexpr (MODE == BP_ACCUM) {
+    float *run = p.volume + ((size_t)b * p.N + n) * p.C;
+    T *mean = p.mean_out ? reinterpret_cast<T *>(p.mean_out) + ((size_t)b * p.N + n) * p.C : nullptr;
+#pragma unroll
+    for (int q = 0; q < MAXCH; ++q) {
+      const int ch = g + q * lpv;
+      if (ch < p.nchunk) {
+        f32x4 s;
+        tv4 y;
+#pragma unroll
+        for (int e = 0; e < VEC; ++e) {
+          s[e] = acc[q][e];
+          y[e] = (T)(cnt ? __fdiv_rn(acc[q][e], dn) : 0.f);
+        }
+        *reinterpret_cast<f32x4 *>(run + ch * 4) = s;
+        if (mean) *reinterpret_cast<tv4 *>(mean + ch * 4) = y;
+      }
+    }
+    if (g == 0) {
+      p.count[(size_t)b * p.N + n] = cnt;
+      if (mean) p.valid[(size_t)b * p.N + n] = cnt > 0 ? 1 : 0;
+    }
+    return;
+  }
   T *dst = reinterpret_cast<T *>(p.volume) + ((size_t)b * p.N + n) * p.C;
 #pragma unroll
   for (int q = 0; q < MAXCH; ++q) {
@@ -161,17 +209,21 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
   }
 }
 
-// volume[b,n,:] = count ? sum / count : 0 (in place), valid = count > 0 (detectors/imvoxelnet.py:70-74 after the
-// all-reduce of the per-rank partial sums).  One float4 per thread.
-__global__ __launch_bounds__(256) void volume_normalize_kernel(float *volume, const int *count, uint8_t *valid, long long total4, int C4) {
+// out[b,n,:] = count ? sum / count : 0, valid = count > 0 (detectors/imvoxelnet.py:70-74 after the all-reduce of the
+// per-rank partial sums, or on the running sums of a streaming scene).  out == sum: in place (ivx_volume_normalize_fwd); otherwise
+// the sums stay intact and T may be __bf16 (one rounding at the store).  One float4 of sums per thread.
+template <typename T>
+__global__ __launch_bounds__(256) void volume_normalize_kernel(const float *sum, T *out, const int *count, uint8_t *valid, long long total4, int C4) {
+  typedef T tv4 __attribute__((ext_vector_type(4)));
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
     const long long vox = i / C4;
     const int cnt = count[vox];
-    f32x4 x = *reinterpret_cast<f32x4 *>(volume + i * 4);
+    const f32x4 x = *reinterpret_cast<const f32x4 *>(sum + i * 4);
     const float dn = (float)cnt;
+    tv4 y;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) x[e] = cnt ? __fdiv_rn(x[e], dn) : 0.f;
-    *reinterpret_cast<f32x4 *>(volume + i * 4) = x;
+    for (int e = 0; e < 4; ++e) y[e] = (T)(cnt ? __fdiv_rn(x[e], dn) : 0.f);
+    *reinterpret_cast<tv4 *>(out + i * 4) = y;
     if (i % C4 == 0) valid[vox] = cnt > 0 ? 1 : 0;
   }
 }
@@ -269,7 +321,7 @@ static int backproject_launch(const float *feat, int32_t B, int32_t V, int32_t F
   IVX_REQUIRE(B <= 65535, "ivx_backproject_mean_fwd: batch too large");
   BpParams p;
   p.feat = feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = volume; p.valid = valid;
-  p.count = count;
+  p.count = count; p.mean_out = nullptr; p.first = 0;
   p.pmax = (mean && V == 1) ? partials : nullptr;
   p.nblk = 0; p.q = 0;
   p.vs0 = voxel_size[0]; p.vs1 = voxel_size[1]; p.vs2 = voxel_size[2];
@@ -284,7 +336,7 @@ static int backproject_launch(const float *feat, int32_t B, int32_t V, int32_t F
     IVX_REQUIRE(vec == 4, "ivx_backproject_sum_fwd: C %% 4 must be 0");
     const int vpb = 256 >> lg;
     p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-    hipLaunchKernelGGL((backproject_mean_kernel<4, false>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
+    hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
     IVX_CHECK_LAUNCH("ivx_backproject_sum_fwd");
     return IVX_OK;
   }
@@ -347,9 +399,72 @@ extern "C" int ivx_volume_normalize_fwd(float *volume, const int32_t *count, int
   const long long total4 = (long long)n_voxels * (C / 4);
   long long blocks = (total4 + 255) / 256;
   if (blocks > 256 * 64) blocks = 256 * 64;
-  hipLaunchKernelGGL(volume_normalize_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume, count, valid, total4, C / 4);
+  hipLaunchKernelGGL(volume_normalize_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume, volume, count, valid, total4, C / 4);
   IVX_CHECK_LAUNCH("ivx_volume_normalize_fwd");
   return IVX_OK;
+}
+
+// Out-of-place ivx_volume_normalize_fwd: the mean of a running (sum, count) volume in fp32 or bf16; the sums are left intact.
+extern "C" int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype,
+                                   uint8_t *valid, ivx_stream_t stream) {
+  IVX_REQUIRE(volume_sum && count && out && valid, "ivx_volume_mean_fwd: null argument");
+  IVX_REQUIRE((const void *)volume_sum != out, "ivx_volume_mean_fwd: out must not be volume_sum (ivx_volume_normalize_fwd works in place)");
+  IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "ivx_volume_mean_fwd: bad dims (C %% 4 must be 0)");
+  IVX_REQUIRE(out_dtype == IVX_F32 || out_dtype == IVX_BF16, "ivx_volume_mean_fwd: out_dtype must be IVX_F32 or IVX_BF16");
+  const long long total4 = (long long)n_voxels * (C / 4);
+  long long blocks = (total4 + 255) / 256;
+  if (blocks > 256 * 64) blocks = 256 * 64;
+  if (out_dtype == IVX_BF16)
+    hipLaunchKernelGGL(volume_normalize_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (__bf16 *)out, count, valid, total4, C / 4);
+  else
+    hipLaunchKernelGGL(volume_normalize_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (float *)out, count, valid, total4, C / 4);
+  IVX_CHECK_LAUNCH("ivx_volume_mean_fwd");
+  return IVX_OK;
+}
+
+// Streaming scenes: add V views to a running (sum, count) volume (BP_ACCUM mode of backproject_mean_kernel).
+template <typename T>
+static int backproject_accum_launch(const char *what, const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
+                                    const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y, int32_t Z,
+                                    float *volume_sum, int32_t *count, int32_t first, void *mean_out, uint8_t *valid_out, ivx_stream_t stream) {
+  IVX_REQUIRE(feat && proj && new_origin && crop_hw && voxel_size && volume_sum && count, "%s: null argument", what);
+  IVX_REQUIRE((mean_out != nullptr) == (valid_out != nullptr), "%s: mean_out and valid_out must both be given or both be NULL", what);
+  IVX_REQUIRE(B > 0 && V > 0 && FH > 0 && FW > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "%s: non-positive dims", what);
+  IVX_REQUIRE(C % 4 == 0, "%s: C %% 4 must be 0", what);
+  IVX_REQUIRE((int64_t)X * Y * Z < (1LL << 31), "%s: voxel grid too large", what);
+  IVX_REQUIRE((int64_t)B * V * FH * FW < (1LL << 31), "%s: feature maps too large", what);
+  IVX_REQUIRE(B <= 65535, "%s: batch too large", what);
+  BpParams p;
+  p.feat = (const float *)feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = volume_sum; p.valid = valid_out;
+  p.count = count; p.mean_out = mean_out; p.first = first; p.pmax = nullptr;
+  p.vs0 = voxel_size[0]; p.vs1 = voxel_size[1]; p.vs2 = voxel_size[2];
+  p.V = V; p.FH = FH; p.FW = FW; p.C = C; p.X = X; p.Y = Y; p.Z = Z; p.N = X * Y * Z;
+  p.nchunk = C / 4;
+  IVX_REQUIRE(p.nchunk <= 64 * 4, "%s: C=%d too large (max 1024)", what, C);
+  int lg = 0;
+  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
+  p.lpv_log2 = lg;
+  const int vpb = 256 >> lg;
+  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
+  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, T>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
+  IVX_CHECK_LAUNCH(what);
+  return IVX_OK;
+}
+
+extern "C" int ivx_backproject_accum_fwd(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
+                                         const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y,
+                                         int32_t Z, float *volume_sum, int32_t *count, int32_t first, float *mean_out, uint8_t *valid_out,
+                                         ivx_stream_t stream) {
+  return backproject_accum_launch<float>("ivx_backproject_accum_fwd", feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z, volume_sum,
+                                         count, first, mean_out, valid_out, stream);
+}
+
+extern "C" int ivx_backproject_accum_fwd_bf16(const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
+                                              const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y,
+                                              int32_t Z, float *volume_sum, int32_t *count, int32_t first, void *mean_out, uint8_t *valid_out,
+                                              ivx_stream_t stream) {
+  return backproject_accum_launch<__bf16>("ivx_backproject_accum_fwd_bf16", feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z,
+                                          volume_sum, count, first, mean_out, valid_out, stream);
 }
 
 // bf16 storage (optional reduced-precision mode): feat / volume are bf16, everything else as ivx_backproject_mean_fwd.
@@ -364,7 +479,7 @@ extern "C" int ivx_backproject_mean_fwd_bf16(const void *feat, int32_t B, int32_
   IVX_REQUIRE((int64_t)X * Y * Z < (1LL << 31) && (int64_t)B * V * FH * FW < (1LL << 31) && B <= 65535, "ivx_backproject_mean_fwd_bf16: problem too large");
   BpParams p;
   p.feat = (const float *)feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = (float *)volume; p.valid = valid;
-  p.count = nullptr; p.pmax = nullptr;
+  p.count = nullptr; p.pmax = nullptr; p.mean_out = nullptr; p.first = 0;
   p.vs0 = voxel_size[0]; p.vs1 = voxel_size[1]; p.vs2 = voxel_size[2];
   p.V = V; p.FH = FH; p.FW = FW; p.C = C; p.X = X; p.Y = Y; p.Z = Z; p.N = X * Y * Z;
   p.nchunk = C / 4;
@@ -374,7 +489,7 @@ extern "C" int ivx_backproject_mean_fwd_bf16(const void *feat, int32_t B, int32_
   p.lpv_log2 = lg;
   const int vpb = 256 >> lg;
   p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-  hipLaunchKernelGGL((backproject_mean_kernel<4, true, __bf16>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
+  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
   IVX_CHECK_LAUNCH("ivx_backproject_mean_fwd_bf16");
   return IVX_OK;
 }

@@ -339,6 +339,13 @@ class ImVoxelNet(nn.Module):
             img = img.unsqueeze(1)
         return self.simple_test(img, [dict(m, **s) for m, s in zip(img_metas, shapes)])
 
+    def open_scene(self, meta):
+        """A streaming scene on this model (scene.SceneSession): add_views / add_views_u8 fold new views into a running volume,
+        detect() works on the views so far.  meta: one img_metas entry without lidar2img['extrinsic'].  Several sessions may be open
+        on one prepared model."""
+        from .scene import SceneSession
+        return SceneSession(self, meta)
+
     @staticmethod
     def _results_one_copy(boxes, scores, labels, count, img_metas, with_yaw=True, indoor=False):
         """bbox3d2result (core/bbox/transforms.py:49-67) for the fixed-size padded device tensors of the anchor tail: ONE

@@ -850,6 +850,72 @@ def volume_normalize_(vol_sum, count):
     return vol_sum, valid.view(torch.bool)
 
 
+def _chk_mask(t, name, shape):
+    if t.dtype not in (torch.uint8, torch.bool):
+        raise TypeError(f'{name} must be uint8 or bool, got {t.dtype}')
+    _chk(t, name, t.dtype)
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f'{name} must have the spatial shape of the volume')
+    return t
+
+
+def backproject_accum_(feat, proj, new_origin, crop_hw, voxel_size, vol_sum, count, first, mean_out=None, valid_out=None):
+    """Streaming scenes: add the V views of `feat` ([B*V,1,FH,FW,C] fp32 or bf16) to the running state vol_sum [B,X,Y,Z,C] fp32 /
+    count [B,X,Y,Z] int32, in place and in view order (ivx_backproject_accum_fwd: after the last chunk the state holds what ONE
+    backproject_mean over all the views computes, bit for bit).  first: start the state from zero without reading it.
+    mean_out [B,X,Y,Z,C] (feat's dtype) + valid_out [B,X,Y,Z] uint8 / bool: the same pass also writes the mean and the mask; both or
+    neither.  Returns (vol_sum, count)."""
+    if feat.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'feat must be float32 or bfloat16, got {feat.dtype}')
+    if (mean_out is None) != (valid_out is None):
+        raise ValueError('mean_out and valid_out must both be given or both be None')
+    _chk(feat, 'feat', feat.dtype)
+    _chk(proj, 'proj')
+    _chk(new_origin, 'new_origin')
+    _chk(crop_hw, 'crop_hw', torch.int32)
+    _chk(vol_sum, 'vol_sum')
+    _chk(count, 'count', torch.int32)
+    B, V = proj.shape[0], proj.shape[1]
+    BV, D, FH, FW, Cn = feat.shape
+    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
+        raise ValueError('feat / proj shapes do not agree')
+    if vol_sum.dim() != 5 or vol_sum.shape[0] != B or vol_sum.shape[-1] != Cn or tuple(count.shape) != tuple(vol_sum.shape[:-1]):
+        raise ValueError('vol_sum must be [B,X,Y,Z,C] and count [B,X,Y,Z] for the features\' B and C')
+    if mean_out is not None:
+        _chk(mean_out, 'mean_out', feat.dtype)
+        if tuple(mean_out.shape) != tuple(vol_sum.shape):
+            raise ValueError('mean_out must have the shape of vol_sum')
+        _chk_mask(valid_out, 'valid_out', count.shape)
+    X, Y, Z = (int(v) for v in vol_sum.shape[1:4])
+    vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
+    name = 'ivx_backproject_accum_fwd_bf16' if feat.dtype == torch.bfloat16 else 'ivx_backproject_accum_fwd'
+    check(getattr(_lib.lib(), name)(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw), vs, X, Y, Z, _ptr(vol_sum),
+                                    _ptr(count), int(bool(first)), _ptr(mean_out), _ptr(valid_out), _stream()), name)
+    return vol_sum, count
+
+
+def volume_mean(vol_sum, count, dtype=torch.float32, out=None, valid_out=None):
+    """Out of place: mean = count ? vol_sum / count : 0 in `dtype` (float32 or bfloat16), valid = count > 0; vol_sum and count stay
+    as they are.  out / valid_out: buffers to write into (allocated when None).  Returns (mean, valid bool [B,X,Y,Z])."""
+    _chk(vol_sum, 'vol_sum')
+    _chk(count, 'count', torch.int32)
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'dtype must be float32 or bfloat16, got {dtype}')
+    if tuple(count.shape) != tuple(vol_sum.shape[:-1]):
+        raise ValueError('count must have the spatial shape of the volume')
+    if out is None:
+        out = torch.empty(vol_sum.shape, device=vol_sum.device, dtype=dtype)
+    elif tuple(_chk(out, 'out', dtype).shape) != tuple(vol_sum.shape):
+        raise ValueError('out must have the shape of vol_sum')
+    if valid_out is None:
+        valid_out = torch.empty(count.shape, device=vol_sum.device, dtype=torch.uint8)
+    else:
+        _chk_mask(valid_out, 'valid_out', count.shape)
+    check(_lib.lib().ivx_volume_mean_fwd(_ptr(vol_sum), _ptr(count), count.numel(), vol_sum.shape[-1], _ptr(out), _DT[dtype], _ptr(valid_out),
+                                         _stream()), 'ivx_volume_mean_fwd')
+    return out, valid_out.view(torch.bool)
+
+
 # ------------------------------------------------------------------ detection tail
 def anchor_head_get_bboxes(head_out, anchors, H, W, num_anchors, num_classes, offs, cfg, dir_offset=0.0,
                            dir_limit_offset=1.0, hw_transposed=False, want_candidates=False):

@@ -442,6 +442,37 @@ int ivx_backproject_sum_fwd(const float *feat, int32_t B, int32_t V, int32_t FH,
 int ivx_volume_normalize_fwd(float *volume, const int32_t *count, int64_t n_voxels, int32_t C, uint8_t *valid,
                              ivx_stream_t stream);
 
+/* Streaming scenes: the views of a scene arrive one after another and are folded into a running volume.
+ * ivx_backproject_accum_fwd adds the V views of this call to a caller-owned state and, optionally, emits the mean in the same
+ * pass.  Geometry and arithmetic are ivx_backproject_mean_fwd's (same kernel template).  C % 4 == 0, C <= 1024.
+ *
+ * feat        [B*V, FH, FW, C]      features of the NEW views only (fp32; bf16 for the _bf16 form)
+ * proj        [B, V, 3, 4]          their projection rows; new_origin [B,3], crop_hw [B,2], voxel_size as above
+ * volume_sum  [B, X, Y, Z, C] fp32  in/out: running sum over the valid views (fp32 in both forms)
+ * count       [B, X, Y, Z] int32    in/out: number of views that saw the voxel so far
+ * first       != 0: the state starts from 0.f / 0 and is NOT read (no memset needed, uninitialised memory is never read);
+ *             0: the accumulators start from the stored sum / count
+ * mean_out    [B, X, Y, Z, C] or NULL  count ? sum / count : 0 after this call (fp32; bf16 with one rounding at the store for
+ *             the _bf16 form); valid_out [B, X, Y, Z] u8 or NULL: count > 0.  Both given or both NULL; with NULL neither is written.
+ * Ordering guarantee: a voxel's views are added strictly in view order with round-to-nearest fp32 additions, continuing the stored
+ * sum.  Views that arrive in the same order therefore give, after the last call, bit for bit the volume and mask of ONE
+ * ivx_backproject_mean_fwd over all of them, whatever the chunking.  One lane group owns a voxel: no atomics, reproducible.
+ * IVX_ERR_INVALID_ARG before any launch: null state or inputs, only one of mean_out / valid_out, non-positive dims, C % 4 != 0,
+ * a grid or feature stack beyond the 31-bit limits of ivx_backproject_mean_fwd.
+ *
+ * ivx_volume_mean_fwd is the out-of-place ivx_volume_normalize_fwd: out = count ? volume_sum / count : 0 (out_dtype IVX_F32 or
+ * IVX_BF16), valid = count > 0, the sums stay intact -- the mean after calls that passed mean_out = NULL.                    */
+int ivx_backproject_accum_fwd(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
+                              const float *new_origin, const int32_t *crop_hw, const float *voxel_size /*host*/, int32_t X, int32_t Y,
+                              int32_t Z, float *volume_sum, int32_t *count, int32_t first, float *mean_out, uint8_t *valid_out,
+                              ivx_stream_t stream);
+int ivx_backproject_accum_fwd_bf16(const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
+                                   const float *new_origin, const int32_t *crop_hw, const float *voxel_size /*host*/, int32_t X, int32_t Y,
+                                   int32_t Z, float *volume_sum, int32_t *count, int32_t first, void *mean_out, uint8_t *valid_out,
+                                   ivx_stream_t stream);
+int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype,
+                        uint8_t *valid, ivx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
  * (mmdet3d/models/dense_heads/anchor3d_head.py:428-517) for a batch, single feature level,
