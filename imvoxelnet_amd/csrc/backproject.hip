@@ -21,6 +21,15 @@
 //             NaN/inf fail, as do the INT64_MIN values the reference's .long() produces for them)
 //   mean    = (sum over valid views in view order) / float(count)  (IEEE divide), 0 if count == 0
 // This file is compiled with -ffp-contract=off.
+//
+// Optional bilinear sampling (BP_BILINEAR, ivx_backproject_fwd_ex; an extra mode outside the reference-parity claims, defined in
+// include/imvoxel.h and pinned to the fp64 reference of tests/ref_unproject.py).  Validity, mask and count are the nearest rule's; with
+// xf = u / w, yf = v / w as above:
+//   x0 = floor(xf), x1 = x0 + 1, y0 = floor(yf), y1 = y0 + 1, each clamped to the crop (border rule)
+//   ax = xf - floor(xf), ay = yf - floor(yf), bx = 1 - ax, by = 1 - ay                         (__fsub_rn)
+//   w00 = bx * by, w10 = ax * by, w01 = bx * ay, w11 = ax * ay                                 (__fmul_rn)
+//   sample = fma(w11, f11, fma(w01, f01, fma(w10, f10, w00 * f00)))                            (__fmul_rn, then three __fmaf_rn)
+// (bp_bilinear_sample below, the one function every mode and element type calls), then the same view sum and division.
 #include "ivx_common.h"
 #include <stdlib.h>
 
@@ -56,7 +65,25 @@ struct BpParams {
 // T = float (the reference's precision) or __bf16 (optional storage mode: features / volume stored as bf16, the view sum
 // and the division in fp32, one rounding at the store; VEC 4 only).
 enum { BP_SUM = 0, BP_MEAN = 1, BP_ACCUM = 2 };
-template <int VEC, int MODE = BP_MEAN, typename T = float>
+// SAMP BP_NEAREST: the reference's gather (the code below is what it was before the parameter existed).  BP_BILINEAR: the projecting
+// lane also leaves the clamped steps to the other three corners and the two fractions; the group receives them through __shfl like the
+// pixel offset, and every lane blends its channel chunk from four 16-byte loads, one chunk at a time (4 corner vectors live, not 16).
+enum { BP_NEAREST = 0, BP_BILINEAR = 1 };
+// The bilinear sample of one channel in the ONE fixed order of include/imvoxel.h.  w = {w00, w10, w01, w11}.
+__device__ __forceinline__ float bp_bilinear_sample(const float f00, const float f10, const float f01, const float f11, const float *w) {
+  float s = __fmul_rn(w[0], f00);
+  s = __fmaf_rn(w[1], f10, s);
+  s = __fmaf_rn(w[2], f01, s);
+  return __fmaf_rn(w[3], f11, s);
+}
+__device__ __forceinline__ void bp_bilinear_weights(const float ax, const float ay, float *w) {
+  const float bx = __fsub_rn(1.0f, ax), by = __fsub_rn(1.0f, ay);
+  w[0] = __fmul_rn(bx, by);
+  w[1] = __fmul_rn(ax, by);
+  w[2] = __fmul_rn(bx, ay);
+  w[3] = __fmul_rn(ax, ay);
+}
+template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST>
 __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p) {
   typedef T tv4 __attribute__((ext_vector_type(4)));
   constexpr bool MEAN = MODE == BP_MEAN;
@@ -117,6 +144,8 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
     // lane g projects view v0 + g
     const int v = v0 + g;
     int off = -1;
+    int step = 0;               // BP_BILINEAR: bit 0 = x1 is one pixel right of x0, bit 1 = y1 is one row below y0 (0 where the clamp joins them)
+    float ax = 0.f, ay = 0.f;   // BP_BILINEAR: the fractions
     if (v < p.V) {
       const float *P = p.proj + ((size_t)b * p.V + v) * 12;
       float u = __fmul_rn(P[0], px);
@@ -135,10 +164,31 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
       const float yr = rintf(__fdiv_rn(w_, d));
       const bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
       if (ok) off = (((b * p.V + v) * p.FH + (int)yr) * p.FW + (int)xr);
+      if constexpr (SAMP == BP_BILINEAR) {
+        if (ok) {               // a valid sample: xf in [-0.5, wc - 0.5], so the floors are in [-1, wc - 1] and fit an int
+          const float xf = __fdiv_rn(u, d), yf = __fdiv_rn(w_, d);
+          const float fx = floorf(xf), fy = floorf(yf);
+          ax = __fsub_rn(xf, fx);
+          ay = __fsub_rn(yf, fy);
+          const int x0 = max((int)fx, 0), x1 = min((int)fx + 1, wc - 1);     // x0 <= wc - 1 and x1 >= 0 already
+          const int y0 = max((int)fy, 0), y1 = min((int)fy + 1, hc - 1);
+          step = (x1 - x0) | ((y1 - y0) << 1);
+          off = (((b * p.V + v) * p.FH + y0) * p.FW + x0);                   // corner 00
+        }
+      }
     }
     const int nv = (p.V - v0) < lpv ? (p.V - v0) : lpv;
     for (int s = 0; s < nv; ++s) {
       const int o = __shfl(off, gbase + s, 64);
+      int dx = 0, dy = 0;       // BP_BILINEAR: element offsets from corner 00 to corners 10 and 01
+      float w[4];
+      if constexpr (SAMP == BP_BILINEAR) {
+        const int st = __shfl(step, gbase + s, 64);
+        const float axs = __shfl(ax, gbase + s, 64), ays = __shfl(ay, gbase + s, 64);
+        dx = (st & 1) * p.C;
+        dy = (st >> 1) * p.FW * p.C;
+        bp_bilinear_weights(axs, ays, w);
+      }
       if (o >= 0) {
         ++cnt;
         const T *src = reinterpret_cast<const T *>(p.feat) + (size_t)o * p.C;
@@ -146,7 +196,17 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
         for (int q = 0; q < MAXCH; ++q) {
           const int ch = g + q * lpv;
           if (ch < p.nchunk) {
-            if constexpr (VEC == 4) {
+            if constexpr (SAMP == BP_BILINEAR && VEC == 4) {
+              const tv4 c00 = *reinterpret_cast<const tv4 *>(src + ch * 4);
+              const tv4 c10 = *reinterpret_cast<const tv4 *>(src + dx + ch * 4);
+              const tv4 c01 = *reinterpret_cast<const tv4 *>(src + dy + ch * 4);
+              const tv4 c11 = *reinterpret_cast<const tv4 *>(src + dy + dx + ch * 4);
+#pragma unroll
+              for (int e = 0; e < 4; ++e)
+                acc[q][e] = __fadd_rn(acc[q][e], bp_bilinear_sample((float)c00[e], (float)c10[e], (float)c01[e], (float)c11[e], w));
+            } else if constexpr (SAMP == BP_BILINEAR) {
+              acc[q][0] = __fadd_rn(acc[q][0], bp_bilinear_sample((float)src[ch], (float)src[dx + ch], (float)src[dy + ch], (float)src[dy + dx + ch], w));
+            } else if constexpr (VEC == 4) {
               const tv4 xr = *reinterpret_cast<const tv4 *>(src + ch * 4);
               const f32x4 x = {(float)xr[0], (float)xr[1], (float)xr[2], (float)xr[3]};
 #pragma unroll
@@ -492,4 +552,85 @@ extern "C" int ivx_backproject_mean_fwd_bf16(const void *feat, int32_t B, int32_
   hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
   IVX_CHECK_LAUNCH("ivx_backproject_mean_fwd_bf16");
   return IVX_OK;
+}
+
+// Bilinear sampling (BP_BILINEAR instantiations of backproject_mean_kernel): every mode, fp32 and bf16.  One view takes the same kernel
+// (its mean divides by a count of 1, which is exact); the nearest single-view copy kernel and its per-workgroup maxima do not apply.
+static int backproject_bilinear_launch(const ivx_backproject_desc *d, const void *feat, const float *proj, const float *new_origin, const int32_t *crop_hw,
+                                       void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream) {
+  const char *what = "ivx_backproject_fwd_ex";
+  const bool bf16 = d->feat_dtype == IVX_BF16;
+  IVX_REQUIRE(feat && proj && new_origin && crop_hw && volume, "%s: null argument", what);
+  if (d->mode == IVX_LIFT_MEAN) {
+    IVX_REQUIRE(valid, "%s: null argument (the mean mode writes valid)", what);
+    IVX_REQUIRE(!count && !mean_out, "%s: the mean mode takes no count / mean_out", what);
+  } else if (d->mode == IVX_LIFT_SUM) {
+    IVX_REQUIRE(count, "%s: null argument (the sum mode writes count)", what);
+    IVX_REQUIRE(!valid && !mean_out, "%s: the sum mode takes no valid / mean_out", what);
+  } else {
+    IVX_REQUIRE(count, "%s: null argument (the accumulate mode updates count)", what);
+    IVX_REQUIRE((mean_out != nullptr) == (valid != nullptr), "%s: mean_out and valid must both be given or both be NULL", what);
+  }
+  IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
+  const int vec = (d->C % 4 == 0) ? 4 : 1;
+  IVX_REQUIRE(vec == 4 || (d->mode == IVX_LIFT_MEAN && !bf16), "%s: C %% 4 must be 0 (every form but the fp32 mean)", what);
+  IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
+  IVX_REQUIRE((int64_t)d->B * d->V * d->FH * d->FW < (1LL << 31), "%s: feature maps too large", what);
+  IVX_REQUIRE(d->B <= 65535, "%s: batch too large", what);
+  BpParams p;
+  p.feat = (const float *)feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = (float *)volume; p.valid = valid;
+  p.count = count; p.mean_out = mean_out; p.first = d->first; p.pmax = nullptr;
+  p.vs0 = d->voxel_size[0]; p.vs1 = d->voxel_size[1]; p.vs2 = d->voxel_size[2];
+  p.V = d->V; p.FH = d->FH; p.FW = d->FW; p.C = d->C; p.X = d->X; p.Y = d->Y; p.Z = d->Z; p.N = d->X * d->Y * d->Z;
+  p.nchunk = (d->C + vec - 1) / vec;
+  IVX_REQUIRE(p.nchunk <= 64 * 4, "%s: C=%d too large (max %d)", what, d->C, 256 * vec);
+  int lg = 0;
+  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
+  p.lpv_log2 = lg;
+  const int vpb = 256 >> lg;
+  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
+  const dim3 grid(bp_grid(p), d->B), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  if (d->mode == IVX_LIFT_MEAN) {
+    if (bf16)
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
+    else if (vec == 4)
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((backproject_mean_kernel<1, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
+  } else if (d->mode == IVX_LIFT_SUM && !bf16) {
+    hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM, float, BP_BILINEAR>), grid, block, 0, st, p);
+  } else {
+    if (d->mode == IVX_LIFT_SUM) p.first = 1;       // bf16 features, fp32 sums: the accumulate kernel from a zero state, no mean
+    if (bf16)
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR>), grid, block, 0, st, p);
+  }
+  IVX_CHECK_LAUNCH(what);
+  return IVX_OK;
+}
+
+// One entry point for both sampling rules and the three modes (include/imvoxel.h).  The nearest rule forwards to the entry points above.
+extern "C" int ivx_backproject_fwd_ex(const ivx_backproject_desc *d, const void *feat, const float *proj, const float *new_origin,
+                                      const int32_t *crop_hw, void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream) {
+  IVX_REQUIRE(d, "ivx_backproject_fwd_ex: null descriptor");
+  IVX_REQUIRE(d->sampling == IVX_SAMPLE_NEAREST || d->sampling == IVX_SAMPLE_BILINEAR, "ivx_backproject_fwd_ex: sampling %d (IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR)", d->sampling);
+  IVX_REQUIRE(d->mode == IVX_LIFT_MEAN || d->mode == IVX_LIFT_SUM || d->mode == IVX_LIFT_ACCUM, "ivx_backproject_fwd_ex: mode %d (IVX_LIFT_MEAN | IVX_LIFT_SUM | IVX_LIFT_ACCUM)", d->mode);
+  IVX_REQUIRE(d->feat_dtype == IVX_F32 || d->feat_dtype == IVX_BF16, "ivx_backproject_fwd_ex: feat_dtype %d (IVX_F32 | IVX_BF16)", d->feat_dtype);
+  if (d->sampling == IVX_SAMPLE_BILINEAR) return backproject_bilinear_launch(d, feat, proj, new_origin, crop_hw, volume, count, mean_out, valid, stream);
+  const bool bf16 = d->feat_dtype == IVX_BF16;
+  const float *vs = d->voxel_size;
+  if (d->mode == IVX_LIFT_MEAN) {
+    IVX_REQUIRE(!count && !mean_out, "ivx_backproject_fwd_ex: the mean mode takes no count / mean_out");
+    if (bf16) return ivx_backproject_mean_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, volume, valid, stream);
+    return ivx_backproject_mean_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, valid, stream);
+  }
+  if (d->mode == IVX_LIFT_SUM) {
+    IVX_REQUIRE(!valid && !mean_out, "ivx_backproject_fwd_ex: the sum mode takes no valid / mean_out");
+    if (bf16) return ivx_backproject_accum_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, 1, nullptr, nullptr, stream);
+    return ivx_backproject_sum_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, stream);
+  }
+  if (bf16) return ivx_backproject_accum_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, d->first, mean_out, valid, stream);
+  return ivx_backproject_accum_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, d->first, (float *)mean_out, valid, stream);
 }

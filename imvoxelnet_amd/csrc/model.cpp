@@ -1244,7 +1244,7 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
       const Step &q = m->steps[j];
       if (q.out != s.in) continue;
       PlanStep &pp = pl->ps[j];
-      if (q.kind == ST_LIFT) {          // the single-view unprojection leaves per-workgroup maxima too
+      if (q.kind == ST_LIFT && m->cfg.sampling == IVX_SAMPLE_NEAREST) {          // the single-view unprojection leaves per-workgroup maxima too (bilinear: the consumer reduces the volume itself, as after a multi-view lift)
         const TInfo &vol = pl->t[q.out];
         const int32_t nb = ivx_backproject_amax_blocks(vol.B, n_views, vol.D, vol.H, vol.W);
         if (nb > 0) {
@@ -1621,6 +1621,17 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
         M_REQUIRE(bd.proj && bd.new_origin && bd.crop, "%s: proj / new_origin / crop_hw are required", who);
         const TInfo &o = pl.t[s.out];
         M_TRY(trace_begin(m, i, 4, 1, 0.0, (double)in.esz * in.elems() + (double)o.esz * o.elems() + (double)o.elems() / o.C, "unprojection", st));
+        if (m->cfg.sampling != IVX_SAMPLE_NEAREST) {      // optional bilinear rule (include/imvoxel.h): one entry point for both storage types and any V
+          ivx_backproject_desc ld = {};
+          ld.B = o.B; ld.V = bd.V; ld.FH = in.H; ld.FW = in.W; ld.C = in.C; ld.X = o.D; ld.Y = o.H; ld.Z = o.W;
+          for (int a = 0; a < 3; ++a) ld.voxel_size[a] = m->cfg.voxel_size[a];
+          ld.feat_dtype = m->cfg.storage == IVX_BF16 ? IVX_BF16 : IVX_F32;
+          ld.mode = IVX_LIFT_MEAN;
+          ld.sampling = m->cfg.sampling;
+          M_TRY(ivx_backproject_fwd_ex(&ld, ptr(s.in), bd.proj, bd.new_origin, bd.crop, ptr(s.out), nullptr, nullptr, (uint8_t *)ptr(s.out2), st));
+          M_TRY(trace_end(m, st));
+          break;
+        }
         if (m->cfg.storage == IVX_BF16) {
           // one view: the lift is a gather-copy (no arithmetic on the features: the reference divides by a count of 1), so a bf16 map
           // with C channels goes through the fp32 kernel as C / 2 32-bit words; several views: sum and division in fp32 (bf16 kernel).
@@ -1754,6 +1765,7 @@ extern "C" int ivx_create(const ivx_model_cfg *cfg, ivx_model **out) {
   M_REQUIRE(cfg->wino_operands == IVX_F32 || cfg->wino_operands == IVX_F16_PAIR, "ivx_create: wino_operands IVX_F32 | IVX_F16_PAIR");
   M_REQUIRE(cfg->trunk_operands == IVX_F32 || cfg->trunk_operands == IVX_F16_PAIR, "ivx_create: trunk_operands IVX_F32 | IVX_F16_PAIR");
   M_REQUIRE(cfg->storage == IVX_F32 || cfg->storage == IVX_BF16, "ivx_create: storage IVX_F32 | IVX_BF16");
+  M_REQUIRE(cfg->sampling == IVX_SAMPLE_NEAREST || cfg->sampling == IVX_SAMPLE_BILINEAR, "ivx_create: sampling IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR");
   if (cfg->storage == IVX_BF16) {
     M_REQUIRE(cfg->fpn_channels % 8 == 0 && cfg->neck_out_channels % 8 == 0, "ivx_create: bf16 storage needs channel counts that are multiples of 8");
   }

@@ -30,6 +30,8 @@ def get_points(n_voxels, voxel_size, origin):
 
 @DETECTORS.register_module()
 class ImVoxelNet(nn.Module):
+    sampling = 'nearest'      # sampling rule of the unprojection, chosen by prepare(sampling=...); a class default, so a detector assembled without __init__ lifts by the reference's rule
+
     def __init__(self, backbone, neck, neck_3d, bbox_head, n_voxels, voxel_size, head_2d=None, train_cfg=None,
                  test_cfg=None, pretrained=None):
         super().__init__()
@@ -48,8 +50,9 @@ class ImVoxelNet(nn.Module):
         self.trunk_fp8 = False
         # weights loaded AFTER prepare() (load_state_dict / data.load_checkpoint) must reach the packed device copies: the
         # sub-modules drop theirs (params.invalidate_packed_on_load), and the detector re-packs in the dtype it was prepared in
+        # (a post hook must return None: prepare() returns the module)
         self.register_load_state_dict_post_hook(
-            lambda mod, keys: mod.prepare(mod._prepared_device, dtype=mod.storage_dtype) if mod._prepared_device is not None else None)
+            lambda mod, keys: mod.prepare(mod._prepared_device, dtype=mod.storage_dtype, sampling=mod.sampling) and None if mod._prepared_device is not None else None)
         self.init_weights(pretrained=pretrained)
 
     def init_weights(self, pretrained=None):
@@ -60,7 +63,7 @@ class ImVoxelNet(nn.Module):
         if self.head_2d is not None:
             self.head_2d.init_weights()
 
-    def prepare(self, device, dtype=torch.float32, native=None):
+    def prepare(self, device, dtype=torch.float32, native=None, sampling='nearest'):
         """Pack every layer's parameters for the device kernels (call again after changing weights).
         native (default: on unless IVX_NATIVE_MODEL=0): build the native model handle (engine.NativeModel over csrc/model.cpp) for every
         family it covers (engine.family) and let simple_test run the whole device side through ONE C-ABI call;
@@ -69,8 +72,15 @@ class ImVoxelNet(nn.Module):
         and the one every parity claim is made for; bfloat16 is an optional reduced-precision mode (fp32 accumulate,
         fp32 epilogues, fp32 head output and detection tail) for every config: with DCNv2 stages the offsets / masks are fp32
         and the deformable columns bf16, with a LayoutHead the pooled C5 and its MLPs are fp32.  The native handle covers it
-        wherever it covers fp32 (engine.eligible)."""
+        wherever it covers fp32 (engine.eligible).
+        sampling: 'nearest' (default: the reference's rule, detectors/imvoxelnet.py:151-152, and the one every parity claim is made for) or
+        'bilinear', an optional extra mode outside those claims (include/imvoxel.h, ivx_backproject_fwd_ex): the four pixels around the
+        projected point, blended in fp32; the valid mask is the nearest rule's.  The choice holds for everything this model lifts: lift_cl,
+        the native handle, simple_test / simple_test_u8 / simple_test_view_sharded and open_scene sessions.  Orthogonal to dtype."""
         from .conv import storage_dtype
+        from ._lib import sampling_id
+        sampling_id(sampling)                    # ValueError for an unknown rule, before anything is packed
+        self.sampling = sampling
         with storage_dtype(dtype):
             for m in (self.backbone, self.neck, self.neck_3d, self.bbox_head):
                 m.prepare(device)
@@ -215,7 +225,7 @@ class ImVoxelNet(nn.Module):
         """FPN level 0 [B*V,1,h,w,C] + metas -> (volume [B,X,Y,Z,C], valid [B,X,Y,Z] bool).
         angles: predicted (pitch, roll) list of the LayoutHead (test mode of the Total configs) or None."""
         proj, new_origin, crop = self._camera_setup(img_metas, 4, p0.device, angles)
-        return ops.backproject_mean(p0, proj, new_origin, crop, self.voxel_size, self.n_voxels)
+        return ops.backproject_mean(p0, proj, new_origin, crop, self.voxel_size, self.n_voxels, sampling=self.sampling)
 
     def detect_cl(self, volume, img_metas, want_candidates=False):
         """Anchor-head configs (KITTI / nuScenes): raw device tensors (boxes, scores, labels, count)."""

@@ -134,7 +134,7 @@ def view_sharded_lift(model, img, img_metas, rank=None, world=None, group=None):
     if v1 > v0:
         p0 = model.features_2d_cl(img_l)
         proj, origin, crop = model._camera_setup(metas_l, 4, p0.device)
-        vol, cnt = ops.backproject_sum(p0, proj, origin, crop, model.voxel_size, model.n_voxels)
+        vol, cnt = ops.backproject_sum(p0, proj, origin, crop, model.voxel_size, model.n_voxels, sampling=getattr(model, 'sampling', 'nearest'))
     else:     # more ranks than views: this rank contributes zeros
         B = img.shape[0]
         cf = model.neck.out_channels
@@ -246,7 +246,7 @@ def view_sharded_neck_slabs(model, img, img_metas, group=None, rank=None, world=
     if v1 > v0:
         p0 = model.features_2d_cl(img_l)
         proj, origin, crop = model._camera_setup(metas_l, 4, p0.device)
-        vol, cnt = ops.backproject_sum(p0, proj, origin, crop, model.voxel_size, model.n_voxels)
+        vol, cnt = ops.backproject_sum(p0, proj, origin, crop, model.voxel_size, model.n_voxels, sampling=getattr(model, 'sampling', 'nearest'))
     else:
         B = img.shape[0]
         vol = torch.zeros((B,) + tuple(model.n_voxels) + (model.neck.out_channels,), device=img.device, dtype=torch.float32)

@@ -124,6 +124,7 @@ def model_cfg(model, with_trunk=True, winograd=None, winograd_tile=None):
     cfg.wino_operands = int(FusedConv.wino_operands)
     cfg.trunk_operands = int(FusedConv.trunk_operands) if with_trunk else 0
     cfg.storage = 1 if getattr(model, 'storage_dtype', None) == torch.bfloat16 else 0       # IVX_BF16: the optional reduced-precision mode
+    cfg.sampling = _lib.sampling_id(getattr(model, 'sampling', 'nearest'))                   # IVX_SAMPLE_BILINEAR: the optional extra sampling rule of the lift
     return cfg
 
 

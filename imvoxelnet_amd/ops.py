@@ -766,15 +766,53 @@ def upsample_trilinear2x(x):
 stage_trace = None
 
 
-def backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
+def backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
+    """sampling: 'nearest' (the reference's rule: the entry points of the parity claims, called exactly as before the option existed) or
+    'bilinear' (optional extra mode, ivx_backproject_fwd_ex; include/imvoxel.h has the definition)."""
+    lift = _backproject_mean if _lib.sampling_id(sampling) == 0 else _backproject_mean_bilinear
     if stage_trace is None:
-        return _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
+        return lift(feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    out = _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
+    out = lift(feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
     e1.record()
     stage_trace.append(('lift', e0, e1))
     return out
+
+
+_LIFT_MEAN, _LIFT_SUM, _LIFT_ACCUM = 0, 1, 2
+
+
+def _backproject_ex(mode, feat, proj, new_origin, crop_hw, voxel_size, xyz, volume, count=None, mean_out=None, valid=None, first=False, sampling=1):
+    """ivx_backproject_fwd_ex on checked tensors (the bilinear rule of the three wrappers below)."""
+    fn = getattr(_lib.lib(), 'ivx_backproject_fwd_ex', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_fwd_ex (bilinear sampling needs version 0.4.4)')
+    B, V = proj.shape[0], proj.shape[1]
+    BV, D, FH, FW, Cn = feat.shape
+    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
+        raise ValueError('feat / proj shapes do not agree')
+    X, Y, Z = (int(v) for v in xyz)
+    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[feat.dtype], mode, int(sampling),
+                             int(bool(first)))
+    check(fn(C.byref(d), _ptr(feat), _ptr(proj), _ptr(new_origin), _ptr(crop_hw), _ptr(volume), _ptr(count), _ptr(mean_out), _ptr(valid), _stream()),
+          'ivx_backproject_fwd_ex')
+
+
+def _backproject_mean_bilinear(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
+    """backproject_mean with the bilinear rule: fp32 or bf16 maps, any number of views through the one kernel template (a single bf16
+    view too: the blend is arithmetic, not a copy)."""
+    if feat.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'feat must be float32 or bfloat16, got {feat.dtype}')
+    _chk(feat, 'feat', feat.dtype)
+    _chk(proj, 'proj')
+    _chk(new_origin, 'new_origin')
+    _chk(crop_hw, 'crop_hw', torch.int32)
+    X, Y, Z = (int(v) for v in n_voxels)
+    vol = torch.empty((proj.shape[0], X, Y, Z, feat.shape[-1]), device=feat.device, dtype=feat.dtype)
+    valid = torch.empty((proj.shape[0], X, Y, Z), device=feat.device, dtype=torch.uint8)
+    _backproject_ex(_LIFT_MEAN, feat, proj, new_origin, crop_hw, voxel_size, (X, Y, Z), vol, valid=valid)
+    return vol, valid.view(torch.bool)
 
 
 def _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
@@ -818,9 +856,10 @@ def _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
     return vol, valid.view(torch.bool)
 
 
-def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
+def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
     """View-sharded mode: like backproject_mean but returns the raw view sum [B,X,Y,Z,C] and the int32 view count
-    [B,X,Y,Z] of THIS rank's views (to be all-reduced, then volume_normalize_)."""
+    [B,X,Y,Z] of THIS rank's views (to be all-reduced, then volume_normalize_).  sampling as for backproject_mean."""
+    sampling = _lib.sampling_id(sampling)
     _chk(feat, 'feat')
     _chk(proj, 'proj')
     _chk(new_origin, 'new_origin')
@@ -832,6 +871,9 @@ def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
     X, Y, Z = (int(v) for v in n_voxels)
     vol = torch.empty((B, X, Y, Z, Cn), device=feat.device, dtype=torch.float32)
     cnt = torch.empty((B, X, Y, Z), device=feat.device, dtype=torch.int32)
+    if sampling:
+        _backproject_ex(_LIFT_SUM, feat, proj, new_origin, crop_hw, voxel_size, (X, Y, Z), vol, count=cnt, sampling=sampling)
+        return vol, cnt
     vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
     check(_lib.lib().ivx_backproject_sum_fwd(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw),
                                              vs, X, Y, Z, _ptr(vol), _ptr(cnt), _stream()), 'ivx_backproject_sum_fwd')
@@ -859,12 +901,13 @@ def _chk_mask(t, name, shape):
     return t
 
 
-def backproject_accum_(feat, proj, new_origin, crop_hw, voxel_size, vol_sum, count, first, mean_out=None, valid_out=None):
+def backproject_accum_(feat, proj, new_origin, crop_hw, voxel_size, vol_sum, count, first, mean_out=None, valid_out=None, sampling='nearest'):
     """Streaming scenes: add the V views of `feat` ([B*V,1,FH,FW,C] fp32 or bf16) to the running state vol_sum [B,X,Y,Z,C] fp32 /
     count [B,X,Y,Z] int32, in place and in view order (ivx_backproject_accum_fwd: after the last chunk the state holds what ONE
     backproject_mean over all the views computes, bit for bit).  first: start the state from zero without reading it.
     mean_out [B,X,Y,Z,C] (feat's dtype) + valid_out [B,X,Y,Z] uint8 / bool: the same pass also writes the mean and the mask; both or
-    neither.  Returns (vol_sum, count)."""
+    neither.  sampling as for backproject_mean (one rule per running volume).  Returns (vol_sum, count)."""
+    sampling = _lib.sampling_id(sampling)
     if feat.dtype not in (torch.float32, torch.bfloat16):
         raise TypeError(f'feat must be float32 or bfloat16, got {feat.dtype}')
     if (mean_out is None) != (valid_out is None):
@@ -887,6 +930,10 @@ def backproject_accum_(feat, proj, new_origin, crop_hw, voxel_size, vol_sum, cou
             raise ValueError('mean_out must have the shape of vol_sum')
         _chk_mask(valid_out, 'valid_out', count.shape)
     X, Y, Z = (int(v) for v in vol_sum.shape[1:4])
+    if sampling:
+        _backproject_ex(_LIFT_ACCUM, feat, proj, new_origin, crop_hw, voxel_size, (X, Y, Z), vol_sum, count=count, mean_out=mean_out, valid=valid_out,
+                        first=first, sampling=sampling)
+        return vol_sum, count
     vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
     name = 'ivx_backproject_accum_fwd_bf16' if feat.dtype == torch.bfloat16 else 'ivx_backproject_accum_fwd'
     check(getattr(_lib.lib(), name)(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw), vs, X, Y, Z, _ptr(vol_sum),

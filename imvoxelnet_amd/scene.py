@@ -9,6 +9,9 @@ The view sum continues the stored fp32 sum in view order, so the volume after th
 same features in the same order (include/imvoxel.h, ivx_backproject_accum_fwd).  The FEATURES of a view may differ in the last bits
 from the one-shot run when the trunk's per-tensor operand scales depend on which views share a call (the default fp16-pair trunk).
 
+The session samples the features by its model's rule (prepare(sampling=...)) in every add; the bit identity with the one-shot lift
+holds for the bilinear rule as well (one sample function, the same view order).
+
 Out of scope: removing or re-weighting views (sliding windows) -- subtracting in fp32 is not the inverse of adding, the state would
 drift away from any one-shot result; batches of scenes in one session (B = 1; open one session per scene, they share the prepared
 model); a model-level C handle for sessions (the state lives here, over the op-level ABI and the handle's sub-range calls).
@@ -124,7 +127,7 @@ class SceneSession:
             self._mean = torch.empty((1, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
             self._valid = torch.empty((1, X, Y, Z), device=dev, dtype=torch.uint8)
         ops.backproject_accum_(p0, proj, origin, crop, m.voxel_size, self._sum, self._count, self.n_views == 0,
-                               self._mean if emit else None, self._valid if emit else None)
+                               self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
         self._origin, self._crop = origin, crop
         self._stale = not emit
         self._hw = (H, W)

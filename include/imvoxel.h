@@ -38,7 +38,8 @@ extern "C" {
 typedef void *ivx_stream_t; /* hipStream_t */
 
 /* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header; 420 = 0.4.2: bf16 storage with
- * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size) and the message of the last failing call on
+ * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size; 440 = 0.4.4: ivx_backproject_fwd_ex / ivx_model_cfg.sampling, the optional
+ * bilinear sampling rule of the unprojection) and the message of the last failing call on
  * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -473,6 +474,56 @@ int ivx_backproject_accum_fwd_bf16(const void *feat, int32_t B, int32_t V, int32
 int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype,
                         uint8_t *valid, ivx_stream_t stream);
 
+/* (0.4.4) Sampling rule of the unprojection.  The entry points above gather the NEAREST pixel, as the reference does
+ * (detectors/imvoxelnet.py:151-152); every reference-parity claim of this library is made for that rule.  IVX_SAMPLE_BILINEAR is an
+ * optional extra mode outside those claims: the four pixels around the projected point, blended in fp32.  It is pinned to an fp64
+ * reference written from the definition below (tests/ref_unproject.py), not to the reference implementation.
+ *
+ * Definition.  Points, projection chain, crop and the two quotients xf = u / d, yf = v / d (fp32, IEEE division) are those of
+ * ivx_backproject_mean_fwd.
+ *   validity  UNCHANGED: a view sees a voxel iff 0 <= rint(xf) < wc, 0 <= rint(yf) < hc and d > 0 (wc, hc: the crop clamped to the
+ *             map).  The valid mask and the per-voxel view count are bit for bit those of the nearest rule.
+ *   corners   x0 = floor(xf), x1 = x0 + 1, y0 = floor(yf), y1 = y0 + 1, each clamped to [0, wc-1] / [0, hc-1] (border rule; a valid
+ *             sample has xf in [-0.5, wc-0.5], so a clamp moves a corner by at most one pixel); converted to int after the validity test.
+ *   weights   ax = xf - floorf(xf), ay = yf - floorf(yf)                       (one fp32 subtraction each, exact for xf, yf >= 0)
+ *             bx = 1 - ax, by = 1 - ay                                          (fp32 subtractions)
+ *             w00 = bx * by, w10 = ax * by, w01 = bx * ay, w11 = ax * ay        (fp32 products; wXY weighs pixel (xX, yY))
+ *   blend     sample = fma(w11, f11, fma(w01, f01, fma(w10, f10, w00 * f00)))   (ONE fixed order: a rounded product, then three fused
+ *             multiply-adds, innermost first; f = the pixel's value converted to fp32)
+ *   mean      the samples are added over the valid views in view order (fp32 additions) and divided by the count (IEEE division),
+ *             0 where no view sees the voxel -- as for the nearest rule.  bf16 storage: weights, blend, sum and division in fp32, one
+ *             rounding at the store.
+ * With ax = ay = 0 the sample is the nearest pixel's value (as a number: -0 becomes +0).  One device function computes the sample in
+ * every mode and element type and the view order is shared, so every chunking of the accumulate mode reproduces the one-shot launch
+ * bit for bit, as for the nearest rule.
+ *
+ * ivx_backproject_fwd_ex is the one entry point for both rules and all modes; the entry points above keep their names and behaviour.
+ *   mode IVX_LIFT_MEAN   volume [B,X,Y,Z,C] (feat_dtype) + valid; count and mean_out must be NULL
+ *        IVX_LIFT_SUM    volume = fp32 view sum + count (ivx_backproject_sum_fwd); valid and mean_out must be NULL.  bf16 features: the
+ *                        accumulate kernel from a zero state (fp32 sums)
+ *        IVX_LIFT_ACCUM  volume = running fp32 sum + count, in/out, `first` as for ivx_backproject_accum_fwd; mean_out (feat_dtype) and
+ *                        valid both given or both NULL
+ * With sampling = IVX_SAMPLE_NEAREST it forwards to the entry points above (same checks, same launches).  A single-view bilinear lift
+ * runs the multi-view kernel (bf16 maps through the bf16 kernel; no per-workgroup maxima: ivx_backproject_amax_blocks describes the
+ * nearest single-view kernel only).  IVX_ERR_INVALID_ARG before any launch: a null descriptor, an unknown sampling, mode or feat_dtype,
+ * and the rules of the mode's entry point above -- null or superfluous pointers, non-positive dims, C % 4 != 0 (every form but the fp32
+ * mean), C above 1024 (256 when C % 4 != 0), a grid or feature stack beyond the 31-bit limits, B > 65535.                    */
+#define IVX_SAMPLE_NEAREST 0
+#define IVX_SAMPLE_BILINEAR 1
+#define IVX_LIFT_MEAN 0
+#define IVX_LIFT_SUM 1
+#define IVX_LIFT_ACCUM 2
+typedef struct ivx_backproject_desc {
+  int32_t B, V, FH, FW, C, X, Y, Z;
+  float voxel_size[3];
+  int32_t feat_dtype; /* IVX_F32 | IVX_BF16: element type of feat, of the mean volume and of mean_out */
+  int32_t mode;       /* IVX_LIFT_MEAN | IVX_LIFT_SUM | IVX_LIFT_ACCUM */
+  int32_t sampling;   /* IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR */
+  int32_t first;      /* IVX_LIFT_ACCUM only */
+} ivx_backproject_desc;
+int ivx_backproject_fwd_ex(const ivx_backproject_desc *d, const void *feat, const float *proj, const float *new_origin,
+                           const int32_t *crop_hw, void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream);
+
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
  * (mmdet3d/models/dense_heads/anchor3d_head.py:428-517) for a batch, single feature level,
@@ -718,6 +769,9 @@ typedef struct ivx_model_cfg {
                                       with a LayoutHead C5 is pooled to fp32 (ivx_global_avgpool_fwd_bf16) and the six MLP linears stay
                                       fp32 layers (fp32 filters, fp32 in and out).  ivx_model_calibrate_fp8 refuses both forms.  The
                                       Winograd and pair forms are fp32-storage forms and are not used */
+  int32_t sampling;                /* (0.4.4) IVX_SAMPLE_NEAREST (0, the reference's rule and the one every parity claim is made for) or
+                                      IVX_SAMPLE_BILINEAR: the lift step runs ivx_backproject_fwd_ex with the bilinear rule (an optional extra
+                                      mode, see there); orthogonal to storage and the operand forms.  Other values: ivx_create refuses */
 } ivx_model_cfg;
 
 int ivx_create(const ivx_model_cfg *cfg, ivx_model **out);
