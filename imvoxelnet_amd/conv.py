@@ -73,17 +73,17 @@ FP8_MAX = 448.0
 def pack_pair_weights(w5, layout=1):
     """fp32 filters [Cout,kd,kh,kw,Cin] (Cin % 16 == 0) -> the IVX_BF16_PAIR operand (include/imvoxel.h): bf16, every value as
     hi = bf16(w), lo = bf16(w - hi), 16-channel groups [hi x16 | lo x16]; layout 0: [Cout,kd,kh,kw,2Cin], layout 1 (Cin % 32 == 0):
-    chunk-major [Cout, 2Cin/64, kd,kh,kw, 64]."""
-    w5 = w5.detach().to(torch.float32)
-    co, kd, kh, kw, ci = w5.shape
+    chunk-major [Cout, 2Cin/64, kd,kh,kw, 64].  Packed by the library's host function ivx_bf16_pair_pack_filters, as in csrc/model.cpp."""
+    import ctypes as C
+    from . import _lib
+    w = w5.detach().to(torch.float32).cpu().contiguous()
+    co, kd, kh, kw, ci = w.shape
     if ci % 16 or (layout == 1 and ci % 32):
         raise ValueError('pair filters need Cin % 16 == 0 (layout 1: % 32)')
-    hi = w5.to(torch.bfloat16)
-    lo = (w5 - hi.to(torch.float32)).to(torch.bfloat16)
-    wp = torch.cat([hi.reshape(co, kd, kh, kw, ci // 16, 16), lo.reshape(co, kd, kh, kw, ci // 16, 16)], dim=-1).reshape(co, kd, kh, kw, 2 * ci)
-    if layout == 1:
-        wp = wp.reshape(co, kd, kh, kw, 2 * ci // 64, 64).permute(0, 4, 1, 2, 3, 5)
-    return wp.contiguous()
+    wp = torch.empty((co, 2 * ci // 64, kd, kh, kw, 64) if layout == 1 else (co, kd, kh, kw, 2 * ci), dtype=torch.bfloat16)
+    _lib.check(_lib.lib().ivx_bf16_pair_pack_filters(C.c_void_p(w.data_ptr()), co, kd * kh * kw, ci, int(layout), C.c_void_p(wp.data_ptr())),
+               'ivx_bf16_pair_pack_filters')
+    return wp.to(w5.device)
 
 
 class QTensor:
@@ -114,36 +114,19 @@ class FusedConv:
     count_flops = False
     flops = 0.0
     exec_flops = 0.0
-    # fp32 3x3xk layers with stride 1 on the first two axes, >= winograd_min_ch input or output channels and
-    # >= winograd_min_pos input positions run as F(m x m, 3x3) (ivx_conv_winograd_fwd).  Measured on the KITTI neck
-    # (batch 4, tools/conv_bench.py --winograd, profiles/r01_conv_layers.log), direct -> m = 2 -> 4 -> 6 in ms:
-    # 256->256 16.1 -> 9.0 -> 5.3 -> 4.3, 128->128 8.2 -> 5.7 -> 3.3 -> 2.7, 64->128 (z stride 2) 4.6 -> 3.9 -> 2.3 -> 1.9,
-    # 64->64 4.8 -> 4.3 -> 2.6 -> 2.2.  Also a gain on the indoor necks down to a few thousand positions (SUN RGB-D fast
-    # 123 -> 165 scenes/s); only the coarsest levels (< winograd_min_pos positions) stay direct.
+    # Which form a layer runs in -- direct, Winograd F(m x m, 3x3) with which tile and operands, or split-operand (bf16 pair) direct -- is the
+    # library's rule, ivx_conv_route (csrc/api_common.cpp: the thresholds and their measurements), which the native handle asks as well.
+    # The attributes below are the switches it takes (ivx_conv_route_opts).
     winograd = os.environ.get('IVX_WINOGRAD', '1') != '0'
-    # m of F(m x m, 3x3): 0 = automatic (6 when a sample's output plane has >= winograd_tile6_min_plane positions on the
-    # transformed axes -- the KITTI / nuScenes necks, full-resolution 2-D maps -- else 4: on the 40 x 40 and 80 x 80 indoor
-    # volumes the 6 x 6 tiles waste up to 10 % at the border and leave too few tiles per plane; measured SUN RGB-D fast
-    # 166 scenes/s with m = 4 vs 157 with m = 6, KITTI 118.6 vs 135.9 images/s); 2, 4 or 6 force one tile everywhere
-    winograd_tile = int(os.environ.get('IVX_WINOGRAD_TILE', '0'))
-    winograd_tile6_min_plane = 16384
-    winograd_min_ch = 64
-    winograd_2d_min_ch = int(os.environ.get('IVX_WINOGRAD_2D_MIN_CH', '128'))   # 2-D 3x3 layers (ResNet conv2, FPN outputs)
-    winograd_min_pos = int(os.environ.get('IVX_WINOGRAD_MIN_POS', '2000'))
-    # Split-operand direct form (include/imvoxel.h IVX_BF16_PAIR) for the layers the Winograd form does not take (1x1, strided, ...):
-    # fp32 activations and filters as (hi, lo) bf16 pairs, three bf16 MFMA products per pair with fp32 accumulation -- 16x the fp32 MFMA
-    # rate at 2^-17 operand precision, one split pass over the input.  Measured on the KITTI neck it loses to the Winograd form
-    # (1.9 / 2.9 / 5.2 ms vs 1.8 / 2.7 / 4.5 for the 64 / 128 / 256-channel layers: the minimal-filtering form needs 5x fewer products).
-    # -1 (default): the rule -- 3x3x3 layers with Cin % 32 == 0 and Cout >= 64 that the Winograd form does not take (the strided convolutions of
-    #     NuScenesImVoxelNeck / FastIndoorImVoxelNeck / the Atlas encoder, and the layers of the coarsest levels: fewer than winograd_min_pos
-    #     positions under a K loop of 13824 .. 27648), from SPLIT_MIN_POS input positions on, when the Winograd-domain GEMMs run on 16-bit operands
-    #     too (wino_operands = 4; with 0 every product of the neck stays on fp32 MFMA).  Measured (tools/neck_layers.py, profiles/r06_split_form.md):
-    #     64 -> 128 stride 2 at 312 x 312 x 12 0.616 -> 0.369 ms, 256 -> 512 stride 2 at 40 x 40 x 16 0.239 -> 0.126, 512 -> 512 at 10 x 10 x 4
-    #     0.084 -> 0.065; 1x1x1 layers and the Cout = 25 head convs gain nothing (HBM / latency-bound) and stay fp32.  csrc/model.cpp plan_conv mirrors it.
-    # 0: off;  1: every 3-D layer with Cin % 32 == 0 from pair_min_pos positions on;  2: 2-D layers as well
+    winograd_tile = int(os.environ.get('IVX_WINOGRAD_TILE', '0'))                # m: 0 = by plane size; 2, 4 or 6 force one tile everywhere
+    # lab overrides of two thresholds of the rule (tools/, tests): channel floor of the 2-D candidates (read when a layer is built; <= 0: the
+    # rule's own) and fewest input positions of the Winograd form (< 0: the rule's own)
+    winograd_2d_min_ch = int(os.environ.get('IVX_WINOGRAD_2D_MIN_CH', '0'))
+    winograd_min_pos = int(os.environ.get('IVX_WINOGRAD_MIN_POS', '-1'))
+    # Split-operand direct form (include/imvoxel.h IVX_BF16_PAIR): -1 (default): the rule;  0: off;  lab modes that only this host has:
+    # 1: every 3-D layer with Cin % 32 == 0 from pair_min_pos positions on;  2: 2-D layers as well
     pair_mode = int(os.environ.get('IVX_CONV_PAIR', '-1'))
     pair_min_pos = 2000
-    SPLIT_MIN_POS = 256
     # Operands of the Winograd-domain GEMMs (ivx_conv_desc.wino_operands): 4 = fp16 (hi, lo) pairs, three fp16 MFMA products per pair
     # (~3.3x the fp32 MFMA rate at 22-bit operands: the error stays at the level of the fp32 form's own rounding);
     # 0 = fp32 MFMA (exact fp32 products)
@@ -207,22 +190,20 @@ class FusedConv:
             co, kd, kh, kw, ci = wp.shape
             wp = wp.reshape(co, kd, kh, kw, ci // ck, ck).permute(0, 4, 1, 2, 3, 5)
         self._w_host = wp.contiguous().to(dtype)
-        # candidate for the minimal-filtering form: keep the tap-major fp32 filters for ivx_conv_winograd_weights
-        # 3-D layers transform their first two axes (the z axis stays direct); a 2-D 3x3 layer [B,1,H,W,C] is the same thing
-        # on the view [B,H,W,1,C] with a 3x3x1 kernel (identical memory for the activations and the tap-major filters)
-        self._w0_host = None
-        self._wino2d = self.kernel == (1, 3, 3) and self.stride == (1, 1, 1)
-        wino3d = self.kernel[0] == 3 and self.kernel[1] == 3 and self.stride[0] == 1 and self.stride[1] == 1
-        min_ch = FusedConv.winograd_2d_min_ch if self._wino2d else FusedConv.winograd_min_ch
-        if ((wino3d or self._wino2d) and dtype == torch.float32 and out_dtype == torch.float32 and self.cin_pad == self.cin
-                and self.cout % 4 == 0 and max(self.cin, self.cout) >= min_ch and self.cin % 4 == 0 and type(self) is FusedConv):
-            w0 = w.permute(0, 2, 3, 4, 1).contiguous()                       # [Cout,kd,kh,kw,Cin]
-            self._w0_host = w0.reshape(self.cout, 3, 3, 1, self.cin) if self._wino2d else w0
-        # candidate for the split-operand form: pair-packed filters (made on the host once)
-        self._wp_host = None
+        # Which forms the layer is a candidate for (ivx_conv_route without a shape; asked with the split rule and the pair operands on: the
+        # switches may change after the layer is built).  Winograd: keep the tap-major fp32 filters for ivx_conv_winograd_weights, with the
+        # kernel as that form sees it -- a 2-D 3x3 layer is a 3x3x1 one (_wino2d; identical memory for the tap-major filters)
+        self._routes = {}
         self._dims = dims
-        self._split_cand = (dims == 3 and self.kernel == (3, 3, 3) and self.cout >= 64 and dtype == torch.float32 and out_dtype == torch.float32
-                            and self.cin_pad == self.cin and self.cin % 32 == 0 and type(self) is FusedConv)
+        cand = self._route(None, split=True, wino_operands=ops.IVX_F16_PAIR)
+        wk = (cand.run.KD, cand.run.KH, cand.run.KW)
+        self._w0_host = None
+        self._wino2d = wk != self.kernel
+        if cand.wino_candidate and type(self) is FusedConv:
+            self._w0_host = w.permute(0, 2, 3, 4, 1).contiguous().reshape(self.cout, *wk, self.cin)      # [Cout,kd,kh,kw,Cin]
+        # split-operand form: pair-packed filters (made on the host once)
+        self._wp_host = None
+        self._split_cand = bool(cand.split_candidate) and type(self) is FusedConv
         if ((self._split_cand and FusedConv.pair_mode < 0) or
                 (dtype == torch.float32 and out_dtype == torch.float32 and self.cin_pad == self.cin and self.cin % 32 == 0 and type(self) is FusedConv
                  and FusedConv.pair_mode >= (1 if dims == 3 else 2))):
@@ -308,7 +289,7 @@ class FusedConv:
         """epi: (scale, shift, res_scale) of this call when they differ from the layer's own (the quantised modes: the tensors'
         scales folded in); the direct kernel only -- the Winograd form is fp32."""
         B = x.shape[0]
-        m, xs, wk, wst, wpad = self.wino_tile(tuple(x.shape), x.dtype, res_mode, naive)
+        m, xs, wk, wst, wpad = self.wino_tile(tuple(x.shape), x.dtype, res_mode, naive)     # (the route of a shape is asked once and kept)
         wino = m > 0
         if not wino and epi is None and self.takes_pair_form(tuple(x.shape), x.dtype, naive):   # layers the Winograd form does not take
             return self._pair(x, res, res_mode, relu, res_after_act, post_scale)
@@ -326,7 +307,7 @@ class FusedConv:
                 ops.winograd_trace = []
             xv = x.view(xs)
             rv = None if res is None else res.view(B, res.shape[2], res.shape[3], 1, self.cout) if self._wino2d else res
-            opnd = self._wino_operands(m)
+            opnd = self._route(tuple(x.shape), res_mode).run.wino_operands
             y = ops.conv_winograd_fwd(xv, self._filters(m, opnd), self.scale, self.shift, wk[2], wst[2], wpad, self.relu if relu is None else relu,
                                       rv, wgt_layout=self.layout, res_after_act=res_after_act, post_scale=post_scale, operands=opnd)
             if FusedConv.trace is not None:
@@ -375,14 +356,14 @@ class FusedConv:
         return y
 
     def takes_pair_form(self, x_shape, dtype=torch.float32, naive=False):
+        """The split-operand form takes an input of shape x_shape (the caller asks after the Winograd form refused)."""
         if self.wp is None or naive or dtype != torch.float32:
             return False
+        if FusedConv.pair_mode < 0:       # the rule
+            return self._split_cand and bool(self._route(tuple(x_shape)).split_fits)
         npos = x_shape[0] * x_shape[1] * x_shape[2] * x_shape[3]
-        if FusedConv.pair_mode < 0:       # the default rule (class comment; csrc/model.cpp plan_conv)
-            ok = self._split_cand and FusedConv.wino_operands == ops.IVX_F16_PAIR and npos >= FusedConv.SPLIT_MIN_POS
-        else:
-            ok = FusedConv.pair_mode >= (1 if self._dims == 3 else 2) and npos >= FusedConv.pair_min_pos
-        return ok and ops.conv_pair_supported(x_shape, self.cout, self.kernel, self.stride, self.padding, 1)
+        return (FusedConv.pair_mode >= (1 if self._dims == 3 else 2) and npos >= FusedConv.pair_min_pos
+                and ops.conv_pair_supported(x_shape, self.cout, self.kernel, self.stride, self.padding, 1))
 
     def _pair(self, x, res, res_mode, relu, res_after_act, post_scale):
         """split pass (fp32 -> bf16 pairs) + the three-product bf16 MFMA kernel with the usual fused fp32 epilogue"""
@@ -412,38 +393,46 @@ class FusedConv:
 
     def wino_tile(self, x_shape, dtype=torch.float32, res_mode=0, naive=False):
         """-> (m, xs, wk, wst, wpad): m = tile of the F(m x m, 3x3) form this layer takes for an input of shape x_shape
-        (0: the direct kernel), and the convolution as the Winograd entry points see it (transformed axes first, direct
-        axis last; a 2-D 3x3 layer [B,1,H,W,C] is the view [B,H,W,1,C] with a 3x3x1 kernel)."""
-        B = x_shape[0]
-        if self._wino2d:
-            xs, wk, wst, wpad = (B, x_shape[2], x_shape[3], 1, self.cin), (3, 3, 1), (1, 1, 1), (self.padding[1], self.padding[2], 0)
-        else:
-            xs, wk, wst, wpad = tuple(x_shape), self.kernel, self.stride, self.padding
-        ok = (self.u is not None and FusedConv.winograd and not naive and res_mode in (0, 1) and dtype == torch.float32
-              and x_shape[0] * x_shape[1] * x_shape[2] * x_shape[3] >= FusedConv.winograd_min_pos)
-        m = FusedConv.winograd_tile or (6 if (xs[1] + 2 * wpad[0] - 2) * (xs[2] + 2 * wpad[1] - 2) >= FusedConv.winograd_tile6_min_plane
-                                        else 4)
-        ok = ok and ops.conv_winograd_supported(xs, self.cout, wk, wst, wpad, m)
-        return (m if ok else 0), xs, wk, wst, wpad
-
-    # a 3x3 layer of the pair chain whose Winograd form (three launches on fp32 tensors, fp16 pair operands in the transformed domain)
-    # beats its direct pair form: wide and on a large map, where the direct form is bound by its 5x as many matrix products (measured,
-    # tools/pio_ab.py: 256 -> 256 at 120x160x50 views 2.25 vs 3.14 ms, at 20 views 1.00 vs 1.30; 256 -> 256 at 30x40x50 0.29 vs 0.21, 128 ->
-    # 128 at 60x80x50 0.36 vs 0.24: the rule below takes only the FPN output conv of the FastIndoor configs).  Mirrored by csrc/model.cpp.
-    WINO_OVER_PAIR_MIN_CH, WINO_OVER_PAIR_MIN_POS = 256, 200000
+        (0: the direct kernel), and the convolution as the entry point of that form sees it (Winograd: transformed axes first,
+        direct axis last; a 2-D 3x3 layer [B,1,H,W,C] is the view [B,H,W,1,C] with a 3x3x1 kernel)."""
+        rt = self._route(tuple(x_shape), res_mode)
+        ok = rt.form == 1 and self.u is not None and not naive and dtype == torch.float32
+        d = rt.run
+        if not ok:
+            return 0, tuple(x_shape), self.kernel, self.stride, self.padding
+        return rt.tile, (d.B, d.D, d.H, d.W, d.Cin), (d.KD, d.KH, d.KW), (d.sd, d.sh, d.sw), (d.pd, d.ph, d.pw)
 
     def prefers_winograd(self, npos):
-        return (self._wino2d and self.u is not None and FusedConv.winograd and FusedConv.wino_operands == ops.IVX_F16_PAIR
-                and self.cin >= FusedConv.WINO_OVER_PAIR_MIN_CH and self.cout >= FusedConv.WINO_OVER_PAIR_MIN_CH
-                and npos >= FusedConv.WINO_OVER_PAIR_MIN_POS and self.cin % 32 == 0)
+        """A 2-D 3x3 layer of the pair chain whose Winograd form (fp32 tensors, fp16 pair operands in the transformed domain) beats its direct
+        pair form on a map of npos positions; the FPN asks it for its output convs (backbones.py), as the native handle does."""
+        return self.u is not None and bool(self._route((npos, 1, 1, 1)).prefers_winograd)
+
+    def _route(self, x_shape, res_mode=0, tile=None, split=None, wino_operands=None):
+        """ivx_conv_route for an input of shape x_shape (None: the candidate query) under the class's switches (tile / split / wino_operands:
+        instead of the class's).  One library call per distinct question; the answers are kept."""
+        import ctypes as C
+        from . import _lib
+        o = _lib.ConvRouteOpts(int(FusedConv.winograd), int(FusedConv.winograd_tile if tile is None else tile),
+                               int(FusedConv.wino_operands if wino_operands is None else wino_operands),
+                               int(FusedConv.pair_mode < 0 if split is None else split), int(FusedConv.winograd_min_pos), int(FusedConv.winograd_2d_min_ch))
+        shape = (0, 0, 0, 0) if x_shape is None else tuple(x_shape[:4])
+        key = (shape, res_mode, o.winograd, o.winograd_tile, o.wino_operands, o.split, o.winograd_min_pos, o.winograd_2d_min_ch)
+        rt = self._routes.get(key)
+        if rt is None:
+            code = {torch.float32: 0, torch.bfloat16: 1, FP8: 2}
+            d = _lib.ConvDesc(*shape, self.cin_pad, self.cout, *self.kernel, *self.stride, *self.padding, 0, int(res_mode), 0, 0, self.layout, 0, 0, 1.0,
+                              code[self.dtype], code[self.out_dtype], 1.0, 0)
+            rt = self._routes[key] = _lib.ConvRoute()
+            _lib.check(_lib.lib().ivx_conv_route(C.byref(d), self.cin, C.byref(o), C.byref(rt)), 'ivx_conv_route')
+        return rt
 
     def _describe(self, x, tile):
         k, st = 'x'.join(map(str, self.kernel)), ''.join(map(str, self.stride))
         return f'{self.cin}->{self.cout} k{k} s{st} in {tuple(x.shape[:4])}' + (f' F{tile}' if tile else '')
 
     def _wino_operands(self, tile):
-        ok = FusedConv.wino_operands == ops.IVX_F16_PAIR and tile >= 4 and self.cin % (32 if self.layout == 1 else 16) == 0
-        return ops.IVX_F16_PAIR if ok else 0
+        """operand type of the Winograd-domain GEMMs of this layer at tile m (ivx_conv_desc.wino_operands)"""
+        return self._route(None, tile=tile).run.wino_operands
 
     def _filters(self, tile, operands=None):
         operands = self._wino_operands(tile) if operands is None else operands

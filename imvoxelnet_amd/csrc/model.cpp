@@ -113,7 +113,7 @@ struct ConvLayer {
   std::string bn;                     // BatchNorm prefix or ""
   // deploy form
   int cin_pad = 0, layout = 0;
-  bool wino_cand = false, wino2d = false, identity_epilogue = true;
+  bool wino_cand = false, identity_epilogue = true;
   float *w = nullptr, *w0 = nullptr, *scale = nullptr, *shift = nullptr;
   std::map<int, float *> u;           // tile * 8 + operand type -> transformed filters
   // fp16-pair form (cfg.trunk_operands = IVX_F16_PAIR; ivx_conv_fwd_pio): pair filters, scale / s_w, and the terms of the output bound
@@ -131,8 +131,8 @@ struct ConvLayer {
   double out_scale_q = 1.0;
   bool pair_ok = false;
   float *wpair = nullptr, *scale_p = nullptr;
-  // split-operand (IVX_BF16_PAIR) form of the 3x3x3 neck layers the Winograd form does not take (strided; fewer than 2000 positions): filters as
-  // conv.py pack_pair_weights(layout 1); the layer's input goes through ivx_bf16_pair_split into the step's workspace (conv.py FusedConv._pair)
+  // split-operand (IVX_BF16_PAIR) form of the 3x3x3 neck layers the Winograd form does not take (ivx_conv_route): filters of
+  // ivx_bf16_pair_pack_filters (layout 1); the layer's input goes through ivx_bf16_pair_split into the step's workspace (conv.py FusedConv._pair)
   bool split_cand = false;
   float *wsplit = nullptr;
   float wbound = 0.f, sbound = 0.f;
@@ -600,6 +600,34 @@ const HostTensor *find_w(const ivx_model *m, const std::string &key) {
   return it == m->weights.end() ? nullptr : &it->second;
 }
 
+// What the library's routing rule (ivx_conv_route) is asked with: the geometry and storage types of layer L on the input tensor `in` (B = 0:
+// no shape yet, the candidate query of pack_layer), and the handle's switches.  IVX_CONV_PAIR=0 turns the split-operand rule off (A/B).
+ivx_conv_desc layer_desc(const ivx_model *m, const ConvLayer &L, const TInfo &in) {
+  ivx_conv_desc d;
+  memset(&d, 0, sizeof(d));
+  d.B = in.B; d.D = in.D; d.H = in.H; d.W = in.W; d.Cin = L.cin_pad; d.Cout = L.cout;
+  d.KD = L.k[0]; d.KH = L.k[1]; d.KW = L.k[2];
+  d.sd = L.s[0]; d.sh = L.s[1]; d.sw = L.s[2];
+  d.pd = L.p[0]; d.ph = L.p[1]; d.pw = L.p[2];
+  d.wgt_layout = L.layout;
+  d.out_mode = L.conv_t ? 1 : 0;
+  if (m->cfg.storage == IVX_BF16 && !L.f32) {   // bf16 storage: the direct kernel on bf16 operands, fp32 accumulate; the head convs write fp32
+    d.in_dtype = IVX_BF16;
+    d.out_dtype = L.out_f32 ? IVX_F32 : IVX_BF16;
+  }
+  return d;
+}
+
+ivx_conv_route_opts route_opts(const ivx_model *m) {
+  static const bool split_rule = !(getenv("IVX_CONV_PAIR") && atoi(getenv("IVX_CONV_PAIR")) == 0);
+  ivx_conv_route_opts o;
+  memset(&o, 0, sizeof(o));
+  o.winograd = m->cfg.winograd; o.winograd_tile = m->cfg.winograd_tile; o.wino_operands = m->cfg.wino_operands;
+  o.split = split_rule ? 1 : 0;
+  o.winograd_min_pos = -1;
+  return o;
+}
+
 // Deploy form of one layer: imvoxelnet_amd/conv.py FusedConv.__init__ in C++ (same fp32 operations in the same order).
 int pack_layer(ivx_model *m, ConvLayer &L, hipStream_t st, std::string *missing) {
   const int kd = L.k[0], kh = L.k[1], kw = L.k[2], taps = kd * kh * kw;
@@ -679,11 +707,12 @@ int pack_layer(ivx_model *m, ConvLayer &L, hipStream_t st, std::string *missing)
     co0 = L.cout;
   }
   M_REQUIRE(co0 == L.cout, "ivx_weights_finalize: layer %s: %d output channels loaded, %d expected", L.name.c_str(), co0, L.cout);
-  // Winograd candidate (FusedConv: 3x3 on the transformed axes with stride 1, fp32, unpadded Cin, >= 64 channels 3-D / 128 2-D)
-  L.wino2d = kd == 1 && kh == 3 && kw == 3 && L.s[0] == 1 && L.s[1] == 1 && L.s[2] == 1;
-  const bool wino3d = kd == 3 && kh == 3 && L.s[0] == 1 && L.s[1] == 1;
-  const int min_ch = L.wino2d ? 128 : 64;
-  L.wino_cand = !bf16 && (wino3d || L.wino2d) && L.cin_pad == L.cin && L.cout % 4 == 0 && std::max(L.cin, L.cout) >= min_ch && L.cin % 4 == 0;
+  // which forms the layer is a candidate for, whatever the shape: what to keep / pack for them (ivx_conv_route)
+  const ivx_conv_desc cand_d = layer_desc(m, L, TInfo());
+  const ivx_conv_route_opts ropts = route_opts(m);
+  ivx_conv_route_out cand;
+  M_TRY(ivx_conv_route(&cand_d, L.cin, &ropts, &cand));
+  L.wino_cand = cand.wino_candidate != 0;
   if (L.wino_cand) M_TRY(dev_upload_sync(m, wp.data(), n_w, &L.w0, st));   // tap-major [Cout,kd,kh,kw,Cin]; (1,3,3) is the same memory as (3,3,1)
   const int ck = bf16 ? 64 : 32;
   const float *w_src = wp.data();
@@ -730,30 +759,11 @@ int pack_layer(ivx_model *m, ConvLayer &L, hipStream_t st, std::string *missing)
     M_TRY(dev_upload(m, scale, &L.scale, st));
     M_TRY(dev_upload(m, shift, &L.shift, st));
   }
-  // Split-operand form (conv.py FusedConv: _split_cand / pack_pair_weights): every fp32 filter as hi = bf16(w), lo = bf16(w - hi), per 16 channels
-  // [hi x16 | lo x16], chunk-major [Cout, 2 Cin / 64, taps, 64]
-  static const bool split_rule = !(getenv("IVX_CONV_PAIR") && atoi(getenv("IVX_CONV_PAIR")) == 0);      // IVX_CONV_PAIR=0: off in both hosts (A/B)
-  L.split_cand = split_rule && !bf16 && m->cfg.wino_operands == IVX_F16_PAIR && L.dims == 3 && kd == 3 && kh == 3 && kw == 3 && !L.conv_t && !L.linear && !L.dcn_cols &&
-                 L.cin_pad == L.cin && L.cin % 32 == 0 && L.cout >= 64;
+  // Split-operand form: the filters as chunk-major IVX_BF16_PAIR values (conv.py pack_pair_weights calls the same packer)
+  L.split_cand = cand.split_candidate && !L.conv_t && !L.linear && !L.dcn_cols;
   if (L.split_cand) {
     std::vector<uint16_t> wb(2 * n_w);
-    const int nch = L.cin / 32;
-    for (int co = 0; co < L.cout; ++co)
-      for (int ch = 0; ch < nch; ++ch)
-        for (int t = 0; t < taps; ++t) {
-          const float *src = &wp[((size_t)co * taps + t) * L.cin + ch * 32];
-          uint16_t *dst = &wb[(((size_t)co * nch + ch) * taps + t) * 64];
-          for (int g = 0; g < 2; ++g)
-            for (int j = 0; j < 16; ++j) {
-              const float w = src[g * 16 + j];
-              const uint16_t hi = f32_to_bf16_bits(w);
-              uint32_t hb = (uint32_t)hi << 16;
-              float hf;
-              memcpy(&hf, &hb, 4);
-              dst[g * 32 + j] = hi;
-              dst[g * 32 + 16 + j] = f32_to_bf16_bits(w - hf);
-            }
-        }
+    M_TRY(ivx_bf16_pair_pack_filters(wp.data(), L.cout, taps, L.cin, 1, wb.data()));
     M_TRY(dev_upload_sync(m, reinterpret_cast<const float *>(wb.data()), n_w, &L.wsplit, st));
   }
   // fp16-pair form of the 2-D trunk (cfg.trunk_operands): pair filters + scale / s_w, and the bound terms (also for the layers that
@@ -822,31 +832,20 @@ int conv_out(const ConvLayer &L, const TInfo &in, TInfo *o) {
   return IVX_OK;
 }
 
-constexpr int64_t SPLIT_MIN_POS = 256;      // conv.py FusedConv.SPLIT_MIN_POS
-// The Winograd decision of FusedConv.wino_tile (conv.py): returns the tile (0 = direct) and the descriptor to run.
+// The form of one conv step (ivx_conv_route): the tile (0 = direct) and the descriptor to run.
 int plan_conv(ivx_model *m, ConvLayer &L, const TInfo &in, const Step &st, const TInfo *res, PlanStep *ps, hipStream_t stream, int out_fmt = 0) {
-  ivx_conv_desc d;
-  memset(&d, 0, sizeof(d));
-  d.B = in.B; d.D = in.D; d.H = in.H; d.W = in.W; d.Cin = in.C; d.Cout = L.cout;
-  d.KD = L.k[0]; d.KH = L.k[1]; d.KW = L.k[2];
-  d.sd = L.s[0]; d.sh = L.s[1]; d.sw = L.s[2];
-  d.pd = L.p[0]; d.ph = L.p[1]; d.pw = L.p[2];
+  M_REQUIRE(in.C == L.cin_pad, "layer %s: input has %d channels, expected %d", L.name.c_str(), in.C, L.cin_pad);
+  ivx_conv_desc d = layer_desc(m, L, in);
   d.relu = L.relu ? 1 : 0;
   d.res_mode = st.res_mode;
   if (st.res_mode == 2) { d.res_h = res->H; d.res_w = res->W; }
-  d.wgt_layout = L.layout; d.post_scale = st.post_scale;
+  d.post_scale = st.post_scale;
   d.res_after_act = st.res_after_act;
-  d.out_mode = L.conv_t ? 1 : 0;
-  M_REQUIRE(in.C == L.cin_pad, "layer %s: input has %d channels, expected %d", L.name.c_str(), in.C, L.cin_pad);
-  if (m->cfg.storage == IVX_BF16 && !L.f32) {   // bf16 storage: the direct kernel on bf16 operands, fp32 accumulate; the head convs write fp32
-    d.in_dtype = IVX_BF16;
-    d.out_dtype = L.out_f32 ? IVX_F32 : IVX_BF16;
-    if (m->fp8_on && L.fp8_eff) {     // e4m3 interior of a bottleneck: tensor scales are folded into scale_q / shift_q
-      d.in_dtype = L.fp8_eff == 1 ? IVX_BF16 : IVX_FP8;
-      d.out_dtype = L.fp8_eff == 3 ? IVX_BF16 : IVX_FP8;
-      if (L.fp8_eff >= 2) d.wgt_layout = L.layout_q;
-      d.res_scale = 1.0f;
-    }
+  if (m->cfg.storage == IVX_BF16 && !L.f32 && m->fp8_on && L.fp8_eff) {     // e4m3 interior of a bottleneck: tensor scales are folded into scale_q / shift_q
+    d.in_dtype = L.fp8_eff == 1 ? IVX_BF16 : IVX_FP8;
+    d.out_dtype = L.fp8_eff == 3 ? IVX_BF16 : IVX_FP8;
+    if (L.fp8_eff >= 2) d.wgt_layout = L.layout_q;
+    d.res_scale = 1.0f;
   }
   if (in.fmt == IVX_F16_PAIR) {      // the fp16-pair form: direct kernel on the 16-bit matrix cores, scales on the device
     M_REQUIRE(L.pair_ok && L.wpair, "internal: layer %s reads a pair tensor but has no pair filters", L.name.c_str());
@@ -867,23 +866,14 @@ int plan_conv(ivx_model *m, ConvLayer &L, const TInfo &in, const Step &st, const
   // an error (round-4 advisor).  Unreachable with ResNet-50 -- a tensor is a pair only when every INPUT consumer reads pairs, and a
   // residual's producer and consumer sit in the same bottleneck -- but the format rule must not rest on that.
   M_REQUIRE(!res || res->fmt == 0, "internal: layer %s has an fp32 input and a pair residual (the pair chain broke between them)", L.name.c_str());
-  int tile = 0;
-  ivx_conv_desc dw = d;
-  if (L.wino_cand && !L.conv_t && m->cfg.winograd && m->cfg.storage == IVX_F32 && (st.res_mode == 0 || st.res_mode == 1) && (int64_t)in.B * in.D * in.H * in.W >= 2000) {
-    if (L.wino2d) {   // [B,1,H,W,C] as [B,H,W,1,C] with a 3x3x1 kernel
-      dw.D = in.H; dw.H = in.W; dw.W = 1;
-      dw.KD = 3; dw.KH = 3; dw.KW = 1; dw.sd = dw.sh = dw.sw = 1;
-      dw.pd = L.p[1]; dw.ph = L.p[2]; dw.pw = 0;
-    }
-    const int64_t plane = (int64_t)(dw.D + 2 * dw.pd - 2) * (dw.H + 2 * dw.ph - 2);
-    tile = m->cfg.winograd_tile ? m->cfg.winograd_tile : (plane >= 16384 ? 6 : 4);
-    ivx_conv_desc probe = dw;
-    probe.relu = 0; probe.res_mode = 0; probe.wgt_layout = 0;
-    if (!ivx_conv_winograd_supported(&probe, tile)) tile = 0;
-    // operands of the transformed-domain GEMMs (FusedConv._wino_operands): fp16 pairs where the layer's channel count allows
-    if (tile >= 4 && m->cfg.wino_operands == IVX_F16_PAIR && L.cin % (L.layout == 1 ? 32 : 16) == 0) dw.wino_operands = IVX_F16_PAIR;
-  }
+  const ivx_conv_route_opts ropts = route_opts(m);
+  ivx_conv_route_out rt;
+  M_TRY(ivx_conv_route(&d, L.cin, &ropts, &rt));
+  // the handle's own gates: only plain convolutions of an fp32 handle leave the direct form, the split-operand form only with its filters packed
+  const bool plain = !L.conv_t && !L.linear && !L.dcn_cols && m->cfg.storage == IVX_F32;
+  const int tile = plain && rt.form == 1 && L.wino_cand ? rt.tile : 0;
   if (tile) {
+    const ivx_conv_desc &dw = rt.run;
     ps->d = dw;
     ps->ws = ivx_conv_winograd_workspace_bytes(&dw, tile);
     M_REQUIRE(ps->ws >= 0, "layer %s: %s", L.name.c_str(), ivx_last_error());
@@ -907,12 +897,10 @@ int plan_conv(ivx_model *m, ConvLayer &L, const TInfo &in, const Step &st, const
       L.u[ukey] = (float *)u;
     }
   } else {
-    // the split-operand form for the 3x3x3 layers the Winograd form did not take (conv.py FusedConv.takes_pair_form, the default rule): the
-    // strided convolutions of the necks and the layers of their coarsest levels; fp32 tensors on both sides, 16-bit matrix cores in between
-    if (L.split_cand && L.wsplit && m->cfg.storage == IVX_F32 && (int64_t)in.B * in.D * in.H * in.W >= SPLIT_MIN_POS && ivx_conv_pair_supported(&d) == 1) {
+    // the split-operand form: fp32 tensors on both sides, 16-bit matrix cores in between; the (hi, lo) copy of the input leads the workspace
+    if (plain && rt.form == 2 && L.split_cand && L.wsplit) {
       ps->split = align256((int64_t)in.elems() * 4);
-      d.in_dtype = IVX_BF16_PAIR;
-      d.wgt_layout = 1;
+      d = rt.run;
     }
     ps->d = d;
     ps->ws = ivx_conv_workspace_bytes(&d);
@@ -954,13 +942,15 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
       }
       if (j < m->trunk0 || j >= m->trunk1 || q.kind != ST_CONV || !m->layers[q.layer].pair_ok) return false;
       {   // a wide 3x3 layer on a large map keeps fp32 tensors and runs in its Winograd form with pair operands in the transformed domain
-          // (conv.py FusedConv.prefers_winograd: 256 -> 256 at 120x160x50 2.25 vs 3.14 ms for the direct pair form)
+          // (ivx_conv_route: prefers_winograd).  Only the FPN output conv is asked: the bottleneck's conv2 always takes the direct pair form in
+          // BOTH hosts (backbones.py _Bottleneck.forward_cl does not consult the predicate either).
         const ConvLayer &Lq = m->layers[q.layer];
-        // Only the FPN output conv: the bottleneck's conv2 always takes the direct pair form in BOTH hosts (backbones.py _Bottleneck.forward_cl
-        // does not consult prefers_winograd; a rule applied to every wide trunk 3x3 here would let the two copies drift apart at 167+ views).
-        if (Lq.name.rfind("neck.fpn_conv", 0) == 0 && Lq.wino2d && Lq.wino_cand && c.winograd && c.wino_operands == IVX_F16_PAIR && Lq.cin >= 256 &&
-            Lq.cout >= 256 && Lq.cin % 32 == 0 && (int64_t)ti.B * ti.H * ti.W >= 200000)
-          return false;
+        if (Lq.name.rfind("neck.fpn_conv", 0) == 0 && Lq.wino_cand) {
+          const ivx_conv_desc dq = layer_desc(m, Lq, ti);
+          const ivx_conv_route_opts ropts = route_opts(m);
+          ivx_conv_route_out rq;
+          if (ivx_conv_route(&dq, Lq.cin, &ropts, &rq) == IVX_OK && rq.prefers_winograd) return false;
+        }
       }
       any = true;
     }

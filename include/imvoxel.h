@@ -39,7 +39,7 @@ typedef void *ivx_stream_t; /* hipStream_t */
 
 /* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header; 420 = 0.4.2: bf16 storage with
  * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size; 440 = 0.4.4: ivx_backproject_fwd_ex / ivx_model_cfg.sampling, the optional
- * bilinear sampling rule of the unprojection) and the message of the last failing call on
+ * bilinear sampling rule of the unprojection; 450 = 0.4.5: ivx_conv_route / ivx_bf16_pair_pack_filters) and the message of the last failing call on
  * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -133,6 +133,10 @@ int ivx_conv_fwd_ws(const ivx_conv_desc *d, const void *in, const void *wgt, con
 int ivx_bf16_pair_split(const float *in, int64_t n, void *out, ivx_stream_t stream);
 int ivx_f16_pair_split(const float *in, int64_t n, float scale, void *out, ivx_stream_t stream);   /* IVX_F16_PAIR of scale * in, saturating */
 int ivx_conv_pair_supported(const ivx_conv_desc *d);
+/* Host-only (both hosts of the library call it): fp32 filters w [Cout][taps][Cin] (tap-major, Cin % 16 == 0) -> the IVX_BF16_PAIR operand
+ * `packed` (2 * Cout * taps * Cin bf16 values): hi = bf16(w), lo = bf16(w - hi), 16-channel groups [hi x16 | lo x16];
+ * wgt_layout 0: [Cout][taps][2 Cin], 1 (Cin % 32 == 0): chunk-major [Cout][2 Cin / 64][taps][64]. */
+int ivx_bf16_pair_pack_filters(const float *w, int32_t Cout, int32_t taps, int32_t Cin, int32_t wgt_layout, void *packed);
 
 /* ---------------------------------------------------------------------------------------
  * Chained fp16-pair activations (0.4.0): the 2-D trunk on the 16-bit matrix cores without split passes.
@@ -283,6 +287,33 @@ int ivx_conv_winograd_output(const ivx_conv_desc *d, int32_t tile, const float *
 int ivx_conv_winograd_fwd(const ivx_conv_desc *d, int32_t tile, const void *in, const float *u, const float *scale,
                           const float *shift, const void *res, void *out, void *workspace, int64_t workspace_bytes,
                           ivx_stream_t stream);
+/* Host-only: the form a convolution layer runs in -- the ONE routing rule of the library, asked by every host of the kernels (the model
+ * handle and imvoxelnet_amd/conv.py FusedConv), so both launch the same kernels on the same shapes.  All thresholds and their measurements
+ * are in csrc/api_common.cpp.
+ *   d         the layer as ivx_conv_fwd sees it (Cin = padded channels, wgt_layout = the layout of its direct filters, res_mode, dtypes);
+ *             B == 0: no shape yet -- only the candidate flags are answered (what the host keeps / packs when it loads the filters) and
+ *             `run` carries the kernel as the Winograd form would see it and the wino_operands a forced tile o->winograd_tile would take
+ *   cin_real  input channels of the layer before padding (the Winograd and split-operand forms need Cin unpadded)
+ * Gates that are a host's own stay with the host: a validation run on the naive kernel, quantised epilogues, transposed / linear / DCN-column
+ * layers, the storage mode of a handle. */
+typedef struct ivx_conv_route_opts {      /* model-level switches that bear on the route */
+  int32_t winograd;                       /* Winograd form on (ivx_model_cfg.winograd / FusedConv.winograd, IVX_WINOGRAD) */
+  int32_t winograd_tile;                  /* 0 = by plane size | 2 | 4 | 6 (IVX_WINOGRAD_TILE) */
+  int32_t wino_operands;                  /* 0 | IVX_F16_PAIR (IVX_WINO_OPERANDS) */
+  int32_t split;                          /* split-operand rule on (IVX_CONV_PAIR != 0) */
+  int64_t winograd_min_pos;               /* < 0: the rule's own value; fewest input positions of the Winograd form otherwise (lab) */
+  int32_t winograd_2d_min_ch;             /* <= 0: the rule's own value; channel floor of the 2-D Winograd candidates otherwise (lab) */
+} ivx_conv_route_opts;
+typedef struct ivx_conv_route {
+  int32_t form;                           /* 0 direct, 1 Winograd, 2 split-operand direct (only where the Winograd form does not apply) */
+  int32_t tile;                           /* m of F(m x m, 3x3) when form == 1, else 0 */
+  int32_t wino_candidate, split_candidate;/* shape-independent: keep the tap-major fp32 filters / pack the IVX_BF16_PAIR filters (under `o`) */
+  int32_t split_fits;                     /* the split-operand rule holds for this shape, whether or not the Winograd form comes first */
+  int32_t prefers_winograd;               /* a 2-D layer of the pair chain that should keep fp32 tensors and run its Winograd form here */
+  ivx_conv_desc run;                      /* descriptor to launch: form 1 the Winograd view (a 2-D layer [B,1,H,W,C] as [B,H,W,1,C] with a 3x3x1
+                                             kernel) with wino_operands set; form 2 in_dtype IVX_BF16_PAIR, wgt_layout 1; form 0 = *d */
+} ivx_conv_route_out;
+int ivx_conv_route(const ivx_conv_desc *d, int32_t cin_real, const ivx_conv_route_opts *o, ivx_conv_route_out *r);
 /* Chained Winograd layers with fp16-pair operands: the scale of V needs max |in|, which ivx_conv_winograd_input takes with a pass over
  * the tensor.  When `in` is the output of another Winograd layer, that layer's output transform can leave one maximum per workgroup
  * (`partials`, ivx_conv_winograd_output_blocks(d, tile) floats, caller-owned device memory) and the consumer's input stage reduces those

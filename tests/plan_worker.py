@@ -1,14 +1,18 @@
 """Worker of tests/test_host_plan.py and tests/test_gpu_plan_switches.py (also imported by them for the in-process checks).
 
 The planner reads IVX_SIDE_STREAM, IVX_FUSE_BOTTLENECK and IVX_FUSE_STEM once per process, so the other setting of a switch needs a fresh
-process: the calling test starts this script with the switch in the environment.  Two jobs, on libimvoxel_hip.so (--lib hip) or on the CPU
+process: the calling test starts this script with the switch in the environment.  Three jobs, on libimvoxel_hip.so (--lib hip) or on the CPU
 restatement of the same ABI (--lib cpu):
 
   plans  build one handle per family, plan one shape each through the *_workspace_bytes queries, read the plans back through the view of
          include/imvoxel_lab.h and run tests/plan_check.py on them; one JSON line with what was seen (sites, fuse values) and any defect.
   run    build a seeded model, run four steps alternating two seeded inputs (A, B, A, B) through ivx_model_detect and save, per step, every
          boundary tensor of the plan (FPN level 0, volume, valid mask, neck output or levels, head output) read out of the arena plus the
-         detections to an .npz; --phases runs the four steps once per trace level in the SAME process (prefix t<level>_)."""
+         detections to an .npz; --phases runs the four steps once per trace level in the SAME process (prefix t<level>_).
+  routes record tests/golden/conv_routes.json: which form every convolution takes (direct, Winograd with which tile and operands, split-operand).
+         Section `layers` (no GPU) asks the FusedConv queries on a grid of layers, shapes and switches; section `plans` (GPU, planning only)
+         reads the conv steps of every family's detect plan at the BASELINE shapes.  Run it at the commit whose rule is to be the reference,
+         BEFORE the rule is touched: tests/test_conv_route.py and tests/test_gpu_plan_switches.py hold every later commit to the file."""
 import argparse
 import ctypes as C
 import json
@@ -312,15 +316,124 @@ def compare_runs(a, b, prefix_a, prefix_b=None):
     return len(names)
 
 
+# ------------------------------------------------------------------------------------------------- job: routes
+ROUTES_FILE = os.path.join(HERE, 'golden', 'conv_routes.json')
+PLAN_MODES = [(0, 4, 4), (0, 0, 0), (1, 4, 4)]           # (storage, trunk_operands, wino_operands) of the handles the plan tests build
+ROUTE_DEFAULTS = dict(winograd=True, winograd_tile=0, wino_operands=IVX_F16_PAIR, pair_mode=-1)      # the switches a route row may override
+# FusedConv arguments (Cout, Cin, kernel, stride, padding, dims, layout) of the grid's layers
+ROUTE_LAYERS = [(co, ci, (3, 3, 3), (1, 1, 1), 1, 3, lay) for co, ci, lay in ((64, 64, None), (128, 128, None), (256, 256, None), (32, 32, None),
+                                                                             (48, 48, 0), (40, 40, None), (25, 64, None))] + \
+               [(128, 64, (3, 3, 3), (1, 1, 2), 1, 3, None), (128, 64, (3, 3, 3), (2, 2, 2), 1, 3, None), (512, 256, (3, 3, 3), (2, 2, 2), 1, 3, None),
+                (128, 64, (1, 1, 1), (1, 1, 1), 0, 3, None)] + \
+               [(c, c, (3, 3), (1, 1), 1, 2, None) for c in (64, 128, 256)] + \
+               [(128, 128, (3, 3), (2, 2), 1, 2, None), (64, 256, (1, 1), (1, 1), 0, 2, None), (64, 3, (7, 7), (2, 2), 3, 2, None)]
+# input shapes (B, D, H, W) on both sides of every threshold: 1980 / 2000 positions, planes of 16256 / 16384 padded positions, 192 / 256 positions,
+# the 31-bit refusals of the split form (64 x 216 x 248 x 12 at 64 channels) and of the Winograd form (one transformed plane past 2 GiB)
+ROUTE_SHAPES_3D = [(1, 9, 11, 20), (1, 10, 10, 20), (1, 127, 128, 2), (1, 128, 128, 2), (1, 8, 8, 3), (1, 8, 8, 4), (1, 40, 40, 16), (64, 216, 248, 12),
+                   (16, 1296, 1296, 12)]
+# ... and for the 2-D layers: the same plane sizes, 197500 / 200000 positions (prefers_winograd), 1980 / 2000 positions, a plane past 2 GiB
+ROUTE_SHAPES_2D = [(1, 1, 127, 128), (1, 1, 128, 128), (50, 1, 50, 79), (50, 1, 50, 80), (1, 1, 36, 55), (1, 1, 40, 50), (64, 1, 2592, 2592)]
+ROUTE_SWITCHES = [{}, dict(winograd=False), dict(winograd_tile=2), dict(winograd_tile=4), dict(winograd_tile=6), dict(wino_operands=0),
+                  dict(pair_mode=0), dict(res_mode=1), dict(res_mode=2), dict(naive=True), dict(winograd_tile=6, wino_operands=0),
+                  dict(winograd_tile=2, wino_operands=0), dict(winograd=False, wino_operands=0), dict(winograd=False, pair_mode=0),
+                  dict(winograd=False, res_mode=2), dict(winograd=False, naive=True), dict(res_mode=2, pair_mode=0), dict(res_mode=1, winograd_tile=4)]
+
+
+def route_layer(spec):
+    """The FusedConv of a ROUTE_LAYERS entry, built on the host under the default switches."""
+    import torch
+    from imvoxelnet_amd.conv import FusedConv
+    co, ci, k, st, pad, dims, lay = spec
+    return FusedConv(torch.zeros(co, ci, *k), stride=tuple(st), padding=pad, dims=dims, layout=lay).to('cpu')
+
+
+class route_switches:
+    """with route_switches(sw): the FusedConv class attributes of ROUTE_DEFAULTS, overridden by the entries of `sw` that name one."""
+
+    def __init__(self, sw):
+        self.sw = dict(ROUTE_DEFAULTS, **{k: v for k, v in sw.items() if k in ROUTE_DEFAULTS})
+
+    def __enter__(self):
+        from imvoxelnet_amd.conv import FusedConv
+        self.old = {k: getattr(FusedConv, k) for k in self.sw}
+        for k, v in self.sw.items():
+            setattr(FusedConv, k, v)
+
+    def __exit__(self, *exc):
+        from imvoxelnet_amd.conv import FusedConv
+        for k, v in self.old.items():
+            setattr(FusedConv, k, v)
+        return False
+
+
+def route_answer(f, shape, sw):
+    """What the FusedConv queries say about layer f on the input `shape` (B, D, H, W) under the switches `sw`:
+    [m, operands of that tile, takes_pair_form, prefers_winograd] and the view [xs, wk, wst, wpad] of wino_tile."""
+    x_shape = tuple(shape) + (f.cin_pad,)
+    with route_switches(sw):
+        m, xs, wk, wst, wpad = f.wino_tile(x_shape, res_mode=sw.get('res_mode', 0), naive=sw.get('naive', False))
+        ans = [int(m), int(f._wino_operands(m)), bool(f.takes_pair_form(x_shape, naive=sw.get('naive', False))),
+               bool(f.prefers_winograd(shape[0] * shape[1] * shape[2] * shape[3]))]
+    return ans, [list(map(int, v)) for v in (xs, wk, wst, wpad)]
+
+
+def conv_rows(plan):
+    """(name, tile, pio, split, ws) of every conv step of a plan read through the plan view."""
+    return [[s['name'], s['tile'], s['pio'], s['split'], s['ws']] for _, s in sorted(plan['steps'].items()) if s['kind'] == 2]
+
+
+def plan_key(fam, mode, shape):
+    return f'{fam} {"/".join(map(str, mode))} {"x".join(map(str, shape))}'
+
+
+def job_routes(args):
+    out = json.load(open(ROUTES_FILE)) if os.path.exists(ROUTES_FILE) else {}
+    out['commit'] = args.commit
+    if args.section in ('layers', 'all'):
+        with route_switches({}):
+            layers = [route_layer(spec) for spec in ROUTE_LAYERS]
+        sec = dict(layers=[list(spec) + [bool(f._split_cand), f._w0_host is not None] for spec, f in zip(ROUTE_LAYERS, layers)],
+                   switches=ROUTE_SWITCHES, views=[], rows=[])
+        for li, f in enumerate(layers):
+            for shape in (ROUTE_SHAPES_3D if f._dims == 3 else ROUTE_SHAPES_2D):
+                for wi, sw in enumerate(ROUTE_SWITCHES):
+                    ans, view = route_answer(f, shape, sw)
+                    if wi == 0:
+                        sec['views'].append([li, list(shape)] + view)
+                    else:
+                        assert view == sec['views'][-1][2:]            # the view is a matter of layer and shape alone
+                    sec['rows'].append([li, list(shape), wi] + ans)
+        out['layers'] = sec
+    if args.section in ('plans', 'all'):
+        L = load_lib('hip')
+        sec = {}
+        for fam in FAMILIES:
+            model = family_model(fam)
+            for mode in PLAN_MODES:
+                hd = Handle(L, model, *mode)
+                try:
+                    for shape in FULL_SHAPES[fam]:
+                        sec[plan_key(fam, mode, shape)] = conv_rows(hd.plan('detect', *shape)[0])
+                finally:
+                    hd.close()
+        out['plans'] = sec
+    with open(args.out or ROUTES_FILE, 'w') as fh:
+        fh.write('{\n' + ',\n'.join(f' {json.dumps(k)}: ' + (json.dumps(v) if k == 'commit' else '{\n' + ',\n'.join(
+            f'  {json.dumps(k2)}: {json.dumps(v2, separators=(",", ":"))}' for k2, v2 in v.items()) + '\n }') for k, v in out.items()) + '\n}\n')
+    print(json.dumps({k: (v if k == 'commit' else {k2: len(v2) for k2, v2 in v.items()} if k == 'layers' else len(v)) for k, v in out.items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('job', choices=['plans', 'run'])
+    ap.add_argument('job', choices=['plans', 'run', 'routes'])
     ap.add_argument('--lib', choices=['cpu', 'hip'], default='cpu')
     ap.add_argument('--config', default='kitti_small')
     ap.add_argument('--phases', default='0', help='comma-separated trace levels; the four steps run once per level')
     ap.add_argument('--out', default=None)
+    ap.add_argument('--section', choices=['layers', 'plans', 'all'], default='all', help='routes: the section(s) to record; the other is kept')
+    ap.add_argument('--commit', default='', help='routes: short hash of the commit whose rule is recorded')
     args = ap.parse_args()
-    {'plans': job_plans, 'run': job_run}[args.job](args)
+    {'plans': job_plans, 'run': job_run, 'routes': job_routes}[args.job](args)
 
 
 if __name__ == '__main__':

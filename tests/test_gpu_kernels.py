@@ -894,7 +894,10 @@ def test_conv_winograd_fused_conv_switch(ia):
         y = f(x, res=res)
     finally:
         FusedConv.count_flops = False
-    m = FusedConv.winograd_tile or (6 if 108 * 124 >= FusedConv.winograd_tile6_min_plane else 4)
+    m = f.wino_tile(tuple(x.shape))[0]
+    assert m == (FusedConv.winograd_tile or 4)               # a padded plane of 108 x 124 positions: below the 16384 of F(6x6, 3x3)
+    if not FusedConv.winograd_tile:                          # ... the rule at that boundary: 127 x 129 = 16383 positions, 128 x 128 = 16384
+        assert f.wino_tile((2, 127, 129, 6, 128))[0] == 4 and f.wino_tile((2, 128, 128, 6, 128))[0] == 6
     tiles = -(-108 // m) * -(-124 // m)
     assert abs(FusedConv.exec_flops / FusedConv.flops - (m + 2) ** 2 * tiles / (9.0 * 108 * 124)) < 1e-6   # the minimal-filtering path ran
     old = FusedConv.winograd

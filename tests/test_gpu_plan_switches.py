@@ -100,10 +100,15 @@ def test_fusion_switches_stay_within_the_pair_chain_bound(tmp_path):
 
 
 def test_plan_invariants_on_the_hip_library():
-    """The checker of tests/test_host_plan.py on libimvoxel_hip.so's plans at the BASELINE shapes, through the same read-only view."""
+    """The checker of tests/test_host_plan.py on libimvoxel_hip.so's plans at the BASELINE shapes, through the same read-only view.  The form
+    of every conv step of the detect plans (tile, pair input, split-operand bytes, workspace) is the one recorded in tests/golden/conv_routes.json
+    before the routing rule became one library function (plan_worker.py routes)."""
+    import json
     import torch
     assert torch.cuda.is_available(), 'gpu tests need a HIP device'
     L = pw.load_lib('hip')
+    routes = json.load(open(pw.ROUTES_FILE))['plans']
+    n_routes = 0
     n_plans = n_site_plans = n_reused = n_chained = 0
     fuse_seen = set()
     for fam in pw.FAMILIES:
@@ -124,6 +129,11 @@ def test_plan_invariants_on_the_hip_library():
                         n_reused += st['reused']
                         n_chained += st['chained']
                         fuse_seen.update(st['fuse'])
+                        if what == 'detect':
+                            want, got = routes[pw.plan_key(fam, mode, shape)], pw.conv_rows(plan)
+                            assert got == want, f'{fam} {mode} detect at {shape}: conv steps (name, tile, pio, split, ws) differ from the recorded routes: ' \
+                                                f'{[(g, w) for g, w in zip(got, want) if g != w][:4]} ({len(got)} steps, {len(want)} recorded)'
+                            n_routes += 1
                         if what == 'detect' and mode == (0, 4, 4):
                             print(f'  {fam} detect at {shape}: total {st["total"]} bytes, workspace {st["ws_bytes"]}, second workspace {st["ws2_bytes"]} '
                                   f'(sized as the whole workspace it would be {st["ws_bytes"]}: total {st["total"] - st["ws2_bytes"] + st["ws_bytes"]})')
@@ -133,5 +143,6 @@ def test_plan_invariants_on_the_hip_library():
     print(f'plans checked {n_plans}, plans with side sites {n_site_plans}, fuse values seen {sorted(fuse_seen)}, reused arena offsets seen {n_reused}, '
           f'chained maxima seen {n_chained}')
     assert n_plans == sum(len(v) for v in pw.FULL_SHAPES.values()) * 3 * 4
+    assert n_routes == len(routes) == n_plans // 4
     assert n_site_plans > 0 and n_reused > 0 and {1, 3, 4, 5} <= fuse_seen
     assert n_chained > 0          # Winograd layers with pair operands hand per-workgroup maxima to each other on this library

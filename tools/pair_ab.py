@@ -51,7 +51,7 @@ def accuracy():
             out[mode] = (e.abs().max().item() / scale, e.pow(2).mean().sqrt().item() / rms)
         print(f'accuracy {ci}->{co} K={27 * ci} act x{act}: ' + ' | '.join(f'{m}: max/max|y| {a:.2e} rms/rms {b:.2e}' for m, (a, b) in out.items()), flush=True)
     FusedConv.winograd_tile = 0
-    FusedConv.winograd_min_pos = 2000
+    FusedConv.winograd_min_pos = -1          # the rule's own value again
     FusedConv.pair_min_pos = 2000
     FusedConv.wino_operands = 0
 
