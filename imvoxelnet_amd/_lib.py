@@ -68,7 +68,7 @@ def sampling_id(sampling):
 
 
 class BackprojectDesc(C.Structure):
-    """ivx_backproject_desc (ivx_backproject_fwd_ex)."""
+    """ivx_backproject_desc (ivx_backproject_fwd_ex, ivx_backproject_gather_fwd)."""
     _fields_ = [(n, C.c_int32) for n in ('B', 'V', 'FH', 'FW', 'C', 'X', 'Y', 'Z')] + [('voxel_size', C.c_float * 3)] + \
                [(n, C.c_int32) for n in ('feat_dtype', 'mode', 'sampling', 'first')]
 
@@ -146,7 +146,7 @@ EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor'
            'ivx_conv_winograd_supported', 'ivx_conv_winograd_weight_elems', 'ivx_conv_winograd_weights', 'ivx_conv_winograd_workspace_bytes',
            'ivx_conv_winograd_input', 'ivx_conv_winograd_gemm', 'ivx_conv_winograd_output', 'ivx_conv_winograd_fwd',
            'ivx_maxpool2d_fwd', 'ivx_maxpool2d_fwd_bf16', 'ivx_maxpool2d_fwd_fp8', 'ivx_global_avgpool_fwd', 'ivx_global_avgpool_fwd_bf16', 'ivx_upsample_trilinear2x_fwd', 'ivx_dcn_im2col_fwd', 'ivx_dcn_im2col_fwd_bf16', 'ivx_dcn_im2col_fwd_pair', 'ivx_nchw_to_nhwc', 'ivx_image_s2d_bf16', 'ivx_nhwc_to_nchw', 'ivx_backproject_mean_fwd', 'ivx_backproject_mean_fwd_amax', 'ivx_backproject_amax_blocks', 'ivx_backproject_mean_fwd_bf16', 'ivx_upsample_trilinear2x_fwd_bf16', 'ivx_backproject_sum_fwd', 'ivx_volume_normalize_fwd',
-           'ivx_backproject_accum_fwd', 'ivx_backproject_accum_fwd_bf16', 'ivx_volume_mean_fwd', 'ivx_backproject_fwd_ex',
+           'ivx_backproject_accum_fwd', 'ivx_backproject_accum_fwd_bf16', 'ivx_volume_mean_fwd', 'ivx_backproject_fwd_ex', 'ivx_backproject_gather_fwd',
            'ivx_anchor_head_workspace_bytes', 'ivx_anchor_head_get_bboxes', 'ivx_fcos_head_workspace_bytes',
            'ivx_fcos_head_level_candidates', 'ivx_nms_workspace_bytes',
            'ivx_nms_bev', 'ivx_boxes_overlap_bev', 'ivx_aligned_3d_nms', 'ivx_aligned_3d_nms_workspace_bytes', 'ivx_aligned_3d_nms_ws', 'ivx_multiclass_nms_workspace_bytes', 'ivx_multiclass_nms_bev',
@@ -250,6 +250,8 @@ def lib():
     L.ivx_volume_mean_fwd.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
     if hasattr(L, 'ivx_backproject_fwd_ex'):       # (0.4.4; an older build of the same ABI, IVX_LIB_PATH, still loads: ops then refuses the bilinear rule)
         L.ivx_backproject_fwd_ex.argtypes = [C.POINTER(BackprojectDesc), vp, vp, vp, vp, vp, vp, vp, vp, vp]
+    if hasattr(L, 'ivx_backproject_gather_fwd'):   # (0.4.6; an older build still loads: ops.backproject_gather_mean and windowed scenes then refuse)
+        L.ivx_backproject_gather_fwd.argtypes = [C.POINTER(BackprojectDesc), i32, vp, vp, vp, vp, vp, vp, vp, vp]
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -32,6 +32,7 @@
 // (bp_bilinear_sample below, the one function every mode and element type calls), then the same view sum and division.
 #include "ivx_common.h"
 #include <stdlib.h>
+#include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -53,6 +54,12 @@ struct BpParams {
   int lpv_log2; // lanes per voxel = 1 << lpv_log2
   float *pmax;  // single-view lift only: per-workgroup max |volume| goes to pmax[blockIdx.y * gridDim.x + blockIdx.x], or NULL
   int nblk, q;  // multi-view kernel: voxel blocks per sample and per XCD (grid.x = 8 * q, see the kernel's block order); q = 0: plain order (A/B)
+};
+// GATHER instantiations of backproject_mean_kernel (the others keep BpParams as their one argument): feat is a pool [S, FH, FW, C], proj a pool
+// [S, 12], and view v of sample b is slot view_slot[b * V + v] of both
+struct BpGatherParams : BpParams {
+  const int *view_slot;     // [B, V]
+  int S;
 };
 
 // MODE BP_MEAN: the reference's view mean + valid mask.  BP_SUM (view-sharded multi-GPU mode): the raw sum over
@@ -83,8 +90,12 @@ __device__ __forceinline__ void bp_bilinear_weights(const float ax, const float 
   w[2] = __fmul_rn(bx, ay);
   w[3] = __fmul_rn(ax, ay);
 }
-template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST>
-__global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p) {
+// GATHER (ivx_backproject_gather_fwd; sliding-window scenes): the views are read through a slot list instead of from one contiguous stack.  Only
+// the projecting lane's addressing differs -- which map and which projection rows view v is --; the broadcast, the sample function, the view-order
+// __fadd_rn chain, the division and the stores are the code of every other mode, so the result is bit for bit the non-gathered launch over a
+// contiguous copy of the listed views.  A slot outside [0, S) is tested before any address is formed: that view sees no voxel (off stays -1).
+template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false>
+__global__ __launch_bounds__(256) void backproject_mean_kernel(const std::conditional_t<GATHER, BpGatherParams, BpParams> p) {
   typedef T tv4 __attribute__((ext_vector_type(4)));
   constexpr bool MEAN = MODE == BP_MEAN;
   const int b = blockIdx.y;
@@ -146,8 +157,16 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
     int off = -1;
     int step = 0;               // BP_BILINEAR: bit 0 = x1 is one pixel right of x0, bit 1 = y1 is one row below y0 (0 where the clamp joins them)
     float ax = 0.f, ay = 0.f;   // BP_BILINEAR: the fractions
-    if (v < p.V) {
-      const float *P = p.proj + ((size_t)b * p.V + v) * 12;
+    int slot = 0;               // GATHER: the slot of this view
+    bool listed = v < p.V;
+    if constexpr (GATHER) {
+      if (listed) {
+        slot = p.view_slot[b * p.V + v];
+        listed = slot >= 0 && slot < p.S;
+      }
+    }
+    if (listed) {
+      const float *P = p.proj + (GATHER ? (size_t)slot : (size_t)b * p.V + v) * 12;
       float u = __fmul_rn(P[0], px);
       u = __fmaf_rn(P[1], py, u);
       u = __fmaf_rn(P[2], pz, u);
@@ -163,7 +182,7 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
       const float xr = rintf(__fdiv_rn(u, d));
       const float yr = rintf(__fdiv_rn(w_, d));
       const bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
-      if (ok) off = (((b * p.V + v) * p.FH + (int)yr) * p.FW + (int)xr);
+      if (ok) off = (((GATHER ? slot : b * p.V + v) * p.FH + (int)yr) * p.FW + (int)xr);
       if constexpr (SAMP == BP_BILINEAR) {
         if (ok) {               // a valid sample: xf in [-0.5, wc - 0.5], so the floors are in [-1, wc - 1] and fit an int
           const float xf = __fdiv_rn(u, d), yf = __fdiv_rn(w_, d);
@@ -173,7 +192,7 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const BpParams p)
           const int x0 = max((int)fx, 0), x1 = min((int)fx + 1, wc - 1);     // x0 <= wc - 1 and x1 >= 0 already
           const int y0 = max((int)fy, 0), y1 = min((int)fy + 1, hc - 1);
           step = (x1 - x0) | ((y1 - y0) << 1);
-          off = (((b * p.V + v) * p.FH + y0) * p.FW + x0);                   // corner 00
+          off = (((GATHER ? slot : b * p.V + v) * p.FH + y0) * p.FW + x0);   // corner 00
         }
       }
     }
@@ -633,4 +652,52 @@ extern "C" int ivx_backproject_fwd_ex(const ivx_backproject_desc *d, const void 
   }
   if (bf16) return ivx_backproject_accum_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, d->first, mean_out, valid, stream);
   return ivx_backproject_accum_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, d->first, (float *)mean_out, valid, stream);
+}
+
+// Gathered mean lift (include/imvoxel.h): the listed views of a feature / projection pool, in list order.  Every shape, one view included, runs
+// the GATHER instantiation of backproject_mean_kernel.
+extern "C" int ivx_backproject_gather_fwd(const ivx_backproject_desc *d, int32_t S, const void *feat_pool, const float *proj_pool, const int32_t *view_slot,
+                                          const float *new_origin, const int32_t *crop_hw, void *volume, uint8_t *valid, ivx_stream_t stream) {
+  const char *what = "ivx_backproject_gather_fwd";
+  IVX_REQUIRE(d, "%s: null descriptor", what);
+  IVX_REQUIRE(d->sampling == IVX_SAMPLE_NEAREST || d->sampling == IVX_SAMPLE_BILINEAR, "%s: sampling %d (IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR)", what, d->sampling);
+  IVX_REQUIRE(d->mode == IVX_LIFT_MEAN, "%s: mode %d (IVX_LIFT_MEAN only)", what, d->mode);
+  IVX_REQUIRE(d->feat_dtype == IVX_F32 || d->feat_dtype == IVX_BF16, "%s: feat_dtype %d (IVX_F32 | IVX_BF16)", what, d->feat_dtype);
+  IVX_REQUIRE(feat_pool && proj_pool && view_slot && new_origin && crop_hw && volume && valid, "%s: null argument", what);
+  IVX_REQUIRE(S > 0, "%s: S=%d slots (the pools need at least one)", what, S);
+  IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
+  IVX_REQUIRE(d->C % 4 == 0, "%s: C %% 4 must be 0", what);
+  IVX_REQUIRE(d->C <= 1024, "%s: C=%d too large (max 1024)", what, d->C);
+  IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
+  IVX_REQUIRE((int64_t)S * d->FH * d->FW < (1LL << 31), "%s: feature pool too large", what);
+  IVX_REQUIRE(d->B <= 65535, "%s: batch too large", what);
+  IVX_REQUIRE((int64_t)d->B * d->V < (1LL << 31), "%s: view list too large", what);
+  BpGatherParams p;
+  p.feat = (const float *)feat_pool; p.proj = proj_pool; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = (float *)volume; p.valid = valid;
+  p.count = nullptr; p.mean_out = nullptr; p.first = 0; p.pmax = nullptr;
+  p.view_slot = view_slot; p.S = S;
+  p.vs0 = d->voxel_size[0]; p.vs1 = d->voxel_size[1]; p.vs2 = d->voxel_size[2];
+  p.V = d->V; p.FH = d->FH; p.FW = d->FW; p.C = d->C; p.X = d->X; p.Y = d->Y; p.Z = d->Z; p.N = d->X * d->Y * d->Z;
+  p.nchunk = d->C / 4;
+  int lg = 0;
+  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
+  p.lpv_log2 = lg;
+  const int vpb = 256 >> lg;
+  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
+  const dim3 grid(bp_grid(p), d->B), block(256);
+  hipStream_t st = (hipStream_t)stream;
+  const bool bf16 = d->feat_dtype == IVX_BF16;
+  if (d->sampling == IVX_SAMPLE_BILINEAR) {
+    if (bf16)
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true>), grid, block, 0, st, p);
+  } else {
+    if (bf16)
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true>), grid, block, 0, st, p);
+    else
+      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true>), grid, block, 0, st, p);
+  }
+  IVX_CHECK_LAUNCH(what);
+  return IVX_OK;
 }

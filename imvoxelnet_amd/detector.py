@@ -349,12 +349,14 @@ class ImVoxelNet(nn.Module):
             img = img.unsqueeze(1)
         return self.simple_test(img, [dict(m, **s) for m, s in zip(img_metas, shapes)])
 
-    def open_scene(self, meta):
+    def open_scene(self, meta, window=None):
         """A streaming scene on this model (scene.SceneSession): add_views / add_views_u8 fold new views into a running volume,
         detect() works on the views so far.  meta: one img_metas entry without lidar2img['extrinsic'].  Several sessions may be open
-        on one prepared model."""
+        on one prepared model.  window=W >= 1: the scene holds the last W views at most (the oldest leaves when a new one arrives,
+        remove_views(ids) drops any) and its volume is exactly the one-shot lift of the views it holds; the trunk still runs once
+        per view.  Costs a ring of W FPN level-0 maps (scene.py has the figures)."""
         from .scene import SceneSession
-        return SceneSession(self, meta)
+        return SceneSession(self, meta, window=window)
 
     @staticmethod
     def _results_one_copy(boxes, scores, labels, count, img_metas, with_yaw=True, indoor=False):

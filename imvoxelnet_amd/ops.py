@@ -856,6 +856,63 @@ def _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
     return vol, valid.view(torch.bool)
 
 
+def backproject_gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
+    """backproject_mean over views listed by slot (ivx_backproject_gather_fwd): pool [S,1,FH,FW,C] (or [S,FH,FW,C]) fp32 or bf16 and
+    proj_pool [S,3,4] hold one view per slot, view_slot [B,V] lists the views of every sample in the order they count.  The result is
+    bit for bit backproject_mean over a contiguous copy of the listed views; slots may repeat, unlisted slots are never read.
+    view_slot: a host sequence / CPU int32 tensor (range-checked here, then uploaded: a slot outside [0, S) raises ValueError) or a
+    device int32 tensor, used as it is (the kernel treats an out-of-range slot as a view that sees nothing).
+    -> volume [B,X,Y,Z,C] (pool's dtype), valid [B,X,Y,Z] bool."""
+    sampling = _lib.sampling_id(sampling)
+    if not isinstance(pool, torch.Tensor) or not isinstance(proj_pool, torch.Tensor):
+        raise TypeError('pool and proj_pool must be torch.Tensors')
+    if pool.dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'pool must be float32 or bfloat16, got {pool.dtype}')
+    if pool.dim() == 5 and pool.shape[1] == 1:
+        pool = pool[:, 0]
+    if pool.dim() != 4 or tuple(proj_pool.shape) != (pool.shape[0], 3, 4):
+        raise ValueError(f'pool must be [S,FH,FW,C] (or [S,1,FH,FW,C]) and proj_pool [S,3,4], got {tuple(pool.shape)} and {tuple(proj_pool.shape)}')
+    S, FH, FW, Cn = (int(v) for v in pool.shape)
+    host = None
+    if not (isinstance(view_slot, torch.Tensor) and view_slot.is_cuda):       # a host list: checked here, uploaded once the pools have passed
+        host = view_slot if isinstance(view_slot, torch.Tensor) else torch.as_tensor(view_slot)
+        if host.dtype not in (torch.int32, torch.int64) or host.dim() != 2 or host.numel() == 0:
+            raise ValueError('a host view_slot must be a [B,V] list / tensor of integers with B, V >= 1')
+        bad = sorted(set(int(v) for v in host.flatten().tolist() if not 0 <= v < S))
+        if bad:
+            raise ValueError(f'view_slot holds slots outside [0, {S}): {bad}')
+    _chk(pool, 'pool', pool.dtype)
+    _chk(proj_pool, 'proj_pool')
+    if host is not None:
+        view_slot = host.to(torch.int32).contiguous().to(pool.device)
+    _chk(view_slot, 'view_slot', torch.int32)
+    if view_slot.dim() != 2 or view_slot.shape[0] < 1 or view_slot.shape[1] < 1:
+        raise ValueError(f'view_slot must be [B,V] with B, V >= 1, got {tuple(view_slot.shape)}')
+    _chk(new_origin, 'new_origin')
+    _chk(crop_hw, 'crop_hw', torch.int32)
+    B, V = (int(v) for v in view_slot.shape)
+    if tuple(new_origin.shape) != (B, 3) or tuple(crop_hw.shape) != (B, 2):
+        raise ValueError('new_origin must be [B,3] and crop_hw [B,2] for the B rows of view_slot')
+    fn = getattr(_lib.lib(), 'ivx_backproject_gather_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_gather_fwd (needs version 0.4.6)')
+    X, Y, Z = (int(v) for v in n_voxels)
+    vol = torch.empty((B, X, Y, Z, Cn), device=pool.device, dtype=pool.dtype)
+    valid = torch.empty((B, X, Y, Z), device=pool.device, dtype=torch.uint8)
+    _backproject_gather(fn, pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, vol, valid, sampling)
+    return vol, valid.view(torch.bool)
+
+
+def _backproject_gather(fn, pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, vol, valid, sampling):
+    """ivx_backproject_gather_fwd on checked tensors: pool [S,FH,FW,C], view_slot [B,V] on the device, vol / valid written in place."""
+    S, FH, FW, Cn = pool.shape
+    B, V = view_slot.shape
+    X, Y, Z = vol.shape[1:4]
+    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], _LIFT_MEAN, int(sampling), 0)
+    check(fn(C.byref(d), S, _ptr(pool), _ptr(proj_pool), _ptr(view_slot), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(valid), _stream()),
+          'ivx_backproject_gather_fwd')
+
+
 def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
     """View-sharded mode: like backproject_mean but returns the raw view sum [B,X,Y,Z,C] and the int32 view count
     [B,X,Y,Z] of THIS rank's views (to be all-reduced, then volume_normalize_).  sampling as for backproject_mean."""

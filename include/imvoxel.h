@@ -39,7 +39,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
 
 /* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header; 420 = 0.4.2: bf16 storage with
  * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size; 440 = 0.4.4: ivx_backproject_fwd_ex / ivx_model_cfg.sampling, the optional
- * bilinear sampling rule of the unprojection; 450 = 0.4.5: ivx_conv_route / ivx_bf16_pair_pack_filters) and the message of the last failing call on
+ * bilinear sampling rule of the unprojection; 450 = 0.4.5: ivx_conv_route / ivx_bf16_pair_pack_filters; 460 = 0.4.6: ivx_backproject_gather_fwd, the mean lift of
+ * views listed by slot, for sliding-window scenes) and the message of the last failing call on
  * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -554,6 +555,28 @@ typedef struct ivx_backproject_desc {
 } ivx_backproject_desc;
 int ivx_backproject_fwd_ex(const ivx_backproject_desc *d, const void *feat, const float *proj, const float *new_origin,
                            const int32_t *crop_hw, void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream);
+
+/* (0.4.6) Gathered mean lift: the views are listed by slot.  A caller that keeps the maps of a changing set of views (a sliding window over a
+ * scan, a replaced keyframe: scene.py) lifts the set it holds NOW in one launch, straight from its ring of slots, with no copy into a
+ * contiguous stack and no subtraction from a running sum.
+ *
+ * d           the descriptor of ivx_backproject_fwd_ex; d->V is the number of LISTED views per sample, d->mode must be IVX_LIFT_MEAN,
+ *             sampling and feat_dtype as there; C % 4 == 0, C <= 1024
+ * feat_pool   [S, FH, FW, C]   (feat_dtype) the slots' FPN level-0 maps
+ * proj_pool   [S, 3, 4]        the slots' projection rows
+ * view_slot   [B, V] int32     DEVICE: view v of sample b is slot view_slot[b*V + v] of both pools
+ * new_origin, crop_hw, volume [B,X,Y,Z,C] (feat_dtype), valid [B,X,Y,Z] u8: as for the mean mode of ivx_backproject_fwd_ex
+ * Contract.  The result equals ivx_backproject_fwd_ex (IVX_LIFT_MEAN, same sampling and feat_dtype) over a contiguous copy of the listed
+ * views, in list order, bit for bit: the same kernel template, of which only the projecting lane's addressing differs.  (One listed view runs
+ * this kernel too: its sum starts from +0, so a -0 feature comes out as +0 where the nearest single-view copy kernel keeps the sign.)  Slots may
+ * repeat: a slot listed twice counts as two views.  A slot outside [0, S) is an unseen view: nothing of it is read and no voxel counts it
+ * (a guard in the kernel, tested before any address is formed; callers should validate their lists).  Unlisted slots are never read, so
+ * they may hold anything.
+ * IVX_ERR_INVALID_ARG before any launch: a null descriptor or pointer, S <= 0, non-positive dims, C % 4 != 0, C > 1024, a mode other than
+ * IVX_LIFT_MEAN, an unknown sampling or feat_dtype, X*Y*Z or S*FH*FW at or beyond 2^31, B > 65535 (or B*V at or beyond 2^31).          */
+int ivx_backproject_gather_fwd(const ivx_backproject_desc *d, int32_t S, const void *feat_pool, const float *proj_pool,
+                               const int32_t *view_slot /*device [B,V]*/, const float *new_origin, const int32_t *crop_hw,
+                               void *volume, uint8_t *valid, ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
