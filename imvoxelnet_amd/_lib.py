@@ -143,6 +143,8 @@ def declare_plan_view(L):
 
 
 EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor', 'ivx_bottleneck_proj_supported', 'ivx_bottleneck_proj_pack', 'ivx_bottleneck_proj_fwd_pio', 'ivx_anchor_head_decode', 'ivx_fcos3d_head_decode', 'ivx_nms_rotated_bev', 'ivx_nms_aligned3d', 'ivx_bottleneck_supported', 'ivx_bottleneck_fwd_pio', 'ivx_amax_f32', 'ivx_stem_pool_filter_bytes', 'ivx_stem_pool_pack_filters', 'ivx_stem_pool_out_dims', 'ivx_stem_pool_fwd_pair', 'ivx_conv_winograd_set_variant', 'ivx_ubench_mfma', 'ivx_ubench_copy', 'ivx_version', 'ivx_last_error', 'ivx_conv_out_dims', 'ivx_conv_fwd', 'ivx_conv_fwd_naive', 'ivx_conv_set_tile_override', 'ivx_conv_set_epilogue_mode', 'ivx_conv_set_plan_mode', 'ivx_topk_set_mode', 'ivx_conv_workspace_bytes', 'ivx_conv_fwd_ws', 'ivx_conv_set_halo_mode', 'ivx_bf16_pair_split', 'ivx_f16_pair_split', 'ivx_conv_pair_supported', 'ivx_bf16_pair_pack_filters', 'ivx_conv_route', 'ivx_conv_pio_workspace_bytes', 'ivx_conv_fwd_pio', 'ivx_conv_fwd_pio_naive', 'ivx_pair_pack_filters', 'ivx_nchw_to_nhwc_amax', 'ivx_maxpool2d_fwd_pair', 'ivx_f16_pair_merge', 'ivx_model_calibrate_fp8', 'ivx_model_calibrate_fp8_ex', 'ivx_amax_bf16', 'ivx_conv_winograd_output_blocks', 'ivx_conv_winograd_issued_fraction', 'ivx_conv_winograd_output_amax', 'ivx_conv_winograd_input_amax', 'ivx_conv_winograd_fused_supported', 'ivx_conv_winograd_fused_blocks', 'ivx_conv_winograd_gemm_output_amax',
+           'ivx_conv_winograd_bg_supported', 'ivx_conv_winograd_bg_bytes', 'ivx_conv_winograd_bg_layer_offset', 'ivx_conv_winograd_bg_plan',
+           'ivx_conv_winograd_input_bg', 'ivx_conv_winograd_gemm_bg', 'ivx_conv_winograd_output_bg',
            'ivx_conv_winograd_supported', 'ivx_conv_winograd_weight_elems', 'ivx_conv_winograd_weights', 'ivx_conv_winograd_workspace_bytes',
            'ivx_conv_winograd_input', 'ivx_conv_winograd_gemm', 'ivx_conv_winograd_output', 'ivx_conv_winograd_fwd',
            'ivx_maxpool2d_fwd', 'ivx_maxpool2d_fwd_bf16', 'ivx_maxpool2d_fwd_fp8', 'ivx_global_avgpool_fwd', 'ivx_global_avgpool_fwd_bf16', 'ivx_upsample_trilinear2x_fwd', 'ivx_dcn_im2col_fwd', 'ivx_dcn_im2col_fwd_bf16', 'ivx_dcn_im2col_fwd_pair', 'ivx_nchw_to_nhwc', 'ivx_image_s2d_bf16', 'ivx_nhwc_to_nchw', 'ivx_backproject_mean_fwd', 'ivx_backproject_mean_fwd_amax', 'ivx_backproject_amax_blocks', 'ivx_backproject_mean_fwd_bf16', 'ivx_upsample_trilinear2x_fwd_bf16', 'ivx_backproject_sum_fwd', 'ivx_volume_normalize_fwd',
@@ -188,6 +190,15 @@ def lib():
     L.ivx_conv_winograd_fused_blocks.argtypes = [C.POINTER(ConvDesc), i32]
     L.ivx_conv_winograd_fused_blocks.restype = i32
     L.ivx_conv_winograd_gemm_output_amax.argtypes = [C.POINTER(ConvDesc), i32, vp, vp, vp, vp, vp, vp, i64, vp, vp]
+    L.ivx_conv_winograd_bg_supported.argtypes = [C.POINTER(ConvDesc), i32]
+    L.ivx_conv_winograd_bg_bytes.argtypes = [C.POINTER(ConvDesc), i32]
+    L.ivx_conv_winograd_bg_bytes.restype = i64
+    L.ivx_conv_winograd_bg_layer_offset.argtypes = [C.POINTER(ConvDesc), i32]
+    L.ivx_conv_winograd_bg_layer_offset.restype = i64
+    L.ivx_conv_winograd_bg_plan.argtypes = [C.POINTER(ConvDesc), vp, i32, C.POINTER(i32), vp, i64, vp]
+    L.ivx_conv_winograd_input_bg.argtypes = [C.POINTER(ConvDesc), i32, vp, vp, i64, vp, i32, vp, vp]
+    L.ivx_conv_winograd_gemm_bg.argtypes = [C.POINTER(ConvDesc), i32, vp, vp, i64, vp, vp]
+    L.ivx_conv_winograd_output_bg.argtypes = [C.POINTER(ConvDesc), i32, vp, vp, vp, vp, vp, i64, vp, vp, vp]
     L.ivx_bf16_pair_split.argtypes = [vp, i64, vp, vp]
     L.ivx_f16_pair_split.argtypes = [vp, i64, f32, vp, vp]
     L.ivx_conv_pair_supported.argtypes = [C.POINTER(ConvDesc)]

@@ -89,6 +89,10 @@ struct ConvParams {
   // the output transform reads -- was a 4-byte hipMemcpyAsync, i.e. one more launch per neck layer); NULL = none
   const unsigned *cp_src;
   unsigned *cp_dst;
+  // Row count of the launch on the DEVICE (conv_wino_halo_kernel / conv_wino_zblk_kernel: the compacted Winograd-domain GEMMs of a neck
+  // whose background tiles are computed once, winograd.hip): *m_dev <= M rows are computed; the grid keeps the size of M rows and the
+  // surplus workgroups return before their first barrier.  NULL = M.
+  const int *m_dev;
   // Phase stagger of the first round of workgroups (pair-IO launches with a residual epilogue, run_conv): workgroups whose XCD-local index q has bit
   // stagger_shift set and q < stagger_first wait stagger_ticks (100 MHz) before their first request, so that the K loops of one half of the resident
   // workgroups overlap the epilogues of the other half for the rest of the launch.  0 ticks = off.
@@ -1451,7 +1455,7 @@ static int fill_params(const ivx_conv_desc *d, const void *in, const void *wgt, 
 #ifdef IVX_CONV_TIMELINE
   p->tl = g_timeline;
 #endif
-  p->cp_src = nullptr; p->cp_dst = nullptr;
+  p->cp_src = nullptr; p->cp_dst = nullptr; p->m_dev = nullptr;
   p->pio = 0; p->in_scale_p = nullptr; p->out_pair = 0; p->res_pair = 0; p->res_scale_p = nullptr; p->out_scale_p = nullptr;
   p->amax_in = p->amax_res = nullptr; p->amax_out = nullptr; p->wbound = 0.f; p->sbound = 0.f;
   if (io) {
@@ -1921,18 +1925,22 @@ __global__ __launch_bounds__(64 * WR * WC, WPE) void conv_wino_halo_kernel(const
   static_assert(sizeof(smem) >= (size_t)NT / 64 * 4096, "4 KB of staging LDS per wave for the transposed epilogue");
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wr = wid / WC, wc = wid % WC;
+  // device-side row count: the XCD quota follows it (the host's q_total would leave whole XCDs with empty tiles)
+  const int M = p.m_dev ? *p.m_dev : p.M;
+  const int q_total = p.m_dev ? ((M + BMO - 1) / BMO + 7) >> 3 : p.q_total;
   int mt, nt;
   {
     const int Nt = (p.Cout + BN - 1) / BN;
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
     const int lt = idx / Nt;
     nt = idx - lt * Nt;
-    mt = xcd * p.q_total + lt;
+    mt = xcd * q_total + lt;
+    if (p.cp_dst && blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) *p.cp_dst = *p.cp_src;      // (before the returns: *m_dev may be 0)
+    if (lt >= q_total) return;                    // (only with m_dev: the grid was sized for p.M rows)
   }
-  if (mt * BMO >= p.M) return;
+  if (mt * BMO >= M) return;
   const int m0 = mt * BMO, n0 = nt * BN;
   const size_t gz = blockIdx.z;
-  if (p.cp_dst && blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) *p.cp_dst = *p.cp_src;
 #ifdef IVX_CONV_TIMELINE
   const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long tl1 = 0, tl2 = 0;
@@ -1954,7 +1962,7 @@ __global__ __launch_bounds__(64 * WR * WC, WPE) void conv_wino_halo_kernel(const
     const int li = j < APASS ? lr + RP * j : BM + (lane >> 2);
     const int row = SW * m0 - 1 + (DI ? (li < BM ? 2 * li : 2 * (li - BM) + 1) : li);
     const bool zr = ZR && !TAIL && li == ZROW;
-    a_base[j] = (row >= 0 && row < SW * p.M && (j < APASS || (lane >> 2) < 2) && !zr) ? ((unsigned)row * (unsigned)p.Cin + cc * EPC) * (unsigned)sizeof(T) : OOB;
+    a_base[j] = (row >= 0 && row < SW * M && (j < APASS || (lane >> 2) < 2) && !zr) ? ((unsigned)row * (unsigned)p.Cin + cc * EPC) * (unsigned)sizeof(T) : OOB;
   }
   // B: LDS row t * BN + n holds filter row n0 + n of tap t; chunk-major K: (32 real channels = 64 stored) x tap
   unsigned b_base[BPASS];
@@ -2097,7 +2105,7 @@ __global__ __launch_bounds__(64 * WR * WC, WPE) void conv_wino_halo_kernel(const
     // the same LDS-transposed 16-byte stores (conv_epilogue_wide), plain values, rows limited to the BM - 2 this tile owns
     float *stage = reinterpret_cast<float *>(smem) + wid_u * 1024;
     float *outp = p.out + gz * (size_t)p.g_out;
-    const int mlim = (m0 + BMO < p.M) ? m0 + BMO : p.M;
+    const int mlim = (m0 + BMO < M) ? m0 + BMO : M;
     const int col_l = lane & 31, hh = lane >> 5, rrow = lane >> 3, c4 = (lane & 7) * 4;
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
@@ -2165,23 +2173,26 @@ __global__ __launch_bounds__(64 * WCOL * (Z / 3) * WN, WPE) void conv_wino_zblk_
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int wid_u = __builtin_amdgcn_readfirstlane(wid);
   const int cg = wid_u / (ZH * WN), zh = (wid_u / WN) % ZH, nb = wid_u % WN;
+  const int M = p.m_dev ? *p.m_dev : p.M;         // device-side row count (see conv_wino_halo_kernel)
+  const int q_total = p.m_dev ? ((M + CT * Z - 1) / (CT * Z) + 7) >> 3 : p.q_total;
   int mt, nt;
   {
     const int Nt = (p.Cout + BN - 1) / BN;
     const int xcd = blockIdx.x & 7, idx = blockIdx.x >> 3;
     const int lt = idx / Nt;
     nt = idx - lt * Nt;
-    mt = xcd * p.q_total + lt;
+    mt = xcd * q_total + lt;
+    if (p.cp_dst && blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) *p.cp_dst = *p.cp_src;
+    if (lt >= q_total) return;
   }
   const int c0 = mt * CT, n0 = nt * BN;          // first column of the tile
   const int m0 = c0 * Z;                         // its first OUTPUT row (columns x Z)
-  if (m0 >= p.M) return;
+  if (m0 >= M) return;
 #ifdef IVX_CONV_TIMELINE
   const unsigned long long tl0 = __builtin_amdgcn_s_memrealtime();
   unsigned long long tl1 = 0, tl2 = 0;
 #endif
   const size_t gz = blockIdx.z;
-  if (p.cp_dst && blockIdx.x == 0 && blockIdx.z == 0 && tid == 0) *p.cp_dst = *p.cp_src;
   const __amdgpu_buffer_rsrc_t rs_in =
       __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)p.in + gz * (size_t)p.g_in * sizeof(T)), 0, in_bytes, 0x00020000);
   const __amdgpu_buffer_rsrc_t rs_w =
@@ -2196,7 +2207,7 @@ __global__ __launch_bounds__(64 * WCOL * (Z / 3) * WN, WPE) void conv_wino_zblk_
     const int li = lr + RP * j;                                  // LDS row: z * CT + c
     const int z = li / CT, c = li - z * CT;
     const int row = (c0 + c) * ZI + z;                           // input plane row of (column, z)
-    a_base[j] = (li < AR && row < SW * p.M) ? ((unsigned)row * (unsigned)p.Cin + cc * EPC) * (unsigned)sizeof(T) : OOB;
+    a_base[j] = (li < AR && row < SW * M) ? ((unsigned)row * (unsigned)p.Cin + cc * EPC) * (unsigned)sizeof(T) : OOB;
   }
 #pragma unroll
   for (int j = 0; j < BPASS; ++j) {
@@ -2286,7 +2297,7 @@ __global__ __launch_bounds__(64 * WCOL * (Z / 3) * WN, WPE) void conv_wino_zblk_
     for (int q = 0; q < 4; ++q) {
       const f32x4 v = *reinterpret_cast<const f32x4 *>(stage + (rrow + 8 * q) * 32 + c4);
       const int m = m0 + (cg * 32 + rrow + 8 * q) * Z + z0 + zo;      // plane row of (column, z)
-      if (m < p.M && nok) *reinterpret_cast<f32x4 *>(outp + (size_t)m * p.Cout + nbc) = v;
+      if (m < M && nok) *reinterpret_cast<f32x4 *>(outp + (size_t)m * p.Cout + nbc) = v;
     }
   }
 #ifdef IVX_CONV_TIMELINE
@@ -2909,8 +2920,49 @@ extern "C" float ivx_conv_winograd_issued_fraction(const ivx_conv_desc *d) {
   return 7.0f / 9.0f;
 }
 
+// The z-halo / z-blocked config (ivx_conv_launch_halo) the library's rule gives one xi convolution of a grouped launch, 0 = another kernel.
+static int grouped_halo_cfg(const ConvParams &p, const ivx_conv_desc *d, int groups) {
+  // z-halo kernel (TU 5): 1x1x3 along z, stride 1, pad 1, chunk-major fp16 pairs -- the ResModule layers of the stack necks
+  if (p.in_pair == 2 && p.kmode == 1 && d->KD == 1 && d->KH == 1 && d->KW == 3 && d->sw == 2 && d->pw == 1 && p.W == 2 * p.Wo && p.Cin % 64 == 0 &&
+      ((g_halo_mode >= 21 && g_halo_mode < 30) || (g_halo_mode >= 40 && g_halo_mode < 50) || g_halo_mode >= 70 || (g_halo_mode < 0 && g_tile_override == 0))) {
+    // (round 4, tools/halo_ab.py, profiles/r04_halo_ab.md: the zero-row form 42 vs 22: 0.494 / 0.790 vs 0.492 / 0.811 ms; de-interleaved staging
+    // 43 / 45: equal -- neither the masks nor the bank conflicts are what this kernel waits for)
+    return g_halo_mode >= 21 ? g_halo_mode : 42;
+  }
+  if (p.in_pair == 2 && p.kmode == 1 && d->KD == 1 && d->KH == 1 && d->KW == 3 && d->sw == 1 && d->pw == 1 && p.Cin % 64 == 0 &&
+      ((g_halo_mode > 0 && g_halo_mode < 21) || (g_halo_mode >= 30 && g_halo_mode < 40) || (g_halo_mode >= 50 && g_halo_mode < 70) ||
+       (g_halo_mode < 0 && g_tile_override == 0))) {
+    // measured (tools/pair_ab.py --halo N, profiles/r03b_pair_ab_halo.log; generic kernel 0.73 / 0.90 / 1.41 ms for Cout 64 / 128 / 256):
+    // with the 16-row tail pass: 128 x 64 at three per CU 0.57 / 0.84 / 1.44, 256 x 64 0.60-0.64 / 0.83 / 1.33, 256 x 128 0.99 / 0.84 / 1.37,
+    // 256 x 256 (16 waves) 1.40-1.44 / 1.19 / 1.24-1.27; every three-buffer ring is slower than its two-buffer form (resident workgroups
+    // hide the load latency better than depth does).  Overlapping tiles without the tail pass: 126 x 64 at FOUR per CU 0.49 / 0.74 / 1.35,
+    // 254 x 64 0.51 / 0.72 / 1.23, 254 x 128 (8 waves, two per CU) 0.65 / 0.64 / 1.15, 254 x 256 1.19 / 1.10 / 1.20
+    // round 4: the zero-row forms (30 / 33: the fragment ADDRESS of a masked tap selected once per tile instead of 32 v_cndmask per group):
+    // 125 x 64 0.487 / 0.756 / 1.410 (= 10), 253 x 128 0.597 / 0.644 / 1.144 (13: 0.607 / 0.653 / 1.167); bit-identical results
+    // round 4, z-blocked tiles for 3-slice columns (50: a tap outside the column is skipped instead of multiplied by zeros: 7 of 9
+    // tap-slices): 256 -> 256 at 216 x 248 x 3 0.99 vs 1.135-1.15 ms, bit-identical; at 6 slices (60) 0.626-0.651 vs 0.637-0.650: a wash
+    // round 6: small volumes (the indoor necks: 200 .. 1600 rows per Winograd position).  The 253 x 128 tile on 8 waves leaves most CUs idle there --
+    // 72 workgroups for 256 -> 256 at 20 x 20 x 8 -- and the 125 x 64 tile at four per CU wins for every Cout: 0.073 -> 0.050 ms (12 launches per ScanNet v1
+    // step), 512 -> 512 0.208 -> 0.163, 128 -> 128 at 40 x 40 x 16 0.037 -> 0.033 (tools/neck_halo_ab.py, profiles/r06_halo_small_volumes.md); bit-identical
+    // results.  Rule: fewer workgroups of the 253 x 128 tile than the chip has slots for them (512).  IVX_HALO_SMALL=0 turns it off (A/B).
+    static const int halo_small = getenv("IVX_HALO_SMALL") ? atoi(getenv("IVX_HALO_SMALL")) : 1;
+    const bool few = halo_small && p.Cout > 64 && !zblk_rule(p) && (long long)((p.M + 252) / 253) * ((p.Cout + 127) / 128) * groups < 512;
+    return g_halo_mode > 0 ? g_halo_mode : ((p.Cout <= 64 || few) ? 30 : (zblk_rule(p) ? 50 : 33));
+  }
+  return 0;
+}
+
+// Internal (winograd.hip): can the grouped launch of `d` take its row count from the device (ConvParams::m_dev)?  Only the z-halo and
+// z-blocked kernels read it.
+int ivx_conv_grouped_rows_dev_ok(const ivx_conv_desc *d, int groups) {
+  ConvParams p;
+  float dummy;
+  if (!d || fill_params(d, &dummy, &dummy, nullptr, nullptr, nullptr, &dummy, &p) != IVX_OK || !dma_applicable(p)) return 0;
+  return grouped_halo_cfg(p, d, groups) != 0;
+}
+
 int ivx_conv_grouped_launch(const ivx_conv_desc *d, int groups, const float *in, long long g_in, const float *wgt, long long g_w,
-                            float *out, long long g_out, hipStream_t st, const unsigned *cp_src, unsigned *cp_dst) {
+                            float *out, long long g_out, hipStream_t st, const unsigned *cp_src, unsigned *cp_dst, const int *m_dev) {
   ConvParams p;
   int rc = fill_params(d, in, wgt, nullptr, nullptr, nullptr, out, &p);
   if (rc != IVX_OK) return rc;
@@ -2932,33 +2984,11 @@ int ivx_conv_grouped_launch(const ivx_conv_desc *d, int groups, const float *in,
     p.cp_src = cp_src; p.cp_dst = cp_dst;
   }
   p.groups = groups; p.g_in = g_in; p.g_w = g_w; p.g_out = g_out;
-  // z-halo kernel (TU 5): 1x1x3 along z, stride 1, pad 1, chunk-major fp16 pairs -- the ResModule layers of the stack necks
-  if (p.in_pair == 2 && p.kmode == 1 && d->KD == 1 && d->KH == 1 && d->KW == 3 && d->sw == 2 && d->pw == 1 && p.W == 2 * p.Wo && p.Cin % 64 == 0 &&
-      ((g_halo_mode >= 21 && g_halo_mode < 30) || (g_halo_mode >= 40 && g_halo_mode < 50) || g_halo_mode >= 70 || (g_halo_mode < 0 && g_tile_override == 0))) {
-    // (round 4, tools/halo_ab.py, profiles/r04_halo_ab.md: the zero-row form 42 vs 22: 0.494 / 0.790 vs 0.492 / 0.811 ms; de-interleaved staging
-    // 43 / 45: equal -- neither the masks nor the bank conflicts are what this kernel waits for)
-    return ivx_conv_launch_halo(p, g_halo_mode >= 21 ? g_halo_mode : 42, st);
-  }
-  if (p.in_pair == 2 && p.kmode == 1 && d->KD == 1 && d->KH == 1 && d->KW == 3 && d->sw == 1 && d->pw == 1 && p.Cin % 64 == 0 &&
-      ((g_halo_mode > 0 && g_halo_mode < 21) || (g_halo_mode >= 30 && g_halo_mode < 40) || (g_halo_mode >= 50 && g_halo_mode < 70) ||
-       (g_halo_mode < 0 && g_tile_override == 0))) {
-    // measured (tools/pair_ab.py --halo N, profiles/r03b_pair_ab_halo.log; generic kernel 0.73 / 0.90 / 1.41 ms for Cout 64 / 128 / 256):
-    // with the 16-row tail pass: 128 x 64 at three per CU 0.57 / 0.84 / 1.44, 256 x 64 0.60-0.64 / 0.83 / 1.33, 256 x 128 0.99 / 0.84 / 1.37,
-    // 256 x 256 (16 waves) 1.40-1.44 / 1.19 / 1.24-1.27; every three-buffer ring is slower than its two-buffer form (resident workgroups
-    // hide the load latency better than depth does).  Overlapping tiles without the tail pass: 126 x 64 at FOUR per CU 0.49 / 0.74 / 1.35,
-    // 254 x 64 0.51 / 0.72 / 1.23, 254 x 128 (8 waves, two per CU) 0.65 / 0.64 / 1.15, 254 x 256 1.19 / 1.10 / 1.20
-    // round 4: the zero-row forms (30 / 33: the fragment ADDRESS of a masked tap selected once per tile instead of 32 v_cndmask per group):
-    // 125 x 64 0.487 / 0.756 / 1.410 (= 10), 253 x 128 0.597 / 0.644 / 1.144 (13: 0.607 / 0.653 / 1.167); bit-identical results
-    // round 4, z-blocked tiles for 3-slice columns (50: a tap outside the column is skipped instead of multiplied by zeros: 7 of 9
-    // tap-slices): 256 -> 256 at 216 x 248 x 3 0.99 vs 1.135-1.15 ms, bit-identical; at 6 slices (60) 0.626-0.651 vs 0.637-0.650: a wash
-    // round 6: small volumes (the indoor necks: 200 .. 1600 rows per Winograd position).  The 253 x 128 tile on 8 waves leaves most CUs idle there --
-    // 72 workgroups for 256 -> 256 at 20 x 20 x 8 -- and the 125 x 64 tile at four per CU wins for every Cout: 0.073 -> 0.050 ms (12 launches per ScanNet v1
-    // step), 512 -> 512 0.208 -> 0.163, 128 -> 128 at 40 x 40 x 16 0.037 -> 0.033 (tools/neck_halo_ab.py, profiles/r06_halo_small_volumes.md); bit-identical
-    // results.  Rule: fewer workgroups of the 253 x 128 tile than the chip has slots for them (512).  IVX_HALO_SMALL=0 turns it off (A/B).
-    static const int halo_small = getenv("IVX_HALO_SMALL") ? atoi(getenv("IVX_HALO_SMALL")) : 1;
-    const bool few = halo_small && p.Cout > 64 && !zblk_rule(p) && (long long)((p.M + 252) / 253) * ((p.Cout + 127) / 128) * groups < 512;
-    const int cfg = g_halo_mode > 0 ? g_halo_mode : ((p.Cout <= 64 || few) ? 30 : (zblk_rule(p) ? 50 : 33));
-    return ivx_conv_launch_halo(p, cfg, st);
+  p.m_dev = m_dev;
+  if (const int halo_cfg = grouped_halo_cfg(p, d, groups)) return ivx_conv_launch_halo(p, halo_cfg, st);
+  if (m_dev) {
+    ivx_set_error("ivx_conv_grouped_launch: only the z-halo and z-blocked kernels take a device-side row count");
+    return IVX_ERR_UNSUPPORTED;
   }
   ConvPlan pl = {g_tile_override, 1, 1, 0, 0, 0, 0};
   if (pl.cfg == 0 && p.in_pair) {

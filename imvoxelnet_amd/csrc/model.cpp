@@ -24,6 +24,23 @@
 
 void ivx_set_error(const char *fmt, ...);
 
+// The background form of the neck is the HIP library's (csrc/winograd.hip).  This file is also compiled over op-level libraries that have no
+// Winograd form at all: weak references, and a plan without the chain where they are absent.
+extern "C" {
+__attribute__((weak)) int ivx_conv_winograd_bg_supported(const ivx_conv_desc *d, int32_t tile);
+__attribute__((weak)) int64_t ivx_conv_winograd_bg_bytes(const ivx_conv_desc *d, int32_t n_layers);
+__attribute__((weak)) int64_t ivx_conv_winograd_bg_layer_offset(const ivx_conv_desc *d, int32_t layer);
+__attribute__((weak)) int ivx_conv_winograd_bg_plan(const ivx_conv_desc *d, const uint8_t *valid, int32_t n_layers, const int32_t *out_slices, void *block,
+                                                    int64_t block_bytes, ivx_stream_t stream);
+__attribute__((weak)) int ivx_conv_winograd_input_bg(const ivx_conv_desc *d, int32_t tile, const void *in, void *workspace, int64_t workspace_bytes,
+                                                     const float *partials, int32_t n_partials, const int32_t *bg, ivx_stream_t stream);
+__attribute__((weak)) int ivx_conv_winograd_gemm_bg(const ivx_conv_desc *d, int32_t tile, const float *u, void *workspace, int64_t workspace_bytes,
+                                                    const int32_t *bg, ivx_stream_t stream);
+__attribute__((weak)) int ivx_conv_winograd_output_bg(const ivx_conv_desc *d, int32_t tile, const float *scale, const float *shift, const void *res,
+                                                      void *out, void *workspace, int64_t workspace_bytes, float *partials, const int32_t *bg,
+                                                      ivx_stream_t stream);
+}
+
 #define M_REQUIRE(cond, ...)        \
   do {                              \
     if (!(cond)) {                  \
@@ -186,6 +203,8 @@ struct PlanStep {
   // the shortcut conv of a block with a downsample runs on the handle's SIDE stream next to conv1 / conv2 (independent: both read the block's
   // input): side = site index + 1 on the shortcut conv's step, join = site index + 1 on the step that reads its output as the residual
   int side = 0, join = 0;
+  // background form of a neck layer (Plan::bg_*): arena offset of the layer's block (slot list, tile -> slot map, counts), -1 = dense
+  int64_t bg = -1;
 };
 
 struct Plan {
@@ -202,6 +221,12 @@ struct Plan {
   int64_t ws2_off = 0, ws2_bytes = 0;     // second split-K workspace (launches on the side stream; ws2_off 0: none): the largest need of a side launch
   int n_sides = 0;
   int s0 = 0, s1 = 0;                     // the step range the plan covers (ivx_model_plan_info)
+  // Background tiles outside the camera frustum (include/imvoxel.h ivx_conv_winograd_bg_plan): the chain of F(6x6,3x3) neck layers that starts
+  // at the unprojection's output computes the tiles whose windows are image-independent once per key.  bg_first: step of the chain's first
+  // layer (-1: none); the plan kernels run right after the unprojection on its `valid` mask and write the block at bg_off.
+  int bg_first = -1, bg_layers = 0;
+  int64_t bg_off = -1, bg_bytes = 0;
+  int32_t bg_zo[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
 };
 
 }  // namespace
@@ -239,7 +264,11 @@ struct ivx_model {
   bool trace_skip = false;             // the open trace_begin recorded nothing (level 3, a stage other than the GEMM)
   int trace_level = 2;                 // 2: every launch group; 1: the 3-D neck stages, the unprojection and the tail individually,
                                        //    the 2-D trunk (image layout change .. FPN level 0) as ONE span (stage 6)
-  struct TraceRec { int step, stage, is3d; double flops, bytes; hipEvent_t e0, e1; std::string name; };
+  struct TraceRec {
+    int step, stage, is3d; double flops, bytes; hipEvent_t e0, e1; std::string name;
+    const int32_t *rows_dev = nullptr;   // background form: the GEMM's row count on the device; flops counts rows_dense rows until it is read
+    double rows_dense = 0.0;
+  };
   std::vector<TraceRec> trace;
   std::vector<hipEvent_t> event_pool;
   size_t events_used = 0;
@@ -1257,6 +1286,40 @@ int make_plan(ivx_model *m, Range r, const std::map<int, TInfo> &inputs, int n_v
       break;
     }
   }
+  // Background tiles of the neck (Plan::bg_*): consecutive F(6x6,3x3) layers from the unprojection's output on, stride 1 and padding 1 in x
+  // and y, each reading the previous one's output, a residual being the volume or an earlier layer's output; the chain ends at the first
+  // layer that does not qualify.  IVX_NECK_BACKGROUND=0: the dense path (A/B).  Results are bit-identical either way.
+  const bool bg_on = !(getenv("IVX_NECK_BACKGROUND") && atoi(getenv("IVX_NECK_BACKGROUND")) == 0);      // (read when a shape is planned)
+  if (bg_on && ivx_conv_winograd_bg_plan && ivx_conv_winograd_bg_supported && m->lift_step >= r.s0 && m->lift_step < r.s1 && c.storage == IVX_F32) {
+    std::vector<int> chain_t = {m->steps[m->lift_step].out};      // tensors whose quiet tiles are equal per key: the volume, then every layer's output
+    std::vector<int> chain_s;
+    for (int i = m->lift_step + 1; i < r.s1 && (int)chain_s.size() < 9; ++i) {
+      const Step &s = m->steps[i];
+      const PlanStep &ps = pl->ps[i];
+      if (s.kind != ST_CONV || s.in != chain_t.back() || ps.tile != 6 || !ivx_conv_winograd_bg_supported(&ps.d, ps.tile)) break;
+      if (s.res >= 0 && (s.res_mode != 1 || std::find(chain_t.begin(), chain_t.end(), s.res) == chain_t.end())) break;
+      if (!chain_s.empty()) {
+        const ivx_conv_desc &d0 = pl->ps[chain_s[0]].d;
+        if (ps.d.B != d0.B || ps.d.D != d0.D || ps.d.H != d0.H) break;
+      }
+      int32_t xo, yo, zo;
+      M_TRY(ivx_conv_out_dims(&ps.d, &xo, &yo, &zo));
+      pl->bg_zo[chain_s.size()] = zo;
+      chain_s.push_back(i);
+      chain_t.push_back(s.out);
+    }
+    if (!chain_s.empty()) {
+      const ivx_conv_desc &d0 = pl->ps[chain_s[0]].d;
+      pl->bg_first = chain_s[0];
+      pl->bg_layers = (int)chain_s.size();
+      pl->bg_bytes = ivx_conv_winograd_bg_bytes(&d0, pl->bg_layers);
+      M_REQUIRE(pl->bg_bytes > 0, "background plan: %s", ivx_last_error());
+      top = align256(top);
+      pl->bg_off = top;
+      top += align256(pl->bg_bytes);
+      for (size_t l = 0; l < chain_s.size(); ++l) pl->ps[chain_s[l]].bg = pl->bg_off + ivx_conv_winograd_bg_layer_offset(&d0, (int32_t)l);
+    }
+  }
   if (n_slots > 0) {        // scalar blocks of the pair chain: IVX_AMAX_SLOTS words + the scale, 512 bytes apart
     top = align256(top);
     pl->scal_off = top;
@@ -1393,6 +1456,27 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
   auto scalep = [&](int t) -> float * { uint32_t *q = slotp(t); return q ? (float *)(q + IVX_AMAX_SLOTS) : nullptr; };
   if (pl.scal_bytes > 0 && r.s0 <= m->trunk0 && r.s1 > m->trunk0)
     M_HIP(hipMemsetAsync(base + pl.scal_off, 0, (size_t)pl.scal_bytes, st), "hipMemsetAsync (amax slots)");
+  // the three stages of a Winograd layer; a layer of the background chain (ps.bg) hands them its block of the plan written after the unprojection
+  auto wino_input = [&](const PlanStep &ps, const void *in) -> int {
+    const float *part = ps.amax_in >= 0 ? (const float *)(base + ps.amax_in) : nullptr;
+    if (ps.bg >= 0) return ivx_conv_winograd_input_bg(&ps.d, ps.tile, in, ws, pl.ws_bytes, part, ps.amax_in_n, (const int32_t *)(base + ps.bg), st);
+    return ivx_conv_winograd_input_amax(&ps.d, ps.tile, in, ws, pl.ws_bytes, part, ps.amax_in_n, st);
+  };
+  auto wino_gemm = [&](const PlanStep &ps, const ConvLayer &L) -> int {
+    const float *u = L.u.at(ps.tile * 8 + ps.d.wino_operands);
+    if (ps.bg >= 0) return ivx_conv_winograd_gemm_bg(&ps.d, ps.tile, u, ws, pl.ws_bytes, (const int32_t *)(base + ps.bg), st);
+    return ivx_conv_winograd_gemm(&ps.d, ps.tile, u, ws, pl.ws_bytes, st);
+  };
+  auto wino_output = [&](const PlanStep &ps, const ConvLayer &L, const void *res, void *out) -> int {
+    float *part = ps.amax_out >= 0 ? (float *)(base + ps.amax_out) : nullptr;
+    if (ps.bg >= 0) return ivx_conv_winograd_output_bg(&ps.d, ps.tile, L.scale, L.shift, res, out, ws, pl.ws_bytes, part, (const int32_t *)(base + ps.bg), st);
+    return ivx_conv_winograd_output_amax(&ps.d, ps.tile, L.scale, L.shift, res, out, ws, pl.ws_bytes, part, st);
+  };
+  // the background plan of the neck: one look at the unprojection's valid mask, on the device
+  auto bg_plan = [&](const Step &lift) -> int {
+    if (pl.bg_first < 0) return IVX_OK;
+    return ivx_conv_winograd_bg_plan(&pl.ps[pl.bg_first].d, (const uint8_t *)ptr(lift.out2), pl.bg_layers, pl.bg_zo, base + pl.bg_off, pl.bg_bytes, st);
+  };
   const bool span2d = m->trace_on && m->trace_level == 1 && m->cfg.with_trunk;     // coarse tracing: the trunk is one span
   std::vector<char> forked((size_t)std::max(pl.n_sides, 1), 0);      // sites whose shortcut conv went to the side stream in this run
   double span_flops = 0.0, span_bytes = 0.0;     // products issued / bytes every launch of the span must move (inputs + outputs + filters, as executed)
@@ -1562,17 +1646,19 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
           M_TRY(ivx_conv_out_dims(&ps.d, &zo_d, &zo_h, &zo));
           const double vb = 4.0 * n * n * tiles * ps.d.W * ps.d.Cin, mb = 4.0 * n * n * tiles * zo * ps.d.Cout;
           M_TRY(trace_begin(m, i, 1, is3d, 0.0, 4.0 * in.elems() + vb, L.name, st));
-          M_TRY(ivx_conv_winograd_input_amax(&ps.d, ps.tile, ptr(s.in), ws, pl.ws_bytes, ps.amax_in >= 0 ? (const float *)(base + ps.amax_in) : nullptr,
-                                             ps.amax_in_n, st));
+          M_TRY(wino_input(ps, ptr(s.in)));
           M_TRY(trace_end(m, st));
           // flops: the matrix-core products the stage issues (pair operands: hi*hi + hi*lo + lo*hi per multiply-add)
           M_TRY(trace_begin(m, i, 2, is3d, (ps.d.wino_operands ? 3.0 : 1.0) * ivx_conv_winograd_issued_fraction(&ps.d) * 2.0 * n * n * tiles * zo * ps.d.Cout * ps.d.KW * ps.d.Cin,
                             vb + mb, L.name, st));      // (the z-blocked tile skips the taps outside a 3-slice column)
-          M_TRY(ivx_conv_winograd_gemm(&ps.d, ps.tile, L.u.at(ps.tile * 8 + ps.d.wino_operands), ws, pl.ws_bytes, st));
+          if (ps.bg >= 0 && m->trace_on && !m->trace_skip) {      // background form: the products issued follow the device-side row count (ivx_model_trace_read)
+            m->trace.back().rows_dev = (const int32_t *)(base + ps.bg) + 1;
+            m->trace.back().rows_dense = (double)tiles * zo;
+          }
+          M_TRY(wino_gemm(ps, L));
           M_TRY(trace_end(m, st));
           M_TRY(trace_begin(m, i, 3, is3d, 0.0, mb + 4.0 * o.elems() * (res ? 2 : 1), L.name, st));
-          M_TRY(ivx_conv_winograd_output_amax(&ps.d, ps.tile, L.scale, L.shift, res, ptr(s.out), ws, pl.ws_bytes,
-                                              ps.amax_out >= 0 ? (float *)(base + ps.amax_out) : nullptr, st));
+          M_TRY(wino_output(ps, L, res, ptr(s.out)));
           M_TRY(trace_end(m, st));
           break;
         }
@@ -1588,11 +1674,9 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
           io.wbound = L.wbound; io.sbound = L.sbound;
           M_TRY(ivx_conv_fwd_pio(&ps.d, &io, ptr(s.in), L.wpair, L.scale_p, L.shift, res, ptr(s.out), cws, cws_bytes, cst));
         } else if (ps.tile) {
-          M_TRY(ivx_conv_winograd_input_amax(&ps.d, ps.tile, ptr(s.in), ws, pl.ws_bytes, ps.amax_in >= 0 ? (const float *)(base + ps.amax_in) : nullptr,
-                                             ps.amax_in_n, st));
-          M_TRY(ivx_conv_winograd_gemm(&ps.d, ps.tile, L.u.at(ps.tile * 8 + ps.d.wino_operands), ws, pl.ws_bytes, st));
-          M_TRY(ivx_conv_winograd_output_amax(&ps.d, ps.tile, L.scale, L.shift, res, ptr(s.out), ws, pl.ws_bytes,
-                                              ps.amax_out >= 0 ? (float *)(base + ps.amax_out) : nullptr, st));
+          M_TRY(wino_input(ps, ptr(s.in)));
+          M_TRY(wino_gemm(ps, L));
+          M_TRY(wino_output(ps, L, res, ptr(s.out)));
         } else if (m->fp8_on && L.fp8_eff) {
           M_TRY(ivx_conv_fwd_ws(&ps.d, ptr(s.in), L.fp8_eff >= 2 ? L.wq : L.w, L.scale_q, L.shift_q, res, ptr(s.out), cws, cws_bytes, cst));
         } else if (ps.split) {     // (hi, lo) bf16 copy of the input at the start of the workspace, then the three-product kernel
@@ -1620,6 +1704,7 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
           ld.sampling = m->cfg.sampling;
           M_TRY(ivx_backproject_fwd_ex(&ld, ptr(s.in), bd.proj, bd.new_origin, bd.crop, ptr(s.out), nullptr, nullptr, (uint8_t *)ptr(s.out2), st));
           M_TRY(trace_end(m, st));
+          M_TRY(bg_plan(s));
           break;
         }
         if (m->cfg.storage == IVX_BF16) {
@@ -1640,6 +1725,7 @@ int run_steps(ivx_model *m, const Plan &pl, Range r, const Bind &bd, void *works
                                             o.D, o.H, o.W, (float *)ptr(s.out), (uint8_t *)ptr(s.out2),
                                             pl.ps[i].amax_out >= 0 ? (float *)(base + pl.ps[i].amax_out) : nullptr, st));
         M_TRY(trace_end(m, st));
+        M_TRY(bg_plan(s));
         break;
       }
       case ST_DCN_COL: {
@@ -2323,7 +2409,13 @@ extern "C" int ivx_model_trace_read(ivx_model *m, int32_t i, ivx_trace_rec *rec)
   float ms = 0.f, start = 0.f;
   M_HIP(hipEventElapsedTime(&ms, r.e0, r.e1), "hipEventElapsedTime (synchronise the stream first)");
   M_HIP(hipEventElapsedTime(&start, m->trace[0].e0, r.e0), "hipEventElapsedTime");
-  rec->step = r.step; rec->stage = r.stage; rec->is3d = r.is3d; rec->ms = ms; rec->start_ms = start; rec->flops = r.flops; rec->bytes = r.bytes;
+  double flops = r.flops;
+  if (r.rows_dev && r.rows_dense > 0.0) {      // background form: count the products issued (the caller has synchronised; the word is the latest forward's)
+    int32_t rows = 0;
+    M_HIP(hipMemcpy(&rows, r.rows_dev, sizeof(rows), hipMemcpyDeviceToHost), "hipMemcpy (GEMM row count)");
+    flops *= (double)rows / r.rows_dense;
+  }
+  rec->step = r.step; rec->stage = r.stage; rec->is3d = r.is3d; rec->ms = ms; rec->start_ms = start; rec->flops = flops; rec->bytes = r.bytes;
   snprintf(rec->name, sizeof(rec->name), "%s", r.name.c_str());
   return IVX_OK;
 }

@@ -22,12 +22,15 @@ int ivx_conv_launch_fold4w(const _Float16 *V, long long vs, const _Float16 *U, l
                            hipStream_t st);
 
 int ivx_conv_grouped_launch(const ivx_conv_desc *d, int groups, const float *in, long long g_in, const float *wgt, long long g_w,
-                            float *out, long long g_out, hipStream_t st, const unsigned *cp_src, unsigned *cp_dst);
+                            float *out, long long g_out, hipStream_t st, const unsigned *cp_src, unsigned *cp_dst, const int *m_dev);
+int ivx_conv_grouped_rows_dev_ok(const ivx_conv_desc *d, int groups);
 int ivx_conv_grouped_fold4(const ivx_conv_desc *d, int groups, const float *in, long long g_in, const float *wgt, long long g_w, const IvxWinoFold *f,
                            hipStream_t st);
 int ivx_conv_fold4_blocks(long long M, int Cout);
 
 namespace {
+
+constexpr int WINO_BG_HDR = 4;      // words in front of a layer's list in its background block
 
 struct WinoP {
   const float *in, *scale, *shift, *res;
@@ -42,6 +45,7 @@ struct WinoP {
   float post_scale;
   float *pmax;              // output transform: per-workgroup max |out| goes to pmax[blockIdx.x] (the next layer's input scale), or NULL
   const unsigned *hdr;      // pair operands: {bits of max |input|, bits of the filter scale} (device; see wino_pair_vscale), else NULL
+  const int *bg;            // background form (see wino_bg_plan_kernel): this layer's block {slots, GEMM rows, -, -, list[tiles], src[tiles]}, else NULL
 #ifdef IVX_CONV_TIMELINE
   unsigned long long *tl;   // debug build (tools/neck_timeline.py): 8 words per workgroup -- s_memrealtime at entry and at the end, HW_ID, XCC_ID
 #endif
@@ -314,7 +318,8 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoP p) {
   static_assert(!PAIR || VW == 2, "pair operands: two channels per lane (one dword of hi, one of lo)");
   const int CV = p.C / VW;
   const long long per_tile = (long long)p.Z * CV;                    // contiguous vectors of one (x, y) column
-  const long long total = (long long)p.B * p.TX * p.TY * per_tile;   // = vectors per xi plane
+  const int *lst = p.bg ? p.bg + WINO_BG_HDR : nullptr;                // background form: slot -> tile (row block t / per_tile of V is a slot)
+  const long long total = (lst ? (long long)p.bg[0] : (long long)p.B * p.TX * p.TY) * per_tile;   // = vectors per xi plane
   const V *in = reinterpret_cast<const V *>(p.in);
   V *Vw = reinterpret_cast<V *>(p.V);
   const float vscale = PAIR ? wino_pair_vscale(p.hdr) : 1.0f;
@@ -322,6 +327,7 @@ __global__ __launch_bounds__(256) void wino_input_kernel(const WinoP p) {
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     const long long zc = t % per_tile;
     long long q = t / per_tile;
+    if (lst) q = lst[q];
     const int ty = (int)(q % p.TY);
     q /= p.TY;
     const int tx = (int)(q % p.TX);
@@ -405,11 +411,13 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoP p) {
   const V *res = reinterpret_cast<const V *>(p.res);
   V *out = reinterpret_cast<V *>(p.out);
   const float mscale = wino_mscale(p.hdr);
+  const int *src = p.bg ? p.bg + WINO_BG_HDR + p.B * p.TX * p.TY : nullptr;      // background form: tile -> slot of M
   float omax = 0.f;
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     const long long zc = t % per_tile;
     const int cv = (int)(zc % CV);
     long long q = t / per_tile;
+    const long long tm = src ? (long long)src[q] * per_tile + zc : t;
     const int ty = (int)(q % p.TY);
     q /= p.TY;
     const int tx = (int)(q % p.TX);
@@ -419,7 +427,7 @@ __global__ __launch_bounds__(256) void wino_output_kernel(const WinoP p) {
     for (int j = 0; j < N; ++j) {
       V m[N];
 #pragma unroll
-      for (int i = 0; i < N; ++i) m[i] = Mw[(long long)(N * i + j) * (p.ms / VW) + t];
+      for (int i = 0; i < N; ++i) m[i] = Mw[(long long)(N * i + j) * (p.ms / VW) + tm];
       V y[MT];
       Wino1D<MT, V>::out(m, y);
 #pragma unroll
@@ -564,16 +572,17 @@ __global__ __launch_bounds__(256, WPE) void wino_output_buf_kernel(const WinoP p
   const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc((void *)(p.res ? p.res : p.out), 0, p.res ? out_bytes : 0u, 0x00020000);
   const unsigned ps = (unsigned)(p.ms * 4);                 // plane stride in bytes
   const float mscale = wino_mscale(p.hdr);
+  const int *src = p.bg ? p.bg + WINO_BG_HDR + p.B * p.TX * p.TY : nullptr;      // background form: tile -> slot of M
   float omax = 0.f;
   for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
     const long long zc = t % per_tile;
     const int cv = (int)(zc % CV);
     long long q = t / per_tile;
+    const unsigned vo = (unsigned)((src ? (long long)src[q] * per_tile + zc : t) * EB);
     const int ty = (int)(q % p.TY);
     q /= p.TY;
     const int tx = (int)(q % p.TX);
     const int b = (int)(q / p.TX);
-    const unsigned vo = (unsigned)(t * EB);
     const V sc = mscale * (p.scale ? reinterpret_cast<const V *>(p.scale)[cv] : vone((V *)nullptr));     // (uniform branches BEFORE the column loop)
     const V sf = p.shift ? reinterpret_cast<const V *>(p.shift)[cv] : vzero((V *)nullptr);
     const int xb = MT * tx, yb = MT * ty;
@@ -708,6 +717,136 @@ ivx_conv_desc wino_group_desc(const ivx_conv_desc *d, const WinoDims &w) {
   return g;
 }
 
+// ---- Background tiles of a neck that starts at the unprojection's output (include/imvoxel.h: ivx_conv_winograd_bg_plan).
+// The unprojection writes exactly 0 to every voxel no camera sees, so whole F(6x6,3x3) tiles of the first layers see an all-zero window and
+// all produce the same M.  Z1(b, T): no valid voxel in tile T's 8 x 8 input window (its columns inside the volume, all z).  A tile of
+// layer L (1-based) of the chain is QUIET when every tile of the grid within Chebyshev distance L - 1 has Z1; its KEY is the four distances
+// to the edges of the tile grid, each capped at L - 1.  By induction over the layers two quiet tiles with equal keys have bit-identical
+// input windows: the window of T at layer L is put together from the layer L - 1 outputs of the tiles T + (-1..1, -1..1) -- all quiet at
+// layer L - 1, their keys (caps L - 2) and whether they exist at all follow from T's key -- and from the zero padding; an output block is
+// a function of M (equal by hypothesis: same V, same filters, same order of products), of the scales (one per tensor) and of the residual,
+// which is the volume (zero under Z1) or an earlier layer's output over the same footprint.  So one REPRESENTATIVE per key -- the lowest
+// tile index -- goes through the input transform and the GEMM, and the output transform, which still visits every tile, reads M at the
+// representative's slot.  Every tensor, the residual reads and the per-workgroup maxima stay bit-identical to the dense path.
+constexpr int WINO_BG_MAXL = 9;                                     // layers of a chain (keys: WINO_BG_MAXL^4 words of LDS)
+constexpr int WINO_BG_KEYS = WINO_BG_MAXL * WINO_BG_MAXL * WINO_BG_MAXL * WINO_BG_MAXL;
+
+// one wave per tile: lane (i, j) looks down column (6 tx - 1 + i, 6 ty - 1 + j)
+__global__ __launch_bounds__(256) void wino_bg_z1_kernel(const unsigned char *__restrict__ valid, int B, int X, int Y, int Z, int TX, int TY,
+                                                         unsigned char *__restrict__ z1) {
+  const int tile = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (tile >= B * TX * TY) return;       // (wave-uniform)
+  const int ty = tile % TY, tx = (tile / TY) % TX, b = tile / (TY * TX);
+  const int x = 6 * tx - 1 + (lane >> 3), y = 6 * ty - 1 + (lane & 7);
+  bool any = false;
+  if ((unsigned)x < (unsigned)X && (unsigned)y < (unsigned)Y) {
+    const unsigned char *v = valid + (((size_t)b * X + x) * Y + y) * Z;
+    for (int z = 0; z < Z; ++z) any |= v[z] != 0;
+  }
+  const bool wave_any = __ballot(any) != 0;
+  if (lane == 0) z1[tile] = wave_any ? 0 : 1;
+}
+
+struct WinoBgPlanP {
+  const unsigned char *z1;
+  unsigned char *scratch;    // quiet maps of the layers when they do not fit in LDS: two maps of nb bytes per layer
+  int *layers;               // per layer: {slots, GEMM rows, image-dependent tiles, keys, list[n], src[n]}, lstride words apart
+  int B, TX, TY, nl, lstride, nb;
+  int zo[WINO_BG_MAXL];      // output slices per column of each layer (GEMM rows = slots * zo)
+};
+constexpr int WINO_BG_LDS_TILES = 16384;      // tiles whose two quiet maps fit in LDS (KITTI size: 1512 per sample)
+
+// exclusive prefix sum over the 1024 threads of the workgroup (wave scans, then the 16 wave totals); *total = the sum
+__device__ __forceinline__ int wino_bg_scan(const int v, int *wsum, int *total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int incl = v;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int x = __shfl_up(incl, o);
+    if (lane >= o) incl += x;
+  }
+  __syncthreads();                     // (the previous scan's totals have been read)
+  if (lane == 63) wsum[wave] = incl;
+  __syncthreads();
+  int base = 0, tot = 0;
+#pragma unroll
+  for (int w = 0; w < 16; ++w) {
+    const int x = wsum[w];
+    base += w < wave ? x : 0;
+    tot += x;
+  }
+  *total = tot;
+  return base + incl - v;
+}
+
+// ONE workgroup per layer: the layer's quiet map by l 3 x 3 erosions of Z1, then an ORDERED compaction (every thread owns a contiguous
+// range of tiles, the ranges are prefix-summed), so the lists are the same from run to run.
+__global__ __launch_bounds__(1024) void wino_bg_plan_kernel(const WinoBgPlanP p) {
+  __shared__ int rep[WINO_BG_KEYS];
+  __shared__ int wsum[16];
+  __shared__ unsigned char qlds[2][WINO_BG_LDS_TILES];
+  const int tid = threadIdx.x, l = blockIdx.x;
+  const int n = p.B * p.TX * p.TY;
+  const int chunk = (n + 1023) / 1024;
+  const int t0 = min(tid * chunk, n), t1 = min(t0 + chunk, n);
+  unsigned char *qa = n <= WINO_BG_LDS_TILES ? qlds[0] : p.scratch + (size_t)(2 * l) * p.nb;
+  unsigned char *qb = n <= WINO_BG_LDS_TILES ? qlds[1] : p.scratch + (size_t)(2 * l + 1) * p.nb;
+  const int cap = l, LK = cap + 1, K = LK * LK * LK * LK;
+  int *blk = p.layers + (size_t)l * p.lstride, *list = blk + WINO_BG_HDR, *src = list + n;
+  auto key = [&](int t) {
+    const int ty = t % p.TY, tx = (t / p.TY) % p.TX;
+    return ((min(tx, cap) * LK + min(p.TX - 1 - tx, cap)) * LK + min(ty, cap)) * LK + min(p.TY - 1 - ty, cap);
+  };
+  for (int t = tid; t < n; t += 1024) qa[t] = p.z1[t];
+  for (int k = tid; k < K; k += 1024) rep[k] = 0x7fffffff;
+  __syncthreads();
+  for (int e = 0; e < l; ++e) {          // quiet at layer e + 2 = the 3 x 3 neighbours inside the grid are quiet at layer e + 1
+    for (int t = tid; t < n; t += 1024) {
+      const int ty = t % p.TY, tx = (t / p.TY) % p.TX, b0 = t - tx * p.TY - ty;     // b0: first tile of the sample
+      int q = 1;
+      for (int dx = -1; dx <= 1; ++dx)
+        for (int dy = -1; dy <= 1; ++dy) {
+          const int xx = tx + dx, yy = ty + dy;
+          if ((unsigned)xx < (unsigned)p.TX && (unsigned)yy < (unsigned)p.TY) q &= qa[b0 + xx * p.TY + yy];
+        }
+      qb[t] = (unsigned char)q;
+    }
+    __syncthreads();                     // (workgroup-scope fence: also for maps in global memory)
+    unsigned char *sw = qa; qa = qb; qb = sw;
+  }
+  int cnt = 0;
+  for (int t = t0; t < t1; ++t) {
+    if (!qa[t]) ++cnt;
+    else atomicMin(&rep[key(t)], t);
+  }
+  int na;
+  int o = wino_bg_scan(cnt, wsum, &na);  // (its barriers also complete the atomics)
+  for (int t = t0; t < t1; ++t)
+    if (!qa[t]) { list[o] = t; src[t] = o; ++o; }
+  const int kchunk = (K + 1023) / 1024, k0 = min(tid * kchunk, K), k1 = min(k0 + kchunk, K);
+  cnt = 0;
+  for (int k = k0; k < k1; ++k) cnt += rep[k] != 0x7fffffff;
+  int nk;
+  int r = wino_bg_scan(cnt, wsum, &nk);
+  for (int k = k0; k < k1; ++k)
+    if (rep[k] != 0x7fffffff) { list[na + r] = rep[k]; rep[k] = r; ++r; }     // rep[k]: now the rank of key k among the keys present
+  __syncthreads();
+  for (int t = t0; t < t1; ++t)
+    if (qa[t]) src[t] = na + rep[key(t)];
+  if (tid == 0) { blk[0] = na + nk; blk[1] = (na + nk) * p.zo[l]; blk[2] = na; blk[3] = nk; }
+}
+
+struct WinoBgLayout { int64_t z1, scratch, layers, lstride, total, nb; int n; };
+WinoBgLayout wino_bg_layout(int B, int TX, int TY, int n_layers) {
+  WinoBgLayout L;
+  L.n = B * TX * TY;
+  L.nb = ivx_align_up((int64_t)L.n, 256);
+  L.z1 = 0; L.scratch = L.nb;
+  L.layers = L.nb + (L.n <= WINO_BG_LDS_TILES ? 0 : 2 * (int64_t)WINO_BG_MAXL * L.nb);
+  L.lstride = ivx_align_up((int64_t)(WINO_BG_HDR + 2 * (int64_t)L.n) * 4, 256) / 4;      // words
+  L.total = L.layers + (int64_t)n_layers * L.lstride * 4;
+  return L;
+}
 unsigned wino_blocks(int64_t items) {
   const int64_t b = (items + 255) / 256;
   return (unsigned)(b < 1 ? 1 : (b > (1 << 20) ? (1 << 20) : b));
@@ -800,6 +939,7 @@ int wino_setup(const ivx_conv_desc *d, int tile, const void *in, const float *sc
   p->relu = d->relu; p->res_mode = d->res_mode; p->res_after_act = d->res_after_act;
   p->post_scale = d->post_scale == 0.f ? 1.0f : d->post_scale;
   p->pmax = nullptr;
+  p->bg = nullptr;
 #ifdef IVX_CONV_TIMELINE
   p->tl = g_wino_timeline;
 #endif
@@ -811,14 +951,24 @@ int wino_setup(const ivx_conv_desc *d, int tile, const void *in, const float *sc
 }  // namespace
 
 // The three stages are separate entry points so that a caller can time them (bench.py); ivx_conv_winograd_fwd runs all.
+static int wino_bg_check(const ivx_conv_desc *d, int32_t tile, const void *bg, const char *who) {
+  if (bg && !ivx_conv_winograd_bg_supported(d, tile)) {
+    ivx_set_error("%s: the layer does not take the background form (ivx_conv_winograd_bg_supported)", who);
+    return IVX_ERR_UNSUPPORTED;
+  }
+  return IVX_OK;
+}
+
 static int wino_input_impl(const ivx_conv_desc *d, int32_t tile, const void *in, void *workspace, int64_t workspace_bytes,
-                           const float *partials, int32_t n_partials, ivx_stream_t stream) {
+                           const float *partials, int32_t n_partials, const int32_t *bg, ivx_stream_t stream) {
   WinoDims w;
   WinoP p;
   float dummy;
   IVX_REQUIRE(in, "ivx_conv_winograd_input: null argument");
   int rc = wino_setup(d, tile, in, nullptr, nullptr, &dummy, &dummy, workspace, workspace_bytes, &w, &p, "ivx_conv_winograd_input");
   if (rc != IVX_OK) return rc;
+  if ((rc = wino_bg_check(d, tile, bg, "ivx_conv_winograd_input")) != IVX_OK) return rc;
+  p.bg = bg;            // (the grid keeps its dense size: the slot count is known on the device only)
   if (d->wino_operands == IVX_F16_PAIR) {
     // max |input| -> header word 0 (the scale of V is derived from it on the device: no host round trip)
     static const bool one_wg = !(getenv("IVX_WINO_AMAX_ONE_WG") && atoi(getenv("IVX_WINO_AMAX_ONE_WG")) == 0);      // =0: the round-5 pair of launches (A/B)
@@ -857,17 +1007,23 @@ static int wino_input_impl(const ivx_conv_desc *d, int32_t tile, const void *in,
 
 extern "C" int ivx_conv_winograd_input(const ivx_conv_desc *d, int32_t tile, const void *in, void *workspace, int64_t workspace_bytes,
                                        ivx_stream_t stream) {
-  return wino_input_impl(d, tile, in, workspace, workspace_bytes, nullptr, 0, stream);
+  return wino_input_impl(d, tile, in, workspace, workspace_bytes, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int ivx_conv_winograd_input_amax(const ivx_conv_desc *d, int32_t tile, const void *in, void *workspace, int64_t workspace_bytes,
                                             const float *partials, int32_t n_partials, ivx_stream_t stream) {
   IVX_REQUIRE(!partials || n_partials > 0, "ivx_conv_winograd_input_amax: partials without a count");
-  return wino_input_impl(d, tile, in, workspace, workspace_bytes, partials, n_partials, stream);
+  return wino_input_impl(d, tile, in, workspace, workspace_bytes, partials, n_partials, nullptr, stream);
 }
 
-extern "C" int ivx_conv_winograd_gemm(const ivx_conv_desc *d, int32_t tile, const float *u, void *workspace, int64_t workspace_bytes,
-                                      ivx_stream_t stream) {
+extern "C" int ivx_conv_winograd_input_bg(const ivx_conv_desc *d, int32_t tile, const void *in, void *workspace, int64_t workspace_bytes,
+                                          const float *partials, int32_t n_partials, const int32_t *bg, ivx_stream_t stream) {
+  IVX_REQUIRE(!partials || n_partials > 0, "ivx_conv_winograd_input_bg: partials without a count");
+  return wino_input_impl(d, tile, in, workspace, workspace_bytes, partials, n_partials, bg, stream);
+}
+
+static int wino_gemm_impl(const ivx_conv_desc *d, int32_t tile, const float *u, void *workspace, int64_t workspace_bytes, const int32_t *bg,
+                          ivx_stream_t stream) {
   WinoDims w;
   WinoP p;
   float dummy;
@@ -880,11 +1036,22 @@ extern "C" int ivx_conv_winograd_gemm(const ivx_conv_desc *d, int32_t tile, cons
   // the filter scale travels with the filters; the output transform reads it from the workspace header: workgroup 0 of the GEMM launch copies
   // the word (a separate 4-byte hipMemcpyAsync was one more launch per layer)
   const unsigned *us = p.hdr ? reinterpret_cast<const unsigned *>(u + (int64_t)w.n2 * d->Cout * d->KW * d->Cin + 1) : nullptr;
+  if ((rc = wino_bg_check(d, tile, bg, "ivx_conv_winograd_gemm")) != IVX_OK) return rc;
   rc = ivx_conv_grouped_launch(&g, w.n2, p.V, el * w.v_stride, u, el * d->Cout * d->KW * d->Cin, p.Mw, w.m_stride, (hipStream_t)stream, us,
-                               p.hdr ? const_cast<unsigned *>(p.hdr) + 1 : nullptr);
+                               p.hdr ? const_cast<unsigned *>(p.hdr) + 1 : nullptr, bg ? bg + 1 : nullptr);      // word 1: slots x output slices
   if (rc != IVX_OK) return rc;
   IVX_CHECK_LAUNCH("ivx_conv_winograd_gemm");
   return IVX_OK;
+}
+
+extern "C" int ivx_conv_winograd_gemm(const ivx_conv_desc *d, int32_t tile, const float *u, void *workspace, int64_t workspace_bytes,
+                                      ivx_stream_t stream) {
+  return wino_gemm_impl(d, tile, u, workspace, workspace_bytes, nullptr, stream);
+}
+
+extern "C" int ivx_conv_winograd_gemm_bg(const ivx_conv_desc *d, int32_t tile, const float *u, void *workspace, int64_t workspace_bytes,
+                                         const int32_t *bg, ivx_stream_t stream) {
+  return wino_gemm_impl(d, tile, u, workspace, workspace_bytes, bg, stream);
 }
 
 // ---- F(4x4,3x3) on fp16-pair operands with the output transform fused into the GEMM launch (conv_igemm.hip conv_wino_fold4_kernel): the
@@ -969,7 +1136,7 @@ extern "C" int32_t ivx_conv_winograd_output_blocks(const ivx_conv_desc *d, int32
 }
 
 static int wino_output_impl(const ivx_conv_desc *d, int32_t tile, const float *scale, const float *shift, const void *res, void *out,
-                            void *workspace, int64_t workspace_bytes, float *partials, ivx_stream_t stream) {
+                            void *workspace, int64_t workspace_bytes, float *partials, const int32_t *bg, ivx_stream_t stream) {
   WinoDims w;
   WinoP p;
   float dummy;
@@ -977,7 +1144,9 @@ static int wino_output_impl(const ivx_conv_desc *d, int32_t tile, const float *s
   IVX_REQUIRE(!d || d->res_mode == 0 || res, "ivx_conv_winograd_output: res_mode set but res is NULL");
   int rc = wino_setup(d, tile, &dummy, scale, shift, res, out, workspace, workspace_bytes, &w, &p, "ivx_conv_winograd_output");
   if (rc != IVX_OK) return rc;
+  if ((rc = wino_bg_check(d, tile, bg, "ivx_conv_winograd_output")) != IVX_OK) return rc;
   p.pmax = partials;
+  p.bg = bg;
   if (tile == 2)
     hipLaunchKernelGGL((wino_output_kernel<2, 4>), dim3(wino_blocks(w.m_elems / 4)), dim3(256), 0, (hipStream_t)stream, p);
   else if (tile == 4)
@@ -1004,12 +1173,70 @@ static int wino_output_impl(const ivx_conv_desc *d, int32_t tile, const float *s
 
 extern "C" int ivx_conv_winograd_output(const ivx_conv_desc *d, int32_t tile, const float *scale, const float *shift, const void *res,
                                         void *out, void *workspace, int64_t workspace_bytes, ivx_stream_t stream) {
-  return wino_output_impl(d, tile, scale, shift, res, out, workspace, workspace_bytes, nullptr, stream);
+  return wino_output_impl(d, tile, scale, shift, res, out, workspace, workspace_bytes, nullptr, nullptr, stream);
 }
 
 extern "C" int ivx_conv_winograd_output_amax(const ivx_conv_desc *d, int32_t tile, const float *scale, const float *shift, const void *res,
                                              void *out, void *workspace, int64_t workspace_bytes, float *partials, ivx_stream_t stream) {
-  return wino_output_impl(d, tile, scale, shift, res, out, workspace, workspace_bytes, partials, stream);
+  return wino_output_impl(d, tile, scale, shift, res, out, workspace, workspace_bytes, partials, nullptr, stream);
+}
+
+extern "C" int ivx_conv_winograd_output_bg(const ivx_conv_desc *d, int32_t tile, const float *scale, const float *shift, const void *res,
+                                           void *out, void *workspace, int64_t workspace_bytes, float *partials, const int32_t *bg,
+                                           ivx_stream_t stream) {
+  return wino_output_impl(d, tile, scale, shift, res, out, workspace, workspace_bytes, partials, bg, stream);
+}
+
+// ---- the background plan (see wino_bg_plan_kernel)
+extern "C" int ivx_conv_winograd_bg_supported(const ivx_conv_desc *d, int32_t tile) {
+  WinoDims w;
+  if (tile != 6 || !d || d->pd != 1 || d->ph != 1 || !ivx_conv_winograd_supported(d, tile)) return 0;
+  if (wino_dims(d, tile, &w, "ivx_conv_winograd_bg_supported") != IVX_OK) return 0;
+  ivx_conv_desc g = wino_group_desc(d, w);
+  g.in_dtype = d->wino_operands;
+  return ivx_conv_grouped_rows_dev_ok(&g, w.n2);      // the GEMM kernel must take its row count from the device
+}
+
+extern "C" int64_t ivx_conv_winograd_bg_bytes(const ivx_conv_desc *d, int32_t n_layers) {
+  WinoDims w;
+  if (wino_dims(d, 6, &w, "ivx_conv_winograd_bg_bytes") != IVX_OK) return -1;
+  IVX_REQUIRE(n_layers >= 1 && n_layers <= WINO_BG_MAXL, "ivx_conv_winograd_bg_bytes: 1 .. %d layers", WINO_BG_MAXL) ;
+  return wino_bg_layout(d->B, w.TX, w.TY, n_layers).total;
+}
+
+extern "C" int64_t ivx_conv_winograd_bg_layer_offset(const ivx_conv_desc *d, int32_t layer) {
+  WinoDims w;
+  if (wino_dims(d, 6, &w, "ivx_conv_winograd_bg_layer_offset") != IVX_OK) return -1;
+  IVX_REQUIRE(layer >= 0 && layer < WINO_BG_MAXL, "ivx_conv_winograd_bg_layer_offset: bad layer");
+  const WinoBgLayout L = wino_bg_layout(d->B, w.TX, w.TY, layer + 1);
+  return L.layers + (int64_t)layer * L.lstride * 4;
+}
+
+extern "C" int ivx_conv_winograd_bg_plan(const ivx_conv_desc *d, const uint8_t *valid, int32_t n_layers, const int32_t *out_slices, void *block,
+                                         int64_t block_bytes, ivx_stream_t stream) {
+  WinoDims w;
+  int rc = wino_dims(d, 6, &w, "ivx_conv_winograd_bg_plan");
+  if (rc != IVX_OK) return rc;
+  IVX_REQUIRE(valid && out_slices && block, "ivx_conv_winograd_bg_plan: null argument");
+  IVX_REQUIRE(n_layers >= 1 && n_layers <= WINO_BG_MAXL, "ivx_conv_winograd_bg_plan: 1 .. %d layers", WINO_BG_MAXL);
+  IVX_REQUIRE(d->pd == 1 && d->ph == 1, "ivx_conv_winograd_bg_plan: the chain's layers pad x and y by 1");
+  const WinoBgLayout L = wino_bg_layout(d->B, w.TX, w.TY, n_layers);
+  if (block_bytes < L.total) {
+    ivx_set_error("ivx_conv_winograd_bg_plan: block too small (%lld < %lld); size it with ivx_conv_winograd_bg_bytes", (long long)block_bytes,
+                  (long long)L.total);
+    return IVX_ERR_WORKSPACE;
+  }
+  char *base = (char *)block;
+  WinoBgPlanP p;
+  p.z1 = (const unsigned char *)(base + L.z1); p.scratch = (unsigned char *)(base + L.scratch);
+  p.layers = (int *)(base + L.layers);
+  p.B = d->B; p.TX = w.TX; p.TY = w.TY; p.nl = n_layers; p.lstride = (int)L.lstride; p.nb = (int)L.nb;
+  for (int l = 0; l < WINO_BG_MAXL; ++l) p.zo[l] = l < n_layers ? out_slices[l] : 0;
+  hipLaunchKernelGGL(wino_bg_z1_kernel, dim3((unsigned)((L.n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, valid, d->B, d->D, d->H, d->W, w.TX, w.TY,
+                     (unsigned char *)(base + L.z1));
+  hipLaunchKernelGGL(wino_bg_plan_kernel, dim3((unsigned)n_layers), dim3(1024), 0, (hipStream_t)stream, p);
+  IVX_CHECK_LAUNCH("ivx_conv_winograd_bg_plan");
+  return IVX_OK;
 }
 
 extern "C" int ivx_conv_winograd_fwd(const ivx_conv_desc *d, int32_t tile, const void *in, const float *u, const float *scale,

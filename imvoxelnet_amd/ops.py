@@ -242,8 +242,33 @@ def conv_winograd_weights(wgt, wgt_layout, tile=2, operands=0):
 winograd_trace = None
 
 
+def winograd_bg_plan(valid, x_shape, Cout, out_slices, wgt_layout=1, operands=IVX_F16_PAIR):
+    """Background plan of a chain of F(6x6,3x3) layers that starts at the unprojection's output (ivx_conv_winograd_bg_plan): valid
+    [B,X,Y,Z] uint8 / bool, x_shape the volume's [B,X,Y,Z,C], out_slices the output z extent of every layer.  Returns (block, views):
+    the device block (uint8) and per layer its int32 view {slots, GEMM rows, image-dependent tiles, keys, list[B TX TY], src[B TX TY]},
+    to be handed to conv_winograd_fwd(bg=...)."""
+    B, X, Y, Z, Cin = x_shape
+    if tuple(valid.shape) != (B, X, Y, Z) or not valid.is_cuda or not valid.is_contiguous() or valid.element_size() != 1:
+        raise ValueError('valid must be a contiguous [B,X,Y,Z] one-byte device tensor')
+    d = _wino_desc(B, X, Y, Z, Cin, Cout, 3, 1, (1, 1, 1), False, wgt_layout, operands=operands)
+    L = _lib.lib()
+    nl = len(out_slices)
+    nb = L.ivx_conv_winograd_bg_bytes(C.byref(d), nl)
+    if nb < 0:
+        check(-1, 'ivx_conv_winograd_bg_bytes')
+    block = torch.zeros((nb,), device=valid.device, dtype=torch.uint8)
+    zo = (C.c_int32 * nl)(*[int(z) for z in out_slices])
+    check(L.ivx_conv_winograd_bg_plan(C.byref(d), _ptr(valid), nl, zo, _ptr(block), nb, _stream()), 'ivx_conv_winograd_bg_plan')
+    n = B * ((X + 5) // 6) * ((Y + 5) // 6)
+    views = []
+    for l in range(nl):
+        off = L.ivx_conv_winograd_bg_layer_offset(C.byref(d), l)
+        views.append(block[off:off + 4 * (4 + 2 * n)].view(torch.int32))
+    return block, views
+
+
 def conv_winograd_fwd(x, u, scale=None, shift=None, kw=3, stride_w=1, padding=(1, 1, 1), relu=False, res=None, out=None,
-                      wgt_layout=0, res_after_act=False, post_scale=1.0, operands=0, amax_in=None, want_amax=False, fused=False):
+                      wgt_layout=0, res_after_act=False, post_scale=1.0, operands=0, amax_in=None, want_amax=False, fused=False, bg=None):
     """Same result as conv_fwd for a 3x3xkw kernel with stride (1,1,stride_w), computed in the F(m x m, 3x3) minimal-filtering
     form (fp32).  x [B,D,H,W,Cin]; u from conv_winograd_weights (its first dimension, 16 / 36 / 64, selects m = 2 / 4 / 6)."""
     _chk(x, 'x')
@@ -289,6 +314,21 @@ def conv_winograd_fwd(x, u, scale=None, shift=None, kw=3, stride_w=1, padding=(1
                                              _stream()), 'ivx_conv_winograd_input_amax')
         check(L.ivx_conv_winograd_gemm_output_amax(C.byref(d), tile, _ptr(u), _ptr(scale), _ptr(shift), _ptr(res), _ptr(out), _ptr(ws), wsb, _ptr(part),
                                                    _stream()), 'ivx_conv_winograd_gemm_output_amax')
+        return (out, part) if want_amax else out
+    if bg is not None:
+        # a layer of a background chain (winograd_bg_plan): the three stages over the plan's slots; partial maxima as in the chained form
+        if not L.ivx_conv_winograd_bg_supported(C.byref(d), tile):
+            raise ValueError('this layer does not take the background form (ivx_conv_winograd_bg_supported)')
+        part = None
+        if want_amax:
+            part = torch.empty((L.ivx_conv_winograd_output_blocks(C.byref(d), tile),), device=x.device, dtype=torch.float32)
+        if amax_in is not None:
+            _chk(amax_in, 'amax_in')
+        check(L.ivx_conv_winograd_input_bg(C.byref(d), tile, _ptr(x), _ptr(ws), wsb, _ptr(amax_in), 0 if amax_in is None else amax_in.numel(),
+                                           _ptr(bg), _stream()), 'ivx_conv_winograd_input_bg')
+        check(L.ivx_conv_winograd_gemm_bg(C.byref(d), tile, _ptr(u), _ptr(ws), wsb, _ptr(bg), _stream()), 'ivx_conv_winograd_gemm_bg')
+        check(L.ivx_conv_winograd_output_bg(C.byref(d), tile, _ptr(scale), _ptr(shift), _ptr(res), _ptr(out), _ptr(ws), wsb, _ptr(part),
+                                            _ptr(bg), _stream()), 'ivx_conv_winograd_output_bg')
         return (out, part) if want_amax else out
     if amax_in is not None or want_amax:
         # chained layers (ivx_conv_winograd_output_amax / _input_amax): amax_in = the producer's per-workgroup maxima of x;

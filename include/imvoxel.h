@@ -338,6 +338,29 @@ int32_t ivx_conv_winograd_fused_blocks(const ivx_conv_desc *d, int32_t tile);
 int ivx_conv_winograd_gemm_output_amax(const ivx_conv_desc *d, int32_t tile, const float *u, const float *scale, const float *shift,
                                        const void *res, void *out, void *workspace, int64_t workspace_bytes, float *partials,
                                        ivx_stream_t stream);
+/* Background tiles of a neck whose first layer reads the unprojection's output.  `valid` [B, X, Y, Z] (ivx_backproject_mean_fwd) marks the
+ * voxels a camera sees; every other voxel of the volume is exactly 0.  For a chain of consecutive F(6x6,3x3) layers with stride 1 and
+ * padding 1 in x and y (each reads the previous one's output; a residual is the volume or an earlier layer's output) a tile of layer L
+ * (1-based) is QUIET when no tile within Chebyshev distance L - 1 of it has a valid voxel in its 8 x 8 layer-1 input window, and two quiet
+ * tiles whose four distances to the edges of the tile grid, capped at L - 1, are equal (their KEY) have bit-identical input windows.
+ * ivx_conv_winograd_bg_plan (two small launches, nothing returns to the host) writes per layer, into `block` (ivx_conv_winograd_bg_bytes,
+ * layer l at ivx_conv_winograd_bg_layer_offset(d, l)): int32 {slots, slots * out_slices[l], image-dependent tiles, keys}, then list[B TX TY]
+ * -- the image-dependent tiles in their order, then one representative (the lowest tile index) per key present, keys ascending by
+ * ((left * L + right) * L + top) * L + bottom -- and src[B TX TY], the slot of every tile.  The _bg stage entry points take a layer's
+ * block: the input transform and the GEMM run over the slots only (their grids keep the dense size; surplus workgroups return at once),
+ * the output transform visits every tile and reads M at its slot, so every tensor is bit-identical to the dense path's.  bg NULL = the
+ * plain entry points.  d: the first layer (all layers share B, X, Y and hence the tile grid); at most 9 layers. */
+int ivx_conv_winograd_bg_supported(const ivx_conv_desc *d, int32_t tile);
+int64_t ivx_conv_winograd_bg_bytes(const ivx_conv_desc *d, int32_t n_layers);
+int64_t ivx_conv_winograd_bg_layer_offset(const ivx_conv_desc *d, int32_t layer);
+int ivx_conv_winograd_bg_plan(const ivx_conv_desc *d, const uint8_t *valid, int32_t n_layers, const int32_t *out_slices, void *block,
+                              int64_t block_bytes, ivx_stream_t stream);
+int ivx_conv_winograd_input_bg(const ivx_conv_desc *d, int32_t tile, const void *in, void *workspace, int64_t workspace_bytes,
+                               const float *partials, int32_t n_partials, const int32_t *bg, ivx_stream_t stream);
+int ivx_conv_winograd_gemm_bg(const ivx_conv_desc *d, int32_t tile, const float *u, void *workspace, int64_t workspace_bytes,
+                              const int32_t *bg, ivx_stream_t stream);
+int ivx_conv_winograd_output_bg(const ivx_conv_desc *d, int32_t tile, const float *scale, const float *shift, const void *res, void *out,
+                                void *workspace, int64_t workspace_bytes, float *partials, const int32_t *bg, ivx_stream_t stream);
 
 
 /* Modulated deformable convolution (DCNv2; mmcv ModulatedDeformConv2dPack, deform_groups = 1) -- nuScenes reference
