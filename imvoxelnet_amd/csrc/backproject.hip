@@ -382,70 +382,159 @@ __global__ __launch_bounds__(256) void backproject_single_view_kernel(const BpPa
   }
 }
 
+// ------------------------------------------------------------------ host: one call path for every lift export
 // A/B knob of the block order (default 0: workgroups in plain voxel order; IVX_BP_ORDER=1: XCD-contiguous eighths, see the kernel)
 static int bp_q(int nblk) {
   static const int xcd_order = getenv("IVX_BP_ORDER") ? atoi(getenv("IVX_BP_ORDER")) : 0;
   return xcd_order ? (nblk + 7) / 8 : 0;
 }
-static unsigned bp_grid(const BpParams &p) { return p.q ? 8u * (unsigned)p.q : (unsigned)p.nblk; }
 
-static int backproject_launch(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
-                              const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y,
-                              int32_t Z, float *volume, uint8_t *valid, int32_t *count, ivx_stream_t stream, float *partials = nullptr) {
-  const bool mean = count == nullptr;
-  IVX_REQUIRE(feat && proj && new_origin && crop_hw && voxel_size && volume && (valid || count), "ivx_backproject_mean_fwd: null argument");
-  IVX_REQUIRE(B > 0 && V > 0 && FH > 0 && FW > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "ivx_backproject_mean_fwd: non-positive dims");
-  IVX_REQUIRE((int64_t)X * Y * Z < (1LL << 31), "ivx_backproject_mean_fwd: voxel grid too large");
-  IVX_REQUIRE((int64_t)B * V * FH * FW < (1LL << 31), "ivx_backproject_mean_fwd: feature maps too large");
-  IVX_REQUIRE(B <= 65535, "ivx_backproject_mean_fwd: batch too large");
-  BpParams p;
-  p.feat = feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = volume; p.valid = valid;
-  p.count = count; p.mean_out = nullptr; p.first = 0;
-  p.pmax = (mean && V == 1) ? partials : nullptr;
-  p.nblk = 0; p.q = 0;
-  p.vs0 = voxel_size[0]; p.vs1 = voxel_size[1]; p.vs2 = voxel_size[2];
-  p.V = V; p.FH = FH; p.FW = FW; p.C = C; p.X = X; p.Y = Y; p.Z = Z; p.N = X * Y * Z;
-  const int vec = (C % 4 == 0) ? 4 : 1;
-  p.nchunk = (C + vec - 1) / vec;
-  IVX_REQUIRE(p.nchunk <= 64 * 4, "ivx_backproject_mean_fwd: C=%d too large (max %d)", C, 256 * vec);
-  int lg = 0;
-  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
-  p.lpv_log2 = lg;
-  if (!mean) {
-    IVX_REQUIRE(vec == 4, "ivx_backproject_sum_fwd: C %% 4 must be 0");
-    const int vpb = 256 >> lg;
-    p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-    hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
-    IVX_CHECK_LAUNCH("ivx_backproject_sum_fwd");
-    return IVX_OK;
+// One lift call as every export states it: bp_run validates it, fills the kernel's parameters and launches the one kernel the table selects.
+struct BpCall {
+  const char *what;                 // the export the caller called, for messages
+  const ivx_backproject_desc *d;    // dims, feat_dtype, mode, sampling, first (the older exports build one; its voxel_size is not read)
+  const float *voxel_size;          // host float[3]: the older exports' argument, d->voxel_size of a descriptor call
+  const void *feat;                 // [B*V, FH, FW, C]; gathered: the pool [S, FH, FW, C]
+  const float *proj;                // [B, V, 12];       gathered: the pool [S, 12]
+  const float *new_origin;
+  const int32_t *crop_hw;
+  void *volume;
+  int32_t *count;
+  void *mean_out;
+  uint8_t *valid;
+  ivx_stream_t stream;
+  float *partials = nullptr;        // ivx_backproject_mean_fwd_amax
+  bool gather = false;              // ivx_backproject_gather_fwd: view_slot [B, V] lists slots of the S-slot pools
+  const int32_t *view_slot = nullptr;
+  int32_t S = 0;
+};
+
+// The descriptor of an older export's argument list (voxel_size stays with the caller's pointer, which may be NULL until validated).
+static ivx_backproject_desc bp_desc(int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, int32_t X, int32_t Y, int32_t Z, int32_t feat_dtype, int32_t mode,
+                                    int32_t first = 0) {
+  return ivx_backproject_desc{B, V, FH, FW, C, X, Y, Z, {0.f, 0.f, 0.f}, feat_dtype, mode, IVX_SAMPLE_NEAREST, first};
+}
+
+// The nearest fp32 mean of ONE view is a bit copy (keeps -0, denormals, bf16 pairs passed as words) and the only lift that writes per-workgroup maxima.
+static bool bp_single_view_copy(const BpCall &c) {
+  return !c.gather && c.d->sampling == IVX_SAMPLE_NEAREST && c.d->mode == IVX_LIFT_MEAN && c.d->feat_dtype == IVX_F32 && c.d->V == 1;
+}
+
+// What a lift accepts: IVX_ERR_INVALID_ARG with a message that names the export, before anything is launched or dereferenced.
+static int bp_validate(const BpCall &c) {
+  const char *what = c.what;
+  const ivx_backproject_desc *d = c.d;
+  IVX_REQUIRE(d, "%s: null descriptor", what);
+  IVX_REQUIRE(d->sampling == IVX_SAMPLE_NEAREST || d->sampling == IVX_SAMPLE_BILINEAR, "%s: sampling %d (IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR)", what, d->sampling);
+  if (c.gather)
+    IVX_REQUIRE(d->mode == IVX_LIFT_MEAN, "%s: mode %d (IVX_LIFT_MEAN only)", what, d->mode);
+  IVX_REQUIRE(d->mode == IVX_LIFT_MEAN || d->mode == IVX_LIFT_SUM || d->mode == IVX_LIFT_ACCUM, "%s: mode %d (IVX_LIFT_MEAN | IVX_LIFT_SUM | IVX_LIFT_ACCUM)", what, d->mode);
+  IVX_REQUIRE(d->feat_dtype == IVX_F32 || d->feat_dtype == IVX_BF16, "%s: feat_dtype %d (IVX_F32 | IVX_BF16)", what, d->feat_dtype);
+  IVX_REQUIRE(c.feat && c.proj && c.new_origin && c.crop_hw && c.voxel_size && c.volume && (!c.gather || c.view_slot), "%s: null argument", what);
+  if (d->mode == IVX_LIFT_MEAN) {
+    IVX_REQUIRE(c.valid, "%s: null argument (the mean mode writes valid)", what);
+    IVX_REQUIRE(!c.count && !c.mean_out, "%s: the mean mode takes no count / mean_out", what);
+  } else if (d->mode == IVX_LIFT_SUM) {
+    IVX_REQUIRE(c.count, "%s: null argument (the sum mode writes count)", what);
+    IVX_REQUIRE(!c.valid && !c.mean_out, "%s: the sum mode takes no valid / mean_out", what);
+  } else {
+    IVX_REQUIRE(c.count, "%s: null argument (the accumulate mode updates count)", what);
+    IVX_REQUIRE((c.mean_out != nullptr) == (c.valid != nullptr), "%s: mean_out and valid must both be given or both be NULL", what);
   }
-  if (V == 1) {
-    // 256 voxels per workgroup regardless of the group width (each lane projects one voxel)
-    dim3 g1((p.N + 255) / 256, B);
-    if (vec == 4)
-      hipLaunchKernelGGL(backproject_single_view_kernel<4>, g1, dim3(256), 0, (hipStream_t)stream, p);
-    else
-      hipLaunchKernelGGL(backproject_single_view_kernel<1>, g1, dim3(256), 0, (hipStream_t)stream, p);
-    IVX_CHECK_LAUNCH("ivx_backproject_mean_fwd");
-    return IVX_OK;
+  if (c.gather) IVX_REQUIRE(c.S > 0, "%s: S=%d slots (the pools need at least one)", what, c.S);
+  IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
+  const int vec = (d->C % 4 == 0) ? 4 : 1;
+  IVX_REQUIRE(vec == 4 || (d->mode == IVX_LIFT_MEAN && d->feat_dtype == IVX_F32 && !c.gather), "%s: C %% 4 must be 0 (every form but the fp32 mean of a view stack)", what);
+  IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
+  if (c.gather) {
+    IVX_REQUIRE((int64_t)c.S * d->FH * d->FW < (1LL << 31), "%s: feature pool too large", what);
+    IVX_REQUIRE((int64_t)d->B * d->V < (1LL << 31), "%s: view list too large", what);
+  } else {
+    IVX_REQUIRE((int64_t)d->B * d->V * d->FH * d->FW < (1LL << 31), "%s: feature maps too large", what);
   }
-  const int vox_per_block = 256 >> lg;
-  p.nblk = (p.N + vox_per_block - 1) / vox_per_block; p.q = bp_q(p.nblk);
-  dim3 grid(bp_grid(p), B);
-  if (vec == 4)
-    hipLaunchKernelGGL(backproject_mean_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  else
-    hipLaunchKernelGGL(backproject_mean_kernel<1>, grid, dim3(256), 0, (hipStream_t)stream, p);
-  IVX_CHECK_LAUNCH("ivx_backproject_mean_fwd");
+  IVX_REQUIRE(d->B <= 65535, "%s: batch too large", what);
+  IVX_REQUIRE((d->C + vec - 1) / vec <= 64 * 4, "%s: C=%d too large (max %d)", what, d->C, 256 * vec);
+  IVX_REQUIRE(!c.partials || bp_single_view_copy(c), "%s: partial maxima come from the single-view kernel only", what);
   return IVX_OK;
 }
 
+// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams (a plain launch passes the base).
+static BpGatherParams bp_fill(const BpCall &c, dim3 *grid) {
+  const ivx_backproject_desc &d = *c.d;
+  BpGatherParams p;
+  p.feat = (const float *)c.feat; p.proj = c.proj; p.new_origin = c.new_origin; p.crop_hw = c.crop_hw;
+  p.volume = (float *)c.volume; p.valid = c.valid; p.count = c.count; p.mean_out = c.mean_out;
+  // the running state is read unless `first`; a bf16 sum is the accumulate kernel from a zero state (bp_launch), so it never reads one
+  p.first = d.mode == IVX_LIFT_ACCUM ? d.first : (d.mode == IVX_LIFT_SUM && d.feat_dtype == IVX_BF16) ? 1 : 0;
+  p.vs0 = c.voxel_size[0]; p.vs1 = c.voxel_size[1]; p.vs2 = c.voxel_size[2];
+  p.V = d.V; p.FH = d.FH; p.FW = d.FW; p.C = d.C; p.X = d.X; p.Y = d.Y; p.Z = d.Z; p.N = d.X * d.Y * d.Z;
+  const int vec = (d.C % 4 == 0) ? 4 : 1;
+  p.nchunk = (d.C + vec - 1) / vec;
+  int lg = 0;
+  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
+  p.lpv_log2 = lg;
+  p.view_slot = c.view_slot; p.S = c.S;
+  if (bp_single_view_copy(c)) {      // 256 voxels per workgroup regardless of the group width (each lane projects one voxel)
+    p.pmax = c.partials; p.nblk = 0; p.q = 0;
+    *grid = dim3((p.N + 255) / 256, d.B);
+    return p;
+  }
+  const int vox_per_block = 256 >> lg;
+  p.pmax = nullptr; p.nblk = (p.N + vox_per_block - 1) / vox_per_block; p.q = bp_q(p.nblk);
+  *grid = dim3(p.q ? 8u * (unsigned)p.q : (unsigned)p.nblk, d.B);
+  return p;
+}
+
+// The selection table: every instantiation of the two lift kernels is launched from exactly one line below.
+static int bp_launch(const BpCall &c, const BpGatherParams &g, const dim3 grid) {
+  const ivx_backproject_desc &d = *c.d;
+  const BpParams &p = g;
+  const bool bf16 = d.feat_dtype == IVX_BF16, bilinear = d.sampling == IVX_SAMPLE_BILINEAR, vec4 = d.C % 4 == 0;
+  // BP_SUM exists for fp32 features only: a bf16 sum runs BP_ACCUM (fp32 sums) with first = 1 and no mean_out (bp_fill, bp_validate)
+  const int mode = d.mode == IVX_LIFT_MEAN ? BP_MEAN : (d.mode == IVX_LIFT_SUM && !bf16) ? BP_SUM : BP_ACCUM;
+  const dim3 block(256);
+  hipStream_t st = (hipStream_t)c.stream;
+  if (c.gather) {                                   // MEAN only, VEC 4 only, one listed view too
+    if (bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true>), grid, block, 0, st, g);
+    else if (bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true>), grid, block, 0, st, g);
+    else if (bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true>), grid, block, 0, st, g);
+    else                   hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true>), grid, block, 0, st, g);
+  } else if (bilinear) {                            // one view too: the blend is arithmetic, not a copy
+    if (mode == BP_MEAN && bf16)       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
+    else if (mode == BP_MEAN && vec4)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
+    else if (mode == BP_MEAN)          hipLaunchKernelGGL((backproject_mean_kernel<1, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
+    else if (mode == BP_SUM)           hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM, float, BP_BILINEAR>), grid, block, 0, st, p);
+    else if (bf16)                     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
+    else                               hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR>), grid, block, 0, st, p);
+  } else if (bp_single_view_copy(c)) {              // nearest fp32 mean of one view: the copy kernel (a bf16 view is not: its mean converts)
+    if (vec4)  hipLaunchKernelGGL(backproject_single_view_kernel<4>, grid, block, 0, st, p);
+    else       hipLaunchKernelGGL(backproject_single_view_kernel<1>, grid, block, 0, st, p);
+  } else {
+    if (mode == BP_MEAN && bf16)       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16>), grid, block, 0, st, p);
+    else if (mode == BP_MEAN && vec4)  hipLaunchKernelGGL(backproject_mean_kernel<4>, grid, block, 0, st, p);
+    else if (mode == BP_MEAN)          hipLaunchKernelGGL(backproject_mean_kernel<1>, grid, block, 0, st, p);
+    else if (mode == BP_SUM)           hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM>), grid, block, 0, st, p);
+    else if (bf16)                     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16>), grid, block, 0, st, p);
+    else                               hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float>), grid, block, 0, st, p);
+  }
+  IVX_CHECK_LAUNCH(c.what);
+  return IVX_OK;
+}
+
+static int bp_run(const BpCall &c) {
+  const int rc = bp_validate(c);
+  if (rc != IVX_OK) return rc;
+  dim3 grid;
+  return bp_launch(c, bp_fill(c, &grid), grid);
+}
+
+// ------------------------------------------------------------------ the exports (include/imvoxel.h): each states its call and runs it
 extern "C" int ivx_backproject_mean_fwd(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C,
                                         const float *proj, const float *new_origin, const int32_t *crop_hw,
                                         const float *voxel_size, int32_t X, int32_t Y, int32_t Z, float *volume,
                                         uint8_t *valid, ivx_stream_t stream) {
-  IVX_REQUIRE(valid, "ivx_backproject_mean_fwd: null argument");
-  return backproject_launch(feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z, volume, valid, nullptr, stream);
+  const ivx_backproject_desc d = bp_desc(B, V, FH, FW, C, X, Y, Z, IVX_F32, IVX_LIFT_MEAN);
+  return bp_run({"ivx_backproject_mean_fwd", &d, voxel_size, feat, proj, new_origin, crop_hw, volume, nullptr, nullptr, valid, stream});
 }
 
 // Single-view lift that also leaves one max |volume| per workgroup: ivx_backproject_amax_blocks(B, V, X, Y, Z) floats (0: this shape
@@ -458,246 +547,84 @@ extern "C" int32_t ivx_backproject_amax_blocks(int32_t B, int32_t V, int32_t X, 
 extern "C" int ivx_backproject_mean_fwd_amax(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
                                              const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y,
                                              int32_t Z, float *volume, uint8_t *valid, float *partials, ivx_stream_t stream) {
-  IVX_REQUIRE(valid, "ivx_backproject_mean_fwd_amax: null argument");
-  IVX_REQUIRE(!partials || V == 1, "ivx_backproject_mean_fwd_amax: partial maxima come from the single-view kernel only");
-  return backproject_launch(feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z, volume, valid, nullptr, stream, partials);
+  const ivx_backproject_desc d = bp_desc(B, V, FH, FW, C, X, Y, Z, IVX_F32, IVX_LIFT_MEAN);
+  return bp_run({"ivx_backproject_mean_fwd_amax", &d, voxel_size, feat, proj, new_origin, crop_hw, volume, nullptr, nullptr, valid, stream, partials});
+}
+
+// bf16 storage (optional reduced-precision mode): feat / volume are bf16, everything else as ivx_backproject_mean_fwd.  One view runs the
+// mean kernel here too; callers that want the copy pass the bf16 map as C/2 32-bit words to ivx_backproject_mean_fwd.  C % 4 == 0.
+extern "C" int ivx_backproject_mean_fwd_bf16(const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C,
+                                             const float *proj, const float *new_origin, const int32_t *crop_hw,
+                                             const float *voxel_size, int32_t X, int32_t Y, int32_t Z, void *volume,
+                                             uint8_t *valid, ivx_stream_t stream) {
+  const ivx_backproject_desc d = bp_desc(B, V, FH, FW, C, X, Y, Z, IVX_BF16, IVX_LIFT_MEAN);
+  return bp_run({"ivx_backproject_mean_fwd_bf16", &d, voxel_size, feat, proj, new_origin, crop_hw, volume, nullptr, nullptr, valid, stream});
 }
 
 extern "C" int ivx_backproject_sum_fwd(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C,
                                        const float *proj, const float *new_origin, const int32_t *crop_hw,
                                        const float *voxel_size, int32_t X, int32_t Y, int32_t Z, float *volume_sum,
                                        int32_t *count, ivx_stream_t stream) {
-  IVX_REQUIRE(count, "ivx_backproject_sum_fwd: null argument");
-  return backproject_launch(feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z, volume_sum, nullptr, count, stream);
-}
-
-extern "C" int ivx_volume_normalize_fwd(float *volume, const int32_t *count, int64_t n_voxels, int32_t C, uint8_t *valid,
-                                        ivx_stream_t stream) {
-  IVX_REQUIRE(volume && count && valid, "ivx_volume_normalize_fwd: null argument");
-  IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "ivx_volume_normalize_fwd: bad dims (C %% 4 must be 0)");
-  const long long total4 = (long long)n_voxels * (C / 4);
-  long long blocks = (total4 + 255) / 256;
-  if (blocks > 256 * 64) blocks = 256 * 64;
-  hipLaunchKernelGGL(volume_normalize_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume, volume, count, valid, total4, C / 4);
-  IVX_CHECK_LAUNCH("ivx_volume_normalize_fwd");
-  return IVX_OK;
-}
-
-// Out-of-place ivx_volume_normalize_fwd: the mean of a running (sum, count) volume in fp32 or bf16; the sums are left intact.
-extern "C" int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype,
-                                   uint8_t *valid, ivx_stream_t stream) {
-  IVX_REQUIRE(volume_sum && count && out && valid, "ivx_volume_mean_fwd: null argument");
-  IVX_REQUIRE((const void *)volume_sum != out, "ivx_volume_mean_fwd: out must not be volume_sum (ivx_volume_normalize_fwd works in place)");
-  IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "ivx_volume_mean_fwd: bad dims (C %% 4 must be 0)");
-  IVX_REQUIRE(out_dtype == IVX_F32 || out_dtype == IVX_BF16, "ivx_volume_mean_fwd: out_dtype must be IVX_F32 or IVX_BF16");
-  const long long total4 = (long long)n_voxels * (C / 4);
-  long long blocks = (total4 + 255) / 256;
-  if (blocks > 256 * 64) blocks = 256 * 64;
-  if (out_dtype == IVX_BF16)
-    hipLaunchKernelGGL(volume_normalize_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (__bf16 *)out, count, valid, total4, C / 4);
-  else
-    hipLaunchKernelGGL(volume_normalize_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (float *)out, count, valid, total4, C / 4);
-  IVX_CHECK_LAUNCH("ivx_volume_mean_fwd");
-  return IVX_OK;
+  const ivx_backproject_desc d = bp_desc(B, V, FH, FW, C, X, Y, Z, IVX_F32, IVX_LIFT_SUM);
+  return bp_run({"ivx_backproject_sum_fwd", &d, voxel_size, feat, proj, new_origin, crop_hw, volume_sum, count, nullptr, nullptr, stream});
 }
 
 // Streaming scenes: add V views to a running (sum, count) volume (BP_ACCUM mode of backproject_mean_kernel).
-template <typename T>
-static int backproject_accum_launch(const char *what, const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
-                                    const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y, int32_t Z,
-                                    float *volume_sum, int32_t *count, int32_t first, void *mean_out, uint8_t *valid_out, ivx_stream_t stream) {
-  IVX_REQUIRE(feat && proj && new_origin && crop_hw && voxel_size && volume_sum && count, "%s: null argument", what);
-  IVX_REQUIRE((mean_out != nullptr) == (valid_out != nullptr), "%s: mean_out and valid_out must both be given or both be NULL", what);
-  IVX_REQUIRE(B > 0 && V > 0 && FH > 0 && FW > 0 && C > 0 && X > 0 && Y > 0 && Z > 0, "%s: non-positive dims", what);
-  IVX_REQUIRE(C % 4 == 0, "%s: C %% 4 must be 0", what);
-  IVX_REQUIRE((int64_t)X * Y * Z < (1LL << 31), "%s: voxel grid too large", what);
-  IVX_REQUIRE((int64_t)B * V * FH * FW < (1LL << 31), "%s: feature maps too large", what);
-  IVX_REQUIRE(B <= 65535, "%s: batch too large", what);
-  BpParams p;
-  p.feat = (const float *)feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = volume_sum; p.valid = valid_out;
-  p.count = count; p.mean_out = mean_out; p.first = first; p.pmax = nullptr;
-  p.vs0 = voxel_size[0]; p.vs1 = voxel_size[1]; p.vs2 = voxel_size[2];
-  p.V = V; p.FH = FH; p.FW = FW; p.C = C; p.X = X; p.Y = Y; p.Z = Z; p.N = X * Y * Z;
-  p.nchunk = C / 4;
-  IVX_REQUIRE(p.nchunk <= 64 * 4, "%s: C=%d too large (max 1024)", what, C);
-  int lg = 0;
-  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
-  p.lpv_log2 = lg;
-  const int vpb = 256 >> lg;
-  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, T>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
-  IVX_CHECK_LAUNCH(what);
-  return IVX_OK;
-}
-
 extern "C" int ivx_backproject_accum_fwd(const float *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
                                          const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y,
                                          int32_t Z, float *volume_sum, int32_t *count, int32_t first, float *mean_out, uint8_t *valid_out,
                                          ivx_stream_t stream) {
-  return backproject_accum_launch<float>("ivx_backproject_accum_fwd", feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z, volume_sum,
-                                         count, first, mean_out, valid_out, stream);
+  const ivx_backproject_desc d = bp_desc(B, V, FH, FW, C, X, Y, Z, IVX_F32, IVX_LIFT_ACCUM, first);
+  return bp_run({"ivx_backproject_accum_fwd", &d, voxel_size, feat, proj, new_origin, crop_hw, volume_sum, count, mean_out, valid_out, stream});
 }
 
 extern "C" int ivx_backproject_accum_fwd_bf16(const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C, const float *proj,
                                               const float *new_origin, const int32_t *crop_hw, const float *voxel_size, int32_t X, int32_t Y,
                                               int32_t Z, float *volume_sum, int32_t *count, int32_t first, void *mean_out, uint8_t *valid_out,
                                               ivx_stream_t stream) {
-  return backproject_accum_launch<__bf16>("ivx_backproject_accum_fwd_bf16", feat, B, V, FH, FW, C, proj, new_origin, crop_hw, voxel_size, X, Y, Z,
-                                          volume_sum, count, first, mean_out, valid_out, stream);
+  const ivx_backproject_desc d = bp_desc(B, V, FH, FW, C, X, Y, Z, IVX_BF16, IVX_LIFT_ACCUM, first);
+  return bp_run({"ivx_backproject_accum_fwd_bf16", &d, voxel_size, feat, proj, new_origin, crop_hw, volume_sum, count, mean_out, valid_out, stream});
 }
 
-// bf16 storage (optional reduced-precision mode): feat / volume are bf16, everything else as ivx_backproject_mean_fwd.
-// Multi-view launches only (with one view the lift is a byte copy: pass the bf16 map as C/2 32-bit words to
-// ivx_backproject_mean_fwd).  C % 4 == 0.
-extern "C" int ivx_backproject_mean_fwd_bf16(const void *feat, int32_t B, int32_t V, int32_t FH, int32_t FW, int32_t C,
-                                             const float *proj, const float *new_origin, const int32_t *crop_hw,
-                                             const float *voxel_size, int32_t X, int32_t Y, int32_t Z, void *volume,
-                                             uint8_t *valid, ivx_stream_t stream) {
-  IVX_REQUIRE(feat && proj && new_origin && crop_hw && voxel_size && volume && valid, "ivx_backproject_mean_fwd_bf16: null argument");
-  IVX_REQUIRE(B > 0 && V > 0 && FH > 0 && FW > 0 && C > 0 && C % 4 == 0 && X > 0 && Y > 0 && Z > 0, "ivx_backproject_mean_fwd_bf16: bad dims (C %% 4 must be 0)");
-  IVX_REQUIRE((int64_t)X * Y * Z < (1LL << 31) && (int64_t)B * V * FH * FW < (1LL << 31) && B <= 65535, "ivx_backproject_mean_fwd_bf16: problem too large");
-  BpParams p;
-  p.feat = (const float *)feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = (float *)volume; p.valid = valid;
-  p.count = nullptr; p.pmax = nullptr; p.mean_out = nullptr; p.first = 0;
-  p.vs0 = voxel_size[0]; p.vs1 = voxel_size[1]; p.vs2 = voxel_size[2];
-  p.V = V; p.FH = FH; p.FW = FW; p.C = C; p.X = X; p.Y = Y; p.Z = Z; p.N = X * Y * Z;
-  p.nchunk = C / 4;
-  IVX_REQUIRE(p.nchunk <= 64 * 4, "ivx_backproject_mean_fwd_bf16: C=%d too large (max 1024)", C);
-  int lg = 0;
-  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
-  p.lpv_log2 = lg;
-  const int vpb = 256 >> lg;
-  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16>), dim3(bp_grid(p), B), dim3(256), 0, (hipStream_t)stream, p);
-  IVX_CHECK_LAUNCH("ivx_backproject_mean_fwd_bf16");
-  return IVX_OK;
-}
-
-// Bilinear sampling (BP_BILINEAR instantiations of backproject_mean_kernel): every mode, fp32 and bf16.  One view takes the same kernel
-// (its mean divides by a count of 1, which is exact); the nearest single-view copy kernel and its per-workgroup maxima do not apply.
-static int backproject_bilinear_launch(const ivx_backproject_desc *d, const void *feat, const float *proj, const float *new_origin, const int32_t *crop_hw,
-                                       void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream) {
-  const char *what = "ivx_backproject_fwd_ex";
-  const bool bf16 = d->feat_dtype == IVX_BF16;
-  IVX_REQUIRE(feat && proj && new_origin && crop_hw && volume, "%s: null argument", what);
-  if (d->mode == IVX_LIFT_MEAN) {
-    IVX_REQUIRE(valid, "%s: null argument (the mean mode writes valid)", what);
-    IVX_REQUIRE(!count && !mean_out, "%s: the mean mode takes no count / mean_out", what);
-  } else if (d->mode == IVX_LIFT_SUM) {
-    IVX_REQUIRE(count, "%s: null argument (the sum mode writes count)", what);
-    IVX_REQUIRE(!valid && !mean_out, "%s: the sum mode takes no valid / mean_out", what);
-  } else {
-    IVX_REQUIRE(count, "%s: null argument (the accumulate mode updates count)", what);
-    IVX_REQUIRE((mean_out != nullptr) == (valid != nullptr), "%s: mean_out and valid must both be given or both be NULL", what);
-  }
-  IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
-  const int vec = (d->C % 4 == 0) ? 4 : 1;
-  IVX_REQUIRE(vec == 4 || (d->mode == IVX_LIFT_MEAN && !bf16), "%s: C %% 4 must be 0 (every form but the fp32 mean)", what);
-  IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
-  IVX_REQUIRE((int64_t)d->B * d->V * d->FH * d->FW < (1LL << 31), "%s: feature maps too large", what);
-  IVX_REQUIRE(d->B <= 65535, "%s: batch too large", what);
-  BpParams p;
-  p.feat = (const float *)feat; p.proj = proj; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = (float *)volume; p.valid = valid;
-  p.count = count; p.mean_out = mean_out; p.first = d->first; p.pmax = nullptr;
-  p.vs0 = d->voxel_size[0]; p.vs1 = d->voxel_size[1]; p.vs2 = d->voxel_size[2];
-  p.V = d->V; p.FH = d->FH; p.FW = d->FW; p.C = d->C; p.X = d->X; p.Y = d->Y; p.Z = d->Z; p.N = d->X * d->Y * d->Z;
-  p.nchunk = (d->C + vec - 1) / vec;
-  IVX_REQUIRE(p.nchunk <= 64 * 4, "%s: C=%d too large (max %d)", what, d->C, 256 * vec);
-  int lg = 0;
-  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
-  p.lpv_log2 = lg;
-  const int vpb = 256 >> lg;
-  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-  const dim3 grid(bp_grid(p), d->B), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  if (d->mode == IVX_LIFT_MEAN) {
-    if (bf16)
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
-    else if (vec == 4)
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
-    else
-      hipLaunchKernelGGL((backproject_mean_kernel<1, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
-  } else if (d->mode == IVX_LIFT_SUM && !bf16) {
-    hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM, float, BP_BILINEAR>), grid, block, 0, st, p);
-  } else {
-    if (d->mode == IVX_LIFT_SUM) p.first = 1;       // bf16 features, fp32 sums: the accumulate kernel from a zero state, no mean
-    if (bf16)
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
-    else
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR>), grid, block, 0, st, p);
-  }
-  IVX_CHECK_LAUNCH(what);
-  return IVX_OK;
-}
-
-// One entry point for both sampling rules and the three modes (include/imvoxel.h).  The nearest rule forwards to the entry points above.
+// One entry point for both sampling rules, the three modes and both feature types (include/imvoxel.h).
 extern "C" int ivx_backproject_fwd_ex(const ivx_backproject_desc *d, const void *feat, const float *proj, const float *new_origin,
                                       const int32_t *crop_hw, void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream) {
-  IVX_REQUIRE(d, "ivx_backproject_fwd_ex: null descriptor");
-  IVX_REQUIRE(d->sampling == IVX_SAMPLE_NEAREST || d->sampling == IVX_SAMPLE_BILINEAR, "ivx_backproject_fwd_ex: sampling %d (IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR)", d->sampling);
-  IVX_REQUIRE(d->mode == IVX_LIFT_MEAN || d->mode == IVX_LIFT_SUM || d->mode == IVX_LIFT_ACCUM, "ivx_backproject_fwd_ex: mode %d (IVX_LIFT_MEAN | IVX_LIFT_SUM | IVX_LIFT_ACCUM)", d->mode);
-  IVX_REQUIRE(d->feat_dtype == IVX_F32 || d->feat_dtype == IVX_BF16, "ivx_backproject_fwd_ex: feat_dtype %d (IVX_F32 | IVX_BF16)", d->feat_dtype);
-  if (d->sampling == IVX_SAMPLE_BILINEAR) return backproject_bilinear_launch(d, feat, proj, new_origin, crop_hw, volume, count, mean_out, valid, stream);
-  const bool bf16 = d->feat_dtype == IVX_BF16;
-  const float *vs = d->voxel_size;
-  if (d->mode == IVX_LIFT_MEAN) {
-    IVX_REQUIRE(!count && !mean_out, "ivx_backproject_fwd_ex: the mean mode takes no count / mean_out");
-    if (bf16) return ivx_backproject_mean_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, volume, valid, stream);
-    return ivx_backproject_mean_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, valid, stream);
-  }
-  if (d->mode == IVX_LIFT_SUM) {
-    IVX_REQUIRE(!valid && !mean_out, "ivx_backproject_fwd_ex: the sum mode takes no valid / mean_out");
-    if (bf16) return ivx_backproject_accum_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, 1, nullptr, nullptr, stream);
-    return ivx_backproject_sum_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, stream);
-  }
-  if (bf16) return ivx_backproject_accum_fwd_bf16(feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, d->first, mean_out, valid, stream);
-  return ivx_backproject_accum_fwd((const float *)feat, d->B, d->V, d->FH, d->FW, d->C, proj, new_origin, crop_hw, vs, d->X, d->Y, d->Z, (float *)volume, count, d->first, (float *)mean_out, valid, stream);
+  return bp_run({"ivx_backproject_fwd_ex", d, d ? d->voxel_size : nullptr, feat, proj, new_origin, crop_hw, volume, count, mean_out, valid, stream});
 }
 
-// Gathered mean lift (include/imvoxel.h): the listed views of a feature / projection pool, in list order.  Every shape, one view included, runs
-// the GATHER instantiation of backproject_mean_kernel.
+// Gathered mean lift (include/imvoxel.h): the listed views of a feature / projection pool, in list order.
 extern "C" int ivx_backproject_gather_fwd(const ivx_backproject_desc *d, int32_t S, const void *feat_pool, const float *proj_pool, const int32_t *view_slot,
                                           const float *new_origin, const int32_t *crop_hw, void *volume, uint8_t *valid, ivx_stream_t stream) {
-  const char *what = "ivx_backproject_gather_fwd";
-  IVX_REQUIRE(d, "%s: null descriptor", what);
-  IVX_REQUIRE(d->sampling == IVX_SAMPLE_NEAREST || d->sampling == IVX_SAMPLE_BILINEAR, "%s: sampling %d (IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR)", what, d->sampling);
-  IVX_REQUIRE(d->mode == IVX_LIFT_MEAN, "%s: mode %d (IVX_LIFT_MEAN only)", what, d->mode);
-  IVX_REQUIRE(d->feat_dtype == IVX_F32 || d->feat_dtype == IVX_BF16, "%s: feat_dtype %d (IVX_F32 | IVX_BF16)", what, d->feat_dtype);
-  IVX_REQUIRE(feat_pool && proj_pool && view_slot && new_origin && crop_hw && volume && valid, "%s: null argument", what);
-  IVX_REQUIRE(S > 0, "%s: S=%d slots (the pools need at least one)", what, S);
-  IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
-  IVX_REQUIRE(d->C % 4 == 0, "%s: C %% 4 must be 0", what);
-  IVX_REQUIRE(d->C <= 1024, "%s: C=%d too large (max 1024)", what, d->C);
-  IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
-  IVX_REQUIRE((int64_t)S * d->FH * d->FW < (1LL << 31), "%s: feature pool too large", what);
-  IVX_REQUIRE(d->B <= 65535, "%s: batch too large", what);
-  IVX_REQUIRE((int64_t)d->B * d->V < (1LL << 31), "%s: view list too large", what);
-  BpGatherParams p;
-  p.feat = (const float *)feat_pool; p.proj = proj_pool; p.new_origin = new_origin; p.crop_hw = crop_hw; p.volume = (float *)volume; p.valid = valid;
-  p.count = nullptr; p.mean_out = nullptr; p.first = 0; p.pmax = nullptr;
-  p.view_slot = view_slot; p.S = S;
-  p.vs0 = d->voxel_size[0]; p.vs1 = d->voxel_size[1]; p.vs2 = d->voxel_size[2];
-  p.V = d->V; p.FH = d->FH; p.FW = d->FW; p.C = d->C; p.X = d->X; p.Y = d->Y; p.Z = d->Z; p.N = d->X * d->Y * d->Z;
-  p.nchunk = d->C / 4;
-  int lg = 0;
-  while ((1 << lg) < p.nchunk && lg < 6) ++lg;
-  p.lpv_log2 = lg;
-  const int vpb = 256 >> lg;
-  p.nblk = (p.N + vpb - 1) / vpb; p.q = bp_q(p.nblk);
-  const dim3 grid(bp_grid(p), d->B), block(256);
-  hipStream_t st = (hipStream_t)stream;
-  const bool bf16 = d->feat_dtype == IVX_BF16;
-  if (d->sampling == IVX_SAMPLE_BILINEAR) {
-    if (bf16)
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true>), grid, block, 0, st, p);
-    else
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true>), grid, block, 0, st, p);
-  } else {
-    if (bf16)
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true>), grid, block, 0, st, p);
-    else
-      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true>), grid, block, 0, st, p);
-  }
+  return bp_run({"ivx_backproject_gather_fwd", d, d ? d->voxel_size : nullptr, feat_pool, proj_pool, new_origin, crop_hw, volume, nullptr, nullptr, valid, stream,
+                 nullptr, true, view_slot, S});
+}
+
+// ------------------------------------------------------------------ mean of a (sum, count) volume
+// out == sum: in place (ivx_volume_normalize_fwd).  Otherwise the sums stay intact and out may be bf16 (ivx_volume_mean_fwd).
+static int volume_normalize_launch(const char *what, const float *sum, void *out, int32_t out_dtype, const int32_t *count, int64_t n_voxels, int32_t C,
+                                   uint8_t *valid, ivx_stream_t stream) {
+  IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "%s: bad dims (C %% 4 must be 0)", what);
+  IVX_REQUIRE(out_dtype == IVX_F32 || out_dtype == IVX_BF16, "%s: out_dtype must be IVX_F32 or IVX_BF16", what);
+  const long long total4 = (long long)n_voxels * (C / 4);
+  long long blocks = (total4 + 255) / 256;
+  if (blocks > 256 * 64) blocks = 256 * 64;
+  if (out_dtype == IVX_BF16)
+    hipLaunchKernelGGL(volume_normalize_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, (__bf16 *)out, count, valid, total4, C / 4);
+  else
+    hipLaunchKernelGGL(volume_normalize_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, (float *)out, count, valid, total4, C / 4);
   IVX_CHECK_LAUNCH(what);
   return IVX_OK;
+}
+
+extern "C" int ivx_volume_normalize_fwd(float *volume, const int32_t *count, int64_t n_voxels, int32_t C, uint8_t *valid,
+                                        ivx_stream_t stream) {
+  IVX_REQUIRE(volume && count && valid, "ivx_volume_normalize_fwd: null argument");
+  return volume_normalize_launch("ivx_volume_normalize_fwd", volume, volume, IVX_F32, count, n_voxels, C, valid, stream);
+}
+
+extern "C" int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype,
+                                   uint8_t *valid, ivx_stream_t stream) {
+  IVX_REQUIRE(volume_sum && count && out && valid, "ivx_volume_mean_fwd: null argument");
+  IVX_REQUIRE((const void *)volume_sum != out, "ivx_volume_mean_fwd: out must not be volume_sum (ivx_volume_normalize_fwd works in place)");
+  return volume_normalize_launch("ivx_volume_mean_fwd", volume_sum, out, out_dtype, count, n_voxels, C, valid, stream);
 }

@@ -805,94 +805,91 @@ def upsample_trilinear2x(x):
 # optional stage timing (bench.py): when a list, backproject_mean appends ('lift', start_event, end_event) around its launch
 stage_trace = None
 
+_LIFT_MEAN, _LIFT_SUM, _LIFT_ACCUM = 0, 1, 2
+_F32_BF16 = (torch.float32, torch.bfloat16)
+# the nearest rule goes to the entry points of the parity claims, called exactly as before ivx_backproject_fwd_ex existed (a library older than 0.4.4 serves it)
+_LIFT_NEAREST = {(_LIFT_MEAN, torch.float32): 'ivx_backproject_mean_fwd', (_LIFT_MEAN, torch.bfloat16): 'ivx_backproject_mean_fwd_bf16',
+                 (_LIFT_SUM, torch.float32): 'ivx_backproject_sum_fwd',
+                 (_LIFT_ACCUM, torch.float32): 'ivx_backproject_accum_fwd', (_LIFT_ACCUM, torch.bfloat16): 'ivx_backproject_accum_fwd_bf16'}
+
+
+def _lift(mode, sampling, feat, proj, new_origin, crop_hw, voxel_size, n_voxels=None, vol=None, count=None, mean_out=None, valid=None, first=False,
+          feat_dtypes=(torch.float32,)):
+    """The one checker and caller of the lifts of a view stack: feat [B*V,1,FH,FW,C] channels-last (one of feat_dtypes), proj [B,V,3,4],
+    new_origin [B,3], crop_hw [B,2] int32, all on the device.  _LIFT_MEAN: allocates vol [B,X,Y,Z,C] (feat's dtype) and valid (uint8);
+    _LIFT_SUM: vol (fp32) and count (int32); _LIFT_ACCUM: the caller's state vol / count, checked here, and its optional mean_out / valid.
+    sampling 0: the older export of (mode, dtype); 1: ivx_backproject_fwd_ex.  Returns (vol, count, valid)."""
+    dtype = getattr(feat, 'dtype', None)
+    _chk(feat, 'feat', dtype if dtype in feat_dtypes else feat_dtypes[0])
+    _chk(proj, 'proj')
+    _chk(new_origin, 'new_origin')
+    _chk(crop_hw, 'crop_hw', torch.int32)
+    if mode == _LIFT_ACCUM:
+        _chk(vol, 'vol_sum')
+        _chk(count, 'count', torch.int32)
+    B, V = proj.shape[0], proj.shape[1]
+    BV, D, FH, FW, Cn = feat.shape
+    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
+        raise ValueError('feat / proj shapes do not agree')
+    if mode == _LIFT_ACCUM:
+        if vol.dim() != 5 or vol.shape[0] != B or vol.shape[-1] != Cn or tuple(count.shape) != tuple(vol.shape[:-1]):
+            raise ValueError('vol_sum must be [B,X,Y,Z,C] and count [B,X,Y,Z] for the features\' B and C')
+        if mean_out is not None:
+            _chk(mean_out, 'mean_out', dtype)
+            if tuple(mean_out.shape) != tuple(vol.shape):
+                raise ValueError('mean_out must have the shape of vol_sum')
+            _chk_mask(valid, 'valid_out', count.shape)
+        X, Y, Z = (int(v) for v in vol.shape[1:4])
+    else:
+        X, Y, Z = (int(v) for v in n_voxels)
+        vol = torch.empty((B, X, Y, Z, Cn), device=feat.device, dtype=dtype if mode == _LIFT_MEAN else torch.float32)
+        if mode == _LIFT_MEAN:
+            valid = torch.empty((B, X, Y, Z), device=feat.device, dtype=torch.uint8)
+        else:
+            count = torch.empty((B, X, Y, Z), device=feat.device, dtype=torch.int32)
+    vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
+    if sampling:
+        name = 'ivx_backproject_fwd_ex'
+        fn = getattr(_lib.lib(), name, None)
+        if fn is None:
+            raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_fwd_ex (bilinear sampling needs version 0.4.4)')
+        d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, vs, _DT[dtype], mode, int(sampling), int(bool(first)))
+        rc = fn(C.byref(d), _ptr(feat), _ptr(proj), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(count), _ptr(mean_out), _ptr(valid), _stream())
+    else:
+        name = _LIFT_NEAREST[mode, dtype]
+        outs = {_LIFT_MEAN: (_ptr(vol), _ptr(valid)), _LIFT_SUM: (_ptr(vol), _ptr(count)),
+                _LIFT_ACCUM: (_ptr(vol), _ptr(count), int(bool(first)), _ptr(mean_out), _ptr(valid))}[mode]
+        rc = getattr(_lib.lib(), name)(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw), vs, X, Y, Z, *outs, _stream())
+    check(rc, name)
+    return vol, count, valid
+
 
 def backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
-    """sampling: 'nearest' (the reference's rule: the entry points of the parity claims, called exactly as before the option existed) or
+    """feat [B*V,1,FH,FW,C] channels-last (fp32 or bf16), proj [B,V,3,4], new_origin [B,3], crop_hw [B,2] int32 (device)
+    -> volume [B,X,Y,Z,C] (feat's dtype), valid [B,X,Y,Z] bool.
+    sampling: 'nearest' (the reference's rule: the entry points of the parity claims, called exactly as before the option existed) or
     'bilinear' (optional extra mode, ivx_backproject_fwd_ex; include/imvoxel.h has the definition)."""
-    lift = _backproject_mean if _lib.sampling_id(sampling) == 0 else _backproject_mean_bilinear
+    sampling = _lib.sampling_id(sampling)
     if stage_trace is None:
-        return lift(feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
+        return _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling)
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
-    out = lift(feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
+    out = _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling)
     e1.record()
     stage_trace.append(('lift', e0, e1))
     return out
 
 
-_LIFT_MEAN, _LIFT_SUM, _LIFT_ACCUM = 0, 1, 2
-
-
-def _backproject_ex(mode, feat, proj, new_origin, crop_hw, voxel_size, xyz, volume, count=None, mean_out=None, valid=None, first=False, sampling=1):
-    """ivx_backproject_fwd_ex on checked tensors (the bilinear rule of the three wrappers below)."""
-    fn = getattr(_lib.lib(), 'ivx_backproject_fwd_ex', None)
-    if fn is None:
-        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_fwd_ex (bilinear sampling needs version 0.4.4)')
-    B, V = proj.shape[0], proj.shape[1]
-    BV, D, FH, FW, Cn = feat.shape
-    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
-        raise ValueError('feat / proj shapes do not agree')
-    X, Y, Z = (int(v) for v in xyz)
-    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[feat.dtype], mode, int(sampling),
-                             int(bool(first)))
-    check(fn(C.byref(d), _ptr(feat), _ptr(proj), _ptr(new_origin), _ptr(crop_hw), _ptr(volume), _ptr(count), _ptr(mean_out), _ptr(valid), _stream()),
-          'ivx_backproject_fwd_ex')
-
-
-def _backproject_mean_bilinear(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
-    """backproject_mean with the bilinear rule: fp32 or bf16 maps, any number of views through the one kernel template (a single bf16
-    view too: the blend is arithmetic, not a copy)."""
-    if feat.dtype not in (torch.float32, torch.bfloat16):
+def _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling):
+    if sampling and feat.dtype not in _F32_BF16:
         raise TypeError(f'feat must be float32 or bfloat16, got {feat.dtype}')
-    _chk(feat, 'feat', feat.dtype)
-    _chk(proj, 'proj')
-    _chk(new_origin, 'new_origin')
-    _chk(crop_hw, 'crop_hw', torch.int32)
-    X, Y, Z = (int(v) for v in n_voxels)
-    vol = torch.empty((proj.shape[0], X, Y, Z, feat.shape[-1]), device=feat.device, dtype=feat.dtype)
-    valid = torch.empty((proj.shape[0], X, Y, Z), device=feat.device, dtype=torch.uint8)
-    _backproject_ex(_LIFT_MEAN, feat, proj, new_origin, crop_hw, voxel_size, (X, Y, Z), vol, valid=valid)
-    return vol, valid.view(torch.bool)
-
-
-def _backproject_mean(feat, proj, new_origin, crop_hw, voxel_size, n_voxels):
-    """feat [B*V,1,FH,FW,C] channels-last, proj [B,V,3,4], new_origin [B,3], crop_hw [B,2] int32 (device)
-    -> volume [B,X,Y,Z,C] (feat's dtype), valid [B,X,Y,Z] bool.
-    bf16 storage (optional reduced-precision mode): with one view the lift is a pure gather-copy (no arithmetic on the
-    features, imvoxelnet.py:75 divides by a count of 1), so a bf16 map with C channels is passed as C/2 32-bit words."""
-    if feat.dtype == torch.bfloat16:
-        if proj.shape[1] == 1 and feat.shape[-1] % 2 == 0:
-            vol, valid = _backproject_mean(feat.view(torch.float32), proj, new_origin, crop_hw, voxel_size, n_voxels)
-            return vol.view(torch.bfloat16), valid
-        _chk(feat, 'feat', torch.bfloat16)
-        _chk(proj, 'proj')
-        _chk(new_origin, 'new_origin')
-        _chk(crop_hw, 'crop_hw', torch.int32)
-        B, V = proj.shape[0], proj.shape[1]
-        BV, D, FH, FW, Cn = feat.shape
-        if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
-            raise ValueError('feat / proj shapes do not agree')
-        X, Y, Z = (int(v) for v in n_voxels)
-        vol = torch.empty((B, X, Y, Z, Cn), device=feat.device, dtype=torch.bfloat16)
-        valid = torch.empty((B, X, Y, Z), device=feat.device, dtype=torch.uint8)
-        vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
-        check(_lib.lib().ivx_backproject_mean_fwd_bf16(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw),
-                                                       vs, X, Y, Z, _ptr(vol), _ptr(valid), _stream()), 'ivx_backproject_mean_fwd_bf16')
-        return vol, valid.view(torch.bool)
-    _chk(feat, 'feat')
-    _chk(proj, 'proj')
-    _chk(new_origin, 'new_origin')
-    _chk(crop_hw, 'crop_hw', torch.int32)
-    B, V = proj.shape[0], proj.shape[1]
-    BV, D, FH, FW, Cn = feat.shape
-    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
-        raise ValueError('feat / proj shapes do not agree')
-    X, Y, Z = (int(v) for v in n_voxels)
-    vol = torch.empty((B, X, Y, Z, Cn), device=feat.device, dtype=torch.float32)
-    valid = torch.empty((B, X, Y, Z), device=feat.device, dtype=torch.uint8)
-    vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
-    check(_lib.lib().ivx_backproject_mean_fwd(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw),
-                                              vs, X, Y, Z, _ptr(vol), _ptr(valid), _stream()), 'ivx_backproject_mean_fwd')
+    if not sampling and feat.dtype == torch.bfloat16 and proj.shape[1] == 1 and feat.shape[-1] % 2 == 0:
+        # bf16 storage (optional reduced-precision mode): with one view the nearest lift is a pure gather-copy (no arithmetic on the features,
+        # imvoxelnet.py:75 divides by a count of 1), so a bf16 map with C channels is passed as C/2 32-bit words.  (The bilinear blend is
+        # arithmetic: a single bf16 view goes through the one kernel template like any other.)
+        vol, valid = _backproject_mean(feat.view(torch.float32), proj, new_origin, crop_hw, voxel_size, n_voxels, sampling)
+        return vol.view(torch.bfloat16), valid
+    vol, _, valid = _lift(_LIFT_MEAN, sampling, feat, proj, new_origin, crop_hw, voxel_size, n_voxels, feat_dtypes=_F32_BF16)
     return vol, valid.view(torch.bool)
 
 
@@ -903,10 +900,20 @@ def backproject_gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, vox
     view_slot: a host sequence / CPU int32 tensor (range-checked here, then uploaded: a slot outside [0, S) raises ValueError) or a
     device int32 tensor, used as it is (the kernel treats an out-of-range slot as a view that sees nothing).
     -> volume [B,X,Y,Z,C] (pool's dtype), valid [B,X,Y,Z] bool."""
+    return _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, n_voxels, sampling)
+
+
+def backproject_gather_mean_(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, vol, valid, sampling='nearest'):
+    """backproject_gather_mean into the caller's buffers (windowed scenes keep theirs): vol [B,X,Y,Z,C] (pool's dtype) and valid
+    [B,X,Y,Z] uint8 / bool are overwritten.  Returns (vol, valid as bool)."""
+    return _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, None, sampling, vol, valid)
+
+
+def _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, n_voxels, sampling, vol=None, valid=None):
     sampling = _lib.sampling_id(sampling)
     if not isinstance(pool, torch.Tensor) or not isinstance(proj_pool, torch.Tensor):
         raise TypeError('pool and proj_pool must be torch.Tensors')
-    if pool.dtype not in (torch.float32, torch.bfloat16):
+    if pool.dtype not in _F32_BF16:
         raise TypeError(f'pool must be float32 or bfloat16, got {pool.dtype}')
     if pool.dim() == 5 and pool.shape[1] == 1:
         pool = pool[:, 0]
@@ -936,44 +943,26 @@ def backproject_gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, vox
     fn = getattr(_lib.lib(), 'ivx_backproject_gather_fwd', None)
     if fn is None:
         raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_gather_fwd (needs version 0.4.6)')
-    X, Y, Z = (int(v) for v in n_voxels)
-    vol = torch.empty((B, X, Y, Z, Cn), device=pool.device, dtype=pool.dtype)
-    valid = torch.empty((B, X, Y, Z), device=pool.device, dtype=torch.uint8)
-    _backproject_gather(fn, pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, vol, valid, sampling)
-    return vol, valid.view(torch.bool)
-
-
-def _backproject_gather(fn, pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, vol, valid, sampling):
-    """ivx_backproject_gather_fwd on checked tensors: pool [S,FH,FW,C], view_slot [B,V] on the device, vol / valid written in place."""
-    S, FH, FW, Cn = pool.shape
-    B, V = view_slot.shape
-    X, Y, Z = vol.shape[1:4]
-    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], _LIFT_MEAN, int(sampling), 0)
+    if vol is None:
+        X, Y, Z = (int(v) for v in n_voxels)
+        vol = torch.empty((B, X, Y, Z, Cn), device=pool.device, dtype=pool.dtype)
+        valid = torch.empty((B, X, Y, Z), device=pool.device, dtype=torch.uint8)
+    else:
+        _chk(vol, 'vol', pool.dtype)
+        if vol.dim() != 5 or vol.shape[0] != B or vol.shape[-1] != Cn:
+            raise ValueError('vol must be [B,X,Y,Z,C] for the B rows of view_slot and the pool\'s C')
+        _chk_mask(valid, 'valid', vol.shape[:-1])
+        X, Y, Z = (int(v) for v in vol.shape[1:4])
+    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], _LIFT_MEAN, sampling, 0)
     check(fn(C.byref(d), S, _ptr(pool), _ptr(proj_pool), _ptr(view_slot), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(valid), _stream()),
           'ivx_backproject_gather_fwd')
+    return vol, valid.view(torch.bool)
 
 
 def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
     """View-sharded mode: like backproject_mean but returns the raw view sum [B,X,Y,Z,C] and the int32 view count
     [B,X,Y,Z] of THIS rank's views (to be all-reduced, then volume_normalize_).  sampling as for backproject_mean."""
-    sampling = _lib.sampling_id(sampling)
-    _chk(feat, 'feat')
-    _chk(proj, 'proj')
-    _chk(new_origin, 'new_origin')
-    _chk(crop_hw, 'crop_hw', torch.int32)
-    B, V = proj.shape[0], proj.shape[1]
-    BV, D, FH, FW, Cn = feat.shape
-    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
-        raise ValueError('feat / proj shapes do not agree')
-    X, Y, Z = (int(v) for v in n_voxels)
-    vol = torch.empty((B, X, Y, Z, Cn), device=feat.device, dtype=torch.float32)
-    cnt = torch.empty((B, X, Y, Z), device=feat.device, dtype=torch.int32)
-    if sampling:
-        _backproject_ex(_LIFT_SUM, feat, proj, new_origin, crop_hw, voxel_size, (X, Y, Z), vol, count=cnt, sampling=sampling)
-        return vol, cnt
-    vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
-    check(_lib.lib().ivx_backproject_sum_fwd(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw),
-                                             vs, X, Y, Z, _ptr(vol), _ptr(cnt), _stream()), 'ivx_backproject_sum_fwd')
+    vol, cnt, _ = _lift(_LIFT_SUM, _lib.sampling_id(sampling), feat, proj, new_origin, crop_hw, voxel_size, n_voxels)
     return vol, cnt
 
 
@@ -1005,36 +994,12 @@ def backproject_accum_(feat, proj, new_origin, crop_hw, voxel_size, vol_sum, cou
     mean_out [B,X,Y,Z,C] (feat's dtype) + valid_out [B,X,Y,Z] uint8 / bool: the same pass also writes the mean and the mask; both or
     neither.  sampling as for backproject_mean (one rule per running volume).  Returns (vol_sum, count)."""
     sampling = _lib.sampling_id(sampling)
-    if feat.dtype not in (torch.float32, torch.bfloat16):
+    if feat.dtype not in _F32_BF16:
         raise TypeError(f'feat must be float32 or bfloat16, got {feat.dtype}')
     if (mean_out is None) != (valid_out is None):
         raise ValueError('mean_out and valid_out must both be given or both be None')
-    _chk(feat, 'feat', feat.dtype)
-    _chk(proj, 'proj')
-    _chk(new_origin, 'new_origin')
-    _chk(crop_hw, 'crop_hw', torch.int32)
-    _chk(vol_sum, 'vol_sum')
-    _chk(count, 'count', torch.int32)
-    B, V = proj.shape[0], proj.shape[1]
-    BV, D, FH, FW, Cn = feat.shape
-    if BV != B * V or D != 1 or tuple(proj.shape[2:]) != (3, 4):
-        raise ValueError('feat / proj shapes do not agree')
-    if vol_sum.dim() != 5 or vol_sum.shape[0] != B or vol_sum.shape[-1] != Cn or tuple(count.shape) != tuple(vol_sum.shape[:-1]):
-        raise ValueError('vol_sum must be [B,X,Y,Z,C] and count [B,X,Y,Z] for the features\' B and C')
-    if mean_out is not None:
-        _chk(mean_out, 'mean_out', feat.dtype)
-        if tuple(mean_out.shape) != tuple(vol_sum.shape):
-            raise ValueError('mean_out must have the shape of vol_sum')
-        _chk_mask(valid_out, 'valid_out', count.shape)
-    X, Y, Z = (int(v) for v in vol_sum.shape[1:4])
-    if sampling:
-        _backproject_ex(_LIFT_ACCUM, feat, proj, new_origin, crop_hw, voxel_size, (X, Y, Z), vol_sum, count=count, mean_out=mean_out, valid=valid_out,
-                        first=first, sampling=sampling)
-        return vol_sum, count
-    vs = (C.c_float * 3)(*[float(v) for v in voxel_size])
-    name = 'ivx_backproject_accum_fwd_bf16' if feat.dtype == torch.bfloat16 else 'ivx_backproject_accum_fwd'
-    check(getattr(_lib.lib(), name)(_ptr(feat), B, V, FH, FW, Cn, _ptr(proj), _ptr(new_origin), _ptr(crop_hw), vs, X, Y, Z, _ptr(vol_sum),
-                                    _ptr(count), int(bool(first)), _ptr(mean_out), _ptr(valid_out), _stream()), name)
+    _lift(_LIFT_ACCUM, sampling, feat, proj, new_origin, crop_hw, voxel_size, vol=vol_sum, count=count, mean_out=mean_out, valid=valid_out, first=first,
+          feat_dtypes=_F32_BF16)
     return vol_sum, count
 
 
@@ -1043,7 +1008,7 @@ def volume_mean(vol_sum, count, dtype=torch.float32, out=None, valid_out=None):
     as they are.  out / valid_out: buffers to write into (allocated when None).  Returns (mean, valid bool [B,X,Y,Z])."""
     _chk(vol_sum, 'vol_sum')
     _chk(count, 'count', torch.int32)
-    if dtype not in (torch.float32, torch.bfloat16):
+    if dtype not in _F32_BF16:
         raise TypeError(f'dtype must be float32 or bfloat16, got {dtype}')
     if tuple(count.shape) != tuple(vol_sum.shape[:-1]):
         raise ValueError('count must have the spatial shape of the volume')

@@ -241,12 +241,9 @@ class SceneSession:
         if self.n_views == 0:
             raise RuntimeError('the scene has no views yet')
         if self._stale and self._window is not None:      # the set changed since the last lift: ONE gathered lift of the views in it, in order
-            fn = getattr(ops._lib.lib(), 'ivx_backproject_gather_fwd', None)
-            if fn is None:
-                raise ops._lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_gather_fwd (windowed scenes need version 0.4.6)')
             view_slot = torch.tensor([[v[1] for v in self._views]], dtype=torch.int32).to(self._ring.device)
-            ops._backproject_gather(fn, self._ring[:, 0], self._pring, view_slot, self._origin, self._crop, self._model.voxel_size, self._mean, self._valid,
-                                    ops._lib.sampling_id(getattr(self._model, 'sampling', 'nearest')))
+            ops.backproject_gather_mean_(self._ring, self._pring, view_slot, self._origin, self._crop, self._model.voxel_size, self._mean, self._valid,
+                                         getattr(self._model, 'sampling', 'nearest'))
             self._stale = False
         if self._stale:
             ops.volume_mean(self._sum, self._count, self._mean.dtype, out=self._mean, valid_out=self._valid)

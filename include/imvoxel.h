@@ -558,7 +558,7 @@ int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count, int64_t n
  *                        accumulate kernel from a zero state (fp32 sums)
  *        IVX_LIFT_ACCUM  volume = running fp32 sum + count, in/out, `first` as for ivx_backproject_accum_fwd; mean_out (feat_dtype) and
  *                        valid both given or both NULL
- * With sampling = IVX_SAMPLE_NEAREST it forwards to the entry points above (same checks, same launches).  A single-view bilinear lift
+ * With sampling = IVX_SAMPLE_NEAREST it runs what the entry points above run (same checks, same launches).  A single-view bilinear lift
  * runs the multi-view kernel (bf16 maps through the bf16 kernel; no per-workgroup maxima: ivx_backproject_amax_blocks describes the
  * nearest single-view kernel only).  IVX_ERR_INVALID_ARG before any launch: a null descriptor, an unknown sampling, mode or feat_dtype,
  * and the rules of the mode's entry point above -- null or superfluous pointers, non-positive dims, C % 4 != 0 (every form but the fp32
