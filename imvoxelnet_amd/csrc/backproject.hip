@@ -61,6 +61,13 @@ struct BpGatherParams : BpParams {
   const int *view_slot;     // [B, V]
   int S;
 };
+// ROWS instantiations (ivx_backproject_lists_fwd; scene batches): the gathered form whose sample b reads and writes row row[b] (NULL: b) of the
+// R-row state / output pools and, in BP_ACCUM, starts from zero by first_list[b] (NULL: `first` for every sample)
+struct BpListParams : BpGatherParams {
+  const int *row;           // [B] or NULL
+  const int *first_list;    // [B] or NULL
+  int R;
+};
 
 // MODE BP_MEAN: the reference's view mean + valid mask.  BP_SUM (view-sharded multi-GPU mode): the raw sum over
 // this rank's views and the per-voxel view count, to be all-reduced and normalised by volume_normalize_kernel.
@@ -94,11 +101,26 @@ __device__ __forceinline__ void bp_bilinear_weights(const float ax, const float 
 // the projecting lane's addressing differs -- which map and which projection rows view v is --; the broadcast, the sample function, the view-order
 // __fadd_rn chain, the division and the stores are the code of every other mode, so the result is bit for bit the non-gathered launch over a
 // contiguous copy of the listed views.  A slot outside [0, S) is tested before any address is formed: that view sees no voxel (off stays -1).
-template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false>
-__global__ __launch_bounds__(256) void backproject_mean_kernel(const std::conditional_t<GATHER, BpGatherParams, BpParams> p) {
+// ROWS (ivx_backproject_lists_fwd; scene batches, ragged one-shot batches; GATHER forms only): sample b keeps its state and writes its outputs in
+// row r = row[b] of pools of R rows, and in BP_ACCUM starts from zero by its own flag.  Only WHERE the state / outputs live and WHETHER the state is
+// read differ; everything between is the code above, so row r is bit for bit what the B = 1 launch over the sample's listed views leaves there.  A
+// row outside [0, R) ends the whole workgroup before any address is formed (r depends on blockIdx.y alone: no lane of it stays behind).  A list of
+// nothing but unseen views adds nothing: with `first` the row becomes zero sum / zero count (mean 0, valid 0), without it the state is stored back
+// as it was loaded (16-byte loads and stores, no arithmetic: every bit pattern survives).
+template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false, bool ROWS = false>
+__global__ __launch_bounds__(256) void backproject_mean_kernel(
+    const std::conditional_t<ROWS, BpListParams, std::conditional_t<GATHER, BpGatherParams, BpParams>> p) {
+  static_assert(!ROWS || (GATHER && VEC == 4 && MODE != BP_SUM), "the ROWS forms are the gathered mean / accumulate kernels");
   typedef T tv4 __attribute__((ext_vector_type(4)));
   constexpr bool MEAN = MODE == BP_MEAN;
   const int b = blockIdx.y;
+  int r = b;                               // the row of the state / outputs of this sample
+  int first = p.first;
+  if constexpr (ROWS) {
+    if (p.row) r = p.row[b];
+    if (r < 0 || r >= p.R) return;
+    if (p.first_list) first = p.first_list[b];
+  }
   const int lpv = 1 << p.lpv_log2;
   const int lane = threadIdx.x & 63;
   const int g = lane & (lpv - 1);        // lane inside the voxel group
@@ -136,8 +158,8 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const std::condit
     for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
   int cnt = 0;
   if constexpr (MODE == BP_ACCUM) {
-    if (active && !p.first) {              // the running state of this voxel (16-byte loads, coalesced as the stores below)
-      const float *run = p.volume + ((size_t)b * p.N + n) * p.C;
+    if (active && !first) {              // the running state of this voxel (16-byte loads, coalesced as the stores below)
+      const float *run = p.volume + ((size_t)r * p.N + n) * p.C;
 #pragma unroll
       for (int q = 0; q < MAXCH; ++q) {
         const int ch = g + q * lpv;
@@ -147,7 +169,7 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const std::condit
           for (int e = 0; e < VEC; ++e) acc[q][e] = x[e];
         }
       }
-      cnt = p.count[(size_t)b * p.N + n];
+      cnt = p.count[(size_t)r * p.N + n];
     }
   }
 
@@ -242,8 +264,8 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const std::condit
   if (!active) return;
   const float dn = (float)cnt;
   if constexpr (MODE == BP_ACCUM) {
-    float *run = p.volume + ((size_t)b * p.N + n) * p.C;
-    T *mean = p.mean_out ? reinterpret_cast<T *>(p.mean_out) + ((size_t)b * p.N + n) * p.C : nullptr;
+    float *run = p.volume + ((size_t)r * p.N + n) * p.C;
+    T *mean = p.mean_out ? reinterpret_cast<T *>(p.mean_out) + ((size_t)r * p.N + n) * p.C : nullptr;
 #pragma unroll
     for (int q = 0; q < MAXCH; ++q) {
       const int ch = g + q * lpv;
@@ -260,12 +282,12 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const std::condit
       }
     }
     if (g == 0) {
-      p.count[(size_t)b * p.N + n] = cnt;
-      if (mean) p.valid[(size_t)b * p.N + n] = cnt > 0 ? 1 : 0;
+      p.count[(size_t)r * p.N + n] = cnt;
+      if (mean) p.valid[(size_t)r * p.N + n] = cnt > 0 ? 1 : 0;
     }
     return;
   }
-  T *dst = reinterpret_cast<T *>(p.volume) + ((size_t)b * p.N + n) * p.C;
+  T *dst = reinterpret_cast<T *>(p.volume) + ((size_t)r * p.N + n) * p.C;
 #pragma unroll
   for (int q = 0; q < MAXCH; ++q) {
     const int ch = g + q * lpv;
@@ -282,9 +304,9 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(const std::condit
   }
   if (g == 0) {
     if (MEAN)
-      p.valid[(size_t)b * p.N + n] = cnt > 0 ? 1 : 0;
+      p.valid[(size_t)r * p.N + n] = cnt > 0 ? 1 : 0;
     else
-      p.count[(size_t)b * p.N + n] = cnt;
+      p.count[(size_t)r * p.N + n] = cnt;
   }
 }
 
@@ -407,6 +429,8 @@ struct BpCall {
   bool gather = false;              // ivx_backproject_gather_fwd: view_slot [B, V] lists slots of the S-slot pools
   const int32_t *view_slot = nullptr;
   int32_t S = 0;
+  bool listed = false;              // ivx_backproject_lists_fwd: the gathered form (gather is set too) with the row / first lists of `lists`
+  const ivx_lift_lists *lists = nullptr;
 };
 
 // The descriptor of an older export's argument list (voxel_size stays with the caller's pointer, which may be NULL until validated).
@@ -426,8 +450,12 @@ static int bp_validate(const BpCall &c) {
   const ivx_backproject_desc *d = c.d;
   IVX_REQUIRE(d, "%s: null descriptor", what);
   IVX_REQUIRE(d->sampling == IVX_SAMPLE_NEAREST || d->sampling == IVX_SAMPLE_BILINEAR, "%s: sampling %d (IVX_SAMPLE_NEAREST | IVX_SAMPLE_BILINEAR)", what, d->sampling);
-  if (c.gather)
+  if (c.listed) {
+    IVX_REQUIRE(c.lists, "%s: null lists", what);
+    IVX_REQUIRE(d->mode == IVX_LIFT_MEAN || d->mode == IVX_LIFT_ACCUM, "%s: mode %d (IVX_LIFT_MEAN | IVX_LIFT_ACCUM: the sum mode has no listed form)", what, d->mode);
+  } else if (c.gather) {
     IVX_REQUIRE(d->mode == IVX_LIFT_MEAN, "%s: mode %d (IVX_LIFT_MEAN only)", what, d->mode);
+  }
   IVX_REQUIRE(d->mode == IVX_LIFT_MEAN || d->mode == IVX_LIFT_SUM || d->mode == IVX_LIFT_ACCUM, "%s: mode %d (IVX_LIFT_MEAN | IVX_LIFT_SUM | IVX_LIFT_ACCUM)", what, d->mode);
   IVX_REQUIRE(d->feat_dtype == IVX_F32 || d->feat_dtype == IVX_BF16, "%s: feat_dtype %d (IVX_F32 | IVX_BF16)", what, d->feat_dtype);
   IVX_REQUIRE(c.feat && c.proj && c.new_origin && c.crop_hw && c.voxel_size && c.volume && (!c.gather || c.view_slot), "%s: null argument", what);
@@ -442,7 +470,12 @@ static int bp_validate(const BpCall &c) {
     IVX_REQUIRE((c.mean_out != nullptr) == (c.valid != nullptr), "%s: mean_out and valid must both be given or both be NULL", what);
   }
   if (c.gather) IVX_REQUIRE(c.S > 0, "%s: S=%d slots (the pools need at least one)", what, c.S);
+  if (c.listed) {
+    IVX_REQUIRE(c.lists->R > 0, "%s: R=%d rows (the state / output pools need at least one)", what, c.lists->R);
+    IVX_REQUIRE(d->mode == IVX_LIFT_ACCUM || !c.lists->first, "%s: the mean mode takes no first list", what);
+  }
   IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
+  if (c.listed) IVX_REQUIRE(c.lists->row || c.lists->R >= d->B, "%s: R=%d rows for B=%d samples and no row list (sample b then uses row b)", what, c.lists->R, d->B);
   const int vec = (d->C % 4 == 0) ? 4 : 1;
   IVX_REQUIRE(vec == 4 || (d->mode == IVX_LIFT_MEAN && d->feat_dtype == IVX_F32 && !c.gather), "%s: C %% 4 must be 0 (every form but the fp32 mean of a view stack)", what);
   IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
@@ -458,10 +491,11 @@ static int bp_validate(const BpCall &c) {
   return IVX_OK;
 }
 
-// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams (a plain launch passes the base).
-static BpGatherParams bp_fill(const BpCall &c, dim3 *grid) {
+// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams / BpListParams (a plain or gathered
+// launch passes the base).
+static BpListParams bp_fill(const BpCall &c, dim3 *grid) {
   const ivx_backproject_desc &d = *c.d;
-  BpGatherParams p;
+  BpListParams p;
   p.feat = (const float *)c.feat; p.proj = c.proj; p.new_origin = c.new_origin; p.crop_hw = c.crop_hw;
   p.volume = (float *)c.volume; p.valid = c.valid; p.count = c.count; p.mean_out = c.mean_out;
   // the running state is read unless `first`; a bf16 sum is the accumulate kernel from a zero state (bp_launch), so it never reads one
@@ -474,6 +508,7 @@ static BpGatherParams bp_fill(const BpCall &c, dim3 *grid) {
   while ((1 << lg) < p.nchunk && lg < 6) ++lg;
   p.lpv_log2 = lg;
   p.view_slot = c.view_slot; p.S = c.S;
+  p.row = c.listed ? c.lists->row : nullptr; p.first_list = c.listed ? c.lists->first : nullptr; p.R = c.listed ? c.lists->R : 0;
   if (bp_single_view_copy(c)) {      // 256 voxels per workgroup regardless of the group width (each lane projects one voxel)
     p.pmax = c.partials; p.nblk = 0; p.q = 0;
     *grid = dim3((p.N + 255) / 256, d.B);
@@ -486,15 +521,25 @@ static BpGatherParams bp_fill(const BpCall &c, dim3 *grid) {
 }
 
 // The selection table: every instantiation of the two lift kernels is launched from exactly one line below.
-static int bp_launch(const BpCall &c, const BpGatherParams &g, const dim3 grid) {
+static int bp_launch(const BpCall &c, const BpListParams &l, const dim3 grid) {
   const ivx_backproject_desc &d = *c.d;
-  const BpParams &p = g;
+  const BpGatherParams &g = l;
+  const BpParams &p = l;
   const bool bf16 = d.feat_dtype == IVX_BF16, bilinear = d.sampling == IVX_SAMPLE_BILINEAR, vec4 = d.C % 4 == 0;
   // BP_SUM exists for fp32 features only: a bf16 sum runs BP_ACCUM (fp32 sums) with first = 1 and no mean_out (bp_fill, bp_validate)
   const int mode = d.mode == IVX_LIFT_MEAN ? BP_MEAN : (d.mode == IVX_LIFT_SUM && !bf16) ? BP_SUM : BP_ACCUM;
   const dim3 block(256);
   hipStream_t st = (hipStream_t)c.stream;
-  if (c.gather) {                                   // MEAN only, VEC 4 only, one listed view too
+  if (c.listed && (mode == BP_ACCUM || l.row)) {    // rows of a state / output pool: MEAN and ACCUM, VEC 4 only (a listed mean with no row list is the gathered launch below)
+    if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true>), grid, block, 0, st, l);
+    else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true>), grid, block, 0, st, l);
+    else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true>), grid, block, 0, st, l);
+    else if (mode == BP_ACCUM)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_NEAREST, true, true>), grid, block, 0, st, l);
+    else if (bilinear && bf16)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true, true>), grid, block, 0, st, l);
+    else if (bilinear)                         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true, true>), grid, block, 0, st, l);
+    else if (bf16)                             hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true, true>), grid, block, 0, st, l);
+    else                                       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true, true>), grid, block, 0, st, l);
+  } else if (c.gather) {                            // MEAN only, VEC 4 only, one listed view too
     if (bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true>), grid, block, 0, st, g);
     else if (bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true>), grid, block, 0, st, g);
     else if (bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true>), grid, block, 0, st, g);
@@ -597,6 +642,14 @@ extern "C" int ivx_backproject_gather_fwd(const ivx_backproject_desc *d, int32_t
                                           const float *new_origin, const int32_t *crop_hw, void *volume, uint8_t *valid, ivx_stream_t stream) {
   return bp_run({"ivx_backproject_gather_fwd", d, d ? d->voxel_size : nullptr, feat_pool, proj_pool, new_origin, crop_hw, volume, nullptr, nullptr, valid, stream,
                  nullptr, true, view_slot, S});
+}
+
+// Listed lift with per-sample state (include/imvoxel.h): the gathered form whose samples name their rows of the state / output pools.
+extern "C" int ivx_backproject_lists_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const void *feat_pool, const float *proj_pool,
+                                         const float *new_origin, const int32_t *crop_hw, void *volume, int32_t *count, void *mean_out, uint8_t *valid,
+                                         ivx_stream_t stream) {
+  return bp_run({"ivx_backproject_lists_fwd", d, d ? d->voxel_size : nullptr, feat_pool, proj_pool, new_origin, crop_hw, volume, count, mean_out, valid, stream,
+                 nullptr, true, l ? l->view_slot : nullptr, l ? l->S : 0, true, l});
 }
 
 // ------------------------------------------------------------------ mean of a (sum, count) volume

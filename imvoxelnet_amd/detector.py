@@ -358,6 +358,61 @@ class ImVoxelNet(nn.Module):
         from .scene import SceneSession
         return SceneSession(self, meta, window=window)
 
+    def open_scenes(self, metas, window=None):
+        """N streaming scenes that share their launches (scene.SceneBatch): per tick one trunk call over the new views of any subset of
+        the scenes, one listed lift into the touched scenes' rows of the state pools, and detect() as one batched neck + head + NMS.
+        metas: one scene meta per scene (intrinsic, origin and box type may differ; image size and model are common).  window as for
+        open_scene, per scene.  Every scene's volume is exact; what is not claimed is in the SceneBatch docstring."""
+        from .scene import SceneBatch
+        return SceneBatch(self, metas, window=window)
+
+    def simple_test_ragged(self, imgs, img_metas):
+        """simple_test for a batch whose samples have DIFFERENT numbers of views: imgs is a list of B tensors [V_b,3,H,W] (common H, W),
+        meta b's lidar2img['extrinsic'] has V_b entries.  One trunk call over the concatenation, ONE ragged lift over the trunk's stack
+        (ops.backproject_lists_mean_), the batched detection stage; results in simple_test's format.  Each sample's volume and mask are
+        bit for bit lift_cl of its own slice of the shared features (masks and counts do not depend on the features at all); the
+        features and the batched neck depend on what shares a call, as for scene batches (scene.SceneBatch), so boxes are not claimed
+        equal to per-sample simple_test calls.  Runs the layer-by-layer composition, not the native handle's per-shape plans."""
+        if self.head_2d is not None:
+            raise NotImplementedError('a model with a head_2d (SUN RGB-D Total) predicts its extrinsics from the image: ragged batches take theirs from the metas')
+        imgs, img_metas = list(imgs), list(img_metas)
+        if not imgs or len(imgs) != len(img_metas):
+            raise ValueError(f'{len(img_metas)} img_metas for {len(imgs)} samples')
+        for b, (im, meta) in enumerate(zip(imgs, img_metas)):
+            if not isinstance(im, torch.Tensor) or im.dim() != 4 or im.shape[0] < 1 or im.shape[1] != 3:
+                raise ValueError(f'imgs[{b}] must be a tensor [V,3,H,W] with V >= 1')
+            if im.dtype != torch.float32:
+                raise TypeError(f'imgs[{b}] must be float32, got {im.dtype}')
+            if tuple(im.shape[2:]) != tuple(imgs[0].shape[2:]):
+                raise ValueError(f'imgs[{b}] is {tuple(im.shape[2:])}, imgs[0] {tuple(imgs[0].shape[2:])}: a ragged batch has one image size')
+            n_ext = len(meta['lidar2img']['extrinsic'])
+            if n_ext != im.shape[0]:
+                raise ValueError(f'sample {b}: {n_ext} extrinsics for {im.shape[0]} views')
+        if not all(im.is_cuda for im in imgs):
+            raise RuntimeError('imgs must be device (HIP) tensors; the MI355X path has no CPU fallback')
+        if self._prepared_device is None:
+            self.prepare(imgs[0].device)
+        counts = [int(im.shape[0]) for im in imgs]
+        volume, valid = self.lift_ragged_cl(self.features_2d_cl(torch.cat(imgs)[None]), img_metas, counts)
+        if isinstance(self.bbox_head, Anchor3DHead):
+            boxes, scores, labels, count = self.detect_cl(volume, img_metas)
+            return self._results_one_copy(boxes, scores, labels, count, img_metas)
+        return [bbox3d2result(b, s, l) for b, s, l in self.detect_indoor_cl(volume, valid, img_metas)]
+
+    def lift_ragged_cl(self, p0, img_metas, counts):
+        """FPN level 0 of the concatenated views [sum(counts),1,h,w,C] + metas -> (volume [B,X,Y,Z,C], valid bool): sample b owns the
+        next counts[b] maps.  One launch; row b is bit for bit lift_cl of sample b's slice."""
+        cpu, B = torch.device('cpu'), len(counts)
+        cams = [self._camera_setup([meta], 4, cpu) for meta in img_metas]
+        proj = torch.cat([c[0][0] for c in cams]).contiguous().to(p0.device)
+        origin, crop = torch.cat([c[1] for c in cams]).to(p0.device), torch.cat([c[2] for c in cams]).to(p0.device)
+        X, Y, Z = self.n_voxels
+        volume = torch.empty((B, X, Y, Z, p0.shape[-1]), device=p0.device, dtype=p0.dtype)
+        valid = torch.empty((B, X, Y, Z), device=p0.device, dtype=torch.uint8)
+        starts = [sum(counts[:b]) for b in range(B)]
+        return ops.backproject_lists_mean_(p0, proj, [list(range(starts[b], starts[b] + counts[b])) for b in range(B)], list(range(B)), origin, crop,
+                                           self.voxel_size, volume, valid, sampling=self.sampling)
+
     @staticmethod
     def _results_one_copy(boxes, scores, labels, count, img_metas, with_yaw=True, indoor=False):
         """bbox3d2result (core/bbox/transforms.py:49-67) for the fixed-size padded device tensors of the anchor tail: ONE

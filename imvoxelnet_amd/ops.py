@@ -959,6 +959,110 @@ def _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, n_
     return vol, valid.view(torch.bool)
 
 
+def backproject_lists_accum_(pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol_sum, count, mean_out=None, valid_out=None,
+                             sampling='nearest'):
+    """backproject_accum_ for B samples that share pools and have RAGGED view lists (ivx_backproject_lists_fwd; scene batches): pool
+    [S,1,FH,FW,C] (or [S,FH,FW,C]) fp32 or bf16 and proj_pool [S,3,4] hold one view per slot; lists: B host lists of slots, of differing
+    lengths (an empty list adds nothing; -1 inside a list is padding, any other slot outside [0, S) raises ValueError); rows: a host list of
+    B DISTINCT ints in [0, R): sample b reads and writes row rows[b] of vol_sum [R,X,Y,Z,C] fp32 / count [R,X,Y,Z] int32 (and of mean_out
+    (pool's dtype) / valid_out, both or neither); first: a host list of B bools, sample b starts its row from zero without reading it.
+    new_origin [B,3] and crop_hw [B,2] are per sample.  Row rows[b] afterwards is bit for bit backproject_accum_ at B = 1 over a contiguous
+    copy of lists[b]'s views; rows named by no sample are neither read nor written.  The three lists go up in one copy; every argument
+    error is raised before any launch.  Returns (vol_sum, count)."""
+    if (mean_out is None) != (valid_out is None):
+        raise ValueError('mean_out and valid_out must both be given or both be None')
+    _lists_lift(_LIFT_ACCUM, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol_sum, count, mean_out, valid_out, sampling)
+    return vol_sum, count
+
+
+def backproject_lists_mean_(pool, proj_pool, lists, rows, new_origin, crop_hw, voxel_size, vol, valid, sampling='nearest'):
+    """backproject_gather_mean_ with RAGGED host lists into rows of the caller's pools: sample b's mean / mask of the views lists[b] go to
+    row rows[b] of vol [R,X,Y,Z,C] (pool's dtype) / valid [R,X,Y,Z] uint8 / bool; the other rows stay as they are.  lists, rows and the
+    errors as for backproject_lists_accum_.  Row rows[b] is bit for bit backproject_mean over a contiguous copy of lists[b]'s views (an
+    empty list: zeros, nothing valid).  Returns (vol, valid as bool)."""
+    _lists_lift(_LIFT_MEAN, pool, proj_pool, lists, rows, None, new_origin, crop_hw, voxel_size, vol, None, None, valid, sampling)
+    return vol, valid.view(torch.bool)
+
+
+def _host_ints(x, name, n=None):
+    """A host sequence of Python / numpy integers (no bools, no tensors) -> list of int."""
+    if isinstance(x, torch.Tensor) or isinstance(x, (str, bytes)) or not hasattr(x, '__len__'):
+        raise TypeError(f'{name} must be a host list of integers')
+    out = []
+    for v in x:
+        if isinstance(v, bool) or not hasattr(v, '__index__'):
+            raise TypeError(f'{name} must hold integers, got {v!r}')
+        out.append(int(v))
+    if n is not None and len(out) != n:
+        raise ValueError(f'{name} has {len(out)} entries for {n} samples')
+    return out
+
+
+def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol, count, mean_out, valid, sampling):
+    """The one checker and caller of ivx_backproject_lists_fwd.  The host lists are checked first (against shapes only), then the tensors;
+    then ONE upload of view_slot [B,Vmax] (-1 padded), row [B] and first [B], and the launch."""
+    sampling = _lib.sampling_id(sampling)
+    for t, name in ((pool, 'pool'), (proj_pool, 'proj_pool'), (vol, 'vol_sum' if mode == _LIFT_ACCUM else 'vol')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch.Tensor')
+    if pool.dtype not in _F32_BF16:
+        raise TypeError(f'pool must be float32 or bfloat16, got {pool.dtype}')
+    if pool.dim() == 5 and pool.shape[1] == 1:
+        pool = pool[:, 0]
+    if pool.dim() != 4 or tuple(proj_pool.shape) != (pool.shape[0], 3, 4):
+        raise ValueError(f'pool must be [S,FH,FW,C] (or [S,1,FH,FW,C]) and proj_pool [S,3,4], got {tuple(pool.shape)} and {tuple(proj_pool.shape)}')
+    S, FH, FW, Cn = (int(v) for v in pool.shape)
+    if vol.dim() != 5 or vol.shape[-1] != Cn:
+        raise ValueError('the state / output volume must be [R,X,Y,Z,C] with the pool\'s C')
+    R, X, Y, Z = (int(v) for v in vol.shape[:4])
+    if isinstance(lists, torch.Tensor) or not hasattr(lists, '__len__') or len(lists) < 1:
+        raise TypeError('lists must be a host list of B >= 1 lists of slots')
+    lists = [_host_ints(l, f'lists[{b}]') for b, l in enumerate(lists)]
+    B = len(lists)
+    bad = sorted({v for l in lists for v in l if v != -1 and not 0 <= v < S})
+    if bad:
+        raise ValueError(f'lists hold slots outside [0, {S}) other than the padding -1: {bad}')
+    rows = _host_ints(rows, 'rows', B)
+    if len(set(rows)) != B:
+        raise ValueError(f'rows must be distinct (two samples on one row race), got {rows}')
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}')
+    if mode == _LIFT_ACCUM:
+        if isinstance(first, torch.Tensor) or not hasattr(first, '__len__') or len(first) != B:
+            raise ValueError(f'first must be a host list of {B} bools')
+        first = [int(bool(f)) for f in first]
+    Vmax = max(1, max(len(l) for l in lists))
+    host = [v for l in lists for v in l + [-1] * (Vmax - len(l))] + rows + (first if mode == _LIFT_ACCUM else [])
+    _chk(pool, 'pool', pool.dtype)
+    _chk(proj_pool, 'proj_pool')
+    _chk(new_origin, 'new_origin')
+    _chk(crop_hw, 'crop_hw', torch.int32)
+    if tuple(new_origin.shape) != (B, 3) or tuple(crop_hw.shape) != (B, 2):
+        raise ValueError('new_origin must be [B,3] and crop_hw [B,2] for the B lists')
+    if mode == _LIFT_ACCUM:
+        _chk(vol, 'vol_sum')
+        _chk(count, 'count', torch.int32)
+        if tuple(count.shape) != (R, X, Y, Z):
+            raise ValueError('count must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
+        if mean_out is not None:
+            _chk(mean_out, 'mean_out', pool.dtype)
+            if tuple(mean_out.shape) != tuple(vol.shape):
+                raise ValueError('mean_out must have the shape of vol_sum')
+            _chk_mask(valid, 'valid_out', count.shape)
+    else:
+        _chk(vol, 'vol', pool.dtype)
+        _chk_mask(valid, 'valid', vol.shape[:-1])
+    fn = getattr(_lib.lib(), 'ivx_backproject_lists_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_lists_fwd (needs version 0.4.7)')
+    dev = torch.tensor(host, dtype=torch.int32).to(pool.device)                  # the one upload: view_slot, row, first
+    p0, n_vs = dev.data_ptr(), B * Vmax
+    l = _lib.LiftLists(S, R, p0, p0 + 4 * n_vs, (p0 + 4 * (n_vs + B)) if mode == _LIFT_ACCUM else None)
+    d = _lib.BackprojectDesc(B, Vmax, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], mode, sampling, 0)
+    check(fn(C.byref(d), C.byref(l), _ptr(pool), _ptr(proj_pool), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(count), _ptr(mean_out), _ptr(valid),
+             _stream()), 'ivx_backproject_lists_fwd')         # (`dev` is released in stream order: the allocator reuses it after this launch)
+
+
 def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
     """View-sharded mode: like backproject_mean but returns the raw view sum [B,X,Y,Z,C] and the int32 view count
     [B,X,Y,Z] of THIS rank's views (to be all-reduced, then volume_normalize_).  sampling as for backproject_mean."""

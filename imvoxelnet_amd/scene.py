@@ -1,4 +1,5 @@
-"""Streaming scenes: add the views of ONE scene to a running volume as they arrive and detect at any time.
+"""Streaming scenes: add the views of a scene (SceneSession) or of N scenes at once (SceneBatch) to running volumes as they arrive and
+detect at any time.
 
 simple_test knows "all views at once": a caller who wants detections while scanning re-runs the 2-D trunk on every frame seen so
 far, and the trunk is the part of a multi-view step that grows with the number of views.  A SceneSession runs the trunk on the NEW
@@ -22,8 +23,18 @@ arrival order -- what an unbounded session given only those views holds.  A full
 ScanNet-fast (C = 256) takes 19.7 MB per slot in fp32, 393 MB at W = 20 (bf16 storage: 9.8 MB, 197 MB); ScanNet-v1 (C = 64) 4.9 MB per
 slot, 98 MB at W = 20 (bf16: 2.5 MB, 49 MB).
 
-Out of scope: re-weighting views; batches of scenes in one session (B = 1; open one session per scene, they share the prepared
-model); a model-level C handle for sessions (the state lives here, over the op-level ABI and the handle's sub-range calls).
+Batches of scenes (model.open_scenes(metas, window=None) -> SceneBatch).  A server that follows several scans at once would otherwise run
+a 1-view trunk call, a B = 1 lift, a B = 1 neck and a B = 1 tail per scene and tick.  A SceneBatch keeps the state of N scenes in pools
+of N rows and shares the launches: one trunk call over all the new views of a tick, ONE listed lift that adds them to the touched
+scenes (ops.backproject_lists_accum_, ivx_backproject_lists_fwd: ragged slot lists, a row and a `first` flag per scene), one batched
+neck + head + NMS in detect().  State per scene: X*Y*Z * (C * (4 + sizeof(element)) + 5) bytes -- ScanNet-fast (40 x 40 x 16, C = 256)
+52.6 MB in fp32 (39.5 MB with bf16 storage), ScanNet-v1 (80 x 80 x 32, C = 64) 105.9 MB (79.7 MB); a windowed batch keeps the mean / mask
+pools and N rings instead of the sums.  The volume of every scene is exact (the one-shot lift of the features it was given, bit for
+bit); the features and the batched neck depend on what shares a call, so boxes are not claimed equal to a single session's: the
+SceneBatch docstring states each claim.  SceneSession is not built on the batch: its path and bits are what they were.
+
+Out of scope: re-weighting views; scene batches across ranks; a model-level C handle for sessions (the state lives here, over the
+op-level ABI and the handle's sub-range calls).
 """
 import numpy as np
 import torch
@@ -258,3 +269,283 @@ class SceneSession:
             boxes, scores, labels, count = m.detect_cl(vol, metas)
             return m._results_one_copy(boxes, scores, labels, count, metas)
         return [bbox3d2result(b, s, l) for b, s, l in m.detect_indoor_cl(vol, valid, metas)]
+
+
+class SceneBatch:
+    """model.open_scenes(metas, window=None): N streaming scenes on one prepared model that share their launches.  metas: one scene meta
+    per scene, as for open_scene (intrinsic, origin and box type may differ; the image size and the model are common).  Per tick,
+    add_views takes the new views of ANY subset of the scenes (0, 1 or several per scene), runs the trunk ONCE over all of them and adds
+    them to the touched scenes in ONE launch (ops.backproject_lists_accum_, ivx_backproject_lists_fwd: ragged slot lists, one row of
+    the state pools per scene, a `first` flag per scene); detect() runs ONE batched neck + head + NMS over the stacked mean rows.
+
+    State, allocated at the first add: sum fp32 [N,X,Y,Z,C], count int32 [N,X,Y,Z], mean [N,X,Y,Z,C] in the storage type, valid uint8
+    [N,X,Y,Z] -- per scene X*Y*Z * (C * (4 + sizeof(element)) + 5) bytes (the module docstring has the ScanNet figures).  window=W keeps
+    no sums: a feature ring [N*W,1,FH,FW,C] (scene s owns slots s*W .. s*W+W-1) and a projection ring [N*W,3,4], per-scene ordered
+    (id, slot, extrinsic) lists with FIFO eviction per scene, and the mean / valid pools; the scenes whose set changed are lifted again, all
+    in one launch (ops.backproject_lists_mean_), when volume() / detect() asks.
+
+    What is exact and what is not.
+      Volume.   Row s of the batch's volume is bit for bit ONE ops.backproject_mean over the features the trunk produced for scene s's
+                views, tick by tick, in arrival order -- what a SceneSession fed the same features holds.  Mask and count do not depend on
+                the features at all: they are the one-shot lift's.
+      Features. With the default fp16-pair trunk the per-tensor operand scales depend on which views share a trunk call, so a view's
+                features may differ in the last bits from those a single session computes for it.
+      Neck and boxes.  The batched neck's operand scales depend on the batch too: there is NO claim that scene s's boxes equal those of
+                a B = 1 SceneSession.detect().
+      Detection stage.  detect() is exactly the model's batched detection stage (detect_cl / detect_indoor_cl) on the stacked rows.
+    A call that raises before its launch leaves every scene as it was."""
+
+    _features = SceneSession._features
+
+    def __init__(self, model, metas, window=None):
+        metas = list(metas)
+        if not metas:
+            raise ValueError('open_scenes needs at least one scene meta')
+        self._scenes = [SceneSession(model, meta, window=window) for meta in metas]      # checks every meta, window and head_2d; used as records only
+        self._model, self._window, self._N = model, self._scenes[0]._window, len(metas)
+        self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
+        self._hw, self._closed = None, False
+        self._cam = [None] * self._N              # per scene: host (new_origin [3], crop [2]) of its last add
+
+    # ------------------------------------------------------------------ state
+    def _check_open(self):
+        if self._closed:
+            raise RuntimeError('this SceneBatch is closed')
+
+    def _scene_index(self, s):
+        if isinstance(s, bool) or not isinstance(s, (int, np.integer)) or not 0 <= s < self._N:
+            raise ValueError(f'unknown scene index {s!r} (this batch has scenes 0 .. {self._N - 1})')
+        return int(s)
+
+    def __len__(self):
+        return self._N
+
+    @property
+    def metas(self):
+        """The scenes' metas: complete simple_test metas of everything added."""
+        return [r.meta for r in self._scenes]
+
+    @property
+    def n_views(self):
+        return [r.n_views for r in self._scenes]
+
+    def view_ids(self, scene):
+        self._check_open()
+        return self._scenes[self._scene_index(scene)].view_ids
+
+    def reset(self, scenes=None):
+        """Forget every view of these scenes (None: all); the pools are kept."""
+        self._check_open()
+        for s in (range(self._N) if scenes is None else [self._scene_index(s) for s in scenes]):
+            self._scenes[s].reset()
+            self._cam[s] = None
+        if not any(self.n_views):
+            self._hw = None
+        return self
+
+    def close(self):
+        self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
+        for r in self._scenes:
+            r.close()
+        self._closed = True
+
+    def remove_views(self, scene, ids):
+        """Drop the views with these ids from one scene of a windowed batch; an unknown id raises KeyError and changes nothing."""
+        self._check_open()
+        self._scenes[self._scene_index(scene)].remove_views(ids)
+        return self
+
+    # ------------------------------------------------------------------ adding views
+    def add_views(self, img, extrinsics, scene, emit=True):
+        """img [T,3,H,W] float32 on the device, extrinsics: T float32 4x4 matrices, scene: T scene indices -- view t belongs to scene
+        scene[t]; the views of one scene count in the order given.  emit=False skips the store of the means (computed when asked).
+        Windowed batch: more than W views for one scene in a call raise ValueError; emit has no effect."""
+        return self._add_views(img, extrinsics, scene, emit, {})
+
+    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, **pipeline_kw):
+        """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
+        ori_shape / pad_shape of every scene's meta, which later frames must reproduce."""
+        from .data import prepare_images_device
+        self._check_open()
+        frames = list(frames)
+        E = SceneSession._check_extrinsics(extrinsics, len(frames))
+        groups = self._groups(scene, len(frames))
+        img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
+        for r in self._scenes:
+            for k, v in shapes[0].items():
+                if any(self.n_views) and k in r.meta and tuple(r.meta[k]) != tuple(v):
+                    raise ValueError(f'{k} {tuple(v)} of these frames differs from the {tuple(r.meta[k])} of the views already in the batch')
+        return self._add_views(img[0], E, scene, emit, shapes[0], groups)
+
+    def _groups(self, scene, T):
+        """scene (T indices) -> {scene: [t, ...]} in first-touch order; the checks that need no device."""
+        if isinstance(scene, torch.Tensor) or not hasattr(scene, '__len__') or len(scene) != T:
+            raise ValueError(f'scene must list one scene index per view: {T} views, got {scene!r}')
+        groups = {}
+        for t, s in enumerate(scene):
+            groups.setdefault(self._scene_index(s), []).append(t)
+        if self._window is not None:
+            for s, ts in groups.items():
+                if len(ts) > self._window:
+                    raise ValueError(f'{len(ts)} views of scene {s} in one call do not fit a window of {self._window}')
+        return groups
+
+    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None):
+        self._check_open()
+        if not isinstance(img, torch.Tensor):
+            raise TypeError('img must be a torch.Tensor [T,3,H,W]')
+        if img.dim() != 4 or img.shape[0] < 1 or img.shape[1] != 3:
+            raise ValueError(f'img must be [T,3,H,W] with T >= 1, got {tuple(img.shape)}')
+        if img.dtype != torch.float32:
+            raise TypeError(f'img must be float32, got {img.dtype}')
+        T, H, W = int(img.shape[0]), int(img.shape[2]), int(img.shape[3])
+        E = SceneSession._check_extrinsics(extrinsics, T)
+        if groups is None:
+            groups = self._groups(scene, T)
+        if self._hw is not None and (H, W) != self._hw:
+            raise ValueError(f'image size {(H, W)} differs from the {self._hw} of the views already in the batch')
+        touched = sorted(groups)
+        for s in touched:
+            meta = dict(self._scenes[s].meta, **shapes)
+            if 'img_shape' not in meta or 'ori_shape' not in meta:
+                raise ValueError('every scene meta needs img_shape and ori_shape (add_views_u8 fills them from its frames)')
+        if not img.is_cuda:
+            raise RuntimeError('img must be a device (HIP) tensor; the MI355X path has no CPU fallback')
+        m = self._model
+        if m._prepared_device is None:
+            m.prepare(img.device)
+        p0 = self._features(img.contiguous())                      # ONE trunk call over the T views of this tick
+        dev = p0.device
+        # host camera set-up: one _compute_projection per touched scene; rows of proj in the order of the T views
+        cpu = torch.device('cpu')
+        proj_h, cam = torch.empty((T, 3, 4), dtype=torch.float32), {}
+        for s in touched:
+            ts = groups[s]
+            r = self._scenes[s]
+            view_meta = dict(r.meta, **shapes)
+            view_meta['lidar2img'] = dict(r.meta['lidar2img'], extrinsic=[E[t] for t in ts])
+            p, origin, crop = m._camera_setup([view_meta], 4, cpu)
+            proj_h[torch.tensor(ts)] = p[0]
+            cam[s] = (origin[0], crop[0])
+        if self._window is not None:
+            return self._add_windowed(p0, proj_h, groups, touched, cam, E, (H, W), shapes)
+        proj, origin, crop = self._upload(dev, proj_h, [cam[s] for s in touched])
+        X, Y, Z = m.n_voxels
+        Cn = p0.shape[-1]
+        if self._sum is None or self._sum.shape[-1] != Cn or self._mean.dtype != p0.dtype:     # the state pools, allocated once
+            N = self._N
+            self._sum = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=torch.float32)
+            self._count = torch.empty((N, X, Y, Z), device=dev, dtype=torch.int32)
+            self._mean = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
+            self._valid = torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8)
+        ops.backproject_lists_accum_(p0, proj, [groups[s] for s in touched], touched, [self._scenes[s].n_views == 0 for s in touched], origin, crop,
+                                     m.voxel_size, self._sum, self._count, self._mean if emit else None, self._valid if emit else None,
+                                     sampling=getattr(m, 'sampling', 'nearest'))
+        self._hw = (H, W)
+        for r in self._scenes:
+            r.meta.update(shapes)
+        for s in touched:
+            r = self._scenes[s]
+            r._stale = not emit
+            r._hw = (H, W)
+            r.meta['lidar2img']['extrinsic'] = r.meta['lidar2img']['extrinsic'] + [E[t] for t in groups[s]]
+            r.n_views += len(groups[s])
+            self._cam[s] = cam[s]
+        return self
+
+    @staticmethod
+    def _upload(dev, proj_h, cams):
+        """Projection rows [T,3,4], new_origin [B,3] and crop [B,2] int32 in ONE host-to-device copy (the crop travels as bits)."""
+        T, B = (proj_h.shape[0] if proj_h is not None else 0), len(cams)
+        parts = ([proj_h.reshape(-1)] if T else []) + [torch.stack([c[0] for c in cams]).reshape(-1).float(),
+                                                       torch.stack([c[1] for c in cams]).to(torch.int32).reshape(-1).view(torch.float32)]
+        buf = torch.cat(parts).to(dev)
+        proj = buf[:T * 12].view(T, 3, 4) if T else None
+        origin = buf[T * 12:T * 12 + B * 3].view(B, 3)
+        crop = buf[T * 12 + B * 3:].view(torch.int32).view(B, 2)
+        return proj, origin, crop
+
+    def _add_windowed(self, p0, proj_h, groups, touched, cam, E, hw, shapes):
+        """The new maps and projection rows into free slots of their scenes' parts of the rings (one index_copy_ each); the oldest views
+        of a full scene leave first.  Everything that can fail comes before the first change of the batch."""
+        m, W, N = self._model, self._window, self._N
+        X, Y, Z = m.n_voxels
+        Cn, dev = p0.shape[-1], p0.device
+        ring, pring, mean, valid = self._ring, self._pring, self._mean, self._valid
+        if ring is None or tuple(ring.shape[1:]) != tuple(p0.shape[1:]) or ring.dtype != p0.dtype:
+            ring = torch.empty((N * W,) + tuple(p0.shape[1:]), device=dev, dtype=p0.dtype)
+            pring = torch.empty((N * W, 3, 4), device=dev, dtype=torch.float32)
+            mean = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
+            valid = torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8)
+        slot_of, new_views = [0] * p0.shape[0], {}
+        for s in touched:
+            r, ts = self._scenes[s], groups[s]
+            kept = r._views[max(0, len(r._views) + len(ts) - W):]
+            used = {v[1] for v in kept}
+            free = [q for q in range(s * W, s * W + W) if q not in used][:len(ts)]
+            for t, q in zip(ts, free):
+                slot_of[t] = q
+            new_views[s] = kept + [(r._next_id + i, free[i], E[t]) for i, t in enumerate(ts)]
+        idx = torch.tensor(slot_of, dtype=torch.int64).to(dev)
+        ring.index_copy_(0, idx, p0)
+        pring.index_copy_(0, idx, proj_h.to(dev))
+        self._ring, self._pring, self._mean, self._valid, self._hw = ring, pring, mean, valid, hw
+        for r in self._scenes:
+            r.meta.update(shapes)
+        for s in touched:
+            r = self._scenes[s]
+            r._next_id += len(groups[s])
+            r._views, r._stale, r._hw = new_views[s], True, hw
+            r.meta['lidar2img']['extrinsic'] = [v[2] for v in r._views]
+            r.n_views = len(r._views)
+            self._cam[s] = cam[s]
+        return self
+
+    # ------------------------------------------------------------------ reading the scenes
+    def _refresh(self, scenes):
+        """Bring the mean / valid rows of these scenes up to date: a windowed batch re-lifts the stale ones only, in ONE launch."""
+        stale = [s for s in scenes if self._scenes[s]._stale]
+        if not stale:
+            return
+        if self._window is not None:
+            _, origin, crop = self._upload(self._ring.device, None, [self._cam[s] for s in stale])
+            ops.backproject_lists_mean_(self._ring, self._pring, [[v[1] for v in self._scenes[s]._views] for s in stale], stale, origin, crop,
+                                        self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+        else:
+            for s in stale:                       # (emit=False adds: the mean of the stored sums, row by row)
+                ops.volume_mean(self._sum[s:s + 1], self._count[s:s + 1], self._mean.dtype, out=self._mean[s:s + 1], valid_out=self._valid[s:s + 1])
+        for s in stale:
+            self._scenes[s]._stale = False
+
+    def _with_views(self, scenes):
+        scenes = [self._scene_index(s) for s in scenes]
+        empty = [s for s in scenes if self._scenes[s].n_views == 0]
+        if empty:
+            raise RuntimeError(f'scenes {empty} have no views yet')
+        return scenes
+
+    def volume(self, scene):
+        """(mean volume [1,X,Y,Z,C], valid bool [1,X,Y,Z]) of one scene: views of the batch's pools, rewritten by later adds."""
+        self._check_open()
+        s, = self._with_views([scene])
+        self._refresh([s])
+        return self._mean[s:s + 1], self._valid[s:s + 1].view(torch.bool)
+
+    def detect(self, scenes=None):
+        """One result dict (boxes_3d, scores_3d, labels_3d) per scene, in the order asked; None: every scene that has views.  ONE batched
+        neck + head + NMS over the stacked mean rows: the pools as they are when all N scenes are asked in order, one index_select
+        otherwise."""
+        self._check_open()
+        scenes = [s for s in range(self._N) if self._scenes[s].n_views] if scenes is None else self._with_views(scenes)
+        if not scenes:
+            raise RuntimeError('no scene of the batch has views yet')
+        self._refresh(scenes)
+        vol, valid = self._mean, self._valid
+        if scenes != list(range(self._N)):
+            idx = torch.tensor(scenes, dtype=torch.int64).to(vol.device)
+            vol, valid = vol.index_select(0, idx), valid.index_select(0, idx)
+        m, metas = self._model, [self._scenes[s].meta for s in scenes]
+        if isinstance(m.bbox_head, Anchor3DHead):
+            boxes, scores, labels, count = m.detect_cl(vol, metas)
+            return m._results_one_copy(boxes, scores, labels, count, metas)
+        return [bbox3d2result(b, s, l) for b, s, l in m.detect_indoor_cl(vol, valid.view(torch.bool), metas)]

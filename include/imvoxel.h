@@ -40,7 +40,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
 /* Library version (major*10000 + minor*100 + patch; 400 = 0.4.0, the struct layouts of this header; 420 = 0.4.2: bf16 storage with
  * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size; 440 = 0.4.4: ivx_backproject_fwd_ex / ivx_model_cfg.sampling, the optional
  * bilinear sampling rule of the unprojection; 450 = 0.4.5: ivx_conv_route / ivx_bf16_pair_pack_filters; 460 = 0.4.6: ivx_backproject_gather_fwd, the mean lift of
- * views listed by slot, for sliding-window scenes) and the message of the last failing call on
+ * views listed by slot, for sliding-window scenes; 470 = 0.4.7: ivx_backproject_lists_fwd, the listed lift with per-sample rows and `first` flags, for
+ * batches of scenes and ragged batches) and the message of the last failing call on
  * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -600,6 +601,49 @@ int ivx_backproject_fwd_ex(const ivx_backproject_desc *d, const void *feat, cons
 int ivx_backproject_gather_fwd(const ivx_backproject_desc *d, int32_t S, const void *feat_pool, const float *proj_pool,
                                const int32_t *view_slot /*device [B,V]*/, const float *new_origin, const int32_t *crop_hw,
                                void *volume, uint8_t *valid, ivx_stream_t stream);
+
+/* (0.4.7) Listed lift with per-sample state: N scenes that share pools, ragged numbers of views.  The gathered form above in the mean AND the
+ * accumulate mode, in which every sample names the row of the state / output pools it owns and, in the accumulate mode, carries its own `first`
+ * flag.  A batch of streaming scenes (scene.py, SceneBatch) adds this tick's views -- 0, 1 or several per scene -- to the touched scenes in ONE
+ * launch; a one-shot batch whose samples have different numbers of views (simple_test_ragged) lifts in one launch too.
+ *
+ * d           the descriptor of ivx_backproject_fwd_ex; d->B samples, d->V = the length of a row of view_slot (the longest list); d->mode
+ *             IVX_LIFT_MEAN or IVX_LIFT_ACCUM (IVX_LIFT_SUM is refused); both sampling rules, both feat_dtypes; C % 4 == 0, C <= 1024
+ * l->S, feat_pool [S,FH,FW,C], proj_pool [S,3,4]: as for ivx_backproject_gather_fwd
+ * l->view_slot  DEVICE [B, V] int32: view v of sample b is that slot of both pools; a slot outside [0, S) is no view, so -1 pads ragged rows
+ *               (anywhere in a row, not only at its end)
+ * l->R, l->row  the pools volume / count / mean_out / valid have R rows ([R,X,Y,Z,C] / [R,X,Y,Z]); DEVICE [B] int32 or NULL: sample b reads and
+ *               writes row row[b]; NULL: row b (then R >= B)
+ * l->first      DEVICE [B] int32 or NULL, IVX_LIFT_ACCUM only: sample b starts its row from zero without reading it where first[b] != 0;
+ *               NULL: d->first for every sample
+ * new_origin [B,3], crop_hw [B,2]: per SAMPLE (indexed by b, not by row)
+ * pointer rules per mode: those of ivx_backproject_fwd_ex (mean: volume + valid, no count / mean_out; accumulate: volume = fp32 sums + count,
+ *               mean_out and valid both given or both NULL)
+ * Contract.
+ *   Equality.   For every sample b, row row[b] of volume / count / mean_out / valid after the call is bit for bit what the B = 1 launch of
+ *               ivx_backproject_fwd_ex leaves (same mode, sampling and feat_dtype, first = first[b]) over a contiguous copy of sample b's
+ *               in-range listed views in list order, starting from that row's stored state: the view-order fp32 addition chain, the sample
+ *               function, the division and the stores are the shared code of the one kernel template.
+ *   Zero views. A sample whose row of view_slot holds no in-range slot adds nothing: with first[b] != 0 its state becomes zero sum / zero count
+ *               (mean 0 / valid 0 where emitted); with first[b] == 0 its state is stored back unchanged, bit for bit (mean / valid, where
+ *               emitted, are those of the stored state).
+ *   Untouched rows.  Rows named by no sample are neither read nor written.
+ *   Row guard.  A row[b] outside [0, R) makes sample b do nothing at all (tested per workgroup before any address is formed, like the slot guard).
+ *   Distinct rows.  The rows of one call must be distinct: two samples on one row race.  This entry cannot check a device list; callers validate
+ *               (ops.backproject_lists_accum_ / _mean_ take the rows as a host list and always do).
+ *   Same as the gather.  With row == NULL, first == NULL and IVX_LIFT_MEAN the launch and the bits are those of ivx_backproject_gather_fwd.
+ * IVX_ERR_INVALID_ARG before any launch: everything ivx_backproject_gather_fwd rejects (with this entry's modes), a null l, R <= 0 (or R < B with
+ * no row list), first != NULL in the mean mode, the sum mode.                                                                                    */
+typedef struct ivx_lift_lists {
+  int32_t S;                 /* slots of feat_pool / proj_pool */
+  int32_t R;                 /* rows of volume / count / mean_out / valid */
+  const int32_t *view_slot;  /* DEVICE [B, V]: view v of sample b is that slot; a slot outside [0, S) is no view (-1 pads ragged rows) */
+  const int32_t *row;        /* DEVICE [B] or NULL (= b): sample b reads and writes THIS row of the output / state pools */
+  const int32_t *first;      /* DEVICE [B] or NULL (= d->first for every sample); IVX_LIFT_ACCUM only */
+} ivx_lift_lists;
+int ivx_backproject_lists_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const void *feat_pool, const float *proj_pool,
+                              const float *new_origin /*[B,3]*/, const int32_t *crop_hw /*[B,2]*/, void *volume, int32_t *count,
+                              void *mean_out, uint8_t *valid, ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
