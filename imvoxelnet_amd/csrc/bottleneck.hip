@@ -17,7 +17,7 @@
 //   Scales    powers of two from BOUNDS, as conv_pair_io (conv_igemm.hip): b1 = max|in| * wbound1 + sbound1, b2 = b1 * wbound2 + sbound2,
 //             b3 = b2 * wbound3 + sbound3 + max|in|; every wave derives them from the input's amax slots -- no pass over a tensor, no
 //             communication.  The looseness compounds over the three layers (the layer-wise chain measures max |mid|): a bound loose by L
-//             costs nothing up to L = 2^18 (ivx_common.h), ResNet-50's are ~2^10 after three layers.
+//             costs nothing up to L = 2^17 (include/imvoxel.h), ResNet-50's are ~2^10 after three layers.
 //   LDS swizzle of the pair tiles: a pixel row is 4P bytes (16-byte chunks [hi8 hi8 lo8 lo8] per 16 channels); chunk c of pixel (y, x) lies at
 //             c ^ (x & 15): the 16 lanes of one ds_read_b128 group hold 16 consecutive x (ds_read_b128 lane groups, MI355X guide), so every
 //             group reads 16 different 16-byte positions of the 256-byte bank window -- for every tap.

@@ -108,7 +108,7 @@ struct PairIO { float inv_in, inv_res, s_out; bool sat; float post; };      // p
 // Every wave computes the same values from the same device words (no communication): the output scale comes from a BOUND of the
 // output -- |out| <= max|in| * wbound + sbound + max|res| with the MEASURED maxima of the operands, which their producers left in the
 // amax slots -- so nothing has to pass over the output before it is written as (hi, lo) halves.  A bound that is loose by a factor L
-// costs nothing up to L = 2^18: a value's error is max(2^-22 |x|, 2^-25 / s), i.e. relative to the tensor's maximum max(2^-22, 2^-40 L).
+// costs nothing up to L = 2^17: a value's error is max(2^-22 |x|, 2^-25 / s), i.e. relative to the tensor's maximum max(2^-22, 2^-39 L).
 __device__ __forceinline__ PairIO conv_pair_io(const ConvParams &p) {
   PairIO io = {1.0f, 1.0f, 1.0f, false, p.post_scale};
   if (p.in_scale_p) io.inv_in = 1.0f / *p.in_scale_p;

@@ -2486,21 +2486,7 @@ extern "C" int ivx_pair_pack_filters(const float *w, int32_t Cout, int32_t taps,
   M_REQUIRE(!packed || (Cin % 32 == 0 && scale_out), "ivx_pair_pack_filters: pair filters need Cin %% 32 == 0 and scale_out");
   const size_t per = (size_t)taps * Cin;
   float amax = 0.f;
-  double wb = 0.0, sb = 0.0;
-  for (int co = 0; co < Cout; ++co) {
-    double l1 = 0.0;
-    const float *r = w + (size_t)co * per;
-    for (size_t k = 0; k < per; ++k) {
-      const float a = fabsf(r[k]);
-      amax = a > amax ? a : amax;
-      l1 += (double)a;
-    }
-    wb = std::max(wb, fabs((double)(scale ? scale[co] : 1.0f)) * l1);
-    sb = std::max(sb, fabs((double)(shift ? shift[co] : 0.0f)));
-  }
-  *wbound = nextafterf((float)wb, INFINITY);      // never below the exact value
-  *sbound = nextafterf((float)sb, INFINITY);
-  if (!packed) return IVX_OK;
+  for (size_t k = 0; k < per * (size_t)Cout; ++k) amax = std::max(amax, fabsf(w[k]));
   float sw = 1.0f;
   if (amax > 0.f && amax < 3.0e38f) {             // as ivx_pow2_scale on the device: max |w| * s_w in [2^14, 2^15)
     int e;
@@ -2510,6 +2496,24 @@ extern "C" int ivx_pair_pack_filters(const float *w, int32_t Cout, int32_t taps,
     sw = ldexpf(1.0f, k);
   }
   const float inv = 1.0f / sw;
+  // The kernels multiply by the values the (hi, lo) halves stand for, and the split rounds some of them upwards (2^-23 of the value): a row
+  // of equal filters that all round up has a larger L1 than the fp32 filters.  The bound takes the larger of the two sums, so that it holds
+  // for the fp32 filters (the stem's fp32 form) and for the pair filters written below or by ivx_stem_pool_pack_filters (same s_w).
+  double wb = 0.0, sb = 0.0;
+  for (int co = 0; co < Cout; ++co) {
+    double l1 = 0.0, l1p = 0.0;
+    const float *r = w + (size_t)co * per;
+    for (size_t k = 0; k < per; ++k) {
+      l1 += (double)fabsf(r[k]);
+      const float y = r[k] * sw, h = f16_bits_to_f32(f32_to_f16_bits(y));
+      l1p += fabs((double)h + (double)f16_bits_to_f32(f32_to_f16_bits(y - h)));
+    }
+    wb = std::max(wb, fabs((double)(scale ? scale[co] : 1.0f)) * std::max(l1, l1p * (double)inv));
+    sb = std::max(sb, fabs((double)(shift ? shift[co] : 0.0f)));
+  }
+  *wbound = nextafterf((float)wb, INFINITY);      // never below the exact value
+  *sbound = nextafterf((float)sb, INFINITY);
+  if (!packed) return IVX_OK;
   for (int co = 0; co < Cout; ++co) scale_out[co] = (scale ? scale[co] : 1.0f) * inv;
   uint16_t *o = (uint16_t *)packed;
   const int nch = Cin / 32;
@@ -2555,10 +2559,23 @@ extern "C" int ivx_bottleneck_proj_pack(const float *w3, const float *scale3, co
     bd = std::max(bd, ld);
     shift_out[n] = shift3[n] + shiftd[n];
   }
+  float wb_all;
+  const int rc = ivx_pair_pack_filters(bank.data(), C, 1, K, nullptr, shift_out, packed, scale_out, &wb_all, sbound);
+  if (rc != IVX_OK) return rc;
+  // the two sums over the values the packed halves stand for as well (ivx_pair_pack_filters: the split rounds some of them upwards)
+  const uint16_t *o = (const uint16_t *)packed;
+  for (int n = 0; n < C; ++n) {
+    double l3 = 0.0, ld = 0.0;
+    for (int k = 0; k < K; ++k) {
+      const uint16_t *g = o + ((size_t)n * (K / 32) + k / 32) * 64 + ((k % 32) / 16) * 32 + k % 16;
+      (k < Cin ? ld : l3) += fabs((double)f16_bits_to_f32(g[0]) + (double)f16_bits_to_f32(g[16]));
+    }
+    b3 = std::max(b3, l3 * (double)scale_out[n]);
+    bd = std::max(bd, ld * (double)scale_out[n]);
+  }
   *wbound3 = nextafterf((float)b3, INFINITY);
   *wboundd = nextafterf((float)bd, INFINITY);
-  float wb_all;
-  return ivx_pair_pack_filters(bank.data(), C, 1, K, nullptr, shift_out, packed, scale_out, &wb_all, sbound);
+  return IVX_OK;
 }
 
 // Host-only: the pair filters of the one-launch stem (csrc/stem.hip) in the order its wave reads them: [column tile 2][step 11][hi, lo][lane 64]

@@ -151,8 +151,9 @@ int ivx_bf16_pair_pack_filters(const float *w, int32_t Cout, int32_t taps, int32
  * bound of the output:  |out| <= max|in| * wbound + sbound + max|res|,  wbound = max_co |scale[co]| * sum_k |w[co][k]|,
  * sbound = max_co |shift[co]|, with the MEASURED maxima of the operands: every epilogue accumulates max |out| (true values) into
  * IVX_AMAX_SLOTS words of the tensor (atomic max on the bits; the caller zeroes them before the producer runs).  The bound
- * puts the largest value below 2^15 (fp16 holds 65504); a bound that is loose by a factor L costs accuracy only beyond L = 2^18
- * (error relative to the tensor's maximum: max(2^-22, 2^-40 L)).
+ * puts the largest value below 2^15 (fp16 holds 65504); a bound that is loose by a factor L costs accuracy only beyond L = 2^17
+ * (error relative to the tensor's maximum: max(2^-22, 2^-39 L) -- s * bound may sit at 2^14, the bottom of its binade, and a subnormal
+ * lo half rounds to 2^-25 in scaled units; tests/ref_pair.py derives it and tests/test_*_pair_range.py check both ends of the rule).
  *   in      IVX_F16_PAIR (d->in_dtype), written with *in_scale (NULL: 1); wgt: IVX_F16_PAIR filters (ivx_conv_desc), their
  *           power-of-two scale folded into scale[] by the caller (scale[co] = bn_scale[co] / s_w: exact)
  *   out     d->out_dtype IVX_F32 or IVX_F16_PAIR (then *out_scale receives its scale; needs amax_in, and amax_res with a residual)
