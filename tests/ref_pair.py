@@ -132,9 +132,9 @@ def out_hw(H, W, k, stride, pad):
     return (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
 
 
-def conv2d(x, w, scale, shift, k, stride, pad, relu=True, res=None, res_mode=0, post_scale=1.0):
+def conv2d(x, w, scale, shift, k, stride, pad, relu=True, res=None, res_mode=0, post_scale=1.0, res_after_act=False):
     """x [B, H, W, Cin], w [Cout, k*k, Cin] (tap-major), fp64.  v = acc * scale + shift; v += res (res_mode 1: the output's shape, 2: nearest
-    neighbour from [B, h, w, Cout]); ReLU; v *= post_scale"""
+    neighbour from [B, h, w, Cout]); ReLU; (res_after_act: the residual is added here instead); v *= post_scale"""
     x, w = np.asarray(x, np.float64), np.asarray(w, np.float64)
     B, H, W, ci = x.shape
     co = w.shape[0]
@@ -147,13 +147,17 @@ def conv2d(x, w, scale, shift, k, stride, pad, relu=True, res=None, res_mode=0, 
             sl = xp[:, ky:ky + (Ho - 1) * stride + 1:stride, kx:kx + (Wo - 1) * stride + 1:stride]
             acc += sl.reshape(-1, ci) @ w[:, ky * k + kx].T
     v = acc.reshape(B, Ho, Wo, co) * np.asarray(scale, np.float64) + np.asarray(shift, np.float64)
+    r = None
     if res is not None:
         r = np.asarray(res, np.float64)
         if res_mode == 2:
             r = r[:, (np.arange(Ho) * r.shape[1]) // Ho][:, :, (np.arange(Wo) * r.shape[2]) // Wo]
+    if r is not None and not res_after_act:
         v = v + r
     if relu:
         v = np.maximum(v, 0.0)
+    if r is not None and res_after_act:
+        v = v + r
     return v * float(post_scale)
 
 
@@ -469,7 +473,7 @@ def pack_cases():
 
 
 # ------------------------------------------------------------------------------------------------------------------ ivx_conv_fwd_pio
-def run_conv(be, x, packed, scale_p, shift, k, stride, pad, wb, sb, relu=True, res=None, res_mode=0, out_pair=True, post_scale=1.0):
+def run_conv(be, x, packed, scale_p, shift, k, stride, pad, wb, sb, relu=True, res=None, res_mode=0, out_pair=True, post_scale=1.0, res_after_act=False):
     """One ivx_conv_fwd_pio call.  x: PairT [B, H, W, Cin]; res: None, a PairT or (fp32 array, its maximum).  The output is pre-filled with
     NaN.  Returns dict(data: float16 pairs or fp32 [B, Ho, Wo, .], scale, rec: the recorded maximum)."""
     L = be.L
@@ -479,7 +483,7 @@ def run_conv(be, x, packed, scale_p, shift, k, stride, pad, wb, sb, relu=True, r
     d = be.ConvDesc()
     d.B, d.D, d.H, d.W, d.Cin, d.Cout, d.KD, d.KH, d.KW = B, 1, H, W, ci, co, 1, k, k
     d.sd, d.sh, d.sw, d.pd, d.ph, d.pw, d.relu, d.wgt_layout = 1, stride, stride, 0, pad, pad, int(relu), 1
-    d.post_scale, d.in_dtype, d.out_dtype, d.res_scale = post_scale, PAIR, PAIR if out_pair else F32, 1.0
+    d.post_scale, d.in_dtype, d.out_dtype, d.res_scale, d.res_after_act = post_scale, PAIR, PAIR if out_pair else F32, 1.0, int(res_after_act)
     io = be.PairIO()
     xin, sl_in = be.up(x.data), be.up(make_slots(x.amax, x.scale))
     io.in_scale, io.amax_in = be.addr(sl_in, 4 * SLOTS), be.addr(sl_in)
@@ -566,7 +570,14 @@ TIGHT_CONV = [(1, (9, 13), 64, 64, 1, 1, '', ('pair',), 1.0),
               (1, (9, 13), 64, 64, 1, 1, 'mixed', ('pair',), 1.0)]                  # filters, scales, shifts and input of both signs
 
 
-def build_tight_conv(be, case, side):
+# res_after_act (out = relu(v) + res: the same bound, and the construction still reaches it -- every term is non-negative): a 1x1 and a 3x3
+# layer of the table above with a pair residual, and the split-K layer, whose reduction kernel has its own epilogue call
+AFTER_ACT_CONV = [(2, (24, 40), 64, 256, 1, 1, 'pair', ('pair',), 1.0),
+                  (2, (17, 23), 64, 64, 3, 1, 'pair', ('f32', 'pair'), 1.0),
+                  (1, (12, 40), 2048, 512, 1, 1, 'pair', ('pair',), 0.5)]
+
+
+def build_tight_conv(be, case, side, res_after_act=False):
     """The tensors of a tight conv case.  Everything is decided here, from the packed filters' decode and in fp64."""
     B, (H, W), ci, co, k, stride, kind, outs, post = case
     pad = k // 2
@@ -600,23 +611,46 @@ def build_tight_conv(be, case, side):
     b64, b32 = conv_bound(x.amax, wb, sb, rmax, post), conv_bound(x.amax, wb, sb, rmax, post, np.float32)
     assert side_ok(b64, T, side), f'bound * 1.001 = {b64!r} is not 2^-12 {side} {T}'
     rval = None if res is None else (res.value if isinstance(res, PairT) else res[0])
-    ref = conv2d(x.value, wdec, sp, shift, k, stride, pad, True, rval, res_mode, post)
+    ref = conv2d(x.value, wdec, sp, shift, k, stride, pad, True, rval, res_mode, post, res_after_act)
     L = b64 / MARGIN / float(np.abs(ref).max())
     assert L <= TIGHT_L, f'the construction reaches the bound only to L = {L}'
     return dict(x=x, packed=packed, sp=sp, shift=shift, k=k, stride=stride, pad=pad, wb=wb, sb=sb, res=res, res_mode=res_mode, post=post,
                 ref=ref, allowed=allowed_scales(b64, b32), L=L, outs=outs)
 
 
-def run_tight_conv(be, case, side):
+def run_tight_conv(be, case, side, res_after_act=False):
     """Returns (worst error / bound, L)."""
-    c = build_tight_conv(be, case, side)
-    name = f'{be.name} tight conv {case} {side}'
+    c = build_tight_conv(be, case, side, res_after_act)
+    name = f'{be.name} tight conv {case} {side}' + (' res_after_act' if res_after_act else '')
     worst = 0.0
     for o in c['outs']:
         got = run_conv(be, c['x'], c['packed'], c['sp'], c['shift'], c['k'], c['stride'], c['pad'], c['wb'], c['sb'], True, c['res'], c['res_mode'],
-                       o == 'pair', c['post'])
+                       o == 'pair', c['post'], res_after_act)
         worst = max(worst, check_pair_output(name, got, c['ref'], c['allowed']) if o == 'pair' else check_f32_output(name, got, c['ref']))
     return worst, c['L']
+
+
+def run_signed_after_act_conv(be, k, post=-1.25):
+    """The tight cases are non-negative, so their ReLU is the identity and the side the residual is added on cannot show.  Here the input,
+    the filters and the pair residual have both signs: out = (relu(v) + res) * post against the plain 2e-5 of the range, with the scale
+    the rule gives the bound (max|in| wbound + sbound + max|res|) |post|.  Condition, by the reference alone: the other residual order
+    and the multiplier before the ReLU each lie more than 100 x that tolerance away on at least 25 % of the elements."""
+    B, H, W, ci, co = 2, 17, 23, 64, 64
+    r = np.random.RandomState(100 + k)
+    w, scale, shift = random_filters(r, co, k * k, ci)
+    x, res = make_pair((r.randn(B, H, W, ci) * 1.5).astype(np.float32)), make_pair(r.randn(B, H, W, co).astype(np.float32))
+    packed, sp, wb, sb = pack_filters(be, w, scale, shift)
+    wdec = filters_decode(packed)
+    ref = conv2d(x.value, wdec, sp, shift, k, 1, k // 2, True, res.value, 1, post, True)
+    far = 100 * VALUE_TOL * float(np.abs(ref).max())
+    swapped = conv2d(x.value, wdec, sp, shift, k, 1, k // 2, True, res.value, 1, post, False)
+    early = conv2d(x.value, wdec, np.asarray(sp, np.float64) * post, np.asarray(shift, np.float64) * post, k, 1, k // 2, True, res.value, 1, 1.0, True)
+    for what, other in (('the other residual order', swapped), ('scaling before the ReLU', early)):
+        frac = float((np.abs(other - ref) > far).mean())
+        assert frac >= 0.25, f'{what} is told apart on {frac:.3f} of the elements only'
+    b64, b32 = conv_bound(x.amax, wb, sb, res.amax, post), conv_bound(x.amax, wb, sb, res.amax, post, np.float32)
+    got = run_conv(be, x, packed, sp, shift, k, 1, k // 2, wb, sb, True, res, 1, True, post, True)
+    return check_pair_output(f'{be.name} conv {k}x{k} res_after_act post_scale {post} on signed data', got, ref, allowed_scales(b64, b32))
 
 
 # loose side: B, (H, W), Cin, Cout, k
