@@ -68,6 +68,13 @@ struct BpListParams : BpGatherParams {
   const int *first_list;    // [B] or NULL
   int R;
 };
+// WEIGHTED instantiations (ivx_backproject_weighted_fwd; fading scenes): the ROWS form whose views carry weights and whose state has a weight sum
+struct BpWeightParams : BpListParams {
+  const float *view_weight; // [S] or NULL (= 1)
+  const float *decay;       // [B] or NULL (= 1); BP_ACCUM
+  float forget_below;       // BP_ACCUM: a faded weight sum below it forgets the voxel; 0 forgets nothing
+  float *wsum;              // [R, N]  BP_ACCUM: the running weight sum, beside count
+};
 
 // MODE BP_MEAN: the reference's view mean + valid mask.  BP_SUM (view-sharded multi-GPU mode): the raw sum over
 // this rank's views and the per-voxel view count, to be all-reduced and normalised by volume_normalize_kernel.
@@ -107,10 +114,17 @@ __device__ __forceinline__ void bp_bilinear_weights(const float ax, const float 
 // row outside [0, R) ends the whole workgroup before any address is formed (r depends on blockIdx.y alone: no lane of it stays behind).  A list of
 // nothing but unseen views adds nothing: with `first` the row becomes zero sum / zero count (mean 0, valid 0), without it the state is stored back
 // as it was loaded (16-byte loads and stores, no arithmetic: every bit pattern survives).
-template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false, bool ROWS = false>
+// WEIGHTED (ivx_backproject_weighted_fwd; fading scenes; ROWS forms only; the definition is in include/imvoxel.h): the projecting lane loads the
+// weight of its view next to its projection rows (both addresses come from the slot alone, so the two loads overlap) -- a weight that fails
+// w > 0 && w < inf makes the view unseen like a failed validity test: no feature address of it is formed -- and broadcasts it with the pixel offset; the view sum is S = fma(w, sample, S), and the weight sum W lives with cnt (every lane of
+// the group carries both, lane g == 0 stores them).  BP_ACCUM fades the state it read, S *= lambda and W *= lambda unless lambda == 1 (uniform
+// per sample), and forgets the voxel whose faded W is below p.forget_below (> 0).  The mean divides by W.  With unit weights fma(1, f, S) is the
+// __fadd_rn of the other forms and W == (float)cnt, so volume / count / mean / valid are theirs bit for bit.
+template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false, bool ROWS = false, bool WEIGHTED = false>
 __global__ __launch_bounds__(256) void backproject_mean_kernel(
-    const std::conditional_t<ROWS, BpListParams, std::conditional_t<GATHER, BpGatherParams, BpParams>> p) {
+    const std::conditional_t<WEIGHTED, BpWeightParams, std::conditional_t<ROWS, BpListParams, std::conditional_t<GATHER, BpGatherParams, BpParams>>> p) {
   static_assert(!ROWS || (GATHER && VEC == 4 && MODE != BP_SUM), "the ROWS forms are the gathered mean / accumulate kernels");
+  static_assert(!WEIGHTED || ROWS, "the WEIGHTED forms are ROWS forms");
   typedef T tv4 __attribute__((ext_vector_type(4)));
   constexpr bool MEAN = MODE == BP_MEAN;
   const int b = blockIdx.y;
@@ -120,6 +134,10 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
     if (p.row) r = p.row[b];
     if (r < 0 || r >= p.R) return;
     if (p.first_list) first = p.first_list[b];
+  }
+  float lam = 1.0f;                        // WEIGHTED BP_ACCUM: the decay of this sample, loaded with the row and the flag (b < B: no guard needed)
+  if constexpr (WEIGHTED && MODE == BP_ACCUM) {
+    if (p.decay) lam = p.decay[b];
   }
   const int lpv = 1 << p.lpv_log2;
   const int lane = threadIdx.x & 63;
@@ -157,6 +175,7 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
 #pragma unroll
     for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
   int cnt = 0;
+  float wacc = 0.f;           // WEIGHTED: the weight sum W of this voxel
   if constexpr (MODE == BP_ACCUM) {
     if (active && !first) {              // the running state of this voxel (16-byte loads, coalesced as the stores below)
       const float *run = p.volume + ((size_t)r * p.N + n) * p.C;
@@ -170,6 +189,24 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
         }
       }
       cnt = p.count[(size_t)r * p.N + n];
+      if constexpr (WEIGHTED) {          // fade, then forget: only a state that was read
+        wacc = p.wsum[(size_t)r * p.N + n];
+        if (lam != 1.0f) {
+#pragma unroll
+          for (int q = 0; q < MAXCH; ++q)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[q][e] = __fmul_rn(lam, acc[q][e]);
+          wacc = __fmul_rn(lam, wacc);
+        }
+        if (p.forget_below > 0.f && !(wacc >= p.forget_below)) {
+#pragma unroll
+          for (int q = 0; q < MAXCH; ++q)
+#pragma unroll
+            for (int e = 0; e < VEC; ++e) acc[q][e] = 0.f;
+          wacc = 0.f;
+          cnt = 0;
+        }
+      }
     }
   }
 
@@ -180,12 +217,16 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
     int step = 0;               // BP_BILINEAR: bit 0 = x1 is one pixel right of x0, bit 1 = y1 is one row below y0 (0 where the clamp joins them)
     float ax = 0.f, ay = 0.f;   // BP_BILINEAR: the fractions
     int slot = 0;               // GATHER: the slot of this view
+    float wt = 1.0f;            // WEIGHTED: its weight
     bool listed = v < p.V;
     if constexpr (GATHER) {
       if (listed) {
         slot = p.view_slot[b * p.V + v];
         listed = slot >= 0 && slot < p.S;
       }
+    }
+    if constexpr (WEIGHTED) {      // loaded beside the projection rows (both need the slot only); tested with the validity below
+      if (listed && p.view_weight) wt = p.view_weight[slot];
     }
     if (listed) {
       const float *P = p.proj + (GATHER ? (size_t)slot : (size_t)b * p.V + v) * 12;
@@ -203,7 +244,8 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
       d = __fmaf_rn(P[11], 1.0f, d);
       const float xr = rintf(__fdiv_rn(u, d));
       const float yr = rintf(__fdiv_rn(w_, d));
-      const bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
+      bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
+      if constexpr (WEIGHTED) ok = ok && wt > 0.f && wt < __builtin_inff();     // NaN, 0, negative and inf: an unseen view (off stays -1)
       if (ok) off = (((GATHER ? slot : b * p.V + v) * p.FH + (int)yr) * p.FW + (int)xr);
       if constexpr (SAMP == BP_BILINEAR) {
         if (ok) {               // a valid sample: xf in [-0.5, wc - 0.5], so the floors are in [-1, wc - 1] and fit an int
@@ -223,6 +265,8 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
       const int o = __shfl(off, gbase + s, 64);
       int dx = 0, dy = 0;       // BP_BILINEAR: element offsets from corner 00 to corners 10 and 01
       float w[4];
+      float ws = 1.0f;          // WEIGHTED: the weight of view v0 + s
+      if constexpr (WEIGHTED) ws = __shfl(wt, gbase + s, 64);
       if constexpr (SAMP == BP_BILINEAR) {
         const int st = __shfl(step, gbase + s, 64);
         const float axs = __shfl(ax, gbase + s, 64), ays = __shfl(ay, gbase + s, 64);
@@ -232,6 +276,7 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
       }
       if (o >= 0) {
         ++cnt;
+        if constexpr (WEIGHTED) wacc = __fadd_rn(wacc, ws);
         const T *src = reinterpret_cast<const T *>(p.feat) + (size_t)o * p.C;
 #pragma unroll
         for (int q = 0; q < MAXCH; ++q) {
@@ -243,15 +288,21 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
               const tv4 c01 = *reinterpret_cast<const tv4 *>(src + dy + ch * 4);
               const tv4 c11 = *reinterpret_cast<const tv4 *>(src + dy + dx + ch * 4);
 #pragma unroll
-              for (int e = 0; e < 4; ++e)
-                acc[q][e] = __fadd_rn(acc[q][e], bp_bilinear_sample((float)c00[e], (float)c10[e], (float)c01[e], (float)c11[e], w));
+              for (int e = 0; e < 4; ++e) {
+                const float f = bp_bilinear_sample((float)c00[e], (float)c10[e], (float)c01[e], (float)c11[e], w);
+                if constexpr (WEIGHTED) acc[q][e] = __fmaf_rn(ws, f, acc[q][e]);
+                else acc[q][e] = __fadd_rn(acc[q][e], f);
+              }
             } else if constexpr (SAMP == BP_BILINEAR) {
               acc[q][0] = __fadd_rn(acc[q][0], bp_bilinear_sample((float)src[ch], (float)src[dx + ch], (float)src[dy + ch], (float)src[dy + dx + ch], w));
             } else if constexpr (VEC == 4) {
               const tv4 xr = *reinterpret_cast<const tv4 *>(src + ch * 4);
               const f32x4 x = {(float)xr[0], (float)xr[1], (float)xr[2], (float)xr[3]};
 #pragma unroll
-              for (int e = 0; e < 4; ++e) acc[q][e] = __fadd_rn(acc[q][e], x[e]);
+              for (int e = 0; e < 4; ++e) {
+                if constexpr (WEIGHTED) acc[q][e] = __fmaf_rn(ws, x[e], acc[q][e]);
+                else acc[q][e] = __fadd_rn(acc[q][e], x[e]);
+              }
             } else {
               acc[q][0] = __fadd_rn(acc[q][0], (float)src[ch]);
             }
@@ -262,6 +313,35 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
   }
 
   if (!active) return;
+  if constexpr (WEIGHTED) {            // the stores of the WEIGHTED forms: the mean divides by the weight sum, seen means W > 0 (VEC 4, BP_MEAN / BP_ACCUM)
+    const bool seen = wacc > 0.f;
+    float *run = MODE == BP_ACCUM ? p.volume + ((size_t)r * p.N + n) * p.C : nullptr;
+    T *mean = MODE == BP_ACCUM ? (p.mean_out ? reinterpret_cast<T *>(p.mean_out) + ((size_t)r * p.N + n) * p.C : nullptr)
+                               : reinterpret_cast<T *>(p.volume) + ((size_t)r * p.N + n) * p.C;
+#pragma unroll
+    for (int q = 0; q < MAXCH; ++q) {
+      const int ch = g + q * lpv;
+      if (ch < p.nchunk) {
+        f32x4 s;
+        tv4 y;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          s[e] = acc[q][e];
+          y[e] = (T)(seen ? __fdiv_rn(acc[q][e], wacc) : 0.f);
+        }
+        if (run) *reinterpret_cast<f32x4 *>(run + ch * 4) = s;
+        if (mean) *reinterpret_cast<tv4 *>(mean + ch * 4) = y;
+      }
+    }
+    if (g == 0) {
+      if constexpr (MODE == BP_ACCUM) {
+        p.count[(size_t)r * p.N + n] = cnt;
+        p.wsum[(size_t)r * p.N + n] = wacc;
+      }
+      if (mean) p.valid[(size_t)r * p.N + n] = seen ? 1 : 0;
+    }
+    return;
+  }
   const float dn = (float)cnt;
   if constexpr (MODE == BP_ACCUM) {
     float *run = p.volume + ((size_t)r * p.N + n) * p.C;
@@ -326,6 +406,23 @@ __global__ __launch_bounds__(256) void volume_normalize_kernel(const float *sum,
     for (int e = 0; e < 4; ++e) y[e] = (T)(cnt ? __fdiv_rn(x[e], dn) : 0.f);
     *reinterpret_cast<tv4 *>(out + i * 4) = y;
     if (i % C4 == 0) valid[vox] = cnt > 0 ? 1 : 0;
+  }
+}
+
+// out[n,:] = W > 0 ? sum / W : 0, valid = W > 0: the mean of a (sum, weight sum) state (ivx_volume_wmean_fwd), the division and the mask of the
+// WEIGHTED accumulate kernel's mean_out.  Out of place only; T may be __bf16 (one rounding at the store).
+template <typename T>
+__global__ __launch_bounds__(256) void volume_wmean_kernel(const float *sum, T *out, const float *wsum, uint8_t *valid, long long total4, int C4) {
+  typedef T tv4 __attribute__((ext_vector_type(4)));
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
+    const long long vox = i / C4;
+    const float W = wsum[vox];
+    const f32x4 x = *reinterpret_cast<const f32x4 *>(sum + i * 4);
+    tv4 y;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) y[e] = (T)(W > 0.f ? __fdiv_rn(x[e], W) : 0.f);
+    *reinterpret_cast<tv4 *>(out + i * 4) = y;
+    if (i % C4 == 0) valid[vox] = W > 0.f ? 1 : 0;
   }
 }
 
@@ -431,6 +528,8 @@ struct BpCall {
   int32_t S = 0;
   bool listed = false;              // ivx_backproject_lists_fwd: the gathered form (gather is set too) with the row / first lists of `lists`
   const ivx_lift_lists *lists = nullptr;
+  bool weighted = false;            // ivx_backproject_weighted_fwd: the listed form (listed and gather are set too) with the weights, decays and weight sums of `weights`
+  const ivx_lift_weights *weights = nullptr;
 };
 
 // The descriptor of an older export's argument list (voxel_size stays with the caller's pointer, which may be NULL until validated).
@@ -476,6 +575,18 @@ static int bp_validate(const BpCall &c) {
   }
   IVX_REQUIRE(d->B > 0 && d->V > 0 && d->FH > 0 && d->FW > 0 && d->C > 0 && d->X > 0 && d->Y > 0 && d->Z > 0, "%s: non-positive dims", what);
   if (c.listed) IVX_REQUIRE(c.lists->row || c.lists->R >= d->B, "%s: R=%d rows for B=%d samples and no row list (sample b then uses row b)", what, c.lists->R, d->B);
+  if (c.weighted) {
+    const ivx_lift_weights *w = c.weights;
+    IVX_REQUIRE(w, "%s: null weights", what);
+    IVX_REQUIRE(w->forget_below >= 0.f && w->forget_below < __builtin_inff(), "%s: forget_below %g (must be >= 0 and finite)", what, (double)w->forget_below);
+    if (d->mode == IVX_LIFT_ACCUM) {
+      IVX_REQUIRE(w->wsum, "%s: null wsum (the accumulate mode updates the weight sums)", what);
+    } else {
+      IVX_REQUIRE(!w->wsum, "%s: the mean mode takes no wsum", what);
+      IVX_REQUIRE(!w->decay, "%s: the mean mode takes no decay list", what);
+      IVX_REQUIRE(w->forget_below == 0.f, "%s: forget_below %g in the mean mode (must be 0: there is no state to forget)", what, (double)w->forget_below);
+    }
+  }
   const int vec = (d->C % 4 == 0) ? 4 : 1;
   IVX_REQUIRE(vec == 4 || (d->mode == IVX_LIFT_MEAN && d->feat_dtype == IVX_F32 && !c.gather), "%s: C %% 4 must be 0 (every form but the fp32 mean of a view stack)", what);
   IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
@@ -491,11 +602,11 @@ static int bp_validate(const BpCall &c) {
   return IVX_OK;
 }
 
-// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams / BpListParams (a plain or gathered
-// launch passes the base).
-static BpListParams bp_fill(const BpCall &c, dim3 *grid) {
+// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams / BpListParams / BpWeightParams (a
+// plain, gathered or listed launch passes the base).
+static BpWeightParams bp_fill(const BpCall &c, dim3 *grid) {
   const ivx_backproject_desc &d = *c.d;
-  BpListParams p;
+  BpWeightParams p;
   p.feat = (const float *)c.feat; p.proj = c.proj; p.new_origin = c.new_origin; p.crop_hw = c.crop_hw;
   p.volume = (float *)c.volume; p.valid = c.valid; p.count = c.count; p.mean_out = c.mean_out;
   // the running state is read unless `first`; a bf16 sum is the accumulate kernel from a zero state (bp_launch), so it never reads one
@@ -509,6 +620,8 @@ static BpListParams bp_fill(const BpCall &c, dim3 *grid) {
   p.lpv_log2 = lg;
   p.view_slot = c.view_slot; p.S = c.S;
   p.row = c.listed ? c.lists->row : nullptr; p.first_list = c.listed ? c.lists->first : nullptr; p.R = c.listed ? c.lists->R : 0;
+  p.view_weight = c.weighted ? c.weights->view_weight : nullptr; p.decay = c.weighted ? c.weights->decay : nullptr;
+  p.forget_below = c.weighted ? c.weights->forget_below : 0.f; p.wsum = c.weighted ? c.weights->wsum : nullptr;
   if (bp_single_view_copy(c)) {      // 256 voxels per workgroup regardless of the group width (each lane projects one voxel)
     p.pmax = c.partials; p.nblk = 0; p.q = 0;
     *grid = dim3((p.N + 255) / 256, d.B);
@@ -521,8 +634,9 @@ static BpListParams bp_fill(const BpCall &c, dim3 *grid) {
 }
 
 // The selection table: every instantiation of the two lift kernels is launched from exactly one line below.
-static int bp_launch(const BpCall &c, const BpListParams &l, const dim3 grid) {
+static int bp_launch(const BpCall &c, const BpWeightParams &w, const dim3 grid) {
   const ivx_backproject_desc &d = *c.d;
+  const BpListParams &l = w;
   const BpGatherParams &g = l;
   const BpParams &p = l;
   const bool bf16 = d.feat_dtype == IVX_BF16, bilinear = d.sampling == IVX_SAMPLE_BILINEAR, vec4 = d.C % 4 == 0;
@@ -530,7 +644,16 @@ static int bp_launch(const BpCall &c, const BpListParams &l, const dim3 grid) {
   const int mode = d.mode == IVX_LIFT_MEAN ? BP_MEAN : (d.mode == IVX_LIFT_SUM && !bf16) ? BP_SUM : BP_ACCUM;
   const dim3 block(256);
   hipStream_t st = (hipStream_t)c.stream;
-  if (c.listed && (mode == BP_ACCUM || l.row)) {    // rows of a state / output pool: MEAN and ACCUM, VEC 4 only (a listed mean with no row list is the gathered launch below)
+  if (c.weighted) {                                 // weights, decay and weight sums: the ROWS forms, with or without a row list
+    if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
+    else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
+    else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
+    else if (mode == BP_ACCUM)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
+    else if (bilinear && bf16)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
+    else if (bilinear)                         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
+    else if (bf16)                             hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
+    else                                       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
+  } else if (c.listed && (mode == BP_ACCUM || l.row)) {    // rows of a state / output pool: MEAN and ACCUM, VEC 4 only (a listed mean with no row list is the gathered launch below)
     if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true>), grid, block, 0, st, l);
     else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true>), grid, block, 0, st, l);
     else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true>), grid, block, 0, st, l);
@@ -652,6 +775,14 @@ extern "C" int ivx_backproject_lists_fwd(const ivx_backproject_desc *d, const iv
                  nullptr, true, l ? l->view_slot : nullptr, l ? l->S : 0, true, l});
 }
 
+// Weighted listed lift (include/imvoxel.h): the listed form with per-view weights, a per-sample decay and the weight sums beside the counts.
+extern "C" int ivx_backproject_weighted_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const ivx_lift_weights *w, const void *feat_pool,
+                                            const float *proj_pool, const float *new_origin, const int32_t *crop_hw, void *volume, int32_t *count, void *mean_out,
+                                            uint8_t *valid, ivx_stream_t stream) {
+  return bp_run({"ivx_backproject_weighted_fwd", d, d ? d->voxel_size : nullptr, feat_pool, proj_pool, new_origin, crop_hw, volume, count, mean_out, valid, stream,
+                 nullptr, true, l ? l->view_slot : nullptr, l ? l->S : 0, true, l, true, w});
+}
+
 // ------------------------------------------------------------------ mean of a (sum, count) volume
 // out == sum: in place (ivx_volume_normalize_fwd).  Otherwise the sums stay intact and out may be bf16 (ivx_volume_mean_fwd).
 static int volume_normalize_launch(const char *what, const float *sum, void *out, int32_t out_dtype, const int32_t *count, int64_t n_voxels, int32_t C,
@@ -680,4 +811,22 @@ extern "C" int ivx_volume_mean_fwd(const float *volume_sum, const int32_t *count
   IVX_REQUIRE(volume_sum && count && out && valid, "ivx_volume_mean_fwd: null argument");
   IVX_REQUIRE((const void *)volume_sum != out, "ivx_volume_mean_fwd: out must not be volume_sum (ivx_volume_normalize_fwd works in place)");
   return volume_normalize_launch("ivx_volume_mean_fwd", volume_sum, out, out_dtype, count, n_voxels, C, valid, stream);
+}
+
+extern "C" int ivx_volume_wmean_fwd(const float *volume_sum, const float *wsum, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype, uint8_t *valid,
+                                    ivx_stream_t stream) {
+  const char *what = "ivx_volume_wmean_fwd";
+  IVX_REQUIRE(volume_sum && wsum && out && valid, "%s: null argument", what);
+  IVX_REQUIRE((const void *)volume_sum != out, "%s: out must not be volume_sum", what);
+  IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "%s: bad dims (C %% 4 must be 0)", what);
+  IVX_REQUIRE(out_dtype == IVX_F32 || out_dtype == IVX_BF16, "%s: out_dtype must be IVX_F32 or IVX_BF16", what);
+  const long long total4 = (long long)n_voxels * (C / 4);
+  long long blocks = (total4 + 255) / 256;
+  if (blocks > 256 * 64) blocks = 256 * 64;
+  if (out_dtype == IVX_BF16)
+    hipLaunchKernelGGL(volume_wmean_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (__bf16 *)out, wsum, valid, total4, C / 4);
+  else
+    hipLaunchKernelGGL(volume_wmean_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (float *)out, wsum, valid, total4, C / 4);
+  IVX_CHECK_LAUNCH(what);
+  return IVX_OK;
 }

@@ -349,22 +349,26 @@ class ImVoxelNet(nn.Module):
             img = img.unsqueeze(1)
         return self.simple_test(img, [dict(m, **s) for m, s in zip(img_metas, shapes)])
 
-    def open_scene(self, meta, window=None):
+    def open_scene(self, meta, window=None, decay=None, forget_below=0.0):
         """A streaming scene on this model (scene.SceneSession): add_views / add_views_u8 fold new views into a running volume,
         detect() works on the views so far.  meta: one img_metas entry without lidar2img['extrinsic'].  Several sessions may be open
         on one prepared model.  window=W >= 1: the scene holds the last W views at most (the oldest leaves when a new one arrives,
         remove_views(ids) drops any) and its volume is exactly the one-shot lift of the views it holds; the trunk still runs once
-        per view.  Costs a ring of W FPN level-0 maps (scene.py has the figures)."""
+        per view.  Costs a ring of W FPN level-0 maps (scene.py has the figures).  decay=lam in (0, 1] (not with window): a fading
+        scene, the weighted running mean -- add_views(..., weights=...) gives every view a confidence, every add_views call fades the
+        state once by lam, and a voxel whose weight sum falls below forget_below becomes unseen again; O(1) state, no ring.  decay=1.0
+        with unit weights holds the bits of a plain session.  A session opened without decay refuses weights."""
         from .scene import SceneSession
-        return SceneSession(self, meta, window=window)
+        return SceneSession(self, meta, window=window, decay=decay, forget_below=forget_below)
 
-    def open_scenes(self, metas, window=None):
+    def open_scenes(self, metas, window=None, decay=None, forget_below=0.0):
         """N streaming scenes that share their launches (scene.SceneBatch): per tick one trunk call over the new views of any subset of
         the scenes, one listed lift into the touched scenes' rows of the state pools, and detect() as one batched neck + head + NMS.
         metas: one scene meta per scene (intrinsic, origin and box type may differ; image size and model are common).  window as for
-        open_scene, per scene.  Every scene's volume is exact; what is not claimed is in the SceneBatch docstring."""
+        open_scene, per scene.  Every scene's volume is exact; what is not claimed is in the SceneBatch docstring.  decay (one value for
+        every scene or one per scene) and forget_below as for open_scene; in a batch only the scenes a call touches fade."""
         from .scene import SceneBatch
-        return SceneBatch(self, metas, window=window)
+        return SceneBatch(self, metas, window=window, decay=decay, forget_below=forget_below)
 
     def simple_test_ragged(self, imgs, img_metas):
         """simple_test for a batch whose samples have DIFFERENT numbers of views: imgs is a list of B tensors [V_b,3,H,W] (common H, W),

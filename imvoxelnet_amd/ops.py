@@ -984,6 +984,48 @@ def backproject_lists_mean_(pool, proj_pool, lists, rows, new_origin, crop_hw, v
     return vol, valid.view(torch.bool)
 
 
+def backproject_weighted_accum_(pool, proj_pool, lists, weights, rows, first, decay, new_origin, crop_hw, voxel_size, vol_sum, wsum, count, mean_out=None,
+                                valid_out=None, forget_below=0.0, sampling='nearest'):
+    """backproject_lists_accum_ with per-view weights, a decay per sample and a forgetting threshold (ivx_backproject_weighted_fwd; fading scenes;
+    include/imvoxel.h has the definition).  pool, proj_pool, lists, rows, first, new_origin, crop_hw, vol_sum, count, mean_out / valid_out: as for
+    backproject_lists_accum_.  weights: the weight of every SLOT of the pool -- a host list of S finite floats >= 0 (0 makes the slot's view unseen;
+    checked here, ValueError), None (1 for every slot), or a device float32 tensor [S], used as it is (the kernel treats NaN, 0, negative and inf as
+    an unseen view).  decay: None (nothing fades) or a host list of B floats in (0, 1]: the state of sample b that is read (first[b] false) is
+    multiplied by decay[b] before this call's views are added.  wsum [R,X,Y,Z] fp32: the running weight sums, in/out beside vol_sum and count.
+    forget_below >= 0: a voxel whose faded weight sum is below it becomes unseen again (sum, weight sum and count zero); 0 forgets nothing.
+    mean = wsum > 0 ? vol_sum / wsum : 0.  With unit weights, no decay and forget_below 0, vol_sum / count / mean_out / valid_out are bit for bit
+    those of backproject_lists_accum_ and wsum == count.  The lists, the weights and the decays go up in one copy; every argument error is raised
+    before any launch.  Returns (vol_sum, wsum, count)."""
+    if (mean_out is None) != (valid_out is None):
+        raise ValueError('mean_out and valid_out must both be given or both be None')
+    _lists_lift(_LIFT_ACCUM, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol_sum, count, mean_out, valid_out, sampling,
+                weighted=dict(weights=weights, decay=decay, forget_below=forget_below, wsum=wsum))
+    return vol_sum, wsum, count
+
+
+def backproject_weighted_mean_(pool, proj_pool, lists, weights, rows, new_origin, crop_hw, voxel_size, vol, valid, sampling='nearest'):
+    """backproject_lists_mean_ with per-view weights: row rows[b] of vol / valid becomes the weighted mean  sum(w * sample) / sum(w)  over the
+    views of lists[b] that see the voxel and the mask sum(w) > 0.  weights as for backproject_weighted_accum_ (per slot).  With unit weights the
+    bits are those of backproject_lists_mean_.  Returns (vol, valid as bool)."""
+    _lists_lift(_LIFT_MEAN, pool, proj_pool, lists, rows, None, new_origin, crop_hw, voxel_size, vol, None, None, valid, sampling,
+                weighted=dict(weights=weights, decay=None, forget_below=0.0, wsum=None))
+    return vol, valid.view(torch.bool)
+
+
+def _host_floats(x, name, n):
+    """A host sequence of n Python / numpy real numbers (no bools, no tensors) -> list of float."""
+    if isinstance(x, torch.Tensor) or isinstance(x, (str, bytes)) or not hasattr(x, '__len__'):
+        raise TypeError(f'{name} must be a host list of floats')
+    out = []
+    for v in x:
+        if isinstance(v, bool) or not hasattr(v, '__float__'):
+            raise TypeError(f'{name} must hold real numbers, got {v!r}')
+        out.append(float(v))
+    if len(out) != n:
+        raise ValueError(f'{name} has {len(out)} entries, expected {n}')
+    return out
+
+
 def _host_ints(x, name, n=None):
     """A host sequence of Python / numpy integers (no bools, no tensors) -> list of int."""
     if isinstance(x, torch.Tensor) or isinstance(x, (str, bytes)) or not hasattr(x, '__len__'):
@@ -998,9 +1040,11 @@ def _host_ints(x, name, n=None):
     return out
 
 
-def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol, count, mean_out, valid, sampling):
+def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol, count, mean_out, valid, sampling, weighted=None):
     """The one checker and caller of ivx_backproject_lists_fwd.  The host lists are checked first (against shapes only), then the tensors;
-    then ONE upload of view_slot [B,Vmax] (-1 padded), row [B] and first [B], and the launch."""
+    then ONE upload of view_slot [B,Vmax] (-1 padded), row [B] and first [B], and the launch.
+    weighted = dict(weights, decay, forget_below, wsum): ivx_backproject_weighted_fwd instead; host weights [S] and decays [B] travel in the same
+    upload (as bits behind the integers)."""
     sampling = _lib.sampling_id(sampling)
     for t, name in ((pool, 'pool'), (proj_pool, 'proj_pool'), (vol, 'vol_sum' if mode == _LIFT_ACCUM else 'vol')):
         if not isinstance(t, torch.Tensor):
@@ -1033,6 +1077,27 @@ def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, 
         first = [int(bool(f)) for f in first]
     Vmax = max(1, max(len(l) for l in lists))
     host = [v for l in lists for v in l + [-1] * (Vmax - len(l))] + rows + (first if mode == _LIFT_ACCUM else [])
+    wdev = hostf = decay = None
+    if weighted is not None:
+        import math
+        wts, decay, forget_below, wsum = weighted['weights'], weighted['decay'], weighted['forget_below'], weighted['wsum']
+        hostf = []
+        if isinstance(wts, torch.Tensor) and wts.is_cuda:
+            wdev = wts                                                                # a device list: used as it is, the kernel guards it
+        elif wts is not None:
+            wts = _host_floats(wts, 'weights', S)
+            if any(not (math.isfinite(w) and w >= 0) for w in wts):
+                raise ValueError(f'weights must be finite and >= 0, got {wts}')
+            hostf += wts
+        if decay is not None:
+            if mode != _LIFT_ACCUM:
+                raise ValueError('the mean mode takes no decay')
+            decay = _host_floats(decay, 'decay', B)
+            if any(not 0 < lam <= 1 for lam in decay):
+                raise ValueError(f'decay must be in (0, 1], got {decay}')
+            hostf += decay
+        if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float)) or not (math.isfinite(forget_below) and forget_below >= 0):
+            raise ValueError(f'forget_below must be a finite number >= 0, got {forget_below!r}')
     _chk(pool, 'pool', pool.dtype)
     _chk(proj_pool, 'proj_pool')
     _chk(new_origin, 'new_origin')
@@ -1052,6 +1117,29 @@ def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, 
     else:
         _chk(vol, 'vol', pool.dtype)
         _chk_mask(valid, 'valid', vol.shape[:-1])
+    if weighted is not None:
+        if wdev is not None and tuple(_chk(wdev, 'weights').shape) != (S,):
+            raise ValueError(f'device weights must be [S] = [{S}], got {tuple(wdev.shape)}')
+        if mode == _LIFT_ACCUM:
+            if not isinstance(wsum, torch.Tensor):
+                raise TypeError('wsum must be a torch.Tensor')
+            if tuple(_chk(wsum, 'wsum').shape) != (R, X, Y, Z):
+                raise ValueError('wsum must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
+        fn = getattr(_lib.lib(), 'ivx_backproject_weighted_fwd', None)
+        if fn is None:
+            raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_weighted_fwd (needs version 0.4.8)')
+        ints = torch.tensor(host, dtype=torch.int32)
+        dev = (torch.cat([ints, torch.tensor(hostf, dtype=torch.float32).view(torch.int32)]) if hostf else ints).to(pool.device)   # the one upload
+        p0, n_vs = dev.data_ptr(), B * Vmax
+        pf = p0 + 4 * len(host)                                                        # the floats: weights [S] (when they came as a host list), then decay [B]
+        n_w = S if (wdev is None and wts is not None) else 0
+        l = _lib.LiftLists(S, R, p0, p0 + 4 * n_vs, (p0 + 4 * (n_vs + B)) if mode == _LIFT_ACCUM else None)
+        w = _lib.LiftWeights(_ptr(wdev) if wdev is not None else (pf if n_w else None), (pf + 4 * n_w) if decay is not None else None, float(forget_below),
+                             _ptr(wsum) if mode == _LIFT_ACCUM else None)
+        d = _lib.BackprojectDesc(B, Vmax, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], mode, sampling, 0)
+        check(fn(C.byref(d), C.byref(l), C.byref(w), _ptr(pool), _ptr(proj_pool), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(count), _ptr(mean_out),
+                 _ptr(valid), _stream()), 'ivx_backproject_weighted_fwd')     # (`dev` is released in stream order, as below)
+        return
     fn = getattr(_lib.lib(), 'ivx_backproject_lists_fwd', None)
     if fn is None:
         raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_lists_fwd (needs version 0.4.7)')
@@ -1126,6 +1214,31 @@ def volume_mean(vol_sum, count, dtype=torch.float32, out=None, valid_out=None):
         _chk_mask(valid_out, 'valid_out', count.shape)
     check(_lib.lib().ivx_volume_mean_fwd(_ptr(vol_sum), _ptr(count), count.numel(), vol_sum.shape[-1], _ptr(out), _DT[dtype], _ptr(valid_out),
                                          _stream()), 'ivx_volume_mean_fwd')
+    return out, valid_out.view(torch.bool)
+
+
+def volume_wmean(vol_sum, wsum, dtype=torch.float32, out=None, valid_out=None):
+    """volume_mean for a weighted state (ivx_volume_wmean_fwd): mean = wsum > 0 ? vol_sum / wsum : 0 in `dtype` (float32 or bfloat16), valid =
+    wsum > 0 -- the mean_out / valid_out of backproject_weighted_accum_ on the same state, bit for bit; vol_sum and wsum stay as they are.
+    Returns (mean, valid bool [R,X,Y,Z])."""
+    _chk(vol_sum, 'vol_sum')
+    _chk(wsum, 'wsum')
+    if dtype not in _F32_BF16:
+        raise TypeError(f'dtype must be float32 or bfloat16, got {dtype}')
+    if tuple(wsum.shape) != tuple(vol_sum.shape[:-1]):
+        raise ValueError('wsum must have the spatial shape of the volume')
+    if out is None:
+        out = torch.empty(vol_sum.shape, device=vol_sum.device, dtype=dtype)
+    elif tuple(_chk(out, 'out', dtype).shape) != tuple(vol_sum.shape):
+        raise ValueError('out must have the shape of vol_sum')
+    if valid_out is None:
+        valid_out = torch.empty(wsum.shape, device=vol_sum.device, dtype=torch.uint8)
+    else:
+        _chk_mask(valid_out, 'valid_out', wsum.shape)
+    fn = getattr(_lib.lib(), 'ivx_volume_wmean_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_wmean_fwd (needs version 0.4.8)')
+    check(fn(_ptr(vol_sum), _ptr(wsum), wsum.numel(), vol_sum.shape[-1], _ptr(out), _DT[dtype], _ptr(valid_out), _stream()), 'ivx_volume_wmean_fwd')
     return out, valid_out.view(torch.bool)
 
 

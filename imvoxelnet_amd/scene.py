@@ -33,7 +33,17 @@ pools and N rings instead of the sums.  The volume of every scene is exact (the 
 bit); the features and the batched neck depend on what shares a call, so boxes are not claimed equal to a single session's: the
 SceneBatch docstring states each claim.  SceneSession is not built on the batch: its path and bits are what they were.
 
-Out of scope: re-weighting views; scene batches across ranks; a model-level C handle for sessions (the state lives here, over the
+Fading scenes (open_scene(meta, decay=lam, forget_below=t) / open_scenes(metas, decay=...)).  The two ways above never forget, or forget exactly
+at the price of a ring of W maps, and both weigh a blurred or badly posed frame like a good one.  A session opened with `decay` keeps the usual
+weighted running mean of a fusing volume instead: every view carries a weight (add_views(..., weights=...), 1 by default), every add_views call is
+one tick -- the state (sum, weight sum) fades by `decay` once, then the call's views are added with their weights -- and a voxel whose faded weight
+sum falls below `forget_below` becomes unseen again.  State: the (sum, count) volume plus one fp32 weight sum per voxel; no ring.  The lift is
+ops.backproject_weighted_accum_ (ivx_backproject_weighted_fwd; include/imvoxel.h has the definition); with decay=1.0 and unit weights the session
+holds, tick by tick, the bits of a plain session.  A windowed scene takes weights too (a weight per kept view, reweight(ids, weights) changes
+them): its re-lift is then the weighted mean of the kept views (ops.backproject_weighted_mean_).  `decay` and `window` are alternative ways to
+forget and exclude each other.
+
+Out of scope: decay on windowed scenes; per-pixel weight maps; scene batches across ranks; a model-level C handle for sessions (the state lives here, over the
 op-level ABI and the handle's sub-range calls).
 """
 import numpy as np
@@ -50,9 +60,13 @@ class SceneSession:
     window=None: the scene only grows (a running (sum, count) volume).  window=W >= 1: the scene holds the last W views at most and
     remove_views works; state: a feature ring [W,FH,FW,C] in the storage type and a projection ring [W,3,4] (allocated at the first
     add; W * FH * FW * C * sizeof(element) bytes: the module docstring has the ScanNet figures), the mean / mask buffers and the
-    ordered host list of (view id, slot) -- no (sum, count) volume."""
+    ordered host list of (view id, slot) -- no (sum, count) volume.
+    decay=lam in (0, 1] (unbounded sessions only): a fading scene -- a weight sum [1,X,Y,Z] fp32 beside (sum, count); every add_views call is one
+    tick: the state is multiplied by lam once, voxels whose weight sum falls below forget_below (>= 0) are forgotten, then the call's views are
+    added with their weights.  Decided here, not lazily: a session opened without decay runs the plain path and refuses weights."""
 
-    def __init__(self, model, meta, window=None):
+    def __init__(self, model, meta, window=None, decay=None, forget_below=0.0):
+        decay, forget_below = self._check_fading(window, decay, forget_below)
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, (int, np.integer)):
                 raise TypeError(f'window must be None or an integer >= 1, got {window!r}')
@@ -79,6 +93,45 @@ class SceneSession:
         self._hw, self._stale, self._closed, self.n_views = None, False, False, 0
         # window=W: the rings, the views in the scene, oldest first, as (id, slot, extrinsic), and the id of the next arrival
         self._window, self._ring, self._pring, self._views, self._next_id = window, None, None, [], 0
+        # decay=lam: the weighted running mean (a weight sum beside sum / count).  window=W: the host ring of the slots' weights, None until a weight is given
+        self._decay, self._forget, self._wsum, self._wring = decay, forget_below, None, None
+
+    @staticmethod
+    def _check_fading(window, decay, forget_below):
+        """(decay, forget_below) as floats (decay None: a plain session); the rules that need no model."""
+        import math
+        if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float, np.integer, np.floating)):
+            raise TypeError(f'forget_below must be a number >= 0, got {forget_below!r}')
+        forget_below = float(forget_below)
+        if not (math.isfinite(forget_below) and forget_below >= 0):
+            raise ValueError(f'forget_below must be finite and >= 0, got {forget_below}')
+        if decay is None:
+            if forget_below != 0:
+                raise ValueError('forget_below needs a fading session: open with decay=... (decay=1.0 fades nothing)')
+            return None, 0.0
+        if window is not None:
+            raise ValueError('decay together with window: the two are alternative ways to forget (a windowed scene takes weights, not a decay)')
+        if isinstance(decay, bool) or not isinstance(decay, (int, float, np.integer, np.floating)):
+            raise TypeError(f'decay must be None or a number in (0, 1], got {decay!r}')
+        decay = float(decay)
+        if not 0 < decay <= 1:
+            raise ValueError(f'decay must be in (0, 1], got {decay}')
+        return decay, forget_below
+
+    @staticmethod
+    def _check_weights(weights, V):
+        """weights: None or V finite floats >= 0 -> list of float."""
+        import math
+        if weights is None:
+            return None
+        if isinstance(weights, torch.Tensor):
+            weights = weights.tolist()
+        w = [float(x) for x in (np.asarray(weights, np.float64).reshape(-1).tolist())]
+        if len(w) != V:
+            raise ValueError(f'{len(w)} weights for {V} views')
+        if any(not (math.isfinite(x) and x >= 0) for x in w):
+            raise ValueError(f'weights must be finite and >= 0, got {w}')
+        return w
 
     # ------------------------------------------------------------------ state
     def _check_open(self):
@@ -90,11 +143,11 @@ class SceneSession:
         self._check_open()
         self.meta['lidar2img']['extrinsic'] = []
         self._hw, self._origin, self._crop, self._stale, self.n_views = None, None, None, False, 0
-        self._views, self._next_id = [], 0
+        self._views, self._next_id, self._wring = [], 0, None
 
     def close(self):
         self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
-        self._ring = self._pring = None
+        self._ring = self._pring = self._wsum = self._wring = None
         self._closed = True
 
     @property
@@ -126,15 +179,17 @@ class SceneSession:
                 raise ValueError(f'every extrinsic must be 4x4, got {e.shape}')
         return E
 
-    def add_views(self, img, extrinsics, emit=True):
+    def add_views(self, img, extrinsics, emit=True, weights=None):
         """img [V,3,H,W] float32 on the device (normalised and padded as for simple_test), extrinsics: V float32 4x4 matrices.
         emit=False skips the store of the mean volume (detect() / volume() then compute it once from the sums): for callers that add
         many chunks between two detections.  Views count in the order they are added.  On a windowed session (window=W) the views go
         into free slots of the ring, the oldest views leaving first when the window is full; more than W views in one call raise
-        ValueError; emit has no effect (the lift runs when volume() / detect() is asked and the set has changed)."""
-        return self._add_views(img, extrinsics, emit, {})
+        ValueError; emit has no effect (the lift runs when volume() / detect() is asked and the set has changed).
+        weights: one finite float >= 0 per view (None: 1; 0: the view does not count), on a session opened with decay= or window=.  On a fading
+        session every call is one tick: the state fades once by `decay`, then these views are added with their weights."""
+        return self._add_views(img, extrinsics, emit, {}, weights)
 
-    def _add_views(self, img, extrinsics, emit, shapes):
+    def _add_views(self, img, extrinsics, emit, shapes, weights=None):
         """add_views with the img_shape / ori_shape / pad_shape of these views (add_views_u8); the session changes only when the
         views are in: a call that raises leaves meta, state and n_views as they were."""
         self._check_open()
@@ -148,6 +203,9 @@ class SceneSession:
         E = self._check_extrinsics(extrinsics, V)
         if self._window is not None and V > self._window:
             raise ValueError(f'{V} views in one call do not fit a window of {self._window}')
+        weights = self._check_weights(weights, V)
+        if weights is not None and self._window is None and self._decay is None:
+            raise ValueError('this session was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
         if self._hw is not None and (H, W) != self._hw:
             raise ValueError(f'image size {(H, W)} differs from the {self._hw} of the views already in the scene')
         meta = dict(self.meta, **shapes)
@@ -165,7 +223,7 @@ class SceneSession:
         else:
             proj, origin, crop = m._compute_projection(view_meta, 4)[None].contiguous().to(p0.device), self._origin, self._crop
         if self._window is not None:
-            return self._add_windowed(p0, proj, origin, crop, E, (H, W), shapes)
+            return self._add_windowed(p0, proj, origin, crop, E, (H, W), shapes, weights)
         if self._sum is None:                     # the state, allocated once: sum fp32, count, mean in the storage type, valid
             X, Y, Z = m.n_voxels
             Cn, dev = p0.shape[-1], p0.device
@@ -173,8 +231,14 @@ class SceneSession:
             self._count = torch.empty((1, X, Y, Z), device=dev, dtype=torch.int32)
             self._mean = torch.empty((1, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
             self._valid = torch.empty((1, X, Y, Z), device=dev, dtype=torch.uint8)
-        ops.backproject_accum_(p0, proj, origin, crop, m.voxel_size, self._sum, self._count, self.n_views == 0,
-                               self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
+            self._wsum = torch.empty((1, X, Y, Z), device=dev, dtype=torch.float32) if self._decay is not None else None
+        if self._decay is not None:                # one tick: fade once, then this call's views with their weights (the call's maps are the pool)
+            ops.backproject_weighted_accum_(p0, proj[0], [list(range(V))], weights, [0], [self.n_views == 0], [self._decay], origin, crop, m.voxel_size,
+                                            self._sum, self._wsum, self._count, self._mean if emit else None, self._valid if emit else None,
+                                            forget_below=self._forget, sampling=getattr(m, 'sampling', 'nearest'))
+        else:
+            ops.backproject_accum_(p0, proj, origin, crop, m.voxel_size, self._sum, self._count, self.n_views == 0,
+                                   self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
         self._origin, self._crop = origin, crop
         self._stale = not emit
         self._hw = (H, W)
@@ -183,7 +247,7 @@ class SceneSession:
         self.n_views += V
         return self
 
-    def _add_windowed(self, p0, proj, origin, crop, E, hw, shapes):
+    def _add_windowed(self, p0, proj, origin, crop, E, hw, shapes, weights=None):
         """The new views' maps p0 [V,1,FH,FW,C] and projection rows proj [1,V,3,4] into free slots of the rings; the oldest views
         leave first when the window is full.  Everything that can fail comes before the first change of the session."""
         m, W, V = self._model, self._window, len(E)
@@ -201,6 +265,11 @@ class SceneSession:
         for i, s in enumerate(slots):
             ring[s].copy_(p0[i])
             pring[s].copy_(proj[0, i])
+        if weights is not None and self._wring is None:
+            self._wring = [1.0] * W                # the weight ring starts with the first weight given; until then the scene runs the unweighted re-lift
+        if self._wring is not None:                # a reused slot takes its new view's weight (1 when none is given)
+            for i, s in enumerate(slots):
+                self._wring[s] = weights[i] if weights is not None else 1.0
         self._ring, self._pring, self._mean, self._valid = ring, pring, mean, valid
         self._views = kept + [(self._next_id + i, slots[i], E[i]) for i in range(V)]
         self._next_id += V
@@ -228,21 +297,46 @@ class SceneSession:
             self.n_views, self._stale = len(self._views), True
         return self
 
-    def add_views_u8(self, frames, extrinsics, img_scale, emit=True, **pipeline_kw):
+    def reweight(self, ids, weights):
+        """Change the weights of views that are in a windowed scene (ids: view_ids; one finite float >= 0 per id; 0 takes the view out of the
+        mean without freeing its slot) and mark the scene stale: the next volume() / detect() lifts the kept views again with the new weights.
+        An unknown id raises KeyError and leaves the scene as it was."""
+        self._check_open()
+        if self._window is None:
+            raise RuntimeError('reweight needs a windowed session: open_scene(meta, window=W)')
+        scalar = isinstance(ids, (int, np.integer))
+        ids = [ids] if scalar else list(ids)
+        weights = self._check_weights([weights] if scalar and not hasattr(weights, '__len__') else weights, len(ids))
+        slot_of = {v[0]: v[1] for v in self._views}
+        unknown = [i for i in ids if i not in slot_of]
+        if unknown:
+            raise KeyError(f'no view with id {unknown} in the scene (view_ids: {sorted(slot_of)})')
+        if ids:
+            if self._wring is None:
+                self._wring = [1.0] * self._window
+            for i, w in zip(ids, weights):
+                self._wring[slot_of[i]] = w
+            self._stale = True
+        return self
+
+    def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
         (data.prepare_images_device; pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device) and fills img_shape / ori_shape /
-        pad_shape of the scene meta.  Later frames must come out at the same shapes."""
+        pad_shape of the scene meta.  Later frames must come out at the same shapes.  weights as for add_views."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
         E = self._check_extrinsics(extrinsics, len(frames))
         if self._window is not None and len(frames) > self._window:
             raise ValueError(f'{len(frames)} views in one call do not fit a window of {self._window}')
+        weights = self._check_weights(weights, len(frames))
+        if weights is not None and self._window is None and self._decay is None:
+            raise ValueError('this session was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)       # one multi-view sample
         for k, v in shapes[0].items():
             if self.n_views and k in self.meta and tuple(self.meta[k]) != tuple(v):
                 raise ValueError(f'{k} {tuple(v)} of these frames differs from the {tuple(self.meta[k])} of the views already in the scene')
-        return self._add_views(img[0], E, emit, shapes[0])
+        return self._add_views(img[0], E, emit, shapes[0], weights)
 
     # ------------------------------------------------------------------ reading the scene
     def volume(self):
@@ -251,10 +345,17 @@ class SceneSession:
         self._check_open()
         if self.n_views == 0:
             raise RuntimeError('the scene has no views yet')
+        if self._stale and self._window is not None and self._wring is not None:      # the same lift with the weight ring: the weighted mean of the kept views
+            ops.backproject_weighted_mean_(self._ring, self._pring, [[v[1] for v in self._views]], self._wring, [0], self._origin, self._crop,
+                                           self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+            self._stale = False
         if self._stale and self._window is not None:      # the set changed since the last lift: ONE gathered lift of the views in it, in order
             view_slot = torch.tensor([[v[1] for v in self._views]], dtype=torch.int32).to(self._ring.device)
             ops.backproject_gather_mean_(self._ring, self._pring, view_slot, self._origin, self._crop, self._model.voxel_size, self._mean, self._valid,
                                          getattr(self._model, 'sampling', 'nearest'))
+            self._stale = False
+        if self._stale and self._decay is not None:       # (emit=False adds on a fading session: the mean of (sum, weight sum))
+            ops.volume_wmean(self._sum, self._wsum, self._mean.dtype, out=self._mean, valid_out=self._valid)
             self._stale = False
         if self._stale:
             ops.volume_mean(self._sum, self._count, self._mean.dtype, out=self._mean, valid_out=self._valid)
@@ -293,15 +394,28 @@ class SceneBatch:
       Neck and boxes.  The batched neck's operand scales depend on the batch too: there is NO claim that scene s's boxes equal those of
                 a B = 1 SceneSession.detect().
       Detection stage.  detect() is exactly the model's batched detection stage (detect_cl / detect_indoor_cl) on the stacked rows.
-    A call that raises before its launch leaves every scene as it was."""
+    A call that raises before its launch leaves every scene as it was.
+
+    Fading batches (open_scenes(metas, decay=lam or [lam_0 .. lam_N-1], forget_below=t); SceneSession has the rules): a weight-sum pool [N,X,Y,Z]
+    fp32 beside the sums, and ONE weighted listed lift per tick (ops.backproject_weighted_accum_).  Every add_views call is one tick FOR THE SCENES
+    IT TOUCHES: only the touched scenes fade (each by its own decay); a scene that gets no view in a call is neither read nor written, so its
+    state does not age.  A caller who wants wall-clock fading gives every scene a view (or a zero-weight view) per tick.  A windowed batch takes
+    weights and reweight(scene, ids, weights); its re-lift is then the weighted mean of the kept views (a host weight ring [N*W])."""
 
     _features = SceneSession._features
 
-    def __init__(self, model, metas, window=None):
+    def __init__(self, model, metas, window=None, decay=None, forget_below=0.0):
         metas = list(metas)
         if not metas:
             raise ValueError('open_scenes needs at least one scene meta')
-        self._scenes = [SceneSession(model, meta, window=window) for meta in metas]      # checks every meta, window and head_2d; used as records only
+        decays = list(decay) if hasattr(decay, '__len__') else [decay] * len(metas)
+        if len(decays) != len(metas):
+            raise ValueError(f'{len(decays)} decays for {len(metas)} scenes (one value for all, or one per scene)')
+        if any(d is None for d in decays) and any(d is not None for d in decays):
+            raise ValueError('decay must be given for every scene of a batch or for none')
+        # checks every meta, window, decay and head_2d; used as records only
+        self._scenes = [SceneSession(model, meta, window=window, decay=d, forget_below=forget_below) for meta, d in zip(metas, decays)]
+        self._fading, self._forget, self._wsum, self._wring = decays[0] is not None, self._scenes[0]._forget, None, None
         self._model, self._window, self._N = model, self._scenes[0]._window, len(metas)
         self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
         self._hw, self._closed = None, False
@@ -339,12 +453,14 @@ class SceneBatch:
         for s in (range(self._N) if scenes is None else [self._scene_index(s) for s in scenes]):
             self._scenes[s].reset()
             self._cam[s] = None
+            if self._wring is not None:
+                self._wring[s * self._window:(s + 1) * self._window] = [1.0] * self._window
         if not any(self.n_views):
             self._hw = None
         return self
 
     def close(self):
-        self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
+        self._sum = self._count = self._mean = self._valid = self._ring = self._pring = self._wsum = self._wring = None
         for r in self._scenes:
             r.close()
         self._closed = True
@@ -355,14 +471,44 @@ class SceneBatch:
         self._scenes[self._scene_index(scene)].remove_views(ids)
         return self
 
+    def reweight(self, scene, ids, weights):
+        """Change the weights of kept views of one scene of a windowed batch (SceneSession.reweight); an unknown id raises KeyError and
+        changes nothing."""
+        self._check_open()
+        s = self._scene_index(scene)
+        r = self._scenes[s]
+        if self._window is None:
+            raise RuntimeError('reweight needs a windowed batch: open_scenes(metas, window=W)')
+        scalar = isinstance(ids, (int, np.integer))
+        ids = [ids] if scalar else list(ids)
+        weights = SceneSession._check_weights([weights] if scalar and not hasattr(weights, '__len__') else weights, len(ids))
+        slot_of = {v[0]: v[1] for v in r._views}      # the batch's slots: scene s owns s*W .. s*W+W-1
+        unknown = [i for i in ids if i not in slot_of]
+        if unknown:
+            raise KeyError(f'no view with id {unknown} in scene {s} (view_ids: {sorted(slot_of)})')
+        if ids:
+            if self._wring is None:
+                self._wring = [1.0] * (self._N * self._window)
+            for i, w in zip(ids, weights):
+                self._wring[slot_of[i]] = w
+            r._stale = True
+        return self
+
     # ------------------------------------------------------------------ adding views
-    def add_views(self, img, extrinsics, scene, emit=True):
+    def add_views(self, img, extrinsics, scene, emit=True, weights=None):
         """img [T,3,H,W] float32 on the device, extrinsics: T float32 4x4 matrices, scene: T scene indices -- view t belongs to scene
         scene[t]; the views of one scene count in the order given.  emit=False skips the store of the means (computed when asked).
-        Windowed batch: more than W views for one scene in a call raise ValueError; emit has no effect."""
-        return self._add_views(img, extrinsics, scene, emit, {})
+        Windowed batch: more than W views for one scene in a call raise ValueError; emit has no effect.
+        weights: one finite float >= 0 per view, on a batch opened with decay= or window=.  Fading batch: one tick for the touched scenes only."""
+        return self._add_views(img, extrinsics, scene, emit, {}, weights=weights)
 
-    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, **pipeline_kw):
+    def _check_weights(self, weights, T):
+        weights = SceneSession._check_weights(weights, T)
+        if weights is not None and self._window is None and not self._fading:
+            raise ValueError('this batch was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
+        return weights
+
+    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, **pipeline_kw):
         """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
         ori_shape / pad_shape of every scene's meta, which later frames must reproduce."""
         from .data import prepare_images_device
@@ -370,12 +516,13 @@ class SceneBatch:
         frames = list(frames)
         E = SceneSession._check_extrinsics(extrinsics, len(frames))
         groups = self._groups(scene, len(frames))
+        weights = self._check_weights(weights, len(frames))
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
         for r in self._scenes:
             for k, v in shapes[0].items():
                 if any(self.n_views) and k in r.meta and tuple(r.meta[k]) != tuple(v):
                     raise ValueError(f'{k} {tuple(v)} of these frames differs from the {tuple(r.meta[k])} of the views already in the batch')
-        return self._add_views(img[0], E, scene, emit, shapes[0], groups)
+        return self._add_views(img[0], E, scene, emit, shapes[0], groups, weights)
 
     def _groups(self, scene, T):
         """scene (T indices) -> {scene: [t, ...]} in first-touch order; the checks that need no device."""
@@ -390,7 +537,7 @@ class SceneBatch:
                     raise ValueError(f'{len(ts)} views of scene {s} in one call do not fit a window of {self._window}')
         return groups
 
-    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None):
+    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None, weights=None):
         self._check_open()
         if not isinstance(img, torch.Tensor):
             raise TypeError('img must be a torch.Tensor [T,3,H,W]')
@@ -402,6 +549,7 @@ class SceneBatch:
         E = SceneSession._check_extrinsics(extrinsics, T)
         if groups is None:
             groups = self._groups(scene, T)
+        weights = self._check_weights(weights, T)
         if self._hw is not None and (H, W) != self._hw:
             raise ValueError(f'image size {(H, W)} differs from the {self._hw} of the views already in the batch')
         touched = sorted(groups)
@@ -428,7 +576,7 @@ class SceneBatch:
             proj_h[torch.tensor(ts)] = p[0]
             cam[s] = (origin[0], crop[0])
         if self._window is not None:
-            return self._add_windowed(p0, proj_h, groups, touched, cam, E, (H, W), shapes)
+            return self._add_windowed(p0, proj_h, groups, touched, cam, E, (H, W), shapes, weights)
         proj, origin, crop = self._upload(dev, proj_h, [cam[s] for s in touched])
         X, Y, Z = m.n_voxels
         Cn = p0.shape[-1]
@@ -438,9 +586,16 @@ class SceneBatch:
             self._count = torch.empty((N, X, Y, Z), device=dev, dtype=torch.int32)
             self._mean = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
             self._valid = torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8)
-        ops.backproject_lists_accum_(p0, proj, [groups[s] for s in touched], touched, [self._scenes[s].n_views == 0 for s in touched], origin, crop,
-                                     m.voxel_size, self._sum, self._count, self._mean if emit else None, self._valid if emit else None,
-                                     sampling=getattr(m, 'sampling', 'nearest'))
+            self._wsum = torch.empty((N, X, Y, Z), device=dev, dtype=torch.float32) if self._fading else None
+        if self._fading:                          # one tick of the touched scenes: each fades by its own decay, the others are not read
+            ops.backproject_weighted_accum_(p0, proj, [groups[s] for s in touched], weights, touched, [self._scenes[s].n_views == 0 for s in touched],
+                                            [self._scenes[s]._decay for s in touched], origin, crop, m.voxel_size, self._sum, self._wsum, self._count,
+                                            self._mean if emit else None, self._valid if emit else None, forget_below=self._forget,
+                                            sampling=getattr(m, 'sampling', 'nearest'))
+        else:
+            ops.backproject_lists_accum_(p0, proj, [groups[s] for s in touched], touched, [self._scenes[s].n_views == 0 for s in touched], origin, crop,
+                                         m.voxel_size, self._sum, self._count, self._mean if emit else None, self._valid if emit else None,
+                                         sampling=getattr(m, 'sampling', 'nearest'))
         self._hw = (H, W)
         for r in self._scenes:
             r.meta.update(shapes)
@@ -465,7 +620,7 @@ class SceneBatch:
         crop = buf[T * 12 + B * 3:].view(torch.int32).view(B, 2)
         return proj, origin, crop
 
-    def _add_windowed(self, p0, proj_h, groups, touched, cam, E, hw, shapes):
+    def _add_windowed(self, p0, proj_h, groups, touched, cam, E, hw, shapes, weights=None):
         """The new maps and projection rows into free slots of their scenes' parts of the rings (one index_copy_ each); the oldest views
         of a full scene leave first.  Everything that can fail comes before the first change of the batch."""
         m, W, N = self._model, self._window, self._N
@@ -489,6 +644,12 @@ class SceneBatch:
         idx = torch.tensor(slot_of, dtype=torch.int64).to(dev)
         ring.index_copy_(0, idx, p0)
         pring.index_copy_(0, idx, proj_h.to(dev))
+        if weights is not None and self._wring is None:
+            self._wring = [1.0] * (N * W)         # the weight ring starts with the first weight given
+        if self._wring is not None:               # a reused slot takes its new view's weight (1 when none is given)
+            for s in touched:
+                for t in groups[s]:
+                    self._wring[slot_of[t]] = weights[t] if weights is not None else 1.0
         self._ring, self._pring, self._mean, self._valid, self._hw = ring, pring, mean, valid, hw
         for r in self._scenes:
             r.meta.update(shapes)
@@ -509,8 +670,15 @@ class SceneBatch:
             return
         if self._window is not None:
             _, origin, crop = self._upload(self._ring.device, None, [self._cam[s] for s in stale])
-            ops.backproject_lists_mean_(self._ring, self._pring, [[v[1] for v in self._scenes[s]._views] for s in stale], stale, origin, crop,
-                                        self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+            if self._wring is not None:
+                ops.backproject_weighted_mean_(self._ring, self._pring, [[v[1] for v in self._scenes[s]._views] for s in stale], self._wring, stale, origin,
+                                               crop, self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+            else:
+                ops.backproject_lists_mean_(self._ring, self._pring, [[v[1] for v in self._scenes[s]._views] for s in stale], stale, origin, crop,
+                                            self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+        elif self._fading:
+            for s in stale:                       # (emit=False adds: the mean of the stored (sum, weight sum), row by row)
+                ops.volume_wmean(self._sum[s:s + 1], self._wsum[s:s + 1], self._mean.dtype, out=self._mean[s:s + 1], valid_out=self._valid[s:s + 1])
         else:
             for s in stale:                       # (emit=False adds: the mean of the stored sums, row by row)
                 ops.volume_mean(self._sum[s:s + 1], self._count[s:s + 1], self._mean.dtype, out=self._mean[s:s + 1], valid_out=self._valid[s:s + 1])

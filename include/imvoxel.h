@@ -41,7 +41,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * DCNv2 stages and the LayoutHead, ivx_dcn_im2col_fwd_bf16 / ivx_global_avgpool_fwd_bf16; 430 = 0.4.3: ivx_image_prep_u8 / ivx_rescale_size; 440 = 0.4.4: ivx_backproject_fwd_ex / ivx_model_cfg.sampling, the optional
  * bilinear sampling rule of the unprojection; 450 = 0.4.5: ivx_conv_route / ivx_bf16_pair_pack_filters; 460 = 0.4.6: ivx_backproject_gather_fwd, the mean lift of
  * views listed by slot, for sliding-window scenes; 470 = 0.4.7: ivx_backproject_lists_fwd, the listed lift with per-sample rows and `first` flags, for
- * batches of scenes and ragged batches) and the message of the last failing call on
+ * batches of scenes and ragged batches; 480 = 0.4.8: ivx_backproject_weighted_fwd / ivx_volume_wmean_fwd, the listed lift with per-view weights,
+ * per-sample decay and a forgetting threshold, for fading scenes) and the message of the last failing call on
  * this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -645,6 +646,61 @@ typedef struct ivx_lift_lists {
 int ivx_backproject_lists_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const void *feat_pool, const float *proj_pool,
                               const float *new_origin /*[B,3]*/, const int32_t *crop_hw /*[B,2]*/, void *volume, int32_t *count,
                               void *mean_out, uint8_t *valid, ivx_stream_t stream);
+
+/* (0.4.8) Weighted listed lift: every view carries a confidence, the running state fades by a factor per call and a voxel that has not been seen
+ * for long enough becomes unseen again -- the weighted running mean of a fusing volume, with O(1) state (fading scenes: scene.py,
+ * open_scene(meta, decay=...)).  It is ivx_backproject_lists_fwd with three more inputs and one more state field; like the bilinear rule it lies
+ * outside the reference-parity claims and is pinned to an fp64 reference written from the definition below (tests/ref_unproject_weighted.py).
+ *
+ * Definition.  The geometry, the validity rule, both sampling rules and the sample function are those of ivx_backproject_lists_fwd.  Per voxel
+ * and per channel, in this order, every operation fp32 and round-to-nearest:
+ *   1. start   S (the sum, [C]), W (the weight sum) and cnt are loaded from the sample's row of volume / wsum / count; with `first` they are
+ *              +0, +0, 0 and the row is not read.
+ *   2. fade    (accumulate mode, and only when the row was read)  lambda = decay[b]:
+ *              if lambda != 1:  S = lambda * S, W = lambda * W                     (one rounded product each; lambda == 1 multiplies nothing)
+ *              then, if forget_below > 0 and !(W >= forget_below):  S = +0, W = +0, cnt = 0        (the voxel is unseen again)
+ *              The branch on lambda is uniform per sample.  For every W >= 0 -- every W this entry ever stores -- the forgetting rule is
+ *              "!(W >= forget_below)"; the threshold 0 forgets nothing, so that with forget_below == 0 and lambda == 1 the state of a sample that
+ *              adds nothing is stored back with every bit pattern intact (no arithmetic touches it), as for ivx_backproject_lists_fwd.
+ *   3. add     over the listed views in list order.  A view counts only if its slot is in [0, S) and its weight w = view_weight[slot] passes
+ *              w > 0 && w < inf: NaN, 0, negative values and +inf fail, and such a view is an unseen view, exactly like a slot outside [0, S) (its
+ *              projection rows may be read, its map is not).
+ *              The view must also see the voxel.  Then  S = fma(w, sample, S),  W = W + w,  ++cnt.
+ *   4. store   S, W and cnt are stored.  Where the mean is emitted: mean = W > 0 ? S / W : 0 (IEEE division; one rounding to bf16 in bf16
+ *              storage), valid = W > 0.
+ * The mean mode has no state and no fade: steps 3 and 4 from zero, and only volume (the mean) and valid are written.
+ * cnt is the number of counted views since the voxel was last forgotten.
+ *
+ * w->view_weight  DEVICE [S] fp32: the weight of slot s (indexed by slot, like the pools); NULL: 1 for every slot
+ * w->decay        DEVICE [B] fp32 or NULL (= 1): lambda of sample b (indexed by b, not by row); IVX_LIFT_ACCUM only
+ * w->forget_below >= 0, finite; IVX_LIFT_ACCUM only (must be 0 in the mean mode)
+ * w->wsum         DEVICE [R,X,Y,Z] fp32 in/out, a state pool beside volume and count; IVX_LIFT_ACCUM: required; mean mode: must be NULL
+ * Everything else, and every rule of ivx_backproject_lists_fwd (rows, row guard, distinct rows, untouched rows, `first`), as there.
+ *
+ * Properties that follow from the definition.
+ *   Unit weights.  With every weight 1, every decay 1 and forget_below 0, the fields volume, count, mean_out and valid are bit for bit those of
+ *               ivx_backproject_lists_fwd on the same lists, and wsum == (float)count: fma(1, f, S) is S + f rounded once, and a sum of k ones
+ *               is exact below 2^24.
+ *   Zero weight.  A view of weight 0 (or NaN, negative, +inf) is bit for bit the same call with that view not listed.
+ *   Power-of-two scale.  Multiplying all weights by 2^k leaves the mean and the mask bit-identical; the sums and wsum scale exactly
+ *               (barring overflow and underflow).
+ *   Guards.     No address depends on a weight or on a decay: bad values can only change numbers.
+ * IVX_ERR_INVALID_ARG before any launch: everything ivx_backproject_lists_fwd rejects, a null w, a missing wsum in the accumulate mode, a
+ * superfluous wsum, a decay list or a nonzero forget_below in the mean mode, a negative or non-finite forget_below.
+ *
+ * ivx_volume_wmean_fwd is the out-of-place mean of a (sum, weight sum) state after calls that passed mean_out = NULL: out = wsum > 0 ?
+ * volume_sum / wsum : 0 (out_dtype IVX_F32 or IVX_BF16), valid = wsum > 0 -- bit for bit the mean_out / valid of the same state.             */
+typedef struct ivx_lift_weights {
+  const float *view_weight;  /* DEVICE [S], the weight of slot s; NULL = 1 for every slot */
+  const float *decay;        /* DEVICE [B] or NULL (= 1); IVX_LIFT_ACCUM only */
+  float forget_below;        /* >= 0, finite; IVX_LIFT_ACCUM only (must be 0 in the mean mode) */
+  float *wsum;               /* DEVICE [R,X,Y,Z] fp32 in/out; IVX_LIFT_ACCUM: required; mean mode: must be NULL */
+} ivx_lift_weights;
+int ivx_backproject_weighted_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const ivx_lift_weights *w, const void *feat_pool,
+                                 const float *proj_pool, const float *new_origin /*[B,3]*/, const int32_t *crop_hw /*[B,2]*/, void *volume,
+                                 int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream);
+int ivx_volume_wmean_fwd(const float *volume_sum, const float *wsum, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype, uint8_t *valid,
+                         ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
