@@ -900,62 +900,14 @@ def backproject_gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, vox
     view_slot: a host sequence / CPU int32 tensor (range-checked here, then uploaded: a slot outside [0, S) raises ValueError) or a
     device int32 tensor, used as it is (the kernel treats an out-of-range slot as a view that sees nothing).
     -> volume [B,X,Y,Z,C] (pool's dtype), valid [B,X,Y,Z] bool."""
-    return _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, n_voxels, sampling)
+    vol, valid = _pooled_lift('gather', _LIFT_MEAN, pool, proj_pool, new_origin, crop_hw, voxel_size, None, None, sampling, view_slot=view_slot, n_voxels=n_voxels)
+    return vol, valid.view(torch.bool)
 
 
 def backproject_gather_mean_(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, vol, valid, sampling='nearest'):
     """backproject_gather_mean into the caller's buffers (windowed scenes keep theirs): vol [B,X,Y,Z,C] (pool's dtype) and valid
     [B,X,Y,Z] uint8 / bool are overwritten.  Returns (vol, valid as bool)."""
-    return _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, None, sampling, vol, valid)
-
-
-def _gather_mean(pool, proj_pool, view_slot, new_origin, crop_hw, voxel_size, n_voxels, sampling, vol=None, valid=None):
-    sampling = _lib.sampling_id(sampling)
-    if not isinstance(pool, torch.Tensor) or not isinstance(proj_pool, torch.Tensor):
-        raise TypeError('pool and proj_pool must be torch.Tensors')
-    if pool.dtype not in _F32_BF16:
-        raise TypeError(f'pool must be float32 or bfloat16, got {pool.dtype}')
-    if pool.dim() == 5 and pool.shape[1] == 1:
-        pool = pool[:, 0]
-    if pool.dim() != 4 or tuple(proj_pool.shape) != (pool.shape[0], 3, 4):
-        raise ValueError(f'pool must be [S,FH,FW,C] (or [S,1,FH,FW,C]) and proj_pool [S,3,4], got {tuple(pool.shape)} and {tuple(proj_pool.shape)}')
-    S, FH, FW, Cn = (int(v) for v in pool.shape)
-    host = None
-    if not (isinstance(view_slot, torch.Tensor) and view_slot.is_cuda):       # a host list: checked here, uploaded once the pools have passed
-        host = view_slot if isinstance(view_slot, torch.Tensor) else torch.as_tensor(view_slot)
-        if host.dtype not in (torch.int32, torch.int64) or host.dim() != 2 or host.numel() == 0:
-            raise ValueError('a host view_slot must be a [B,V] list / tensor of integers with B, V >= 1')
-        bad = sorted(set(int(v) for v in host.flatten().tolist() if not 0 <= v < S))
-        if bad:
-            raise ValueError(f'view_slot holds slots outside [0, {S}): {bad}')
-    _chk(pool, 'pool', pool.dtype)
-    _chk(proj_pool, 'proj_pool')
-    if host is not None:
-        view_slot = host.to(torch.int32).contiguous().to(pool.device)
-    _chk(view_slot, 'view_slot', torch.int32)
-    if view_slot.dim() != 2 or view_slot.shape[0] < 1 or view_slot.shape[1] < 1:
-        raise ValueError(f'view_slot must be [B,V] with B, V >= 1, got {tuple(view_slot.shape)}')
-    _chk(new_origin, 'new_origin')
-    _chk(crop_hw, 'crop_hw', torch.int32)
-    B, V = (int(v) for v in view_slot.shape)
-    if tuple(new_origin.shape) != (B, 3) or tuple(crop_hw.shape) != (B, 2):
-        raise ValueError('new_origin must be [B,3] and crop_hw [B,2] for the B rows of view_slot')
-    fn = getattr(_lib.lib(), 'ivx_backproject_gather_fwd', None)
-    if fn is None:
-        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_gather_fwd (needs version 0.4.6)')
-    if vol is None:
-        X, Y, Z = (int(v) for v in n_voxels)
-        vol = torch.empty((B, X, Y, Z, Cn), device=pool.device, dtype=pool.dtype)
-        valid = torch.empty((B, X, Y, Z), device=pool.device, dtype=torch.uint8)
-    else:
-        _chk(vol, 'vol', pool.dtype)
-        if vol.dim() != 5 or vol.shape[0] != B or vol.shape[-1] != Cn:
-            raise ValueError('vol must be [B,X,Y,Z,C] for the B rows of view_slot and the pool\'s C')
-        _chk_mask(valid, 'valid', vol.shape[:-1])
-        X, Y, Z = (int(v) for v in vol.shape[1:4])
-    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], _LIFT_MEAN, sampling, 0)
-    check(fn(C.byref(d), S, _ptr(pool), _ptr(proj_pool), _ptr(view_slot), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(valid), _stream()),
-          'ivx_backproject_gather_fwd')
+    _pooled_lift('gather', _LIFT_MEAN, pool, proj_pool, new_origin, crop_hw, voxel_size, vol, valid, sampling, view_slot=view_slot)
     return vol, valid.view(torch.bool)
 
 
@@ -971,7 +923,8 @@ def backproject_lists_accum_(pool, proj_pool, lists, rows, first, new_origin, cr
     error is raised before any launch.  Returns (vol_sum, count)."""
     if (mean_out is None) != (valid_out is None):
         raise ValueError('mean_out and valid_out must both be given or both be None')
-    _lists_lift(_LIFT_ACCUM, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol_sum, count, mean_out, valid_out, sampling)
+    _pooled_lift('lists', _LIFT_ACCUM, pool, proj_pool, new_origin, crop_hw, voxel_size, vol_sum, valid_out, sampling, lists=lists, rows=rows, first=first,
+                 count=count, mean_out=mean_out)
     return vol_sum, count
 
 
@@ -980,7 +933,7 @@ def backproject_lists_mean_(pool, proj_pool, lists, rows, new_origin, crop_hw, v
     row rows[b] of vol [R,X,Y,Z,C] (pool's dtype) / valid [R,X,Y,Z] uint8 / bool; the other rows stay as they are.  lists, rows and the
     errors as for backproject_lists_accum_.  Row rows[b] is bit for bit backproject_mean over a contiguous copy of lists[b]'s views (an
     empty list: zeros, nothing valid).  Returns (vol, valid as bool)."""
-    _lists_lift(_LIFT_MEAN, pool, proj_pool, lists, rows, None, new_origin, crop_hw, voxel_size, vol, None, None, valid, sampling)
+    _pooled_lift('lists', _LIFT_MEAN, pool, proj_pool, new_origin, crop_hw, voxel_size, vol, valid, sampling, lists=lists, rows=rows)
     return vol, valid.view(torch.bool)
 
 
@@ -998,8 +951,8 @@ def backproject_weighted_accum_(pool, proj_pool, lists, weights, rows, first, de
     before any launch.  Returns (vol_sum, wsum, count)."""
     if (mean_out is None) != (valid_out is None):
         raise ValueError('mean_out and valid_out must both be given or both be None')
-    _lists_lift(_LIFT_ACCUM, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol_sum, count, mean_out, valid_out, sampling,
-                weighted=dict(weights=weights, decay=decay, forget_below=forget_below, wsum=wsum))
+    _pooled_lift('weighted', _LIFT_ACCUM, pool, proj_pool, new_origin, crop_hw, voxel_size, vol_sum, valid_out, sampling, lists=lists, rows=rows, first=first,
+                 count=count, mean_out=mean_out, weighted=dict(weights=weights, decay=decay, forget_below=forget_below, wsum=wsum))
     return vol_sum, wsum, count
 
 
@@ -1007,8 +960,8 @@ def backproject_weighted_mean_(pool, proj_pool, lists, weights, rows, new_origin
     """backproject_lists_mean_ with per-view weights: row rows[b] of vol / valid becomes the weighted mean  sum(w * sample) / sum(w)  over the
     views of lists[b] that see the voxel and the mask sum(w) > 0.  weights as for backproject_weighted_accum_ (per slot).  With unit weights the
     bits are those of backproject_lists_mean_.  Returns (vol, valid as bool)."""
-    _lists_lift(_LIFT_MEAN, pool, proj_pool, lists, rows, None, new_origin, crop_hw, voxel_size, vol, None, None, valid, sampling,
-                weighted=dict(weights=weights, decay=None, forget_below=0.0, wsum=None))
+    _pooled_lift('weighted', _LIFT_MEAN, pool, proj_pool, new_origin, crop_hw, voxel_size, vol, valid, sampling, lists=lists, rows=rows,
+                 weighted=dict(weights=weights, decay=None, forget_below=0.0, wsum=None))
     return vol, valid.view(torch.bool)
 
 
@@ -1040,13 +993,25 @@ def _host_ints(x, name, n=None):
     return out
 
 
-def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, voxel_size, vol, count, mean_out, valid, sampling, weighted=None):
-    """The one checker and caller of ivx_backproject_lists_fwd.  The host lists are checked first (against shapes only), then the tensors;
-    then ONE upload of view_slot [B,Vmax] (-1 padded), row [B] and first [B], and the launch.
-    weighted = dict(weights, decay, forget_below, wsum): ivx_backproject_weighted_fwd instead; host weights [S] and decays [B] travel in the same
-    upload (as bits behind the integers)."""
+# the three lifts that read their views from a pool by slot: the export of each form and the library version that brought it
+_POOLED = {'gather': ('ivx_backproject_gather_fwd', '0.4.6'), 'lists': ('ivx_backproject_lists_fwd', '0.4.7'),
+           'weighted': ('ivx_backproject_weighted_fwd', '0.4.8')}
+
+
+def _pooled_lift(form, mode, pool, proj_pool, new_origin, crop_hw, voxel_size, vol, valid, sampling, view_slot=None, n_voxels=None, lists=None, rows=None,
+                 first=None, count=None, mean_out=None, weighted=None):
+    """The one checker and caller of the lifts over pool [S,1,FH,FW,C] / proj_pool [S,3,4]; form is a key of _POOLED.
+    'gather' (_LIFT_MEAN only): view_slot [B,V], sample b writes row b.  A host list / CPU tensor is range-checked and uploaded; a device
+      int32 tensor is used as it is (no copy).  n_voxels given: vol / valid are allocated here; else the caller's, with B rows.
+    'lists': B ragged host lists, rows [B] and (accumulate mode) first [B] into the caller's vol [R,X,Y,Z,C] / count / mean_out / valid.
+    'weighted': the same with weighted = dict(weights, decay, forget_below, wsum); host weights [S] and decays [B] travel in the same upload
+      (as bits behind the integers).
+    The host lists are checked first (against shapes only), then the tensors; then ONE upload of view_slot [B,V] (-1 padded), row [B] and
+    first [B], and the launch.  Returns (vol, valid)."""
+    import math
     sampling = _lib.sampling_id(sampling)
-    for t, name in ((pool, 'pool'), (proj_pool, 'proj_pool'), (vol, 'vol_sum' if mode == _LIFT_ACCUM else 'vol')):
+    alloc = n_voxels is not None
+    for t, name in ((pool, 'pool'), (proj_pool, 'proj_pool')) + (() if alloc else ((vol, 'vol_sum' if mode == _LIFT_ACCUM else 'vol'),)):
         if not isinstance(t, torch.Tensor):
             raise TypeError(f'{name} must be a torch.Tensor')
     if pool.dtype not in _F32_BF16:
@@ -1056,32 +1021,43 @@ def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, 
     if pool.dim() != 4 or tuple(proj_pool.shape) != (pool.shape[0], 3, 4):
         raise ValueError(f'pool must be [S,FH,FW,C] (or [S,1,FH,FW,C]) and proj_pool [S,3,4], got {tuple(pool.shape)} and {tuple(proj_pool.shape)}')
     S, FH, FW, Cn = (int(v) for v in pool.shape)
-    if vol.dim() != 5 or vol.shape[-1] != Cn:
+    if alloc:
+        X, Y, Z = (int(v) for v in n_voxels)
+    elif vol.dim() != 5 or vol.shape[-1] != Cn:
         raise ValueError('the state / output volume must be [R,X,Y,Z,C] with the pool\'s C')
-    R, X, Y, Z = (int(v) for v in vol.shape[:4])
-    if isinstance(lists, torch.Tensor) or not hasattr(lists, '__len__') or len(lists) < 1:
-        raise TypeError('lists must be a host list of B >= 1 lists of slots')
-    lists = [_host_ints(l, f'lists[{b}]') for b, l in enumerate(lists)]
-    B = len(lists)
-    bad = sorted({v for l in lists for v in l if v != -1 and not 0 <= v < S})
-    if bad:
-        raise ValueError(f'lists hold slots outside [0, {S}) other than the padding -1: {bad}')
-    rows = _host_ints(rows, 'rows', B)
-    if len(set(rows)) != B:
-        raise ValueError(f'rows must be distinct (two samples on one row race), got {rows}')
-    if any(not 0 <= r < R for r in rows):
-        raise ValueError(f'rows must be in [0, {R}), got {rows}')
-    if mode == _LIFT_ACCUM:
-        if isinstance(first, torch.Tensor) or not hasattr(first, '__len__') or len(first) != B:
-            raise ValueError(f'first must be a host list of {B} bools')
-        first = [int(bool(f)) for f in first]
-    Vmax = max(1, max(len(l) for l in lists))
-    host = [v for l in lists for v in l + [-1] * (Vmax - len(l))] + rows + (first if mode == _LIFT_ACCUM else [])
-    wdev = hostf = decay = None
+    else:
+        R, X, Y, Z = (int(v) for v in vol.shape[:4])
+    host, hostf = [], []                           # what goes up: the integers (view_slot, then row and first), the floats behind them
+    if form != 'gather':
+        if isinstance(lists, torch.Tensor) or not hasattr(lists, '__len__') or len(lists) < 1:
+            raise TypeError('lists must be a host list of B >= 1 lists of slots')
+        lists = [_host_ints(l, f'lists[{b}]') for b, l in enumerate(lists)]
+        B = len(lists)
+        bad = sorted({v for l in lists for v in l if v != -1 and not 0 <= v < S})
+        if bad:
+            raise ValueError(f'lists hold slots outside [0, {S}) other than the padding -1: {bad}')
+        rows = _host_ints(rows, 'rows', B)
+        if len(set(rows)) != B:
+            raise ValueError(f'rows must be distinct (two samples on one row race), got {rows}')
+        if any(not 0 <= r < R for r in rows):
+            raise ValueError(f'rows must be in [0, {R}), got {rows}')
+        if mode == _LIFT_ACCUM:
+            if isinstance(first, torch.Tensor) or not hasattr(first, '__len__') or len(first) != B:
+                raise ValueError(f'first must be a host list of {B} bools')
+            first = [int(bool(f)) for f in first]
+        V = max(1, max(len(l) for l in lists))
+        host = [v for l in lists for v in l + [-1] * (V - len(l))] + rows + (first if mode == _LIFT_ACCUM else [])
+    elif not (isinstance(view_slot, torch.Tensor) and view_slot.is_cuda):       # a host list: checked here, uploaded once the pools have passed
+        slots = view_slot if isinstance(view_slot, torch.Tensor) else torch.as_tensor(view_slot)
+        if slots.dtype not in (torch.int32, torch.int64) or slots.dim() != 2 or slots.numel() == 0:
+            raise ValueError('a host view_slot must be a [B,V] list / tensor of integers with B, V >= 1')
+        (B, V), host = (int(v) for v in slots.shape), slots.flatten().tolist()
+        bad = sorted({v for v in host if not 0 <= v < S})
+        if bad:
+            raise ValueError(f'view_slot holds slots outside [0, {S}): {bad}')
+    wdev = decay = None
     if weighted is not None:
-        import math
         wts, decay, forget_below, wsum = weighted['weights'], weighted['decay'], weighted['forget_below'], weighted['wsum']
-        hostf = []
         if isinstance(wts, torch.Tensor) and wts.is_cuda:
             wdev = wts                                                                # a device list: used as it is, the kernel guards it
         elif wts is not None:
@@ -1100,11 +1076,19 @@ def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, 
             raise ValueError(f'forget_below must be a finite number >= 0, got {forget_below!r}')
     _chk(pool, 'pool', pool.dtype)
     _chk(proj_pool, 'proj_pool')
+    if form == 'gather' and not host:                                             # a device list: used as it is, the kernel guards it
+        _chk(view_slot, 'view_slot', torch.int32)
+        if view_slot.dim() != 2 or view_slot.shape[0] < 1 or view_slot.shape[1] < 1:
+            raise ValueError(f'view_slot must be [B,V] with B, V >= 1, got {tuple(view_slot.shape)}')
+        B, V = (int(v) for v in view_slot.shape)
     _chk(new_origin, 'new_origin')
     _chk(crop_hw, 'crop_hw', torch.int32)
     if tuple(new_origin.shape) != (B, 3) or tuple(crop_hw.shape) != (B, 2):
-        raise ValueError('new_origin must be [B,3] and crop_hw [B,2] for the B lists')
-    if mode == _LIFT_ACCUM:
+        raise ValueError(f'new_origin must be [B,3] and crop_hw [B,2] for the B {"rows of view_slot" if form == "gather" else "lists"}')
+    if alloc:
+        vol = torch.empty((B, X, Y, Z, Cn), device=pool.device, dtype=pool.dtype)
+        valid = torch.empty((B, X, Y, Z), device=pool.device, dtype=torch.uint8)
+    elif mode == _LIFT_ACCUM:
         _chk(vol, 'vol_sum')
         _chk(count, 'count', torch.int32)
         if tuple(count.shape) != (R, X, Y, Z):
@@ -1116,6 +1100,8 @@ def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, 
             _chk_mask(valid, 'valid_out', count.shape)
     else:
         _chk(vol, 'vol', pool.dtype)
+        if form == 'gather' and R != B:
+            raise ValueError('vol must be [B,X,Y,Z,C] for the B rows of view_slot and the pool\'s C')
         _chk_mask(valid, 'valid', vol.shape[:-1])
     if weighted is not None:
         if wdev is not None and tuple(_chk(wdev, 'weights').shape) != (S,):
@@ -1125,30 +1111,31 @@ def _lists_lift(mode, pool, proj_pool, lists, rows, first, new_origin, crop_hw, 
                 raise TypeError('wsum must be a torch.Tensor')
             if tuple(_chk(wsum, 'wsum').shape) != (R, X, Y, Z):
                 raise ValueError('wsum must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
-        fn = getattr(_lib.lib(), 'ivx_backproject_weighted_fwd', None)
-        if fn is None:
-            raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_weighted_fwd (needs version 0.4.8)')
-        ints = torch.tensor(host, dtype=torch.int32)
-        dev = (torch.cat([ints, torch.tensor(hostf, dtype=torch.float32).view(torch.int32)]) if hostf else ints).to(pool.device)   # the one upload
-        p0, n_vs = dev.data_ptr(), B * Vmax
-        pf = p0 + 4 * len(host)                                                        # the floats: weights [S] (when they came as a host list), then decay [B]
-        n_w = S if (wdev is None and wts is not None) else 0
-        l = _lib.LiftLists(S, R, p0, p0 + 4 * n_vs, (p0 + 4 * (n_vs + B)) if mode == _LIFT_ACCUM else None)
-        w = _lib.LiftWeights(_ptr(wdev) if wdev is not None else (pf if n_w else None), (pf + 4 * n_w) if decay is not None else None, float(forget_below),
-                             _ptr(wsum) if mode == _LIFT_ACCUM else None)
-        d = _lib.BackprojectDesc(B, Vmax, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], mode, sampling, 0)
-        check(fn(C.byref(d), C.byref(l), C.byref(w), _ptr(pool), _ptr(proj_pool), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(count), _ptr(mean_out),
-                 _ptr(valid), _stream()), 'ivx_backproject_weighted_fwd')     # (`dev` is released in stream order, as below)
-        return
-    fn = getattr(_lib.lib(), 'ivx_backproject_lists_fwd', None)
+    export, since = _POOLED[form]
+    fn = getattr(_lib.lib(), export, None)
     if fn is None:
-        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_backproject_lists_fwd (needs version 0.4.7)')
-    dev = torch.tensor(host, dtype=torch.int32).to(pool.device)                  # the one upload: view_slot, row, first
-    p0, n_vs = dev.data_ptr(), B * Vmax
-    l = _lib.LiftLists(S, R, p0, p0 + 4 * n_vs, (p0 + 4 * (n_vs + B)) if mode == _LIFT_ACCUM else None)
-    d = _lib.BackprojectDesc(B, Vmax, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], mode, sampling, 0)
-    check(fn(C.byref(d), C.byref(l), _ptr(pool), _ptr(proj_pool), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(count), _ptr(mean_out), _ptr(valid),
-             _stream()), 'ivx_backproject_lists_fwd')         # (`dev` is released in stream order: the allocator reuses it after this launch)
+        raise _lib.IvxError(f'this build of libimvoxel_hip.so has no {export} (needs version {since})')
+    if host:                                       # the one upload (`dev` is released in stream order: the allocator reuses it after this launch)
+        ints = torch.tensor(host, dtype=torch.int32)
+        dev = (torch.cat([ints, torch.tensor(hostf, dtype=torch.float32).view(torch.int32)]) if hostf else ints).to(pool.device)
+        p0, n_vs = dev.data_ptr(), B * V
+    d = _lib.BackprojectDesc(B, V, FH, FW, Cn, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), _DT[pool.dtype], mode, sampling, 0)
+    if form == 'gather':
+        rc = fn(C.byref(d), S, _ptr(pool), _ptr(proj_pool), C.c_void_p(p0) if host else _ptr(view_slot), _ptr(new_origin), _ptr(crop_hw), _ptr(vol),
+                _ptr(valid), _stream())
+    else:
+        l = _lib.LiftLists(S, R, p0, p0 + 4 * n_vs, (p0 + 4 * (n_vs + B)) if mode == _LIFT_ACCUM else None)
+        tensors = (_ptr(pool), _ptr(proj_pool), _ptr(new_origin), _ptr(crop_hw), _ptr(vol), _ptr(count), _ptr(mean_out), _ptr(valid), _stream())
+        if form == 'lists':
+            rc = fn(C.byref(d), C.byref(l), *tensors)
+        else:
+            pf = p0 + 4 * len(host)                                                # the floats: weights [S] (when they came as a host list), then decay [B]
+            n_w = S if (wdev is None and wts is not None) else 0
+            w = _lib.LiftWeights(_ptr(wdev) if wdev is not None else (pf if n_w else None), (pf + 4 * n_w) if decay is not None else None,
+                                 float(forget_below), _ptr(wsum) if mode == _LIFT_ACCUM else None)
+            rc = fn(C.byref(d), C.byref(l), C.byref(w), *tensors)
+    check(rc, export)
+    return vol, valid
 
 
 def backproject_sum(feat, proj, new_origin, crop_hw, voxel_size, n_voxels, sampling='nearest'):
@@ -1198,22 +1185,30 @@ def backproject_accum_(feat, proj, new_origin, crop_hw, voxel_size, vol_sum, cou
 def volume_mean(vol_sum, count, dtype=torch.float32, out=None, valid_out=None):
     """Out of place: mean = count ? vol_sum / count : 0 in `dtype` (float32 or bfloat16), valid = count > 0; vol_sum and count stay
     as they are.  out / valid_out: buffers to write into (allocated when None).  Returns (mean, valid bool [B,X,Y,Z])."""
+    return _mean_of_state('ivx_volume_mean_fwd', None, vol_sum, count, 'count', torch.int32, dtype, out, valid_out)
+
+
+def _mean_of_state(export, since, vol_sum, den, den_name, den_dtype, dtype, out, valid_out):
+    """The one body of volume_mean (den: the int32 count) and volume_wmean (den: the fp32 weight sum); since: the library version that brought
+    the export, when an older library may lack it."""
     _chk(vol_sum, 'vol_sum')
-    _chk(count, 'count', torch.int32)
+    _chk(den, den_name, den_dtype)
     if dtype not in _F32_BF16:
         raise TypeError(f'dtype must be float32 or bfloat16, got {dtype}')
-    if tuple(count.shape) != tuple(vol_sum.shape[:-1]):
-        raise ValueError('count must have the spatial shape of the volume')
+    if tuple(den.shape) != tuple(vol_sum.shape[:-1]):
+        raise ValueError(f'{den_name} must have the spatial shape of the volume')
     if out is None:
         out = torch.empty(vol_sum.shape, device=vol_sum.device, dtype=dtype)
     elif tuple(_chk(out, 'out', dtype).shape) != tuple(vol_sum.shape):
         raise ValueError('out must have the shape of vol_sum')
     if valid_out is None:
-        valid_out = torch.empty(count.shape, device=vol_sum.device, dtype=torch.uint8)
+        valid_out = torch.empty(den.shape, device=vol_sum.device, dtype=torch.uint8)
     else:
-        _chk_mask(valid_out, 'valid_out', count.shape)
-    check(_lib.lib().ivx_volume_mean_fwd(_ptr(vol_sum), _ptr(count), count.numel(), vol_sum.shape[-1], _ptr(out), _DT[dtype], _ptr(valid_out),
-                                         _stream()), 'ivx_volume_mean_fwd')
+        _chk_mask(valid_out, 'valid_out', den.shape)
+    fn = getattr(_lib.lib(), export) if since is None else getattr(_lib.lib(), export, None)
+    if fn is None:
+        raise _lib.IvxError(f'this build of libimvoxel_hip.so has no {export} (needs version {since})')
+    check(fn(_ptr(vol_sum), _ptr(den), den.numel(), vol_sum.shape[-1], _ptr(out), _DT[dtype], _ptr(valid_out), _stream()), export)
     return out, valid_out.view(torch.bool)
 
 
@@ -1221,25 +1216,7 @@ def volume_wmean(vol_sum, wsum, dtype=torch.float32, out=None, valid_out=None):
     """volume_mean for a weighted state (ivx_volume_wmean_fwd): mean = wsum > 0 ? vol_sum / wsum : 0 in `dtype` (float32 or bfloat16), valid =
     wsum > 0 -- the mean_out / valid_out of backproject_weighted_accum_ on the same state, bit for bit; vol_sum and wsum stay as they are.
     Returns (mean, valid bool [R,X,Y,Z])."""
-    _chk(vol_sum, 'vol_sum')
-    _chk(wsum, 'wsum')
-    if dtype not in _F32_BF16:
-        raise TypeError(f'dtype must be float32 or bfloat16, got {dtype}')
-    if tuple(wsum.shape) != tuple(vol_sum.shape[:-1]):
-        raise ValueError('wsum must have the spatial shape of the volume')
-    if out is None:
-        out = torch.empty(vol_sum.shape, device=vol_sum.device, dtype=dtype)
-    elif tuple(_chk(out, 'out', dtype).shape) != tuple(vol_sum.shape):
-        raise ValueError('out must have the shape of vol_sum')
-    if valid_out is None:
-        valid_out = torch.empty(wsum.shape, device=vol_sum.device, dtype=torch.uint8)
-    else:
-        _chk_mask(valid_out, 'valid_out', wsum.shape)
-    fn = getattr(_lib.lib(), 'ivx_volume_wmean_fwd', None)
-    if fn is None:
-        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_wmean_fwd (needs version 0.4.8)')
-    check(fn(_ptr(vol_sum), _ptr(wsum), wsum.numel(), vol_sum.shape[-1], _ptr(out), _DT[dtype], _ptr(valid_out), _stream()), 'ivx_volume_wmean_fwd')
-    return out, valid_out.view(torch.bool)
+    return _mean_of_state('ivx_volume_wmean_fwd', '0.4.8', vol_sum, wsum, 'wsum', torch.float32, dtype, out, valid_out)
 
 
 # ------------------------------------------------------------------ detection tail

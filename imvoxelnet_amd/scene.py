@@ -43,9 +43,19 @@ holds, tick by tick, the bits of a plain session.  A windowed scene takes weight
 them): its re-lift is then the weighted mean of the kept views (ops.backproject_weighted_mean_).  `decay` and `window` are alternative ways to
 forget and exclude each other.
 
+How the module is laid out.  Every host rule is written once.  _SceneRecord is the host state of ONE scene (meta, view list, ids, stale flag, image
+size, window, decay, threshold) with the rules that need no device: the checks of meta / window / fading, reset, view_ids, remove_views, which slots
+of a range [base, base + W) a windowed add frees and fills, the id-to-slot lookup, the body of reweight.  The argument checks of an add (images,
+extrinsics, weights, image size), the weight-ring update, the trunk call and the detection tail are module functions.  A SceneSession IS such a
+record plus its own buffers and launches; a SceneBatch HOLDS N records (_scenes) plus its pools and launches.  Only the launches differ between
+the two, for a measured reason (profiles/scene_batch.md: the listed lift at one row is about 20 us slower than the plain one), so they stay in
+the classes, and nothing shared asks which class called it: wording that differs in a noun is passed in.
+
 Out of scope: decay on windowed scenes; per-pixel weight maps; scene batches across ranks; a model-level C handle for sessions (the state lives here, over the
 op-level ABI and the handle's sub-range calls).
 """
+import math
+
 import numpy as np
 import torch
 
@@ -54,16 +64,85 @@ from .boxes import bbox3d2result
 from .heads import Anchor3DHead
 
 
-class SceneSession:
-    """model.open_scene(meta): meta as one entry of simple_test's img_metas without lidar2img['extrinsic'] -- the extrinsics come with
-    the views.  img_shape / ori_shape (/ pad_shape) may be left out when the views come through add_views_u8, which fills them.
-    window=None: the scene only grows (a running (sum, count) volume).  window=W >= 1: the scene holds the last W views at most and
-    remove_views works; state: a feature ring [W,FH,FW,C] in the storage type and a projection ring [W,3,4] (allocated at the first
-    add; W * FH * FW * C * sizeof(element) bytes: the module docstring has the ScanNet figures), the mean / mask buffers and the
-    ordered host list of (view id, slot) -- no (sum, count) volume.
-    decay=lam in (0, 1] (unbounded sessions only): a fading scene -- a weight sum [1,X,Y,Z] fp32 beside (sum, count); every add_views call is one
-    tick: the state is multiplied by lam once, voxels whose weight sum falls below forget_below (>= 0) are forgotten, then the call's views are
-    added with their weights.  Decided here, not lazily: a session opened without decay runs the plain path and refuses weights."""
+# ------------------------------------------------------------------ the argument checks of an add: they need no device and no scene
+def _check_images(img, n):
+    """img [n,3,H,W] float32 (n: the caller's letter for the views of a call, 'V' or 'T') -> (n, H, W)."""
+    if not isinstance(img, torch.Tensor):
+        raise TypeError(f'img must be a torch.Tensor [{n},3,H,W]')
+    if img.dim() != 4 or img.shape[0] < 1 or img.shape[1] != 3:
+        raise ValueError(f'img must be [{n},3,H,W] with {n} >= 1, got {tuple(img.shape)}')
+    if img.dtype != torch.float32:
+        raise TypeError(f'img must be float32, got {img.dtype}')
+    return int(img.shape[0]), int(img.shape[2]), int(img.shape[3])
+
+
+def _check_extrinsics(extrinsics, V):
+    E = [np.asarray(e) for e in extrinsics]
+    if len(E) != V:
+        raise ValueError(f'{len(E)} extrinsics for {V} views')
+    for e in E:
+        if e.dtype != np.float32:
+            raise TypeError(f'extrinsics must be float32 (as the reference datasets produce), got {e.dtype}')
+        if e.shape != (4, 4):
+            raise ValueError(f'every extrinsic must be 4x4, got {e.shape}')
+    return E
+
+
+def _check_weights(weights, V):
+    """weights: None or V finite floats >= 0 -> list of float."""
+    if weights is None:
+        return None
+    if isinstance(weights, torch.Tensor):
+        weights = weights.tolist()
+    w = [float(x) for x in (np.asarray(weights, np.float64).reshape(-1).tolist())]
+    if len(w) != V:
+        raise ValueError(f'{len(w)} weights for {V} views')
+    if any(not (math.isfinite(x) and x >= 0) for x in w):
+        raise ValueError(f'weights must be finite and >= 0, got {w}')
+    return w
+
+
+def _check_size(hw, have, where):
+    """The image size of a call against the one of the views already in `where` ('scene' / 'batch'; have None: there are none)."""
+    if have is not None and hw != have:
+        raise ValueError(f'image size {hw} differs from the {have} of the views already in the {where}')
+
+
+def _ring_weights(wring, size, slots, weights):
+    """The host weight ring after a windowed add that put its views into `slots`: the ring (None until then, and the re-lift unweighted) starts
+    with the first weight given; from then on a reused slot takes its new view's weight (1 when the call gives none)."""
+    if weights is not None and wring is None:
+        wring = [1.0] * size
+    if wring is not None:
+        for i, s in enumerate(slots):
+            wring[s] = weights[i] if weights is not None else 1.0
+    return wring
+
+
+# ------------------------------------------------------------------ the two model calls around the lift
+def _trunk(m, img):
+    """[V,3,H,W] -> FPN level 0 of these views.  The native handle's trunk sub-range is the same kernels with the same plans as
+    features_2d_cl in one C call (equal bit for bit: tests/test_gpu_engine.py)."""
+    nat = m._native
+    if nat is not None and nat.cfg.with_trunk and img.shape[-2] % 32 == 0 and img.shape[-1] % 32 == 0:
+        return nat.backbone_fpn(img)
+    return m.features_2d_cl(img[None])
+
+
+def _detect(m, vol, valid, metas):
+    """The model's detection stage on mean rows vol [B,X,Y,Z,C] / valid bool [B,X,Y,Z]: one result dict per meta."""
+    if isinstance(m.bbox_head, Anchor3DHead):
+        boxes, scores, labels, count = m.detect_cl(vol, metas)
+        return m._results_one_copy(boxes, scores, labels, count, metas)
+    return [bbox3d2result(b, s, l) for b, s, l in m.detect_indoor_cl(vol, valid, metas)]
+
+
+# ------------------------------------------------------------------ one scene on the host
+class _SceneRecord:
+    """The host state of one scene and every rule that needs no device.  meta: a complete simple_test meta of everything added; n_views;
+    _views: the views of a windowed scene, oldest first, as (id, slot, extrinsic); _next_id: the id of the next arrival; _stale: the mean is
+    behind the state; _hw: the image size of the views in the scene; _window, _decay, _forget as opened.  No device buffers: a SceneSession
+    adds its own, a SceneBatch keeps pools beside N of these."""
 
     def __init__(self, model, meta, window=None, decay=None, forget_below=0.0):
         decay, forget_below = self._check_fading(window, decay, forget_below)
@@ -88,18 +167,13 @@ class SceneSession:
             raise ValueError(f'lidar2img intrinsic must be at least 3x3, got {K.shape}')
         l2i['extrinsic'] = []                     # grows with the views: `meta` stays a complete simple_test meta of everything added
         meta['lidar2img'] = l2i
-        self._model, self.meta = model, meta
-        self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
-        self._hw, self._stale, self._closed, self.n_views = None, False, False, 0
-        # window=W: the rings, the views in the scene, oldest first, as (id, slot, extrinsic), and the id of the next arrival
-        self._window, self._ring, self._pring, self._views, self._next_id = window, None, None, [], 0
-        # decay=lam: the weighted running mean (a weight sum beside sum / count).  window=W: the host ring of the slots' weights, None until a weight is given
-        self._decay, self._forget, self._wsum, self._wring = decay, forget_below, None, None
+        self.meta, self.n_views, self._hw, self._stale = meta, 0, None, False
+        self._window, self._views, self._next_id = window, [], 0
+        self._decay, self._forget = decay, forget_below
 
     @staticmethod
     def _check_fading(window, decay, forget_below):
         """(decay, forget_below) as floats (decay None: a plain session); the rules that need no model."""
-        import math
         if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float, np.integer, np.floating)):
             raise TypeError(f'forget_below must be a number >= 0, got {forget_below!r}')
         forget_below = float(forget_below)
@@ -118,20 +192,119 @@ class SceneSession:
             raise ValueError(f'decay must be in (0, 1], got {decay}')
         return decay, forget_below
 
-    @staticmethod
-    def _check_weights(weights, V):
-        """weights: None or V finite floats >= 0 -> list of float."""
-        import math
-        if weights is None:
-            return None
-        if isinstance(weights, torch.Tensor):
-            weights = weights.tolist()
-        w = [float(x) for x in (np.asarray(weights, np.float64).reshape(-1).tolist())]
-        if len(w) != V:
-            raise ValueError(f'{len(w)} weights for {V} views')
-        if any(not (math.isfinite(x) and x >= 0) for x in w):
-            raise ValueError(f'weights must be finite and >= 0, got {w}')
-        return w
+    def reset(self):
+        """Forget every view."""
+        self.meta['lidar2img']['extrinsic'] = []
+        self.n_views, self._hw, self._stale = 0, None, False
+        self._views, self._next_id = [], 0
+
+    @property
+    def view_ids(self):
+        """The ids of the views in the scene, oldest first.  An id is the view's arrival ordinal since reset()."""
+        if self._window is None:
+            return list(range(self.n_views))
+        return [v[0] for v in self._views]
+
+    # ---- what a call may ask of this scene (each raises before anything changes)
+    def _check_fits(self, V, of=''):
+        """V views `of` this scene (' of scene 2'; '': the caller has one scene) in one call fit its window."""
+        if self._window is not None and V > self._window:
+            raise ValueError(f'{V} views{of} in one call do not fit a window of {self._window}')
+
+    def _take_weights(self, weights, V, what):
+        """_check_weights, and the refusal of a scene opened plain (what: 'session' / 'batch', as the caller was opened)."""
+        weights = _check_weights(weights, V)
+        if weights is not None and self._window is None and self._decay is None:
+            raise ValueError(f'this {what} was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
+        return weights
+
+    def _check_shapes(self, shapes, have_views, where):
+        """The img_shape / ori_shape / pad_shape of new frames (add_views_u8) against this meta's, once `where` ('scene' / 'batch') has views."""
+        for k, v in shapes.items():
+            if have_views and k in self.meta and tuple(self.meta[k]) != tuple(v):
+                raise ValueError(f'{k} {tuple(v)} of these frames differs from the {tuple(self.meta[k])} of the views already in the {where}')
+
+    def _slot_of(self, ids, where='the scene'):
+        """{id: slot} of the views in a windowed scene; an id of `ids` that is not among them raises KeyError."""
+        slot_of = {v[0]: v[1] for v in self._views}
+        unknown = [i for i in ids if i not in slot_of]
+        if unknown:
+            raise KeyError(f'no view with id {unknown} in {where} (view_ids: {sorted(slot_of)})')
+        return slot_of
+
+    # ---- adding and removing views
+    def _free_slots(self, V, base=0):
+        """The slot rule of a windowed add of V views into the slots [base, base + W): (kept, slots) -- the newest W - V views stay, the
+        leavers' slots are free for this call's views, and the free slots are handed out in order.  Changes nothing."""
+        W = self._window
+        kept = self._views[max(0, len(self._views) + V - W):]
+        used = {v[1] for v in kept}
+        return kept, [s for s in range(base, base + W) if s not in used][:V]
+
+    def _admit(self, kept, slots, E, hw):
+        """A windowed add is in: the views with extrinsics E sit in `slots` behind `kept` (_free_slots)."""
+        self._views = kept + [(self._next_id + i, s, e) for i, (s, e) in enumerate(zip(slots, E))]
+        self._next_id += len(E)
+        self._hw, self._stale = hw, True
+        self.meta['lidar2img']['extrinsic'] = [v[2] for v in self._views]
+        self.n_views = len(self._views)
+
+    def _grow(self, E, hw, stale):
+        """An unbounded add is in: the views with extrinsics E count behind those in the scene; stale: the call stored no mean."""
+        self._hw, self._stale = hw, stale
+        self.meta['lidar2img']['extrinsic'] = self.meta['lidar2img']['extrinsic'] + E
+        self.n_views += len(E)
+
+    def remove_views(self, ids):
+        """Drop the views with these ids (view_ids) from a windowed scene and free their slots; an unknown id raises KeyError and
+        leaves the scene as it was."""
+        if self._window is None:
+            raise RuntimeError('remove_views needs a windowed session: open_scene(meta, window=W)')
+        ids = [ids] if isinstance(ids, (int, np.integer)) else list(ids)
+        self._slot_of(ids)
+        drop = set(ids)
+        if drop:
+            self._views = [v for v in self._views if v[0] not in drop]
+            self.meta['lidar2img']['extrinsic'] = [v[2] for v in self._views]
+            self.n_views, self._stale = len(self._views), True
+        return self
+
+    def _reweight(self, ids, weights, wring, n_scenes, windowed, where):
+        """The body of reweight on the caller's host weight ring (None: not started; n_scenes * W slots): the ring with the weights of these
+        views changed, and the scene stale.  windowed / where: the caller's words for what it needs and where the ids were looked for."""
+        if self._window is None:
+            raise RuntimeError(f'reweight needs a windowed {windowed}')
+        scalar = isinstance(ids, (int, np.integer))
+        ids = [ids] if scalar else list(ids)
+        weights = _check_weights([weights] if scalar and not hasattr(weights, '__len__') else weights, len(ids))
+        slot_of = self._slot_of(ids, where)
+        if ids:
+            if wring is None:
+                wring = [1.0] * (n_scenes * self._window)
+            for i, w in zip(ids, weights):
+                wring[slot_of[i]] = w
+            self._stale = True
+        return wring
+
+
+class SceneSession(_SceneRecord):
+    """model.open_scene(meta): meta as one entry of simple_test's img_metas without lidar2img['extrinsic'] -- the extrinsics come with
+    the views.  img_shape / ori_shape (/ pad_shape) may be left out when the views come through add_views_u8, which fills them.
+    window=None: the scene only grows (a running (sum, count) volume).  window=W >= 1: the scene holds the last W views at most and
+    remove_views works; state: a feature ring [W,FH,FW,C] in the storage type and a projection ring [W,3,4] (allocated at the first
+    add; W * FH * FW * C * sizeof(element) bytes: the module docstring has the ScanNet figures), the mean / mask buffers and the
+    ordered host list of (view id, slot) -- no (sum, count) volume.
+    decay=lam in (0, 1] (unbounded sessions only): a fading scene -- a weight sum [1,X,Y,Z] fp32 beside (sum, count); every add_views call is one
+    tick: the state is multiplied by lam once, voxels whose weight sum falls below forget_below (>= 0) are forgotten, then the call's views are
+    added with their weights.  Decided here, not lazily: a session opened without decay runs the plain path and refuses weights.
+    The session is a _SceneRecord (the host state and its rules) with its own device buffers, camera uploads and launches."""
+
+    def __init__(self, model, meta, window=None, decay=None, forget_below=0.0):
+        super().__init__(model, meta, window, decay, forget_below)
+        self._model, self._closed = model, False
+        self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
+        # window=W: the rings, and the host ring of the slots' weights, None until a weight is given.  decay=lam: a weight sum beside sum / count
+        self._ring = self._pring = self._wring = self._wsum = None
 
     # ------------------------------------------------------------------ state
     def _check_open(self):
@@ -141,43 +314,17 @@ class SceneSession:
     def reset(self):
         """Forget every view; the buffers are kept and the next add starts them from zero."""
         self._check_open()
-        self.meta['lidar2img']['extrinsic'] = []
-        self._hw, self._origin, self._crop, self._stale, self.n_views = None, None, None, False, 0
-        self._views, self._next_id, self._wring = [], 0, None
+        super().reset()
+        self._origin = self._crop = self._wring = None
 
     def close(self):
         self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
         self._ring = self._pring = self._wsum = self._wring = None
         self._closed = True
 
-    @property
-    def view_ids(self):
-        """The ids of the views in the scene, oldest first.  An id is the view's arrival ordinal since reset()."""
-        if self._window is None:
-            return list(range(self.n_views))
-        return [v[0] for v in self._views]
-
     # ------------------------------------------------------------------ adding views
     def _features(self, img):
-        """[V,3,H,W] -> FPN level 0 of these views.  The native handle's trunk sub-range is the same kernels with the same plans as
-        features_2d_cl in one C call (equal bit for bit: tests/test_gpu_engine.py)."""
-        m = self._model
-        nat = m._native
-        if nat is not None and nat.cfg.with_trunk and img.shape[-2] % 32 == 0 and img.shape[-1] % 32 == 0:
-            return nat.backbone_fpn(img)
-        return m.features_2d_cl(img[None])
-
-    @staticmethod
-    def _check_extrinsics(extrinsics, V):
-        E = [np.asarray(e) for e in extrinsics]
-        if len(E) != V:
-            raise ValueError(f'{len(E)} extrinsics for {V} views')
-        for e in E:
-            if e.dtype != np.float32:
-                raise TypeError(f'extrinsics must be float32 (as the reference datasets produce), got {e.dtype}')
-            if e.shape != (4, 4):
-                raise ValueError(f'every extrinsic must be 4x4, got {e.shape}')
-        return E
+        return _trunk(self._model, img)
 
     def add_views(self, img, extrinsics, emit=True, weights=None):
         """img [V,3,H,W] float32 on the device (normalised and padded as for simple_test), extrinsics: V float32 4x4 matrices.
@@ -193,21 +340,11 @@ class SceneSession:
         """add_views with the img_shape / ori_shape / pad_shape of these views (add_views_u8); the session changes only when the
         views are in: a call that raises leaves meta, state and n_views as they were."""
         self._check_open()
-        if not isinstance(img, torch.Tensor):
-            raise TypeError('img must be a torch.Tensor [V,3,H,W]')
-        if img.dim() != 4 or img.shape[0] < 1 or img.shape[1] != 3:
-            raise ValueError(f'img must be [V,3,H,W] with V >= 1, got {tuple(img.shape)}')
-        if img.dtype != torch.float32:
-            raise TypeError(f'img must be float32, got {img.dtype}')
-        V, H, W = int(img.shape[0]), int(img.shape[2]), int(img.shape[3])
-        E = self._check_extrinsics(extrinsics, V)
-        if self._window is not None and V > self._window:
-            raise ValueError(f'{V} views in one call do not fit a window of {self._window}')
-        weights = self._check_weights(weights, V)
-        if weights is not None and self._window is None and self._decay is None:
-            raise ValueError('this session was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
-        if self._hw is not None and (H, W) != self._hw:
-            raise ValueError(f'image size {(H, W)} differs from the {self._hw} of the views already in the scene')
+        V, H, W = _check_images(img, 'V')
+        E = _check_extrinsics(extrinsics, V)
+        self._check_fits(V)
+        weights = self._take_weights(weights, V, 'session')
+        _check_size((H, W), self._hw, 'scene')
         meta = dict(self.meta, **shapes)
         if 'img_shape' not in meta or 'ori_shape' not in meta:
             raise ValueError('the scene meta needs img_shape and ori_shape (add_views_u8 fills them from its frames)')
@@ -223,7 +360,17 @@ class SceneSession:
         else:
             proj, origin, crop = m._compute_projection(view_meta, 4)[None].contiguous().to(p0.device), self._origin, self._crop
         if self._window is not None:
-            return self._add_windowed(p0, proj, origin, crop, E, (H, W), shapes, weights)
+            self._add_windowed(p0, proj, E, (H, W), weights)
+        else:
+            self._add_unbounded(p0, proj, origin, crop, E, (H, W), weights, emit)
+        self._origin, self._crop = origin, crop
+        self.meta.update(shapes)
+        return self
+
+    def _add_unbounded(self, p0, proj, origin, crop, E, hw, weights, emit):
+        """The new views' maps p0 [V,1,FH,FW,C] added to the running (sum, count) state in one launch: the plain lift, or one tick of the
+        weighted one on a fading session."""
+        m = self._model
         if self._sum is None:                     # the state, allocated once: sum fp32, count, mean in the storage type, valid
             X, Y, Z = m.n_voxels
             Cn, dev = p0.shape[-1], p0.device
@@ -233,24 +380,18 @@ class SceneSession:
             self._valid = torch.empty((1, X, Y, Z), device=dev, dtype=torch.uint8)
             self._wsum = torch.empty((1, X, Y, Z), device=dev, dtype=torch.float32) if self._decay is not None else None
         if self._decay is not None:                # one tick: fade once, then this call's views with their weights (the call's maps are the pool)
-            ops.backproject_weighted_accum_(p0, proj[0], [list(range(V))], weights, [0], [self.n_views == 0], [self._decay], origin, crop, m.voxel_size,
+            ops.backproject_weighted_accum_(p0, proj[0], [list(range(len(E)))], weights, [0], [self.n_views == 0], [self._decay], origin, crop, m.voxel_size,
                                             self._sum, self._wsum, self._count, self._mean if emit else None, self._valid if emit else None,
                                             forget_below=self._forget, sampling=getattr(m, 'sampling', 'nearest'))
         else:
             ops.backproject_accum_(p0, proj, origin, crop, m.voxel_size, self._sum, self._count, self.n_views == 0,
                                    self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
-        self._origin, self._crop = origin, crop
-        self._stale = not emit
-        self._hw = (H, W)
-        self.meta.update(shapes)
-        self.meta['lidar2img']['extrinsic'] = self.meta['lidar2img']['extrinsic'] + E
-        self.n_views += V
-        return self
+        self._grow(E, hw, stale=not emit)
 
-    def _add_windowed(self, p0, proj, origin, crop, E, hw, shapes, weights=None):
+    def _add_windowed(self, p0, proj, E, hw, weights):
         """The new views' maps p0 [V,1,FH,FW,C] and projection rows proj [1,V,3,4] into free slots of the rings; the oldest views
         leave first when the window is full.  Everything that can fail comes before the first change of the session."""
-        m, W, V = self._model, self._window, len(E)
+        m, W = self._model, self._window
         X, Y, Z = m.n_voxels
         Cn, dev = p0.shape[-1], p0.device
         ring, pring, mean, valid = self._ring, self._pring, self._mean, self._valid
@@ -259,64 +400,26 @@ class SceneSession:
             pring = torch.empty((W, 3, 4), device=dev, dtype=torch.float32)
             mean = torch.empty((1, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
             valid = torch.empty((1, X, Y, Z), device=dev, dtype=torch.uint8)
-        kept = self._views[max(0, len(self._views) + V - W):]
-        used = {v[1] for v in kept}
-        slots = [s for s in range(W) if s not in used][:V]     # the slots of the views that leave are free for this call's views
+        kept, slots = self._free_slots(len(E))
         for i, s in enumerate(slots):
             ring[s].copy_(p0[i])
             pring[s].copy_(proj[0, i])
-        if weights is not None and self._wring is None:
-            self._wring = [1.0] * W                # the weight ring starts with the first weight given; until then the scene runs the unweighted re-lift
-        if self._wring is not None:                # a reused slot takes its new view's weight (1 when none is given)
-            for i, s in enumerate(slots):
-                self._wring[s] = weights[i] if weights is not None else 1.0
+        self._wring = _ring_weights(self._wring, W, slots, weights)
         self._ring, self._pring, self._mean, self._valid = ring, pring, mean, valid
-        self._views = kept + [(self._next_id + i, slots[i], E[i]) for i in range(V)]
-        self._next_id += V
-        self._origin, self._crop, self._hw, self._stale = origin, crop, hw, True
-        self.meta.update(shapes)
-        self.meta['lidar2img']['extrinsic'] = [v[2] for v in self._views]
-        self.n_views = len(self._views)
-        return self
+        self._admit(kept, slots, E, hw)
 
     def remove_views(self, ids):
         """Drop the views with these ids (view_ids) from a windowed scene and free their slots; an unknown id raises KeyError and
         leaves the scene as it was."""
         self._check_open()
-        if self._window is None:
-            raise RuntimeError('remove_views needs a windowed session: open_scene(meta, window=W)')
-        ids = [ids] if isinstance(ids, (int, np.integer)) else list(ids)
-        have = {v[0] for v in self._views}
-        unknown = [i for i in ids if i not in have]
-        if unknown:
-            raise KeyError(f'no view with id {unknown} in the scene (view_ids: {sorted(have)})')
-        drop = set(ids)
-        if drop:
-            self._views = [v for v in self._views if v[0] not in drop]
-            self.meta['lidar2img']['extrinsic'] = [v[2] for v in self._views]
-            self.n_views, self._stale = len(self._views), True
-        return self
+        return super().remove_views(ids)
 
     def reweight(self, ids, weights):
         """Change the weights of views that are in a windowed scene (ids: view_ids; one finite float >= 0 per id; 0 takes the view out of the
         mean without freeing its slot) and mark the scene stale: the next volume() / detect() lifts the kept views again with the new weights.
         An unknown id raises KeyError and leaves the scene as it was."""
         self._check_open()
-        if self._window is None:
-            raise RuntimeError('reweight needs a windowed session: open_scene(meta, window=W)')
-        scalar = isinstance(ids, (int, np.integer))
-        ids = [ids] if scalar else list(ids)
-        weights = self._check_weights([weights] if scalar and not hasattr(weights, '__len__') else weights, len(ids))
-        slot_of = {v[0]: v[1] for v in self._views}
-        unknown = [i for i in ids if i not in slot_of]
-        if unknown:
-            raise KeyError(f'no view with id {unknown} in the scene (view_ids: {sorted(slot_of)})')
-        if ids:
-            if self._wring is None:
-                self._wring = [1.0] * self._window
-            for i, w in zip(ids, weights):
-                self._wring[slot_of[i]] = w
-            self._stale = True
+        self._wring = self._reweight(ids, weights, self._wring, 1, 'session: open_scene(meta, window=W)', 'the scene')
         return self
 
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, **pipeline_kw):
@@ -326,16 +429,11 @@ class SceneSession:
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
-        E = self._check_extrinsics(extrinsics, len(frames))
-        if self._window is not None and len(frames) > self._window:
-            raise ValueError(f'{len(frames)} views in one call do not fit a window of {self._window}')
-        weights = self._check_weights(weights, len(frames))
-        if weights is not None and self._window is None and self._decay is None:
-            raise ValueError('this session was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
+        E = _check_extrinsics(extrinsics, len(frames))
+        self._check_fits(len(frames))
+        weights = self._take_weights(weights, len(frames), 'session')
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)       # one multi-view sample
-        for k, v in shapes[0].items():
-            if self.n_views and k in self.meta and tuple(self.meta[k]) != tuple(v):
-                raise ValueError(f'{k} {tuple(v)} of these frames differs from the {tuple(self.meta[k])} of the views already in the scene')
+        self._check_shapes(shapes[0], self.n_views, 'scene')
         return self._add_views(img[0], E, emit, shapes[0], weights)
 
     # ------------------------------------------------------------------ reading the scene
@@ -345,31 +443,30 @@ class SceneSession:
         self._check_open()
         if self.n_views == 0:
             raise RuntimeError('the scene has no views yet')
-        if self._stale and self._window is not None and self._wring is not None:      # the same lift with the weight ring: the weighted mean of the kept views
-            ops.backproject_weighted_mean_(self._ring, self._pring, [[v[1] for v in self._views]], self._wring, [0], self._origin, self._crop,
-                                           self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
-            self._stale = False
-        if self._stale and self._window is not None:      # the set changed since the last lift: ONE gathered lift of the views in it, in order
-            view_slot = torch.tensor([[v[1] for v in self._views]], dtype=torch.int32).to(self._ring.device)
-            ops.backproject_gather_mean_(self._ring, self._pring, view_slot, self._origin, self._crop, self._model.voxel_size, self._mean, self._valid,
-                                         getattr(self._model, 'sampling', 'nearest'))
-            self._stale = False
-        if self._stale and self._decay is not None:       # (emit=False adds on a fading session: the mean of (sum, weight sum))
-            ops.volume_wmean(self._sum, self._wsum, self._mean.dtype, out=self._mean, valid_out=self._valid)
-            self._stale = False
         if self._stale:
-            ops.volume_mean(self._sum, self._count, self._mean.dtype, out=self._mean, valid_out=self._valid)
+            self._refresh()
             self._stale = False
         return self._mean, self._valid.view(torch.bool)
+
+    def _refresh(self):
+        """Bring the mean / valid buffers up to date with the state, in one launch."""
+        m = self._model
+        if self._window is not None and self._wring is not None:      # the same lift with the weight ring: the weighted mean of the kept views
+            ops.backproject_weighted_mean_(self._ring, self._pring, [[v[1] for v in self._views]], self._wring, [0], self._origin, self._crop,
+                                           m.voxel_size, self._mean, self._valid, sampling=getattr(m, 'sampling', 'nearest'))
+        elif self._window is not None:                                # the set changed since the last lift: ONE gathered lift of the views in it, in order
+            view_slot = torch.tensor([[v[1] for v in self._views]], dtype=torch.int32).to(self._ring.device)
+            ops.backproject_gather_mean_(self._ring, self._pring, view_slot, self._origin, self._crop, m.voxel_size, self._mean, self._valid,
+                                         getattr(m, 'sampling', 'nearest'))
+        elif self._decay is not None:                                 # (emit=False adds on a fading session: the mean of (sum, weight sum))
+            ops.volume_wmean(self._sum, self._wsum, self._mean.dtype, out=self._mean, valid_out=self._valid)
+        else:
+            ops.volume_mean(self._sum, self._count, self._mean.dtype, out=self._mean, valid_out=self._valid)
 
     def detect(self):
         """Detections from the views so far: [dict(boxes_3d, scores_3d, labels_3d)] as simple_test returns for one sample."""
         vol, valid = self.volume()
-        m, metas = self._model, [self.meta]
-        if isinstance(m.bbox_head, Anchor3DHead):
-            boxes, scores, labels, count = m.detect_cl(vol, metas)
-            return m._results_one_copy(boxes, scores, labels, count, metas)
-        return [bbox3d2result(b, s, l) for b, s, l in m.detect_indoor_cl(vol, valid, metas)]
+        return _detect(self._model, vol, valid, [self.meta])
 
 
 class SceneBatch:
@@ -383,7 +480,8 @@ class SceneBatch:
     [N,X,Y,Z] -- per scene X*Y*Z * (C * (4 + sizeof(element)) + 5) bytes (the module docstring has the ScanNet figures).  window=W keeps
     no sums: a feature ring [N*W,1,FH,FW,C] (scene s owns slots s*W .. s*W+W-1) and a projection ring [N*W,3,4], per-scene ordered
     (id, slot, extrinsic) lists with FIFO eviction per scene, and the mean / valid pools; the scenes whose set changed are lifted again, all
-    in one launch (ops.backproject_lists_mean_), when volume() / detect() asks.
+    in one launch (ops.backproject_lists_mean_), when volume() / detect() asks.  The host state of scene s is the _SceneRecord _scenes[s]:
+    the rules of a scene are the record's, the pools, the packed camera upload and the launches are the batch's.
 
     What is exact and what is not.
       Volume.   Row s of the batch's volume is bit for bit ONE ops.backproject_mean over the features the trunk produced for scene s's
@@ -402,8 +500,6 @@ class SceneBatch:
     state does not age.  A caller who wants wall-clock fading gives every scene a view (or a zero-weight view) per tick.  A windowed batch takes
     weights and reweight(scene, ids, weights); its re-lift is then the weighted mean of the kept views (a host weight ring [N*W])."""
 
-    _features = SceneSession._features
-
     def __init__(self, model, metas, window=None, decay=None, forget_below=0.0):
         metas = list(metas)
         if not metas:
@@ -413,8 +509,7 @@ class SceneBatch:
             raise ValueError(f'{len(decays)} decays for {len(metas)} scenes (one value for all, or one per scene)')
         if any(d is None for d in decays) and any(d is not None for d in decays):
             raise ValueError('decay must be given for every scene of a batch or for none')
-        # checks every meta, window, decay and head_2d; used as records only
-        self._scenes = [SceneSession(model, meta, window=window, decay=d, forget_below=forget_below) for meta, d in zip(metas, decays)]
+        self._scenes = [_SceneRecord(model, meta, window, d, forget_below) for meta, d in zip(metas, decays)]      # checks every meta, window, decay and head_2d
         self._fading, self._forget, self._wsum, self._wring = decays[0] is not None, self._scenes[0]._forget, None, None
         self._model, self._window, self._N = model, self._scenes[0]._window, len(metas)
         self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
@@ -461,8 +556,6 @@ class SceneBatch:
 
     def close(self):
         self._sum = self._count = self._mean = self._valid = self._ring = self._pring = self._wsum = self._wring = None
-        for r in self._scenes:
-            r.close()
         self._closed = True
 
     def remove_views(self, scene, ids):
@@ -475,26 +568,14 @@ class SceneBatch:
         """Change the weights of kept views of one scene of a windowed batch (SceneSession.reweight); an unknown id raises KeyError and
         changes nothing."""
         self._check_open()
-        s = self._scene_index(scene)
-        r = self._scenes[s]
-        if self._window is None:
-            raise RuntimeError('reweight needs a windowed batch: open_scenes(metas, window=W)')
-        scalar = isinstance(ids, (int, np.integer))
-        ids = [ids] if scalar else list(ids)
-        weights = SceneSession._check_weights([weights] if scalar and not hasattr(weights, '__len__') else weights, len(ids))
-        slot_of = {v[0]: v[1] for v in r._views}      # the batch's slots: scene s owns s*W .. s*W+W-1
-        unknown = [i for i in ids if i not in slot_of]
-        if unknown:
-            raise KeyError(f'no view with id {unknown} in scene {s} (view_ids: {sorted(slot_of)})')
-        if ids:
-            if self._wring is None:
-                self._wring = [1.0] * (self._N * self._window)
-            for i, w in zip(ids, weights):
-                self._wring[slot_of[i]] = w
-            r._stale = True
+        s = self._scene_index(scene)              # (the record's slots are the batch's: scene s owns s*W .. s*W+W-1)
+        self._wring = self._scenes[s]._reweight(ids, weights, self._wring, self._N, 'batch: open_scenes(metas, window=W)', f'scene {s}')
         return self
 
     # ------------------------------------------------------------------ adding views
+    def _features(self, img):
+        return _trunk(self._model, img)
+
     def add_views(self, img, extrinsics, scene, emit=True, weights=None):
         """img [T,3,H,W] float32 on the device, extrinsics: T float32 4x4 matrices, scene: T scene indices -- view t belongs to scene
         scene[t]; the views of one scene count in the order given.  emit=False skips the store of the means (computed when asked).
@@ -502,26 +583,18 @@ class SceneBatch:
         weights: one finite float >= 0 per view, on a batch opened with decay= or window=.  Fading batch: one tick for the touched scenes only."""
         return self._add_views(img, extrinsics, scene, emit, {}, weights=weights)
 
-    def _check_weights(self, weights, T):
-        weights = SceneSession._check_weights(weights, T)
-        if weights is not None and self._window is None and not self._fading:
-            raise ValueError('this batch was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
-        return weights
-
     def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, **pipeline_kw):
         """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
         ori_shape / pad_shape of every scene's meta, which later frames must reproduce."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
-        E = SceneSession._check_extrinsics(extrinsics, len(frames))
+        E = _check_extrinsics(extrinsics, len(frames))
         groups = self._groups(scene, len(frames))
-        weights = self._check_weights(weights, len(frames))
+        weights = self._scenes[0]._take_weights(weights, len(frames), 'batch')
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
         for r in self._scenes:
-            for k, v in shapes[0].items():
-                if any(self.n_views) and k in r.meta and tuple(r.meta[k]) != tuple(v):
-                    raise ValueError(f'{k} {tuple(v)} of these frames differs from the {tuple(r.meta[k])} of the views already in the batch')
+            r._check_shapes(shapes[0], any(self.n_views), 'batch')
         return self._add_views(img[0], E, scene, emit, shapes[0], groups, weights)
 
     def _groups(self, scene, T):
@@ -531,27 +604,18 @@ class SceneBatch:
         groups = {}
         for t, s in enumerate(scene):
             groups.setdefault(self._scene_index(s), []).append(t)
-        if self._window is not None:
-            for s, ts in groups.items():
-                if len(ts) > self._window:
-                    raise ValueError(f'{len(ts)} views of scene {s} in one call do not fit a window of {self._window}')
+        for s, ts in groups.items():
+            self._scenes[s]._check_fits(len(ts), f' of scene {s}')
         return groups
 
     def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None, weights=None):
         self._check_open()
-        if not isinstance(img, torch.Tensor):
-            raise TypeError('img must be a torch.Tensor [T,3,H,W]')
-        if img.dim() != 4 or img.shape[0] < 1 or img.shape[1] != 3:
-            raise ValueError(f'img must be [T,3,H,W] with T >= 1, got {tuple(img.shape)}')
-        if img.dtype != torch.float32:
-            raise TypeError(f'img must be float32, got {img.dtype}')
-        T, H, W = int(img.shape[0]), int(img.shape[2]), int(img.shape[3])
-        E = SceneSession._check_extrinsics(extrinsics, T)
+        T, H, W = _check_images(img, 'T')
+        E = _check_extrinsics(extrinsics, T)
         if groups is None:
             groups = self._groups(scene, T)
-        weights = self._check_weights(weights, T)
-        if self._hw is not None and (H, W) != self._hw:
-            raise ValueError(f'image size {(H, W)} differs from the {self._hw} of the views already in the batch')
+        weights = self._scenes[0]._take_weights(weights, T, 'batch')      # (the scenes of a batch are opened alike)
+        _check_size((H, W), self._hw, 'batch')
         touched = sorted(groups)
         for s in touched:
             meta = dict(self._scenes[s].meta, **shapes)
@@ -563,7 +627,6 @@ class SceneBatch:
         if m._prepared_device is None:
             m.prepare(img.device)
         p0 = self._features(img.contiguous())                      # ONE trunk call over the T views of this tick
-        dev = p0.device
         # host camera set-up: one _compute_projection per touched scene; rows of proj in the order of the T views
         cpu = torch.device('cpu')
         proj_h, cam = torch.empty((T, 3, 4), dtype=torch.float32), {}
@@ -576,35 +639,13 @@ class SceneBatch:
             proj_h[torch.tensor(ts)] = p[0]
             cam[s] = (origin[0], crop[0])
         if self._window is not None:
-            return self._add_windowed(p0, proj_h, groups, touched, cam, E, (H, W), shapes, weights)
-        proj, origin, crop = self._upload(dev, proj_h, [cam[s] for s in touched])
-        X, Y, Z = m.n_voxels
-        Cn = p0.shape[-1]
-        if self._sum is None or self._sum.shape[-1] != Cn or self._mean.dtype != p0.dtype:     # the state pools, allocated once
-            N = self._N
-            self._sum = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=torch.float32)
-            self._count = torch.empty((N, X, Y, Z), device=dev, dtype=torch.int32)
-            self._mean = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
-            self._valid = torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8)
-            self._wsum = torch.empty((N, X, Y, Z), device=dev, dtype=torch.float32) if self._fading else None
-        if self._fading:                          # one tick of the touched scenes: each fades by its own decay, the others are not read
-            ops.backproject_weighted_accum_(p0, proj, [groups[s] for s in touched], weights, touched, [self._scenes[s].n_views == 0 for s in touched],
-                                            [self._scenes[s]._decay for s in touched], origin, crop, m.voxel_size, self._sum, self._wsum, self._count,
-                                            self._mean if emit else None, self._valid if emit else None, forget_below=self._forget,
-                                            sampling=getattr(m, 'sampling', 'nearest'))
+            self._add_windowed(p0, proj_h, groups, touched, E, (H, W), weights)
         else:
-            ops.backproject_lists_accum_(p0, proj, [groups[s] for s in touched], touched, [self._scenes[s].n_views == 0 for s in touched], origin, crop,
-                                         m.voxel_size, self._sum, self._count, self._mean if emit else None, self._valid if emit else None,
-                                         sampling=getattr(m, 'sampling', 'nearest'))
+            self._add_unbounded(p0, proj_h, groups, touched, cam, E, (H, W), weights, emit)
         self._hw = (H, W)
         for r in self._scenes:
             r.meta.update(shapes)
         for s in touched:
-            r = self._scenes[s]
-            r._stale = not emit
-            r._hw = (H, W)
-            r.meta['lidar2img']['extrinsic'] = r.meta['lidar2img']['extrinsic'] + [E[t] for t in groups[s]]
-            r.n_views += len(groups[s])
             self._cam[s] = cam[s]
         return self
 
@@ -620,7 +661,32 @@ class SceneBatch:
         crop = buf[T * 12 + B * 3:].view(torch.int32).view(B, 2)
         return proj, origin, crop
 
-    def _add_windowed(self, p0, proj_h, groups, touched, cam, E, hw, shapes, weights=None):
+    def _add_unbounded(self, p0, proj_h, groups, touched, cam, E, hw, weights, emit):
+        """The new maps p0 [T,1,FH,FW,C] added to the rows of the touched scenes in ONE listed launch (the call's maps are the pool): the plain
+        listed lift, or one tick of the weighted one on a fading batch."""
+        m, dev = self._model, p0.device
+        proj, origin, crop = self._upload(dev, proj_h, [cam[s] for s in touched])
+        X, Y, Z = m.n_voxels
+        Cn = p0.shape[-1]
+        if self._sum is None or self._sum.shape[-1] != Cn or self._mean.dtype != p0.dtype:     # the state pools, allocated once
+            N = self._N
+            self._sum = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=torch.float32)
+            self._count = torch.empty((N, X, Y, Z), device=dev, dtype=torch.int32)
+            self._mean = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
+            self._valid = torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8)
+            self._wsum = torch.empty((N, X, Y, Z), device=dev, dtype=torch.float32) if self._fading else None
+        lists, first = [groups[s] for s in touched], [self._scenes[s].n_views == 0 for s in touched]
+        if self._fading:                          # one tick of the touched scenes: each fades by its own decay, the others are not read
+            ops.backproject_weighted_accum_(p0, proj, lists, weights, touched, first, [self._scenes[s]._decay for s in touched], origin, crop,
+                                            m.voxel_size, self._sum, self._wsum, self._count, self._mean if emit else None,
+                                            self._valid if emit else None, forget_below=self._forget, sampling=getattr(m, 'sampling', 'nearest'))
+        else:
+            ops.backproject_lists_accum_(p0, proj, lists, touched, first, origin, crop, m.voxel_size, self._sum, self._count,
+                                         self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
+        for s in touched:
+            self._scenes[s]._grow([E[t] for t in groups[s]], hw, stale=not emit)
+
+    def _add_windowed(self, p0, proj_h, groups, touched, E, hw, weights):
         """The new maps and projection rows into free slots of their scenes' parts of the rings (one index_copy_ each); the oldest views
         of a full scene leave first.  Everything that can fail comes before the first change of the batch."""
         m, W, N = self._model, self._window, self._N
@@ -632,35 +698,18 @@ class SceneBatch:
             pring = torch.empty((N * W, 3, 4), device=dev, dtype=torch.float32)
             mean = torch.empty((N, X, Y, Z, Cn), device=dev, dtype=p0.dtype)
             valid = torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8)
-        slot_of, new_views = [0] * p0.shape[0], {}
-        for s in touched:
-            r, ts = self._scenes[s], groups[s]
-            kept = r._views[max(0, len(r._views) + len(ts) - W):]
-            used = {v[1] for v in kept}
-            free = [q for q in range(s * W, s * W + W) if q not in used][:len(ts)]
-            for t, q in zip(ts, free):
+        slot_of, placed = [0] * p0.shape[0], {}
+        for s in touched:                         # scene s owns the slots s*W .. s*W+W-1
+            placed[s] = self._scenes[s]._free_slots(len(groups[s]), s * W)
+            for t, q in zip(groups[s], placed[s][1]):
                 slot_of[t] = q
-            new_views[s] = kept + [(r._next_id + i, free[i], E[t]) for i, t in enumerate(ts)]
         idx = torch.tensor(slot_of, dtype=torch.int64).to(dev)
         ring.index_copy_(0, idx, p0)
         pring.index_copy_(0, idx, proj_h.to(dev))
-        if weights is not None and self._wring is None:
-            self._wring = [1.0] * (N * W)         # the weight ring starts with the first weight given
-        if self._wring is not None:               # a reused slot takes its new view's weight (1 when none is given)
-            for s in touched:
-                for t in groups[s]:
-                    self._wring[slot_of[t]] = weights[t] if weights is not None else 1.0
-        self._ring, self._pring, self._mean, self._valid, self._hw = ring, pring, mean, valid, hw
-        for r in self._scenes:
-            r.meta.update(shapes)
+        self._wring = _ring_weights(self._wring, N * W, slot_of, weights)
+        self._ring, self._pring, self._mean, self._valid = ring, pring, mean, valid
         for s in touched:
-            r = self._scenes[s]
-            r._next_id += len(groups[s])
-            r._views, r._stale, r._hw = new_views[s], True, hw
-            r.meta['lidar2img']['extrinsic'] = [v[2] for v in r._views]
-            r.n_views = len(r._views)
-            self._cam[s] = cam[s]
-        return self
+            self._scenes[s]._admit(*placed[s], [E[t] for t in groups[s]], hw)
 
     # ------------------------------------------------------------------ reading the scenes
     def _refresh(self, scenes):
@@ -668,14 +717,16 @@ class SceneBatch:
         stale = [s for s in scenes if self._scenes[s]._stale]
         if not stale:
             return
+        m = self._model
         if self._window is not None:
             _, origin, crop = self._upload(self._ring.device, None, [self._cam[s] for s in stale])
+            lists = [[v[1] for v in self._scenes[s]._views] for s in stale]
             if self._wring is not None:
-                ops.backproject_weighted_mean_(self._ring, self._pring, [[v[1] for v in self._scenes[s]._views] for s in stale], self._wring, stale, origin,
-                                               crop, self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+                ops.backproject_weighted_mean_(self._ring, self._pring, lists, self._wring, stale, origin, crop, m.voxel_size, self._mean, self._valid,
+                                               sampling=getattr(m, 'sampling', 'nearest'))
             else:
-                ops.backproject_lists_mean_(self._ring, self._pring, [[v[1] for v in self._scenes[s]._views] for s in stale], stale, origin, crop,
-                                            self._model.voxel_size, self._mean, self._valid, sampling=getattr(self._model, 'sampling', 'nearest'))
+                ops.backproject_lists_mean_(self._ring, self._pring, lists, stale, origin, crop, m.voxel_size, self._mean, self._valid,
+                                            sampling=getattr(m, 'sampling', 'nearest'))
         elif self._fading:
             for s in stale:                       # (emit=False adds: the mean of the stored (sum, weight sum), row by row)
                 ops.volume_wmean(self._sum[s:s + 1], self._wsum[s:s + 1], self._mean.dtype, out=self._mean[s:s + 1], valid_out=self._valid[s:s + 1])
@@ -712,8 +763,5 @@ class SceneBatch:
         if scenes != list(range(self._N)):
             idx = torch.tensor(scenes, dtype=torch.int64).to(vol.device)
             vol, valid = vol.index_select(0, idx), valid.index_select(0, idx)
-        m, metas = self._model, [self._scenes[s].meta for s in scenes]
-        if isinstance(m.bbox_head, Anchor3DHead):
-            boxes, scores, labels, count = m.detect_cl(vol, metas)
-            return m._results_one_copy(boxes, scores, labels, count, metas)
-        return [bbox3d2result(b, s, l) for b, s, l in m.detect_indoor_cl(vol, valid.view(torch.bool), metas)]
+        return _detect(self._model, vol, valid.view(torch.bool), [self._scenes[s].meta for s in scenes])
+
