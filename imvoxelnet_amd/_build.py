@@ -23,6 +23,7 @@ SOURCES = [
     ('winograd.hip', []),
     ('pool_layout.hip', []),
     ('backproject.hip', ['-ffp-contract=off']),
+    ('volume_scroll.hip', []),
     ('anchor_tail.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('dcn.hip', []),

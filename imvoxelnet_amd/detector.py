@@ -187,10 +187,16 @@ class ImVoxelNet(nn.Module):
         from .engine import compute_projection
         return compute_projection(intrinsic.numpy(), [e.numpy() for e in extrinsics], ratio)
 
+    def _new_origin(self, origin):
+        """The grid's corner term of a meta's lidar2img['origin']: origin - n_voxels / 2 * voxel_size in torch fp32 (detectors/imvoxelnet.py:139),
+        a host tensor [3].  The one statement of the rule: _camera_setup and a scrolling scene (scene.py) both call it."""
+        origin = torch.tensor(origin)
+        if origin.dtype != torch.float32:
+            origin = origin.float()
+        return origin - torch.tensor(self.n_voxels) / 2. * torch.tensor(self.voxel_size)
+
     def _camera_setup(self, img_metas, stride, device, angles=None):
         proj, orig, crop = [], [], []
-        nv = torch.tensor(self.n_voxels)
-        vs = torch.tensor(self.voxel_size)
         for b, meta in enumerate(img_metas):
             # the reference hands the whole batch's angle list to every sample (:60), which only works at batch size 1
             # (the SUN RGB-D Total test setting); here sample b gets its own prediction
@@ -198,10 +204,7 @@ class ImVoxelNet(nn.Module):
             if p.dtype != torch.float32:
                 raise TypeError('lidar2img intrinsic/extrinsic must be float32 (as the reference datasets produce)')
             proj.append(p)
-            origin = torch.tensor(meta['lidar2img']['origin'])
-            if origin.dtype != torch.float32:
-                origin = origin.float()
-            orig.append(origin - nv / 2. * vs)                      # :139
+            orig.append(self._new_origin(meta['lidar2img']['origin']))      # :139
             crop.append([meta['img_shape'][0] // stride, meta['img_shape'][1] // stride])   # :67-68
         V = proj[0].shape[0]
         if any(p.shape[0] != V for p in proj):

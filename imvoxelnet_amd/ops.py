@@ -1219,6 +1219,57 @@ def volume_wmean(vol_sum, wsum, dtype=torch.float32, out=None, valid_out=None):
     return _mean_of_state('ivx_volume_wmean_fwd', '0.4.8', vol_sum, wsum, 'wsum', torch.float32, dtype, out, valid_out)
 
 
+def volume_scroll_(vol_sum, count, rows, shifts, wsum=None):
+    """Scrolling scenes: move rows of the state pools vol_sum [R,X,Y,Z,C] fp32 / count [R,X,Y,Z] int32 (/ wsum [R,X,Y,Z] fp32) by whole voxels,
+    in place (ivx_volume_scroll_fwd): for sample b, row rows[b] becomes new[i,j,k] = old[i+sx, j+sy, k+sz] with (sx, sy, sz) = shifts[b] where that
+    source lies inside the grid and an unseen voxel (all bits zero) elsewhere -- a pure move of bits, NaN payloads, -0 and denormals included.
+    rows: B distinct host integers in [0, R); shifts: B host triples of integers (one triple alone for B = 1).  Rows not named are neither read
+    nor written.  Every check comes before the one C call, so a call that raises changes nothing.  Returns (vol_sum, count)."""
+    for t, name in ((vol_sum, 'vol_sum'), (count, 'count')) + (((wsum, 'wsum'),) if wsum is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch.Tensor')
+    if vol_sum.dim() != 5:
+        raise ValueError(f'vol_sum must be [R,X,Y,Z,C], got {tuple(vol_sum.shape)}')
+    R, X, Y, Z, Cn = (int(v) for v in vol_sum.shape)
+    rows = _host_ints(rows, 'rows')
+    if not rows:
+        raise ValueError('rows must name at least one row')
+    if isinstance(shifts, torch.Tensor) or isinstance(shifts, (str, bytes)) or not hasattr(shifts, '__len__'):
+        raise TypeError('shifts must be a host list of (sx, sy, sz) integer triples')
+    if len(rows) == 1 and len(shifts) == 3 and not any(hasattr(s, '__len__') for s in shifts):
+        shifts = [shifts]
+    shifts = [_host_ints(s, f'shifts[{b}]') for b, s in enumerate(shifts)]
+    if len(shifts) != len(rows) or any(len(s) != 3 for s in shifts):
+        raise ValueError(f'shifts must hold one (sx, sy, sz) triple per row: {len(rows)} rows, got {shifts}')
+    if any(not -2 ** 31 <= v < 2 ** 31 for s in shifts for v in s):
+        raise ValueError(f'shifts must fit int32, got {shifts}')
+    if len(set(rows)) != len(rows):
+        raise ValueError(f'rows must be distinct (two samples on one row race), got {rows}')
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}')
+    if Cn % 4:
+        raise ValueError(f'vol_sum must have C % 4 == 0, got C = {Cn}')
+    if tuple(count.shape) != (R, X, Y, Z):
+        raise ValueError('count must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
+    if wsum is not None and tuple(wsum.shape) != (R, X, Y, Z):
+        raise ValueError('wsum must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
+    _chk(vol_sum, 'vol_sum')
+    _chk(count, 'count', torch.int32)
+    if wsum is not None:
+        _chk(wsum, 'wsum')
+        if wsum.device != vol_sum.device:
+            raise ValueError('wsum must be on the device of vol_sum')
+    if count.device != vol_sum.device:
+        raise ValueError('count must be on the device of vol_sum')
+    fn = getattr(_lib.lib(), 'ivx_volume_scroll_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_scroll_fwd (needs version 0.4.9)')
+    B = len(rows)
+    check(fn(B, (C.c_int32 * B)(*rows), (C.c_int32 * (3 * B))(*[v for s in shifts for v in s]), R, X, Y, Z, Cn, _ptr(vol_sum), _ptr(count), _ptr(wsum),
+             _stream()), 'ivx_volume_scroll_fwd')
+    return vol_sum, count
+
+
 # ------------------------------------------------------------------ detection tail
 def anchor_head_get_bboxes(head_out, anchors, H, W, num_anchors, num_classes, offs, cfg, dir_offset=0.0,
                            dir_limit_offset=1.0, hw_transposed=False, want_candidates=False):

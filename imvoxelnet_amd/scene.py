@@ -43,6 +43,16 @@ holds, tick by tick, the bits of a plain session.  A windowed scene takes weight
 them): its re-lift is then the weighted mean of the kept views (ops.backproject_weighted_mean_).  `decay` and `window` are alternative ways to
 forget and exclude each other.
 
+Scrolling scenes (SceneSession.scroll(voxels) / scroll_to(center), SceneBatch.scroll(scenes, voxels)).  Forgetting what lies behind a moving
+platform is half of following it; the other half is carrying the grid along, or every new view of a robot that has left the 6.4 m ScanNet grid
+sees no voxel.  scroll moves the grid by whole voxels: the state (sum, count, weight sum) of a plain or fading scene is shifted in place by
+ops.volume_scroll_ (ivx_volume_scroll_fwd, csrc/volume_scroll.hip: a pure move of bits, voxels that enter are unseen), a windowed scene has
+nothing to move and lifts its kept views again, and the meta's origin follows ONE rule, scrolled_origin = float32(origin) + float32(voxels) *
+float32(voxel_size), from which the device new_origin is recomputed by the model's own rule.  Everything after a scroll is the existing lift at
+the new origin, so a scrolled scene is, bit for bit, a scene opened at the new origin whose state is the moved state.  A scroll is not a tick:
+nothing fades.  Like bilinear sampling and fading it is an extra outside the reference-parity claims; a session that never scrolls runs the code
+it ran before.  Models with an Anchor3DHead refuse: their anchors are fixed in the LiDAR frame.
+
 How the module is laid out.  Every host rule is written once.  _SceneRecord is the host state of ONE scene (meta, view list, ids, stale flag, image
 size, window, decay, threshold) with the rules that need no device: the checks of meta / window / fading, reset, view_ids, remove_views, which slots
 of a range [base, base + W) a windowed add frees and fills, the id-to-slot lookup, the body of reweight.  The argument checks of an add (images,
@@ -51,8 +61,9 @@ record plus its own buffers and launches; a SceneBatch HOLDS N records (_scenes)
 the two, for a measured reason (profiles/scene_batch.md: the listed lift at one row is about 20 us slower than the plain one), so they stay in
 the classes, and nothing shared asks which class called it: wording that differs in a noun is passed in.
 
-Out of scope: decay on windowed scenes; per-pixel weight maps; scene batches across ranks; a model-level C handle for sessions (the state lives here, over the
-op-level ABI and the handle's sub-range calls).
+Out of scope: decay on windowed scenes; per-pixel weight maps; scrolling by a fraction of a voxel or by a rotation (both would resample the state);
+scrolling a model with an Anchor3DHead (its boxes would have to be translated); scene batches across ranks; a model-level C handle for sessions
+(the state lives here, over the op-level ABI and the handle's sub-range calls).
 """
 import math
 
@@ -119,6 +130,24 @@ def _ring_weights(wring, size, slots, weights):
     return wring
 
 
+# ------------------------------------------------------------------ scrolling: the host rules
+def scrolled_origin(origin, voxels, voxel_size):
+    """The origin rule of a scroll, per component in fp32:  float32(origin) + float32(voxels) * float32(voxel_size)  -- the product is rounded,
+    then the sum.  -> float32 array [3]."""
+    return np.asarray(origin, np.float32) + np.asarray(voxels).astype(np.float32) * np.asarray(voxel_size, np.float32)
+
+
+def _check_scroll(model, voxels):
+    """voxels of a scroll -> [sx, sy, sz] as ints; a model whose head has anchors refuses."""
+    if isinstance(getattr(model, 'bbox_head', None), Anchor3DHead):
+        raise NotImplementedError('scroll: the anchors of an Anchor3DHead are fixed in the LiDAR frame (anchor_generator ranges), so its boxes would not '
+                                  'follow the grid; translating them is out of scope')
+    s = ops._host_ints(voxels, 'voxels')
+    if len(s) != 3 or any(not -2 ** 31 <= v < 2 ** 31 for v in s):
+        raise ValueError(f'voxels must be three int32 integers (sx, sy, sz), got {voxels!r}')
+    return s
+
+
 # ------------------------------------------------------------------ the two model calls around the lift
 def _trunk(m, img):
     """[V,3,H,W] -> FPN level 0 of these views.  The native handle's trunk sub-range is the same kernels with the same plans as
@@ -170,6 +199,7 @@ class _SceneRecord:
         self.meta, self.n_views, self._hw, self._stale = meta, 0, None, False
         self._window, self._views, self._next_id = window, [], 0
         self._decay, self._forget = decay, forget_below
+        self._scrolled = (0, 0, 0)
 
     @staticmethod
     def _check_fading(window, decay, forget_below):
@@ -197,6 +227,25 @@ class _SceneRecord:
         self.meta['lidar2img']['extrinsic'] = []
         self.n_views, self._hw, self._stale = 0, None, False
         self._views, self._next_id = [], 0
+        self._scrolled = (0, 0, 0)
+
+    @property
+    def scrolled(self):
+        """The cumulative shift (sx, sy, sz) in voxels since the scene was opened or reset() (the origin stays where the scrolls took it)."""
+        return self._scrolled
+
+    def _scroll(self, s, origin):
+        """A scroll by s is in: `origin` (scrolled_origin of this meta's) replaces the meta's, and the mean of a scene with views is behind."""
+        self.meta['lidar2img']['origin'] = origin
+        self._scrolled = tuple(a + b for a, b in zip(self._scrolled, s))
+        self._stale = self._stale or self.n_views > 0
+
+    def _scroll_to(self, center, voxel_size):
+        """The shift that brings the grid's origin nearest to `center`: rint((center - origin) / voxel_size) per axis in float64, as ints."""
+        c = np.asarray(center, np.float64).reshape(-1)
+        if c.shape != (3,) or not np.isfinite(c).all():
+            raise ValueError(f'center must be three finite coordinates, got {center!r}')
+        return [int(v) for v in np.rint((c - np.asarray(self.meta['lidar2img']['origin'], np.float64)) / np.asarray(voxel_size, np.float64))]
 
     @property
     def view_ids(self):
@@ -422,6 +471,39 @@ class SceneSession(_SceneRecord):
         self._wring = self._reweight(ids, weights, self._wring, 1, 'session: open_scene(meta, window=W)', 'the scene')
         return self
 
+    # ------------------------------------------------------------------ scrolling
+    def scroll(self, voxels):
+        """Move the grid by voxels = (sx, sy, sz) whole voxels: what was at index i + s is afterwards at index i, voxels that enter the grid are
+        unseen, and meta['lidar2img']['origin'] becomes scrolled_origin(origin, voxels, voxel_size), a float32 array, from which the device
+        new_origin follows by the model's own rule -- so detect() returns boxes in world coordinates through the unchanged head code.
+        After scroll the session behaves exactly like a session opened at the new origin whose state is the moved state: every later add is the
+        existing lift at that origin.  Plain and fading sessions move (sum, count[, weight sum]) in place in one ops.volume_scroll_ (a pure move
+        of bits; a scroll is not a tick, nothing fades) and recompute the mean when it is next asked for.  A windowed session has no state to
+        move: its next volume() / detect() is the gathered re-lift of the kept views at the new origin, bit for bit their one-shot lift there.
+        An empty scene only changes its origin.  A zero shift changes nothing.  A model with an Anchor3DHead raises NotImplementedError.  A call
+        that raises leaves the session as it was.  Returns self."""
+        self._check_open()
+        s = _check_scroll(self._model, voxels)
+        if not any(s):
+            return self
+        m = self._model
+        origin = scrolled_origin(self.meta['lidar2img']['origin'], s, m.voxel_size)
+        new_origin = m._new_origin(origin)[None].contiguous().to(self._origin.device) if self._origin is not None else None
+        if self._window is None and self.n_views:
+            ops.volume_scroll_(self._sum, self._count, [0], [s], self._wsum)
+        self._origin = new_origin
+        self._scroll(s, origin)
+        return self
+
+    def scroll_to(self, center):
+        """Host-only convenience: scroll by rint((center - origin) / voxel_size) per axis (computed in float64), so that the grid's origin comes as
+        near to `center` as whole voxels allow.  Applies the shift when it is non-zero and returns it as (sx, sy, sz)."""
+        self._check_open()
+        s = self._scroll_to(center, self._model.voxel_size)
+        if any(s):
+            self.scroll(s)
+        return tuple(s)
+
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
         (data.prepare_images_device; pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device) and fills img_shape / ori_shape /
@@ -570,6 +652,36 @@ class SceneBatch:
         self._check_open()
         s = self._scene_index(scene)              # (the record's slots are the batch's: scene s owns s*W .. s*W+W-1)
         self._wring = self._scenes[s]._reweight(ids, weights, self._wring, self._N, 'batch: open_scenes(metas, window=W)', f'scene {s}')
+        return self
+
+    def scrolled(self, scene):
+        """The cumulative shift of one scene since it was opened or reset."""
+        self._check_open()
+        return self._scenes[self._scene_index(scene)].scrolled
+
+    def scroll(self, scenes, voxels):
+        """SceneSession.scroll for scenes of the batch: one scene index with one (sx, sy, sz), or a list of distinct indices with one triple each.
+        All named scenes move in ONE ops.volume_scroll_ on their rows of the pools; their metas and host camera records follow the same origin
+        rule.  Scenes not named are neither read nor written.  A call that raises leaves every scene as it was."""
+        self._check_open()
+        if isinstance(scenes, (int, np.integer)) and not isinstance(scenes, bool):
+            scenes, voxels = [scenes], [voxels]
+        if isinstance(scenes, torch.Tensor) or not hasattr(scenes, '__len__') or isinstance(voxels, torch.Tensor) or not hasattr(voxels, '__len__') \
+                or len(scenes) != len(voxels):
+            raise ValueError(f'scroll takes one scene index with one (sx, sy, sz), or lists of both of one length, got {scenes!r} and {voxels!r}')
+        scenes = [self._scene_index(s) for s in scenes]
+        if len(set(scenes)) != len(scenes):
+            raise ValueError(f'a scene can be scrolled once per call, got {scenes}')
+        m = self._model
+        moves = [(s, v) for s, v in zip(scenes, [_check_scroll(m, v) for v in voxels]) if any(v)]
+        origins = [scrolled_origin(self._scenes[s].meta['lidar2img']['origin'], v, m.voxel_size) for s, v in moves]
+        rows = [(s, v) for s, v in moves if self._window is None and self._scenes[s].n_views]
+        if rows:
+            ops.volume_scroll_(self._sum, self._count, [s for s, _ in rows], [v for _, v in rows], self._wsum)
+        for (s, v), origin in zip(moves, origins):
+            self._scenes[s]._scroll(v, origin)
+            if self._cam[s] is not None:
+                self._cam[s] = (m._new_origin(origin), self._cam[s][1])
         return self
 
     # ------------------------------------------------------------------ adding views

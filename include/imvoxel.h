@@ -42,8 +42,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * bilinear sampling rule of the unprojection; 450 = 0.4.5: ivx_conv_route / ivx_bf16_pair_pack_filters; 460 = 0.4.6: ivx_backproject_gather_fwd, the mean lift of
  * views listed by slot, for sliding-window scenes; 470 = 0.4.7: ivx_backproject_lists_fwd, the listed lift with per-sample rows and `first` flags, for
  * batches of scenes and ragged batches; 480 = 0.4.8: ivx_backproject_weighted_fwd / ivx_volume_wmean_fwd, the listed lift with per-view weights,
- * per-sample decay and a forgetting threshold, for fading scenes) and the message of the last failing call on
- * this thread (never NULL). */
+ * per-sample decay and a forgetting threshold, for fading scenes; 490 = 0.4.9: ivx_volume_scroll_fwd, the in-place voxel shift of rows of the state
+ * pools, for scrolling scenes) and the message of the last failing call on this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
 
@@ -701,6 +701,41 @@ int ivx_backproject_weighted_fwd(const ivx_backproject_desc *d, const ivx_lift_l
                                  int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream);
 int ivx_volume_wmean_fwd(const float *volume_sum, const float *wsum, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype, uint8_t *valid,
                          ivx_stream_t stream);
+
+/* (0.4.9) In-place voxel shift of rows of the state pools: a scene's grid moves with its platform (scrolling scenes: scene.py,
+ * SceneSession.scroll / SceneBatch.scroll).  Moving the state by whole voxels is a pure move of bits, and everything a scene does afterwards is
+ * the existing lift at the moved origin, so the operation is pinned bit for bit with no tolerance (tests/ref_volume_scroll.py restates the
+ * definition in numpy).  Like the bilinear rule and fading it lies outside the reference-parity claims.
+ *
+ * Definition.  For sample b with r = row[b] and (sx, sy, sz) = shift[3b .. 3b+2], on row r of every field:
+ *     new[i,j,k] = old[i+sx, j+sy, k+sz]      where (i+sx, j+sy, k+sz) lies inside [0,X) x [0,Y) x [0,Z)
+ *     new[i,j,k] = unseen                      everywhere else: sums +0, count 0, weight sum +0 (all bits zero)
+ *   The fields are moved as raw words -- volume_sum as 16-byte words, count and wsum as 4-byte words -- with no float arithmetic.
+ *
+ * B           samples of this call
+ * row         HOST [B] int32: sample b moves row row[b] of the pools
+ * shift       HOST [B,3] int32: its shift in voxels along x, y, z (any int32; content at index i+s is afterwards at index i)
+ * R, X, Y, Z, C  the pools have R rows of X*Y*Z voxels; C % 4 == 0
+ * volume_sum  DEVICE [R,X,Y,Z,C] fp32 in/out, 16-byte aligned
+ * count       DEVICE [R,X,Y,Z] int32 in/out
+ * wsum        DEVICE [R,X,Y,Z] fp32 in/out, or NULL (a state without a weight sum)
+ * row and shift are host lists on purpose: unlike the device lists of the lifts this entry checks everything before any launch, and nothing
+ * is uploaded (rows and shifts reach the kernel by value, 32 samples per launch).
+ *
+ * Properties.
+ *   Named rows.      Bit for bit the definition: every bit pattern survives the move, NaN payloads, -0 and denormals included.
+ *   Untouched rows.  Rows named by no sample are neither read nor written.
+ *   In place.        No scratch, no atomics, no barriers: one pass per axis with a non-zero shift, in the order x, y, z (the three axis maps
+ *                    commute, so the order does not show in the result), at most three launches for the sums and three for count / wsum per 32
+ *                    samples.  csrc/volume_scroll.hip states why a pass may overwrite the line it reads.
+ *   Large shifts.    |s| >= the axis length on any axis leaves the row all zero.
+ *   Zero shifts.     A sample whose shift is (0,0,0) is not touched; a call whose shifts are all zero is valid and launches nothing.
+ *   Composition.     scroll(s) then scroll(t) equals scroll(s + t) on every voxel whose source stayed inside the grid in between, and zero elsewhere;
+ *                    scroll(s) then scroll(-s) zeroes exactly the shell the first one vacated.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names this entry: a null row, shift, volume_sum or count; a non-positive B, R, X, Y,
+ * Z or C; C % 4 != 0; X*Y*Z at or beyond 2^31; a row outside [0, R); two samples on one row (they would race).                                  */
+int ivx_volume_scroll_fwd(int32_t B, const int32_t *row /*host [B]*/, const int32_t *shift /*host [B,3]*/, int32_t R, int32_t X, int32_t Y, int32_t Z,
+                          int32_t C, float *volume_sum, int32_t *count, float *wsum /*or NULL*/, ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
