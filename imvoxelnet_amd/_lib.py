@@ -84,6 +84,12 @@ class LiftWeights(C.Structure):
     _fields_ = [('view_weight', C.c_void_p), ('decay', C.c_void_p), ('forget_below', C.c_float), ('wsum', C.c_void_p)]
 
 
+class LiftMaps(C.Structure):
+    """ivx_lift_maps (ivx_backproject_mapped_fwd): the per-slot pixel-weight and depth maps of a mapped lift and the gate around a measured depth; the
+    pointers are device addresses."""
+    _fields_ = [('pixel_weight', C.c_void_p), ('depth', C.c_void_p), ('behind', C.c_float), ('front', C.c_float)]
+
+
 class PairIO(C.Structure):
     """ivx_pair_io: device-side scales / amax slots of a convolution on fp16-pair activations (ivx_conv_fwd_pio)."""
     _fields_ = [('in_scale', C.c_void_p), ('res_scale', C.c_void_p), ('res_dtype', C.c_int32), ('out_scale', C.c_void_p), ('amax_in', C.c_void_p),
@@ -160,7 +166,7 @@ EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor'
            'ivx_conv_winograd_input', 'ivx_conv_winograd_gemm', 'ivx_conv_winograd_output', 'ivx_conv_winograd_fwd',
            'ivx_maxpool2d_fwd', 'ivx_maxpool2d_fwd_bf16', 'ivx_maxpool2d_fwd_fp8', 'ivx_global_avgpool_fwd', 'ivx_global_avgpool_fwd_bf16', 'ivx_upsample_trilinear2x_fwd', 'ivx_dcn_im2col_fwd', 'ivx_dcn_im2col_fwd_bf16', 'ivx_dcn_im2col_fwd_pair', 'ivx_nchw_to_nhwc', 'ivx_image_s2d_bf16', 'ivx_nhwc_to_nchw', 'ivx_backproject_mean_fwd', 'ivx_backproject_mean_fwd_amax', 'ivx_backproject_amax_blocks', 'ivx_backproject_mean_fwd_bf16', 'ivx_upsample_trilinear2x_fwd_bf16', 'ivx_backproject_sum_fwd', 'ivx_volume_normalize_fwd',
            'ivx_backproject_accum_fwd', 'ivx_backproject_accum_fwd_bf16', 'ivx_volume_mean_fwd', 'ivx_backproject_fwd_ex', 'ivx_backproject_gather_fwd',
-           'ivx_backproject_lists_fwd', 'ivx_backproject_weighted_fwd', 'ivx_volume_wmean_fwd', 'ivx_volume_scroll_fwd',
+           'ivx_backproject_lists_fwd', 'ivx_backproject_weighted_fwd', 'ivx_volume_wmean_fwd', 'ivx_volume_scroll_fwd', 'ivx_backproject_mapped_fwd',
            'ivx_anchor_head_workspace_bytes', 'ivx_anchor_head_get_bboxes', 'ivx_fcos_head_workspace_bytes',
            'ivx_fcos_head_level_candidates', 'ivx_nms_workspace_bytes',
            'ivx_nms_bev', 'ivx_boxes_overlap_bev', 'ivx_aligned_3d_nms', 'ivx_aligned_3d_nms_workspace_bytes', 'ivx_aligned_3d_nms_ws', 'ivx_multiclass_nms_workspace_bytes', 'ivx_multiclass_nms_bev',
@@ -282,6 +288,9 @@ def lib():
         L.ivx_volume_wmean_fwd.argtypes = [vp, vp, i64, i32, vp, i32, vp, vp]
     if hasattr(L, 'ivx_volume_scroll_fwd'):        # (0.4.9; an older build still loads: ops.volume_scroll_ and scrolling scenes then refuse)
         L.ivx_volume_scroll_fwd.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), i32, i32, i32, i32, i32, vp, vp, vp, vp]
+    if hasattr(L, 'ivx_backproject_mapped_fwd'):   # (0.5.0; an older build still loads: ops.backproject_mapped_accum_ / _mean_ and the scenes' pixel maps then refuse)
+        L.ivx_backproject_mapped_fwd.argtypes = [C.POINTER(BackprojectDesc), C.POINTER(LiftLists), C.POINTER(LiftWeights), C.POINTER(LiftMaps), vp, vp, vp, vp, vp, vp, vp,
+                                                 vp, vp]
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -75,6 +75,12 @@ struct BpWeightParams : BpListParams {
   float forget_below;       // BP_ACCUM: a faded weight sum below it forgets the voxel; 0 forgets nothing
   float *wsum;              // [R, N]  BP_ACCUM: the running weight sum, beside count
 };
+// MAPPED instantiations (ivx_backproject_mapped_fwd; pixel maps): the WEIGHTED form whose views bring a per-pixel confidence and / or a depth map
+struct BpMapParams : BpWeightParams {
+  const float *pixel_weight; // [S, FH, FW] or NULL (= 1)
+  const float *depth;        // [S, FH, FW] or NULL (no gate)
+  float behind, front;       // the gate around a measured depth D: the view counts where D - front <= d <= D + behind; read only with depth
+};
 
 // MODE BP_MEAN: the reference's view mean + valid mask.  BP_SUM (view-sharded multi-GPU mode): the raw sum over
 // this rank's views and the per-voxel view count, to be all-reduced and normalised by volume_normalize_kernel.
@@ -120,11 +126,19 @@ __device__ __forceinline__ void bp_bilinear_weights(const float ax, const float 
 // the group carries both, lane g == 0 stores them).  BP_ACCUM fades the state it read, S *= lambda and W *= lambda unless lambda == 1 (uniform
 // per sample), and forgets the voxel whose faded W is below p.forget_below (> 0).  The mean divides by W.  With unit weights fma(1, f, S) is the
 // __fadd_rn of the other forms and W == (float)cnt, so volume / count / mean / valid are theirs bit for bit.
-template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false, bool ROWS = false, bool WEIGHTED = false>
+// MAPPED (ivx_backproject_mapped_fwd; pixel maps; WEIGHTED forms only; the definition is in include/imvoxel.h): once its validity test has passed, the
+// projecting lane reads the two maps at the NEAREST pixel of its view (the pixel the validity rule rounds to, under BP_BILINEAR too, where `off` is
+// corner 00 and the index is formed apart); both addresses come from slot and pixel alone, so the two loads overlap and no address depends on a
+// map's value.  A measured depth D (D > 0 && D < inf) keeps the view only where D - front <= d <= D + behind (one rounded sum, one rounded
+// difference); the weight becomes w = wt * pixel_weight (one rounded product) and must pass w > 0 && w < inf again.  A view that fails either test
+// is unseen (off stays -1), and `wt` carries the effective weight through the existing __shfl: the group's inner loop is the WEIGHTED one.
+template <int VEC, int MODE = BP_MEAN, typename T = float, int SAMP = BP_NEAREST, bool GATHER = false, bool ROWS = false, bool WEIGHTED = false,
+          bool MAPPED = false>
 __global__ __launch_bounds__(256) void backproject_mean_kernel(
-    const std::conditional_t<WEIGHTED, BpWeightParams, std::conditional_t<ROWS, BpListParams, std::conditional_t<GATHER, BpGatherParams, BpParams>>> p) {
+    const std::conditional_t<MAPPED, BpMapParams, std::conditional_t<WEIGHTED, BpWeightParams, std::conditional_t<ROWS, BpListParams, std::conditional_t<GATHER, BpGatherParams, BpParams>>>> p) {
   static_assert(!ROWS || (GATHER && VEC == 4 && MODE != BP_SUM), "the ROWS forms are the gathered mean / accumulate kernels");
   static_assert(!WEIGHTED || ROWS, "the WEIGHTED forms are ROWS forms");
+  static_assert(!MAPPED || WEIGHTED, "the MAPPED forms are WEIGHTED forms");
   typedef T tv4 __attribute__((ext_vector_type(4)));
   constexpr bool MEAN = MODE == BP_MEAN;
   const int b = blockIdx.y;
@@ -246,6 +260,18 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
       const float yr = rintf(__fdiv_rn(w_, d));
       bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
       if constexpr (WEIGHTED) ok = ok && wt > 0.f && wt < __builtin_inff();     // NaN, 0, negative and inf: an unseen view (off stays -1)
+      if constexpr (MAPPED) {
+        if (ok) {                 // the nearest pixel is inside the crop, hence inside the map: slot in [0, S), (int)yr in [0, FH), (int)xr in [0, FW)
+          const int pix = (slot * p.FH + (int)yr) * p.FW + (int)xr;
+          const float D = p.depth ? p.depth[pix] : 0.f;
+          const float pw = p.pixel_weight ? p.pixel_weight[pix] : 1.0f;
+          if (D > 0.f && D < __builtin_inff()) ok = d <= __fadd_rn(D, p.behind) && d >= __fsub_rn(D, p.front);     // 0, negative, NaN, +inf: no measurement, no gate
+          if (p.pixel_weight) {
+            wt = __fmul_rn(wt, pw);
+            ok = ok && wt > 0.f && wt < __builtin_inff();
+          }
+        }
+      }
       if (ok) off = (((GATHER ? slot : b * p.V + v) * p.FH + (int)yr) * p.FW + (int)xr);
       if constexpr (SAMP == BP_BILINEAR) {
         if (ok) {               // a valid sample: xf in [-0.5, wc - 0.5], so the floors are in [-1, wc - 1] and fit an int
@@ -530,6 +556,8 @@ struct BpCall {
   const ivx_lift_lists *lists = nullptr;
   bool weighted = false;            // ivx_backproject_weighted_fwd: the listed form (listed and gather are set too) with the weights, decays and weight sums of `weights`
   const ivx_lift_weights *weights = nullptr;
+  bool mapped = false;              // ivx_backproject_mapped_fwd with at least one map: the weighted form (weighted, listed and gather are set too) with the maps and the gate of `maps`
+  const ivx_lift_maps *maps = nullptr;
 };
 
 // The descriptor of an older export's argument list (voxel_size stays with the caller's pointer, which may be NULL until validated).
@@ -587,6 +615,11 @@ static int bp_validate(const BpCall &c) {
       IVX_REQUIRE(w->forget_below == 0.f, "%s: forget_below %g in the mean mode (must be 0: there is no state to forget)", what, (double)w->forget_below);
     }
   }
+  if (c.mapped && c.maps->depth) {
+    const ivx_lift_maps *m = c.maps;
+    IVX_REQUIRE(m->behind >= 0.f && m->front >= 0.f, "%s: gate (behind %g, front %g): both must be >= 0 (+inf: no limit on that side), never NaN", what, (double)m->behind,
+                (double)m->front);
+  }
   const int vec = (d->C % 4 == 0) ? 4 : 1;
   IVX_REQUIRE(vec == 4 || (d->mode == IVX_LIFT_MEAN && d->feat_dtype == IVX_F32 && !c.gather), "%s: C %% 4 must be 0 (every form but the fp32 mean of a view stack)", what);
   IVX_REQUIRE((int64_t)d->X * d->Y * d->Z < (1LL << 31), "%s: voxel grid too large", what);
@@ -602,11 +635,11 @@ static int bp_validate(const BpCall &c) {
   return IVX_OK;
 }
 
-// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams / BpListParams / BpWeightParams (a
-// plain, gathered or listed launch passes the base).
-static BpWeightParams bp_fill(const BpCall &c, dim3 *grid) {
+// The kernel's parameters and grid of a validated call: the one place that writes a BpParams / BpGatherParams / BpListParams / BpWeightParams /
+// BpMapParams (a plain, gathered, listed or weighted launch passes the base).
+static BpMapParams bp_fill(const BpCall &c, dim3 *grid) {
   const ivx_backproject_desc &d = *c.d;
-  BpWeightParams p;
+  BpMapParams p;
   p.feat = (const float *)c.feat; p.proj = c.proj; p.new_origin = c.new_origin; p.crop_hw = c.crop_hw;
   p.volume = (float *)c.volume; p.valid = c.valid; p.count = c.count; p.mean_out = c.mean_out;
   // the running state is read unless `first`; a bf16 sum is the accumulate kernel from a zero state (bp_launch), so it never reads one
@@ -622,6 +655,8 @@ static BpWeightParams bp_fill(const BpCall &c, dim3 *grid) {
   p.row = c.listed ? c.lists->row : nullptr; p.first_list = c.listed ? c.lists->first : nullptr; p.R = c.listed ? c.lists->R : 0;
   p.view_weight = c.weighted ? c.weights->view_weight : nullptr; p.decay = c.weighted ? c.weights->decay : nullptr;
   p.forget_below = c.weighted ? c.weights->forget_below : 0.f; p.wsum = c.weighted ? c.weights->wsum : nullptr;
+  p.pixel_weight = c.mapped ? c.maps->pixel_weight : nullptr; p.depth = c.mapped ? c.maps->depth : nullptr;
+  p.behind = c.mapped && c.maps->depth ? c.maps->behind : 0.f; p.front = c.mapped && c.maps->depth ? c.maps->front : 0.f;
   if (bp_single_view_copy(c)) {      // 256 voxels per workgroup regardless of the group width (each lane projects one voxel)
     p.pmax = c.partials; p.nblk = 0; p.q = 0;
     *grid = dim3((p.N + 255) / 256, d.B);
@@ -634,8 +669,9 @@ static BpWeightParams bp_fill(const BpCall &c, dim3 *grid) {
 }
 
 // The selection table: every instantiation of the two lift kernels is launched from exactly one line below.
-static int bp_launch(const BpCall &c, const BpWeightParams &w, const dim3 grid) {
+static int bp_launch(const BpCall &c, const BpMapParams &m, const dim3 grid) {
   const ivx_backproject_desc &d = *c.d;
+  const BpWeightParams &w = m;
   const BpListParams &l = w;
   const BpGatherParams &g = l;
   const BpParams &p = l;
@@ -644,7 +680,16 @@ static int bp_launch(const BpCall &c, const BpWeightParams &w, const dim3 grid) 
   const int mode = d.mode == IVX_LIFT_MEAN ? BP_MEAN : (d.mode == IVX_LIFT_SUM && !bf16) ? BP_SUM : BP_ACCUM;
   const dim3 block(256);
   hipStream_t st = (hipStream_t)c.stream;
-  if (c.weighted) {                                 // weights, decay and weight sums: the ROWS forms, with or without a row list
+  if (c.mapped) {                                   // pixel maps: the WEIGHTED forms with a confidence and / or a gated depth per pixel
+    if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
+    else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
+    else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
+    else if (mode == BP_ACCUM)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
+    else if (bilinear && bf16)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
+    else if (bilinear)                         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
+    else if (bf16)                             hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
+    else                                       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
+  } else if (c.weighted) {                          // weights, decay and weight sums: the ROWS forms, with or without a row list
     if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
     else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
     else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
@@ -781,6 +826,15 @@ extern "C" int ivx_backproject_weighted_fwd(const ivx_backproject_desc *d, const
                                             uint8_t *valid, ivx_stream_t stream) {
   return bp_run({"ivx_backproject_weighted_fwd", d, d ? d->voxel_size : nullptr, feat_pool, proj_pool, new_origin, crop_hw, volume, count, mean_out, valid, stream,
                  nullptr, true, l ? l->view_slot : nullptr, l ? l->S : 0, true, l, true, w});
+}
+
+// Weighted listed lift with pixel maps (include/imvoxel.h): per view a confidence per pixel and / or a depth map with a gate.  No map: the weighted entry's launch.
+extern "C" int ivx_backproject_mapped_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const ivx_lift_weights *w, const ivx_lift_maps *m,
+                                          const void *feat_pool, const float *proj_pool, const float *new_origin, const int32_t *crop_hw, void *volume,
+                                          int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream) {
+  const bool mapped = m && (m->pixel_weight || m->depth);
+  return bp_run({"ivx_backproject_mapped_fwd", d, d ? d->voxel_size : nullptr, feat_pool, proj_pool, new_origin, crop_hw, volume, count, mean_out, valid, stream,
+                 nullptr, true, l ? l->view_slot : nullptr, l ? l->S : 0, true, l, true, w, mapped, mapped ? m : nullptr});
 }
 
 // ------------------------------------------------------------------ mean of a (sum, count) volume

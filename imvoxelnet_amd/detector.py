@@ -352,7 +352,7 @@ class ImVoxelNet(nn.Module):
             img = img.unsqueeze(1)
         return self.simple_test(img, [dict(m, **s) for m, s in zip(img_metas, shapes)])
 
-    def open_scene(self, meta, window=None, decay=None, forget_below=0.0):
+    def open_scene(self, meta, window=None, decay=None, forget_below=0.0, depth_gate=None):
         """A streaming scene on this model (scene.SceneSession): add_views / add_views_u8 fold new views into a running volume,
         detect() works on the views so far.  meta: one img_metas entry without lidar2img['extrinsic'].  Several sessions may be open
         on one prepared model.  window=W >= 1: the scene holds the last W views at most (the oldest leaves when a new one arrives,
@@ -360,18 +360,22 @@ class ImVoxelNet(nn.Module):
         per view.  Costs a ring of W FPN level-0 maps (scene.py has the figures).  decay=lam in (0, 1] (not with window): a fading
         scene, the weighted running mean -- add_views(..., weights=...) gives every view a confidence, every add_views call fades the
         state once by lam, and a voxel whose weight sum falls below forget_below becomes unseen again; O(1) state, no ring.  decay=1.0
-        with unit weights holds the bits of a plain session.  A session opened without decay refuses weights."""
+        with unit weights holds the bits of a plain session.  A session opened without decay refuses weights.  Sessions that take weights also
+        take pixel maps, add_views(..., pixel_weights=..., depths=...): a confidence per pixel and, with depth_gate=(behind, front) given
+        here (two numbers >= 0, inf allowed), a measured depth per pixel that lets a view count only at voxels within the gate of the surface
+        the pixel shows (scene.py, "Pixel maps").  depth_gate=None: depth maps are refused."""
         from .scene import SceneSession
-        return SceneSession(self, meta, window=window, decay=decay, forget_below=forget_below)
+        return SceneSession(self, meta, window=window, decay=decay, forget_below=forget_below, depth_gate=depth_gate)
 
-    def open_scenes(self, metas, window=None, decay=None, forget_below=0.0):
+    def open_scenes(self, metas, window=None, decay=None, forget_below=0.0, depth_gate=None):
         """N streaming scenes that share their launches (scene.SceneBatch): per tick one trunk call over the new views of any subset of
         the scenes, one listed lift into the touched scenes' rows of the state pools, and detect() as one batched neck + head + NMS.
         metas: one scene meta per scene (intrinsic, origin and box type may differ; image size and model are common).  window as for
         open_scene, per scene.  Every scene's volume is exact; what is not claimed is in the SceneBatch docstring.  decay (one value for
-        every scene or one per scene) and forget_below as for open_scene; in a batch only the scenes a call touches fade."""
+        every scene or one per scene) and forget_below as for open_scene; in a batch only the scenes a call touches fade.  depth_gate (one gate
+        for every scene) and the pixel maps of add_views as for open_scene."""
         from .scene import SceneBatch
-        return SceneBatch(self, metas, window=window, decay=decay, forget_below=forget_below)
+        return SceneBatch(self, metas, window=window, decay=decay, forget_below=forget_below, depth_gate=depth_gate)
 
     def simple_test_ragged(self, imgs, img_metas):
         """simple_test for a batch whose samples have DIFFERENT numbers of views: imgs is a list of B tensors [V_b,3,H,W] (common H, W),

@@ -6,6 +6,7 @@ pointers plus the current HIP stream to libimvoxel_hip.so.
 Internal activation layout is channels-last: 5-D [B, D, H, W, C] (a 2-D map has D == 1).
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -965,6 +966,49 @@ def backproject_weighted_mean_(pool, proj_pool, lists, weights, rows, new_origin
     return vol, valid.view(torch.bool)
 
 
+def backproject_mapped_accum_(pool, proj_pool, lists, weights, rows, first, decay, new_origin, crop_hw, voxel_size, vol_sum, wsum, count, mean_out=None,
+                              valid_out=None, forget_below=0.0, sampling='nearest', pixel_weight=None, depth=None, gate=(math.inf, math.inf)):
+    """backproject_weighted_accum_ whose views bring pixel maps (ivx_backproject_mapped_fwd; include/imvoxel.h has the definition).  pixel_weight: a
+    device float32 tensor [S,FH,FW] (or [S,1,FH,FW]), one confidence map per SLOT of the pool at feature resolution, or None (1 everywhere): the
+    weight of a view at a voxel is weights[slot] * pixel_weight[slot, y, x] at the nearest pixel the voxel projects to (one rounded product), and
+    the view counts there only if the product passes  w > 0 && w < inf.  depth: a device float32 tensor of the same shape, the measured depth per
+    pixel in the units of the projection's third coordinate, or None (no gate); gate = (behind, front), two numbers >= 0 (inf: no limit on that
+    side, the default): where the pixel has a measurement D (D > 0 && D < inf; 0, negative, NaN and inf are holes and gate nothing) the view counts
+    only at voxels of depth d with  D - front <= d <= D + behind.  The maps are used as they are (no copy; unlisted slots are never read); under the
+    bilinear rule they are read at the nearest pixel too.  With both maps None this is backproject_weighted_accum_ (the same launch; the gate is
+    still checked).  Everything else, and the returns, as there; every argument error is raised before any launch."""
+    if (mean_out is None) != (valid_out is None):
+        raise ValueError('mean_out and valid_out must both be given or both be None')
+    _pooled_lift('mapped', _LIFT_ACCUM, pool, proj_pool, new_origin, crop_hw, voxel_size, vol_sum, valid_out, sampling, lists=lists, rows=rows, first=first,
+                 count=count, mean_out=mean_out, weighted=dict(weights=weights, decay=decay, forget_below=forget_below, wsum=wsum),
+                 maps=dict(pixel_weight=pixel_weight, depth=depth, gate=gate))
+    return vol_sum, wsum, count
+
+
+def backproject_mapped_mean_(pool, proj_pool, lists, weights, rows, new_origin, crop_hw, voxel_size, vol, valid, sampling='nearest', pixel_weight=None,
+                             depth=None, gate=(math.inf, math.inf)):
+    """backproject_weighted_mean_ with the pixel maps of backproject_mapped_accum_: row rows[b] of vol / valid becomes  sum(w * sample) / sum(w)  over
+    the views of lists[b] that count at the voxel (seen, inside the gate of their depth map, w = weight * pixel weight valid) and the mask
+    sum(w) > 0.  Returns (vol, valid as bool)."""
+    _pooled_lift('mapped', _LIFT_MEAN, pool, proj_pool, new_origin, crop_hw, voxel_size, vol, valid, sampling, lists=lists, rows=rows,
+                 weighted=dict(weights=weights, decay=None, forget_below=0.0, wsum=None), maps=dict(pixel_weight=pixel_weight, depth=depth, gate=gate))
+    return vol, valid.view(torch.bool)
+
+
+def check_gate(gate):
+    """gate = (behind, front) of a depth map: two real numbers >= 0, +inf allowed (no limit on that side), never NaN -> (float, float)."""
+    if isinstance(gate, (torch.Tensor, str, bytes)) or not hasattr(gate, '__len__') or len(gate) != 2:
+        raise TypeError(f'gate must be (behind, front), two numbers >= 0, got {gate!r}')
+    g = []
+    for v in gate:
+        if isinstance(v, bool) or not hasattr(v, '__float__'):
+            raise TypeError(f'gate must hold two real numbers, got {v!r}')
+        g.append(float(v))
+    if any(not v >= 0 for v in g):
+        raise ValueError(f'gate (behind, front) must be >= 0 (inf: no limit on that side) and not NaN, got {tuple(g)}')
+    return g[0], g[1]
+
+
 def _host_floats(x, name, n):
     """A host sequence of n Python / numpy real numbers (no bools, no tensors) -> list of float."""
     if isinstance(x, torch.Tensor) or isinstance(x, (str, bytes)) or not hasattr(x, '__len__'):
@@ -995,20 +1039,21 @@ def _host_ints(x, name, n=None):
 
 # the three lifts that read their views from a pool by slot: the export of each form and the library version that brought it
 _POOLED = {'gather': ('ivx_backproject_gather_fwd', '0.4.6'), 'lists': ('ivx_backproject_lists_fwd', '0.4.7'),
-           'weighted': ('ivx_backproject_weighted_fwd', '0.4.8')}
+           'weighted': ('ivx_backproject_weighted_fwd', '0.4.8'), 'mapped': ('ivx_backproject_mapped_fwd', '0.5.0')}
 
 
 def _pooled_lift(form, mode, pool, proj_pool, new_origin, crop_hw, voxel_size, vol, valid, sampling, view_slot=None, n_voxels=None, lists=None, rows=None,
-                 first=None, count=None, mean_out=None, weighted=None):
+                 first=None, count=None, mean_out=None, weighted=None, maps=None):
     """The one checker and caller of the lifts over pool [S,1,FH,FW,C] / proj_pool [S,3,4]; form is a key of _POOLED.
     'gather' (_LIFT_MEAN only): view_slot [B,V], sample b writes row b.  A host list / CPU tensor is range-checked and uploaded; a device
       int32 tensor is used as it is (no copy).  n_voxels given: vol / valid are allocated here; else the caller's, with B rows.
     'lists': B ragged host lists, rows [B] and (accumulate mode) first [B] into the caller's vol [R,X,Y,Z,C] / count / mean_out / valid.
     'weighted': the same with weighted = dict(weights, decay, forget_below, wsum); host weights [S] and decays [B] travel in the same upload
       (as bits behind the integers).
+    'mapped': 'weighted' with maps = dict(pixel_weight, depth, gate): device fp32 maps [S,FH,FW] (or [S,1,FH,FW]) or None, used as they are, and the
+      host gate (behind, front); with both maps None the call goes out as 'weighted'.
     The host lists are checked first (against shapes only), then the tensors; then ONE upload of view_slot [B,V] (-1 padded), row [B] and
     first [B], and the launch.  Returns (vol, valid)."""
-    import math
     sampling = _lib.sampling_id(sampling)
     alloc = n_voxels is not None
     for t, name in ((pool, 'pool'), (proj_pool, 'proj_pool')) + (() if alloc else ((vol, 'vol_sum' if mode == _LIFT_ACCUM else 'vol'),)):
@@ -1074,8 +1119,26 @@ def _pooled_lift(form, mode, pool, proj_pool, new_origin, crop_hw, voxel_size, v
             hostf += decay
         if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float)) or not (math.isfinite(forget_below) and forget_below >= 0):
             raise ValueError(f'forget_below must be a finite number >= 0, got {forget_below!r}')
+    mdev = {}
+    if maps is not None:                           # the gate and the maps' shapes are host rules; device, dtype and layout come with the other tensors
+        gate = check_gate(maps['gate'])
+        for name in ('pixel_weight', 'depth'):
+            t = maps[name]
+            if t is None:
+                continue
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f'{name} must be None or a torch.Tensor [S,FH,FW]')
+            if t.dim() == 4 and t.shape[1] == 1:
+                t = t[:, 0]
+            if tuple(t.shape) != (S, FH, FW):
+                raise ValueError(f'{name} must be [S,FH,FW] = [{S},{FH},{FW}] (or [S,1,FH,FW]) for this pool, got {tuple(maps[name].shape)}')
+            mdev[name] = t
+        if not mdev:
+            form = 'weighted'
     _chk(pool, 'pool', pool.dtype)
     _chk(proj_pool, 'proj_pool')
+    for name, t in mdev.items():
+        _chk(t, name)
     if form == 'gather' and not host:                                             # a device list: used as it is, the kernel guards it
         _chk(view_slot, 'view_slot', torch.int32)
         if view_slot.dim() != 2 or view_slot.shape[0] < 1 or view_slot.shape[1] < 1:
@@ -1129,11 +1192,12 @@ def _pooled_lift(form, mode, pool, proj_pool, new_origin, crop_hw, voxel_size, v
         if form == 'lists':
             rc = fn(C.byref(d), C.byref(l), *tensors)
         else:
+            extra = (C.byref(_lib.LiftMaps(_ptr(mdev.get('pixel_weight')), _ptr(mdev.get('depth')), *gate)),) if form == 'mapped' else ()
             pf = p0 + 4 * len(host)                                                # the floats: weights [S] (when they came as a host list), then decay [B]
             n_w = S if (wdev is None and wts is not None) else 0
             w = _lib.LiftWeights(_ptr(wdev) if wdev is not None else (pf if n_w else None), (pf + 4 * n_w) if decay is not None else None,
                                  float(forget_below), _ptr(wsum) if mode == _LIFT_ACCUM else None)
-            rc = fn(C.byref(d), C.byref(l), C.byref(w), *tensors)
+            rc = fn(C.byref(d), C.byref(l), C.byref(w), *extra, *tensors)
     check(rc, export)
     return vol, valid
 

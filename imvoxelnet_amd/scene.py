@@ -53,15 +53,31 @@ the new origin, so a scrolled scene is, bit for bit, a scene opened at the new o
 nothing fades.  Like bilinear sampling and fading it is an extra outside the reference-parity claims; a session that never scrolls runs the code
 it ran before.  Models with an Anchor3DHead refuse: their anchors are fixed in the LiDAR frame.
 
+Pixel maps (add_views(..., pixel_weights=..., depths=...); open_scene(meta, ..., depth_gate=(behind, front))).  A weight per view scales a whole
+frame, but a person walking through the scan, the robot's own arm, lens dirt and the black border after undistortion are properties of pixels, and
+an RGB-D camera knows which voxels on a pixel's ray lie behind the surface it shows.  Sessions that take weights (decay= or window=) take two
+optional maps per view at feature resolution: a confidence map that multiplies the view's weight per pixel, and a depth map that, with the gate
+fixed at open, lets the view count at a voxel only where the voxel's depth d lies within D - front .. D + behind of the measured D (occlusion carving,
+or a truncation band; a pixel with no measurement -- 0, negative, NaN, inf -- gates nothing).  Both are read at the nearest pixel the voxel projects
+to, in the same single launch (ops.backproject_mapped_accum_ / _mean_, ivx_backproject_mapped_fwd; include/imvoxel.h has the definition).  Each map
+is one float32 tensor [V,FH,FW], host or device, or [V,H,W] at the padded input size, which is reduced by the strided pick map[:, ::s, ::s] with
+s = H // FH (pick_map: feature pixel (x, y) is input pixel (s*x, s*y), as in the projection rule; exact); add_views_u8 takes feature resolution only.
+Fading scenes consume the maps in the tick's launch and keep nothing.  Windowed scenes keep two device rings beside the feature ring ([W,FH,FW] fp32
+each, 77 KB per slot at 480 x 640; [N*W,FH,FW] in a batch, scene s owning slots s*W .. s*W+W-1), each allocated when its first map is given -- weights
+filled with 1, depths with 0 (no measurement) -- and a slot reused by a view without a map goes back to 1 / 0; eviction, remove_views and scroll need
+nothing further, because maps travel with slots and are per view, not per voxel.  depth_gate=None (the default) refuses depth maps; a plain session
+refuses both.  A session that never passes a map calls the ops it called before.
+
 How the module is laid out.  Every host rule is written once.  _SceneRecord is the host state of ONE scene (meta, view list, ids, stale flag, image
 size, window, decay, threshold) with the rules that need no device: the checks of meta / window / fading, reset, view_ids, remove_views, which slots
 of a range [base, base + W) a windowed add frees and fills, the id-to-slot lookup, the body of reweight.  The argument checks of an add (images,
-extrinsics, weights, image size), the weight-ring update, the trunk call and the detection tail are module functions.  A SceneSession IS such a
+extrinsics, weights, pixel maps, image size), the strided pick of a map, the weight-ring and map-ring updates, the trunk call and the detection tail are module functions.  A SceneSession IS such a
 record plus its own buffers and launches; a SceneBatch HOLDS N records (_scenes) plus its pools and launches.  Only the launches differ between
 the two, for a measured reason (profiles/scene_batch.md: the listed lift at one row is about 20 us slower than the plain one), so they stay in
 the classes, and nothing shared asks which class called it: wording that differs in a noun is passed in.
 
-Out of scope: decay on windowed scenes; per-pixel weight maps; scrolling by a fraction of a voxel or by a rotation (both would resample the state);
+Out of scope: decay on windowed scenes; resizing pixel maps through the add_views_u8 pipeline, a soft (ramp) or signed-distance gate, maps for plain
+sessions and for simple_test; scrolling by a fraction of a voxel or by a rotation (both would resample the state);
 scrolling a model with an Anchor3DHead (its boxes would have to be translated); scene batches across ranks; a model-level C handle for sessions
 (the state lives here, over the op-level ABI and the handle's sub-range calls).
 """
@@ -130,6 +146,69 @@ def _ring_weights(wring, size, slots, weights):
     return wring
 
 
+# ------------------------------------------------------------------ pixel maps: the host rules
+MAP_FILL = {'pixel_weights': 1.0, 'depths': 0.0}      # what a view without a map has: confidence 1 everywhere, no measurement anywhere
+
+
+def _check_map(t, name, V):
+    """A pixel map argument of an add before the trunk has run: None, or one float32 tensor [V,h,w] (host or device) -> the tensor."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f'{name} must be None or one float32 torch.Tensor [V,FH,FW] (or [V,H,W]), got {type(t).__name__}')
+    if t.dtype != torch.float32:
+        raise TypeError(f'{name} must be float32, got {t.dtype}')
+    if t.dim() != 3 or t.shape[0] != V:
+        raise ValueError(f'{name} must be [V,FH,FW] at feature resolution or [V,H,W] at the input size for the {V} views of this call, got {tuple(t.shape)}')
+    return t
+
+
+def pick_map(t, name, hw, fhw, strided=True):
+    """A checked map [V,h,w] at the feature resolution fhw = (FH, FW) of images of the padded size hw = (H, W): a map that has it is taken as it
+    is; one at the input size is reduced by the strided pick  map[:, ::s, ::s]  with s = H // FH -- feature pixel (x, y) is input pixel
+    (s*x, s*y), as in the model's projection rule -- which moves numbers and rounds nothing.  strided=False (frames resized on the device:
+    add_views_u8) takes feature resolution only.  Any other shape raises ValueError."""
+    (H, W), (FH, FW) = hw, fhw
+    if tuple(t.shape[1:]) == (FH, FW):
+        return t
+    s = H // FH
+    if strided and tuple(t.shape[1:]) == (H, W) and s >= 1 and W // FW == s and tuple(t[:, ::s, ::s].shape[1:]) == (FH, FW):
+        return t[:, ::s, ::s]
+    raise ValueError(f'{name} must be [V,{FH},{FW}] at feature resolution' + (f' or [V,{H},{W}] at the input size' if strided else
+                     ' (frames that are resized on the device take no maps at the input size)') + f', got {tuple(t.shape)}')
+
+
+def _ring_map(ring, size, fhw, dev, slots, maps, fill):
+    """The device ring [size,FH,FW] fp32 of one kind of map after a windowed add that put its views into `slots`: the ring (None until then, and
+    the re-lift without that map) starts with the first map given, filled with `fill`; from then on a reused slot takes its new view's map
+    (`fill` when the call gives none).  A ring of another feature size (after reset()) is dropped first.  maps: [len(slots),FH,FW] or None."""
+    if ring is not None and tuple(ring.shape[1:]) != tuple(fhw):
+        ring = None
+    if maps is not None and ring is None:
+        ring = torch.full((size,) + tuple(fhw), fill, dtype=torch.float32, device=dev)
+    if ring is not None:
+        idx = torch.tensor(list(slots), dtype=torch.int64).to(dev)
+        if maps is not None:
+            ring.index_copy_(0, idx, maps.to(dev))
+        else:
+            ring.index_fill_(0, idx, fill)
+    return ring
+
+
+def _lift_maps(pixel_weight, depth, gate):
+    """('mapped', the map arguments of the mapped ops) when a map is there, ('weighted', {}) otherwise: a scene that never sees a map calls the
+    weighted ops it called before maps existed."""
+    if pixel_weight is None and depth is None:
+        return 'weighted', {}
+    return 'mapped', dict(pixel_weight=pixel_weight, depth=depth, gate=gate if gate is not None else (math.inf, math.inf))
+
+
+def _maps_at(maps, hw, p0, strided=True):
+    """The checked maps of an add (pixel_weights, depths) at the resolution of the trunk's output p0 [V,1,FH,FW,C], on its device, contiguous."""
+    fhw = tuple(int(v) for v in p0.shape[-3:-1])
+    return tuple(None if t is None else pick_map(t, name, hw, fhw, strided).to(p0.device).contiguous() for t, name in zip(maps, MAP_FILL))
+
+
 # ------------------------------------------------------------------ scrolling: the host rules
 def scrolled_origin(origin, voxels, voxel_size):
     """The origin rule of a scroll, per component in fp32:  float32(origin) + float32(voxels) * float32(voxel_size)  -- the product is rounded,
@@ -170,11 +249,14 @@ def _detect(m, vol, valid, metas):
 class _SceneRecord:
     """The host state of one scene and every rule that needs no device.  meta: a complete simple_test meta of everything added; n_views;
     _views: the views of a windowed scene, oldest first, as (id, slot, extrinsic); _next_id: the id of the next arrival; _stale: the mean is
-    behind the state; _hw: the image size of the views in the scene; _window, _decay, _forget as opened.  No device buffers: a SceneSession
+    behind the state; _hw: the image size of the views in the scene; _window, _decay, _forget, _gate (the depth gate, None: depths are refused) as opened.  No device buffers: a SceneSession
     adds its own, a SceneBatch keeps pools beside N of these."""
 
-    def __init__(self, model, meta, window=None, decay=None, forget_below=0.0):
+    def __init__(self, model, meta, window=None, decay=None, forget_below=0.0, depth_gate=None):
         decay, forget_below = self._check_fading(window, decay, forget_below)
+        gate = None if depth_gate is None else ops.check_gate(depth_gate)
+        if gate is not None and window is None and decay is None:
+            raise ValueError('depth_gate needs a session that takes weights: open with decay=... (decay=1.0 fades nothing) or with window=W')
         if window is not None:
             if isinstance(window, bool) or not isinstance(window, (int, np.integer)):
                 raise TypeError(f'window must be None or an integer >= 1, got {window!r}')
@@ -198,7 +280,7 @@ class _SceneRecord:
         meta['lidar2img'] = l2i
         self.meta, self.n_views, self._hw, self._stale = meta, 0, None, False
         self._window, self._views, self._next_id = window, [], 0
-        self._decay, self._forget = decay, forget_below
+        self._decay, self._forget, self._gate = decay, forget_below, gate
         self._scrolled = (0, 0, 0)
 
     @staticmethod
@@ -266,6 +348,16 @@ class _SceneRecord:
         if weights is not None and self._window is None and self._decay is None:
             raise ValueError(f'this {what} was opened plain and takes no weights: open it with decay=1.0 (weights, nothing fades) or with window=W')
         return weights
+
+    def _take_maps(self, pixel_weights, depths, V, what):
+        """_check_map of both pixel maps of an add, the refusal of a scene opened plain (in the wording of the weights' refusal) and of depths on
+        a scene opened without depth_gate -> (pixel_weights, depths)."""
+        maps = tuple(_check_map(t, name, V) for t, name in zip((pixel_weights, depths), MAP_FILL))
+        if any(t is not None for t in maps) and self._window is None and self._decay is None:
+            raise ValueError(f'this {what} was opened plain and takes no pixel maps: open it with decay=1.0 (weights, nothing fades) or with window=W')
+        if maps[1] is not None and self._gate is None:
+            raise ValueError(f'this {what} was opened without depth_gate and takes no depths: open it with depth_gate=(behind, front)')
+        return maps
 
     def _check_shapes(self, shapes, have_views, where):
         """The img_shape / ori_shape / pad_shape of new frames (add_views_u8) against this meta's, once `where` ('scene' / 'batch') has views."""
@@ -346,14 +438,18 @@ class SceneSession(_SceneRecord):
     decay=lam in (0, 1] (unbounded sessions only): a fading scene -- a weight sum [1,X,Y,Z] fp32 beside (sum, count); every add_views call is one
     tick: the state is multiplied by lam once, voxels whose weight sum falls below forget_below (>= 0) are forgotten, then the call's views are
     added with their weights.  Decided here, not lazily: a session opened without decay runs the plain path and refuses weights.
+    depth_gate=(behind, front) (with decay= or window= only; two numbers >= 0, inf: no limit on that side): the gate of the depth maps that
+    add_views(..., depths=) may bring, fixed here like decay; None: depth maps are refused.  Pixel maps (the module docstring) need no state on a
+    fading session; a windowed one keeps a device ring [W,FH,FW] fp32 per kind of map from the first map it is given.
     The session is a _SceneRecord (the host state and its rules) with its own device buffers, camera uploads and launches."""
 
-    def __init__(self, model, meta, window=None, decay=None, forget_below=0.0):
-        super().__init__(model, meta, window, decay, forget_below)
+    def __init__(self, model, meta, window=None, decay=None, forget_below=0.0, depth_gate=None):
+        super().__init__(model, meta, window, decay, forget_below, depth_gate)
         self._model, self._closed = model, False
         self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
         # window=W: the rings, and the host ring of the slots' weights, None until a weight is given.  decay=lam: a weight sum beside sum / count
         self._ring = self._pring = self._wring = self._wsum = None
+        self._mring = self._dring = None          # window=W: the device rings of the slots' pixel-weight / depth maps [W,FH,FW], each None until a map is given
 
     # ------------------------------------------------------------------ state
     def _check_open(self):
@@ -364,28 +460,33 @@ class SceneSession(_SceneRecord):
         """Forget every view; the buffers are kept and the next add starts them from zero."""
         self._check_open()
         super().reset()
-        self._origin = self._crop = self._wring = None
+        self._origin = self._crop = self._wring = self._mring = self._dring = None
 
     def close(self):
         self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
-        self._ring = self._pring = self._wsum = self._wring = None
+        self._ring = self._pring = self._wsum = self._wring = self._mring = self._dring = None
         self._closed = True
 
     # ------------------------------------------------------------------ adding views
     def _features(self, img):
         return _trunk(self._model, img)
 
-    def add_views(self, img, extrinsics, emit=True, weights=None):
+    def add_views(self, img, extrinsics, emit=True, weights=None, pixel_weights=None, depths=None):
         """img [V,3,H,W] float32 on the device (normalised and padded as for simple_test), extrinsics: V float32 4x4 matrices.
         emit=False skips the store of the mean volume (detect() / volume() then compute it once from the sums): for callers that add
         many chunks between two detections.  Views count in the order they are added.  On a windowed session (window=W) the views go
         into free slots of the ring, the oldest views leaving first when the window is full; more than W views in one call raise
         ValueError; emit has no effect (the lift runs when volume() / detect() is asked and the set has changed).
         weights: one finite float >= 0 per view (None: 1; 0: the view does not count), on a session opened with decay= or window=.  On a fading
-        session every call is one tick: the state fades once by `decay`, then these views are added with their weights."""
-        return self._add_views(img, extrinsics, emit, {}, weights)
+        session every call is one tick: the state fades once by `decay`, then these views are added with their weights.
+        pixel_weights, depths (sessions that take weights; depths need depth_gate= at open): one float32 tensor each, host or device, [V,FH,FW] at
+        the resolution of the features or [V,H,W] at the size of img, which is reduced by the exact strided pick map[:, ::s, ::s], s = H // FH
+        (pick_map); other shapes raise ValueError.  A view's weight at a voxel is its weight times the confidence of the pixel the voxel
+        projects to; a pixel with a measured depth D lets the view count only at voxels of depth D - front .. D + behind (the module docstring,
+        "Pixel maps")."""
+        return self._add_views(img, extrinsics, emit, {}, weights, (pixel_weights, depths))
 
-    def _add_views(self, img, extrinsics, emit, shapes, weights=None):
+    def _add_views(self, img, extrinsics, emit, shapes, weights=None, maps=(None, None), strided=True):
         """add_views with the img_shape / ori_shape / pad_shape of these views (add_views_u8); the session changes only when the
         views are in: a call that raises leaves meta, state and n_views as they were."""
         self._check_open()
@@ -393,6 +494,7 @@ class SceneSession(_SceneRecord):
         E = _check_extrinsics(extrinsics, V)
         self._check_fits(V)
         weights = self._take_weights(weights, V, 'session')
+        maps = self._take_maps(*maps, V, 'session')
         _check_size((H, W), self._hw, 'scene')
         meta = dict(self.meta, **shapes)
         if 'img_shape' not in meta or 'ori_shape' not in meta:
@@ -403,22 +505,24 @@ class SceneSession(_SceneRecord):
         if m._prepared_device is None:
             m.prepare(img.device)
         p0 = self._features(img.contiguous())
+        maps = _maps_at(maps, (H, W), p0, strided)     # (a map of the wrong size raises here: the session has not changed yet)
         view_meta = dict(meta, lidar2img=dict(meta['lidar2img'], extrinsic=E))
         if self._origin is None:                  # new_origin and the crop do not depend on the views: uploaded once per scene
             proj, origin, crop = m._camera_setup([view_meta], 4, p0.device)
         else:
             proj, origin, crop = m._compute_projection(view_meta, 4)[None].contiguous().to(p0.device), self._origin, self._crop
         if self._window is not None:
-            self._add_windowed(p0, proj, E, (H, W), weights)
+            self._add_windowed(p0, proj, E, (H, W), weights, maps)
         else:
-            self._add_unbounded(p0, proj, origin, crop, E, (H, W), weights, emit)
+            self._add_unbounded(p0, proj, origin, crop, E, (H, W), weights, emit, maps)
         self._origin, self._crop = origin, crop
         self.meta.update(shapes)
         return self
 
-    def _add_unbounded(self, p0, proj, origin, crop, E, hw, weights, emit):
+    def _add_unbounded(self, p0, proj, origin, crop, E, hw, weights, emit, maps=(None, None)):
         """The new views' maps p0 [V,1,FH,FW,C] added to the running (sum, count) state in one launch: the plain lift, or one tick of the
-        weighted one on a fading session."""
+        weighted one on a fading session -- with the call's pixel maps [V,FH,FW], which are consumed here and not kept (no map: the weighted
+        launch as it was)."""
         m = self._model
         if self._sum is None:                     # the state, allocated once: sum fp32, count, mean in the storage type, valid
             X, Y, Z = m.n_voxels
@@ -429,17 +533,20 @@ class SceneSession(_SceneRecord):
             self._valid = torch.empty((1, X, Y, Z), device=dev, dtype=torch.uint8)
             self._wsum = torch.empty((1, X, Y, Z), device=dev, dtype=torch.float32) if self._decay is not None else None
         if self._decay is not None:                # one tick: fade once, then this call's views with their weights (the call's maps are the pool)
-            ops.backproject_weighted_accum_(p0, proj[0], [list(range(len(E)))], weights, [0], [self.n_views == 0], [self._decay], origin, crop, m.voxel_size,
-                                            self._sum, self._wsum, self._count, self._mean if emit else None, self._valid if emit else None,
-                                            forget_below=self._forget, sampling=getattr(m, 'sampling', 'nearest'))
+            form, kw = _lift_maps(*maps, self._gate)
+            getattr(ops, f'backproject_{form}_accum_')(p0, proj[0], [list(range(len(E)))], weights, [0], [self.n_views == 0], [self._decay], origin, crop,
+                                                       m.voxel_size, self._sum, self._wsum, self._count, self._mean if emit else None,
+                                                       self._valid if emit else None, forget_below=self._forget,
+                                                       sampling=getattr(m, 'sampling', 'nearest'), **kw)
         else:
             ops.backproject_accum_(p0, proj, origin, crop, m.voxel_size, self._sum, self._count, self.n_views == 0,
                                    self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
         self._grow(E, hw, stale=not emit)
 
-    def _add_windowed(self, p0, proj, E, hw, weights):
-        """The new views' maps p0 [V,1,FH,FW,C] and projection rows proj [1,V,3,4] into free slots of the rings; the oldest views
-        leave first when the window is full.  Everything that can fail comes before the first change of the session."""
+    def _add_windowed(self, p0, proj, E, hw, weights, maps=(None, None)):
+        """The new views' maps p0 [V,1,FH,FW,C] and projection rows proj [1,V,3,4] into free slots of the rings, their pixel maps into the same
+        slots of the map rings; the oldest views leave first when the window is full.  Everything that can fail comes before the first
+        change of the session."""
         m, W = self._model, self._window
         X, Y, Z = m.n_voxels
         Cn, dev = p0.shape[-1], p0.device
@@ -454,6 +561,8 @@ class SceneSession(_SceneRecord):
             ring[s].copy_(p0[i])
             pring[s].copy_(proj[0, i])
         self._wring = _ring_weights(self._wring, W, slots, weights)
+        self._mring = _ring_map(self._mring, W, p0.shape[-3:-1], dev, slots, maps[0], MAP_FILL['pixel_weights'])
+        self._dring = _ring_map(self._dring, W, p0.shape[-3:-1], dev, slots, maps[1], MAP_FILL['depths'])
         self._ring, self._pring, self._mean, self._valid = ring, pring, mean, valid
         self._admit(kept, slots, E, hw)
 
@@ -504,19 +613,21 @@ class SceneSession(_SceneRecord):
             self.scroll(s)
         return tuple(s)
 
-    def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, **pipeline_kw):
+    def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
         (data.prepare_images_device; pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device) and fills img_shape / ori_shape /
-        pad_shape of the scene meta.  Later frames must come out at the same shapes.  weights as for add_views."""
+        pad_shape of the scene meta.  Later frames must come out at the same shapes.  weights as for add_views; pixel_weights and depths at
+        feature resolution [V,FH,FW] only (the frames are resized on the device; resizing maps with them is out of scope)."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
         E = _check_extrinsics(extrinsics, len(frames))
         self._check_fits(len(frames))
         weights = self._take_weights(weights, len(frames), 'session')
+        maps = self._take_maps(pixel_weights, depths, len(frames), 'session')
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)       # one multi-view sample
         self._check_shapes(shapes[0], self.n_views, 'scene')
-        return self._add_views(img[0], E, emit, shapes[0], weights)
+        return self._add_views(img[0], E, emit, shapes[0], weights, maps, strided=False)
 
     # ------------------------------------------------------------------ reading the scene
     def volume(self):
@@ -533,9 +644,11 @@ class SceneSession(_SceneRecord):
     def _refresh(self):
         """Bring the mean / valid buffers up to date with the state, in one launch."""
         m = self._model
-        if self._window is not None and self._wring is not None:      # the same lift with the weight ring: the weighted mean of the kept views
-            ops.backproject_weighted_mean_(self._ring, self._pring, [[v[1] for v in self._views]], self._wring, [0], self._origin, self._crop,
-                                           m.voxel_size, self._mean, self._valid, sampling=getattr(m, 'sampling', 'nearest'))
+        if self._window is not None and (self._wring is not None or self._mring is not None or self._dring is not None):
+            # the same lift with the weight ring and the map rings that exist: the weighted mean of the kept views (no map ring: the weighted launch)
+            form, kw = _lift_maps(self._mring, self._dring, self._gate)
+            getattr(ops, f'backproject_{form}_mean_')(self._ring, self._pring, [[v[1] for v in self._views]], self._wring, [0], self._origin, self._crop,
+                                                      m.voxel_size, self._mean, self._valid, sampling=getattr(m, 'sampling', 'nearest'), **kw)
         elif self._window is not None:                                # the set changed since the last lift: ONE gathered lift of the views in it, in order
             view_slot = torch.tensor([[v[1] for v in self._views]], dtype=torch.int32).to(self._ring.device)
             ops.backproject_gather_mean_(self._ring, self._pring, view_slot, self._origin, self._crop, m.voxel_size, self._mean, self._valid,
@@ -580,9 +693,13 @@ class SceneBatch:
     fp32 beside the sums, and ONE weighted listed lift per tick (ops.backproject_weighted_accum_).  Every add_views call is one tick FOR THE SCENES
     IT TOUCHES: only the touched scenes fade (each by its own decay); a scene that gets no view in a call is neither read nor written, so its
     state does not age.  A caller who wants wall-clock fading gives every scene a view (or a zero-weight view) per tick.  A windowed batch takes
-    weights and reweight(scene, ids, weights); its re-lift is then the weighted mean of the kept views (a host weight ring [N*W])."""
+    weights and reweight(scene, ids, weights); its re-lift is then the weighted mean of the kept views (a host weight ring [N*W]).
 
-    def __init__(self, model, metas, window=None, decay=None, forget_below=0.0):
+    Pixel maps (open_scenes(metas, ..., depth_gate=(behind, front)), add_views(..., pixel_weights=, depths=); SceneSession has the rules): one gate for
+    every scene; row t of a map tensor belongs to view t of the call.  A fading batch passes the call's maps to the tick's one launch; a windowed
+    batch keeps device rings [N*W,FH,FW] beside the feature ring, scene s owning slots s*W .. s*W+W-1 as for the features."""
+
+    def __init__(self, model, metas, window=None, decay=None, forget_below=0.0, depth_gate=None):
         metas = list(metas)
         if not metas:
             raise ValueError('open_scenes needs at least one scene meta')
@@ -591,8 +708,9 @@ class SceneBatch:
             raise ValueError(f'{len(decays)} decays for {len(metas)} scenes (one value for all, or one per scene)')
         if any(d is None for d in decays) and any(d is not None for d in decays):
             raise ValueError('decay must be given for every scene of a batch or for none')
-        self._scenes = [_SceneRecord(model, meta, window, d, forget_below) for meta, d in zip(metas, decays)]      # checks every meta, window, decay and head_2d
+        self._scenes = [_SceneRecord(model, meta, window, d, forget_below, depth_gate) for meta, d in zip(metas, decays)]      # checks every meta, window, decay, gate and head_2d
         self._fading, self._forget, self._wsum, self._wring = decays[0] is not None, self._scenes[0]._forget, None, None
+        self._mring = self._dring = None          # windowed: the device rings of the slots' pixel maps [N*W,FH,FW], each None until a map is given
         self._model, self._window, self._N = model, self._scenes[0]._window, len(metas)
         self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
         self._hw, self._closed = None, False
@@ -637,7 +755,7 @@ class SceneBatch:
         return self
 
     def close(self):
-        self._sum = self._count = self._mean = self._valid = self._ring = self._pring = self._wsum = self._wring = None
+        self._sum = self._count = self._mean = self._valid = self._ring = self._pring = self._wsum = self._wring = self._mring = self._dring = None
         self._closed = True
 
     def remove_views(self, scene, ids):
@@ -688,26 +806,28 @@ class SceneBatch:
     def _features(self, img):
         return _trunk(self._model, img)
 
-    def add_views(self, img, extrinsics, scene, emit=True, weights=None):
+    def add_views(self, img, extrinsics, scene, emit=True, weights=None, pixel_weights=None, depths=None):
         """img [T,3,H,W] float32 on the device, extrinsics: T float32 4x4 matrices, scene: T scene indices -- view t belongs to scene
         scene[t]; the views of one scene count in the order given.  emit=False skips the store of the means (computed when asked).
         Windowed batch: more than W views for one scene in a call raise ValueError; emit has no effect.
-        weights: one finite float >= 0 per view, on a batch opened with decay= or window=.  Fading batch: one tick for the touched scenes only."""
-        return self._add_views(img, extrinsics, scene, emit, {}, weights=weights)
+        weights: one finite float >= 0 per view, on a batch opened with decay= or window=.  Fading batch: one tick for the touched scenes only.
+        pixel_weights, depths: one float32 tensor [T,FH,FW] or [T,H,W] each, as for SceneSession.add_views (row t is view t's map)."""
+        return self._add_views(img, extrinsics, scene, emit, {}, weights=weights, maps=(pixel_weights, depths))
 
-    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, **pipeline_kw):
+    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, **pipeline_kw):
         """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
-        ori_shape / pad_shape of every scene's meta, which later frames must reproduce."""
+        ori_shape / pad_shape of every scene's meta, which later frames must reproduce.  Pixel maps at feature resolution only."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
         E = _check_extrinsics(extrinsics, len(frames))
         groups = self._groups(scene, len(frames))
         weights = self._scenes[0]._take_weights(weights, len(frames), 'batch')
+        maps = self._scenes[0]._take_maps(pixel_weights, depths, len(frames), 'batch')
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
         for r in self._scenes:
             r._check_shapes(shapes[0], any(self.n_views), 'batch')
-        return self._add_views(img[0], E, scene, emit, shapes[0], groups, weights)
+        return self._add_views(img[0], E, scene, emit, shapes[0], groups, weights, maps, strided=False)
 
     def _groups(self, scene, T):
         """scene (T indices) -> {scene: [t, ...]} in first-touch order; the checks that need no device."""
@@ -720,13 +840,14 @@ class SceneBatch:
             self._scenes[s]._check_fits(len(ts), f' of scene {s}')
         return groups
 
-    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None, weights=None):
+    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None, weights=None, maps=(None, None), strided=True):
         self._check_open()
         T, H, W = _check_images(img, 'T')
         E = _check_extrinsics(extrinsics, T)
         if groups is None:
             groups = self._groups(scene, T)
         weights = self._scenes[0]._take_weights(weights, T, 'batch')      # (the scenes of a batch are opened alike)
+        maps = self._scenes[0]._take_maps(*maps, T, 'batch')
         _check_size((H, W), self._hw, 'batch')
         touched = sorted(groups)
         for s in touched:
@@ -739,6 +860,7 @@ class SceneBatch:
         if m._prepared_device is None:
             m.prepare(img.device)
         p0 = self._features(img.contiguous())                      # ONE trunk call over the T views of this tick
+        maps = _maps_at(maps, (H, W), p0, strided)                 # (a map of the wrong size raises here: the batch has not changed yet)
         # host camera set-up: one _compute_projection per touched scene; rows of proj in the order of the T views
         cpu = torch.device('cpu')
         proj_h, cam = torch.empty((T, 3, 4), dtype=torch.float32), {}
@@ -751,9 +873,9 @@ class SceneBatch:
             proj_h[torch.tensor(ts)] = p[0]
             cam[s] = (origin[0], crop[0])
         if self._window is not None:
-            self._add_windowed(p0, proj_h, groups, touched, E, (H, W), weights)
+            self._add_windowed(p0, proj_h, groups, touched, E, (H, W), weights, maps)
         else:
-            self._add_unbounded(p0, proj_h, groups, touched, cam, E, (H, W), weights, emit)
+            self._add_unbounded(p0, proj_h, groups, touched, cam, E, (H, W), weights, emit, maps)
         self._hw = (H, W)
         for r in self._scenes:
             r.meta.update(shapes)
@@ -773,9 +895,9 @@ class SceneBatch:
         crop = buf[T * 12 + B * 3:].view(torch.int32).view(B, 2)
         return proj, origin, crop
 
-    def _add_unbounded(self, p0, proj_h, groups, touched, cam, E, hw, weights, emit):
+    def _add_unbounded(self, p0, proj_h, groups, touched, cam, E, hw, weights, emit, maps=(None, None)):
         """The new maps p0 [T,1,FH,FW,C] added to the rows of the touched scenes in ONE listed launch (the call's maps are the pool): the plain
-        listed lift, or one tick of the weighted one on a fading batch."""
+        listed lift, or one tick of the weighted one on a fading batch, with the call's pixel maps [T,FH,FW] (consumed here, not kept)."""
         m, dev = self._model, p0.device
         proj, origin, crop = self._upload(dev, proj_h, [cam[s] for s in touched])
         X, Y, Z = m.n_voxels
@@ -789,18 +911,21 @@ class SceneBatch:
             self._wsum = torch.empty((N, X, Y, Z), device=dev, dtype=torch.float32) if self._fading else None
         lists, first = [groups[s] for s in touched], [self._scenes[s].n_views == 0 for s in touched]
         if self._fading:                          # one tick of the touched scenes: each fades by its own decay, the others are not read
-            ops.backproject_weighted_accum_(p0, proj, lists, weights, touched, first, [self._scenes[s]._decay for s in touched], origin, crop,
-                                            m.voxel_size, self._sum, self._wsum, self._count, self._mean if emit else None,
-                                            self._valid if emit else None, forget_below=self._forget, sampling=getattr(m, 'sampling', 'nearest'))
+            form, kw = _lift_maps(*maps, self._scenes[0]._gate)
+            getattr(ops, f'backproject_{form}_accum_')(p0, proj, lists, weights, touched, first, [self._scenes[s]._decay for s in touched], origin, crop,
+                                                       m.voxel_size, self._sum, self._wsum, self._count, self._mean if emit else None,
+                                                       self._valid if emit else None, forget_below=self._forget,
+                                                       sampling=getattr(m, 'sampling', 'nearest'), **kw)
         else:
             ops.backproject_lists_accum_(p0, proj, lists, touched, first, origin, crop, m.voxel_size, self._sum, self._count,
                                          self._mean if emit else None, self._valid if emit else None, sampling=getattr(m, 'sampling', 'nearest'))
         for s in touched:
             self._scenes[s]._grow([E[t] for t in groups[s]], hw, stale=not emit)
 
-    def _add_windowed(self, p0, proj_h, groups, touched, E, hw, weights):
-        """The new maps and projection rows into free slots of their scenes' parts of the rings (one index_copy_ each); the oldest views
-        of a full scene leave first.  Everything that can fail comes before the first change of the batch."""
+    def _add_windowed(self, p0, proj_h, groups, touched, E, hw, weights, maps=(None, None)):
+        """The new maps and projection rows into free slots of their scenes' parts of the rings (one index_copy_ each), the pixel maps into the
+        same slots of the map rings; the oldest views of a full scene leave first.  Everything that can fail comes before the first change
+        of the batch."""
         m, W, N = self._model, self._window, self._N
         X, Y, Z = m.n_voxels
         Cn, dev = p0.shape[-1], p0.device
@@ -819,6 +944,8 @@ class SceneBatch:
         ring.index_copy_(0, idx, p0)
         pring.index_copy_(0, idx, proj_h.to(dev))
         self._wring = _ring_weights(self._wring, N * W, slot_of, weights)
+        self._mring = _ring_map(self._mring, N * W, p0.shape[-3:-1], dev, slot_of, maps[0], MAP_FILL['pixel_weights'])
+        self._dring = _ring_map(self._dring, N * W, p0.shape[-3:-1], dev, slot_of, maps[1], MAP_FILL['depths'])
         self._ring, self._pring, self._mean, self._valid = ring, pring, mean, valid
         for s in touched:
             self._scenes[s]._admit(*placed[s], [E[t] for t in groups[s]], hw)
@@ -833,9 +960,10 @@ class SceneBatch:
         if self._window is not None:
             _, origin, crop = self._upload(self._ring.device, None, [self._cam[s] for s in stale])
             lists = [[v[1] for v in self._scenes[s]._views] for s in stale]
-            if self._wring is not None:
-                ops.backproject_weighted_mean_(self._ring, self._pring, lists, self._wring, stale, origin, crop, m.voxel_size, self._mean, self._valid,
-                                               sampling=getattr(m, 'sampling', 'nearest'))
+            if self._wring is not None or self._mring is not None or self._dring is not None:
+                form, kw = _lift_maps(self._mring, self._dring, self._scenes[0]._gate)
+                getattr(ops, f'backproject_{form}_mean_')(self._ring, self._pring, lists, self._wring, stale, origin, crop, m.voxel_size, self._mean,
+                                                          self._valid, sampling=getattr(m, 'sampling', 'nearest'), **kw)
             else:
                 ops.backproject_lists_mean_(self._ring, self._pring, lists, stale, origin, crop, m.voxel_size, self._mean, self._valid,
                                             sampling=getattr(m, 'sampling', 'nearest'))

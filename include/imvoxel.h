@@ -43,7 +43,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * views listed by slot, for sliding-window scenes; 470 = 0.4.7: ivx_backproject_lists_fwd, the listed lift with per-sample rows and `first` flags, for
  * batches of scenes and ragged batches; 480 = 0.4.8: ivx_backproject_weighted_fwd / ivx_volume_wmean_fwd, the listed lift with per-view weights,
  * per-sample decay and a forgetting threshold, for fading scenes; 490 = 0.4.9: ivx_volume_scroll_fwd, the in-place voxel shift of rows of the state
- * pools, for scrolling scenes) and the message of the last failing call on this thread (never NULL). */
+ * pools, for scrolling scenes; 500 = 0.5.0: ivx_backproject_mapped_fwd, the weighted lift with a per-pixel confidence map and a gated depth map
+ * per view) and the message of the last failing call on this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
 
@@ -701,6 +702,56 @@ int ivx_backproject_weighted_fwd(const ivx_backproject_desc *d, const ivx_lift_l
                                  int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream);
 int ivx_volume_wmean_fwd(const float *volume_sum, const float *wsum, int64_t n_voxels, int32_t C, void *out, int32_t out_dtype, uint8_t *valid,
                          ivx_stream_t stream);
+
+/* (0.5.0) Pixel maps for the weighted listed lift: every view may bring a per-pixel confidence and a measured depth per pixel, both at feature
+ * resolution, and the lift honours them in its one launch.  The confidence multiplies the view's weight per pixel (a person walking through the
+ * scan, the robot's own arm, the black border after undistortion); the depth, with a gate (behind, front), lets a view count at a voxel only
+ * where the voxel lies within the gate of the surface the pixel shows (occlusion carving, or a truncation band, for RGB-D cameras) instead of
+ * smearing the pixel's feature along its whole ray.  It is ivx_backproject_weighted_fwd with one more struct; like the bilinear rule, fading
+ * and scrolling it lies outside the reference-parity claims and is pinned to an fp64 reference written from the definition below
+ * (tests/ref_unproject_maps.py).
+ *
+ * Definition.  Everything in the definition of ivx_backproject_weighted_fwd stays: start, fade, forget, store, both modes, both sampling rules,
+ * both storage types, rows, `first`, guards.  Only step 3, "a view counts", gains two tests.  Both are evaluated at the NEAREST pixel (xr, yr) =
+ * (rint(u / d), rint(v / d)), the pixel the validity rule rounds to -- under the bilinear rule as well: the mask is the nearest rule's, and so
+ * are the maps.  Every operation is fp32, round-to-nearest, no contraction.
+ *   As before: the view's slot is in [0, S); its weight wv = view_weight[slot] passes wv > 0 && wv < inf; the view sees the voxel, with third
+ *              homogeneous coordinate d -- the d of the validity test; with the usual intrinsic (last row 0 0 1) the depth along the optical
+ *              axis in the extrinsic's units.
+ *   3a. gate   (depth != NULL)  D = depth[slot, yr, xr].  If D > 0 && D < inf (a measurement) the view counts only if d <= D + behind and
+ *              d >= D - front; the sum and the difference are each rounded once.  A pixel without a measurement (0, negative, NaN, +inf)
+ *              gates nothing.
+ *   3b. weight w = wv * pixel_weight[slot, yr, xr], one rounded product (w = wv when the map is NULL).  The view counts only if
+ *              w > 0 && w < inf.
+ *   Then, as before:  S = fma(w, sample, S),  W = W + w,  ++cnt.
+ * No address depends on a map's value, and the map addresses are formed from slot and pixel only after the validity test has passed: unlisted
+ * slots of the maps, and pixels no voxel projects to, are never read.
+ *
+ * m->pixel_weight  DEVICE [S, FH, FW] fp32, indexed by slot like the pools; NULL: 1 everywhere
+ * m->depth         DEVICE [S, FH, FW] fp32, in the units of the third homogeneous coordinate; NULL: no gate
+ * m->behind, m->front  >= 0, may be +inf (no limit on that side), never NaN; read only when depth != NULL
+ * Everything else as for ivx_backproject_weighted_fwd.
+ *
+ * Properties that follow from the definition.
+ *   No maps.       m == NULL, or both pointers NULL, launches the kernel of ivx_backproject_weighted_fwd and gives its bits.
+ *   Neutral maps.  A pixel_weight of all ones gives, bit for bit, ivx_backproject_weighted_fwd (wv * 1 is wv).  So does a depth of nothing but
+ *                  non-measurements, and so does any depth with behind = front = +inf.
+ *   Constant map.  pixel_weight[slot] == c everywhere is bit for bit ivx_backproject_weighted_fwd with view_weight[slot] replaced by the
+ *                  rounded wv * c.
+ *   Blocked view.  A pixel_weight that is 0, NaN, negative or +inf on every pixel of a slot is bit for bit the call with that view not listed;
+ *                  so is a gate that excludes every voxel the view sees.
+ *   Power of two.  Scaling every pixel_weight by 2^k keeps the mean and the mask bit-identical and scales the sums and wsum exactly
+ *                  (barring overflow and underflow).
+ * IVX_ERR_INVALID_ARG before any launch: everything ivx_backproject_weighted_fwd rejects; depth != NULL with a behind or front that is
+ * negative or NaN.                                                                                                                       */
+typedef struct ivx_lift_maps {
+  const float *pixel_weight; /* DEVICE [S, FH, FW] fp32, indexed by slot like the pools; NULL = 1 everywhere */
+  const float *depth;        /* DEVICE [S, FH, FW] fp32, same units as the third homogeneous coordinate; NULL = no gate */
+  float behind, front;       /* >= 0, may be +inf (no limit on that side), never NaN; read only when depth != NULL */
+} ivx_lift_maps;
+int ivx_backproject_mapped_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const ivx_lift_weights *w, const ivx_lift_maps *m,
+                               const void *feat_pool, const float *proj_pool, const float *new_origin /*[B,3]*/, const int32_t *crop_hw /*[B,2]*/,
+                               void *volume, int32_t *count, void *mean_out, uint8_t *valid, ivx_stream_t stream);
 
 /* (0.4.9) In-place voxel shift of rows of the state pools: a scene's grid moves with its platform (scrolling scenes: scene.py,
  * SceneSession.scroll / SceneBatch.scroll).  Moving the state by whole voxels is a pure move of bits, and everything a scene does afterwards is
