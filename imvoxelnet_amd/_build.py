@@ -24,6 +24,7 @@ SOURCES = [
     ('pool_layout.hip', []),
     ('backproject.hip', ['-ffp-contract=off']),
     ('volume_scroll.hip', []),
+    ('view_coverage.hip', ['-ffp-contract=off']),
     ('anchor_tail.hip', ['-ffp-contract=off']),
     ('preprocess.hip', ['-ffp-contract=off']),
     ('dcn.hip', []),
@@ -50,7 +51,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, 'ivx_common.h'),
+    headers = [os.path.join(CSRC, 'ivx_common.h'), os.path.join(CSRC, 'lift_geometry.h'),
                os.path.join(os.path.dirname(os.path.dirname(CSRC)), 'include', 'imvoxel.h')]
     objs, jobs = [], []
     for entry in SOURCES:

@@ -67,6 +67,10 @@ def sampling_id(sampling):
         raise ValueError(f"sampling must be 'nearest' or 'bilinear', got {sampling!r}") from None
 
 
+# what the state of a scene is to ivx_view_coverage_fwd: IVX_STATE_NONE (an empty scene) | _COUNT (int32 view counts) | _WSUM (fp32 weight sums) | _MASK (uint8 valid)
+STATE_NONE, STATE_COUNT, STATE_WSUM, STATE_MASK = 0, 1, 2, 3
+
+
 class BackprojectDesc(C.Structure):
     """ivx_backproject_desc (ivx_backproject_fwd_ex, ivx_backproject_gather_fwd)."""
     _fields_ = [(n, C.c_int32) for n in ('B', 'V', 'FH', 'FW', 'C', 'X', 'Y', 'Z')] + [('voxel_size', C.c_float * 3)] + \
@@ -167,6 +171,7 @@ EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor'
            'ivx_maxpool2d_fwd', 'ivx_maxpool2d_fwd_bf16', 'ivx_maxpool2d_fwd_fp8', 'ivx_global_avgpool_fwd', 'ivx_global_avgpool_fwd_bf16', 'ivx_upsample_trilinear2x_fwd', 'ivx_dcn_im2col_fwd', 'ivx_dcn_im2col_fwd_bf16', 'ivx_dcn_im2col_fwd_pair', 'ivx_nchw_to_nhwc', 'ivx_image_s2d_bf16', 'ivx_nhwc_to_nchw', 'ivx_backproject_mean_fwd', 'ivx_backproject_mean_fwd_amax', 'ivx_backproject_amax_blocks', 'ivx_backproject_mean_fwd_bf16', 'ivx_upsample_trilinear2x_fwd_bf16', 'ivx_backproject_sum_fwd', 'ivx_volume_normalize_fwd',
            'ivx_backproject_accum_fwd', 'ivx_backproject_accum_fwd_bf16', 'ivx_volume_mean_fwd', 'ivx_backproject_fwd_ex', 'ivx_backproject_gather_fwd',
            'ivx_backproject_lists_fwd', 'ivx_backproject_weighted_fwd', 'ivx_volume_wmean_fwd', 'ivx_volume_scroll_fwd', 'ivx_backproject_mapped_fwd',
+           'ivx_view_coverage_fwd',
            'ivx_anchor_head_workspace_bytes', 'ivx_anchor_head_get_bboxes', 'ivx_fcos_head_workspace_bytes',
            'ivx_fcos_head_level_candidates', 'ivx_nms_workspace_bytes',
            'ivx_nms_bev', 'ivx_boxes_overlap_bev', 'ivx_aligned_3d_nms', 'ivx_aligned_3d_nms_workspace_bytes', 'ivx_aligned_3d_nms_ws', 'ivx_multiclass_nms_workspace_bytes', 'ivx_multiclass_nms_bev',
@@ -291,6 +296,8 @@ def lib():
     if hasattr(L, 'ivx_backproject_mapped_fwd'):   # (0.5.0; an older build still loads: ops.backproject_mapped_accum_ / _mean_ and the scenes' pixel maps then refuse)
         L.ivx_backproject_mapped_fwd.argtypes = [C.POINTER(BackprojectDesc), C.POINTER(LiftLists), C.POINTER(LiftWeights), C.POINTER(LiftMaps), vp, vp, vp, vp, vp, vp, vp,
                                                  vp, vp]
+    if hasattr(L, 'ivx_view_coverage_fwd'):        # (0.5.1; an older build still loads: ops.view_coverage and the scenes' coverage() / min_novelty= then refuse)
+        L.ivx_view_coverage_fwd.argtypes = [C.POINTER(BackprojectDesc), C.POINTER(LiftLists), C.POINTER(LiftMaps), vp, vp, vp, vp, i32, f32, vp, vp]
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

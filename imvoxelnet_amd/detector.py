@@ -363,7 +363,10 @@ class ImVoxelNet(nn.Module):
         with unit weights holds the bits of a plain session.  A session opened without decay refuses weights.  Sessions that take weights also
         take pixel maps, add_views(..., pixel_weights=..., depths=...): a confidence per pixel and, with depth_gate=(behind, front) given
         here (two numbers >= 0, inf allowed), a measured depth per pixel that lets a view count only at voxels within the gate of the surface
-        the pixel shows (scene.py, "Pixel maps").  depth_gate=None: depth maps are refused."""
+        the pixel shows (scene.py, "Pixel maps").  depth_gate=None: depth maps are refused.  Every session answers coverage(extrinsics) --
+        per candidate pose the voxels the lift would count it at and those of them the scene has no evidence for yet, one small launch, no
+        trunk -- and add_views(..., min_novelty=m) uses it as a keyframe gate that drops redundant views before the trunk runs (scene.py,
+        "View coverage and the keyframe gate")."""
         from .scene import SceneSession
         return SceneSession(self, meta, window=window, decay=decay, forget_below=forget_below, depth_gate=depth_gate)
 
@@ -373,7 +376,9 @@ class ImVoxelNet(nn.Module):
         metas: one scene meta per scene (intrinsic, origin and box type may differ; image size and model are common).  window as for
         open_scene, per scene.  Every scene's volume is exact; what is not claimed is in the SceneBatch docstring.  decay (one value for
         every scene or one per scene) and forget_below as for open_scene; in a batch only the scenes a call touches fade.  depth_gate (one gate
-        for every scene) and the pixel maps of add_views as for open_scene."""
+        for every scene) and the pixel maps of add_views as for open_scene.  coverage(extrinsics, scene) counts what candidate views of any
+        subset of the scenes would add in ONE launch, and add_views(..., min_novelty=m) gates a tick's views with it: a scene whose views are
+        all rejected is untouched and does not fade."""
         from .scene import SceneBatch
         return SceneBatch(self, metas, window=window, decay=decay, forget_below=forget_below, depth_gate=depth_gate)
 

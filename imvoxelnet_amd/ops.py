@@ -1334,6 +1334,100 @@ def volume_scroll_(vol_sum, count, rows, shifts, wsum=None):
     return vol_sum, count
 
 
+_STATE_KIND = {torch.int32: _lib.STATE_COUNT, torch.float32: _lib.STATE_WSUM, torch.uint8: _lib.STATE_MASK, torch.bool: _lib.STATE_MASK}
+MAX_COVERAGE_VIEWS = 256      # candidates per sample of one view_coverage call (the kernel's counters live in LDS)
+
+
+def view_coverage(proj_pool, lists, rows, new_origin, crop_hw, voxel_size, n_voxels, fhw, state=None, fresh_below=1.0, pixel_weight=None, depth=None,
+                  gate=None, out=None):
+    """View coverage (ivx_view_coverage_fwd; include/imvoxel.h has the definition): for sample b (a scene) and each candidate view of lists[b] --
+    slots of proj_pool [S,3,4], -1 pads -- the number of voxels of the grid n_voxels = (X, Y, Z) at (new_origin[b], crop_hw[b], voxel_size) the
+    lift would count the view at, and how many of those hold less than fresh_below of evidence in row rows[b] of `state`.  The decision is the
+    lift's own, bit for bit, with the maps pixel_weight / depth [S,FH,FW] (or [S,1,FH,FW]; None: no map) and gate = (behind, front) (None: no
+    limit) of backproject_mapped_accum_; fhw = (FH, FW) is the feature-map size the crop is clamped to.  state: None (an empty scene: every seen
+    voxel is fresh; R = max(rows) + 1), or a device tensor [R,X,Y,Z]: int32 view counts, float32 weight sums, or uint8 / bool valid mask.  fresh =
+    not (evidence >= fresh_below); fresh_below finite and > 0.  lists and rows are host lists, checked as the listed lifts check them (rows
+    distinct and in range) and uploaded in ONE copy; nothing but the result is written.  out: a device int32 tensor [B,V,2] to write into (V = the
+    longest list), zeroed by the call.  Returns out [B,V,2] int32 on the device: (seen, fresh) per candidate, (0, 0) for padding.  Integer
+    counting: the result does not depend on the order of arrival.  Every argument error is raised before any launch."""
+    if not isinstance(proj_pool, torch.Tensor):
+        raise TypeError('proj_pool must be a torch.Tensor')
+    if proj_pool.dim() != 3 or tuple(proj_pool.shape[1:]) != (3, 4) or proj_pool.shape[0] < 1:
+        raise ValueError(f'proj_pool must be [S,3,4] with S >= 1, got {tuple(proj_pool.shape)}')
+    S = int(proj_pool.shape[0])
+    if isinstance(lists, torch.Tensor) or not hasattr(lists, '__len__') or len(lists) < 1:
+        raise TypeError('lists must be a host list of B >= 1 lists of slots')
+    lists = [_host_ints(l, f'lists[{b}]') for b, l in enumerate(lists)]
+    B = len(lists)
+    bad = sorted({v for l in lists for v in l if v != -1 and not 0 <= v < S})
+    if bad:
+        raise ValueError(f'lists hold slots outside [0, {S}) other than the padding -1: {bad}')
+    V = max(1, max(len(l) for l in lists))
+    if V > MAX_COVERAGE_VIEWS:
+        raise ValueError(f'{V} candidate views for one sample (at most {MAX_COVERAGE_VIEWS} per call)')
+    rows = _host_ints(rows, 'rows', B)
+    if len(set(rows)) != B:
+        raise ValueError(f'rows must be distinct (two samples on one row race), got {rows}')
+    X, Y, Z = _host_ints(n_voxels, 'n_voxels', 3)
+    FH, FW = _host_ints(fhw, 'fhw', 2)
+    if min(X, Y, Z, FH, FW) < 1:
+        raise ValueError(f'n_voxels and fhw must be positive, got {(X, Y, Z)} and {(FH, FW)}')
+    if state is None:
+        kind, R = _lib.STATE_NONE, max(rows) + 1
+    else:
+        if not isinstance(state, torch.Tensor):
+            raise TypeError('state must be None or a torch.Tensor [R,X,Y,Z]')
+        if state.dtype not in _STATE_KIND:
+            raise TypeError(f'state must be int32 (counts), float32 (weight sums) or uint8 / bool (valid mask), got {state.dtype}')
+        if state.dim() != 4 or tuple(state.shape[1:]) != (X, Y, Z):
+            raise ValueError(f'state must be [R,X,Y,Z] = [R,{X},{Y},{Z}] for this grid, got {tuple(state.shape)}')
+        kind, R = _STATE_KIND[state.dtype], int(state.shape[0])
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}' if state is not None else f'rows must be >= 0, got {rows}')
+    if isinstance(fresh_below, bool) or not hasattr(fresh_below, '__float__') or isinstance(fresh_below, torch.Tensor) \
+            or not (math.isfinite(float(fresh_below)) and float(fresh_below) > 0):
+        raise ValueError(f'fresh_below must be a finite number > 0, got {fresh_below!r}')
+    gate = check_gate(gate) if gate is not None else (math.inf, math.inf)
+    mdev = {}
+    for name, t in (('pixel_weight', pixel_weight), ('depth', depth)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be None or a torch.Tensor [S,FH,FW]')
+        if t.dim() == 4 and t.shape[1] == 1:
+            t = t[:, 0]
+        if tuple(t.shape) != (S, FH, FW):
+            raise ValueError(f'{name} must be [S,FH,FW] = [{S},{FH},{FW}] (or [S,1,FH,FW]) for this pool, got {tuple(t.shape)}')
+        mdev[name] = t
+    if out is not None and (not isinstance(out, torch.Tensor) or tuple(out.shape) != (B, V, 2)):
+        raise ValueError(f'out must be an int32 tensor [B,V,2] = [{B},{V},2]')
+    _chk(proj_pool, 'proj_pool')
+    for name, t in mdev.items():
+        _chk(t, name)
+    _chk(new_origin, 'new_origin')
+    _chk(crop_hw, 'crop_hw', torch.int32)
+    if tuple(new_origin.shape) != (B, 3) or tuple(crop_hw.shape) != (B, 2):
+        raise ValueError('new_origin must be [B,3] and crop_hw [B,2] for the B lists')
+    if state is not None:
+        _chk(state, 'state', state.dtype)
+    if out is None:
+        out = torch.empty((B, V, 2), device=proj_pool.device, dtype=torch.int32)
+    else:
+        _chk(out, 'out', torch.int32)
+    fn = getattr(_lib.lib(), 'ivx_view_coverage_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_view_coverage_fwd (needs version 0.5.1)')
+    # the one upload: view_slot [B,V] (-1 padded), then row [B] (`dev` is released in stream order: the allocator reuses it after this launch)
+    dev = torch.tensor([v for l in lists for v in l + [-1] * (V - len(l))] + rows, dtype=torch.int32).to(proj_pool.device)
+    p0 = dev.data_ptr()
+    d = _lib.BackprojectDesc(B, V, FH, FW, 0, X, Y, Z, (C.c_float * 3)(*[float(v) for v in voxel_size]), 0, 0, 0, 0)
+    l = _lib.LiftLists(S, R, p0, p0 + 4 * B * V, None)
+    m = _lib.LiftMaps(_ptr(mdev.get('pixel_weight')), _ptr(mdev.get('depth')), *gate)
+    check(fn(C.byref(d), C.byref(l), C.byref(m), _ptr(proj_pool), _ptr(new_origin), _ptr(crop_hw), _ptr(state), kind, float(fresh_below), _ptr(out), _stream()),
+          'ivx_view_coverage_fwd')
+    return out
+
+
 # ------------------------------------------------------------------ detection tail
 def anchor_head_get_bboxes(head_out, anchors, H, W, num_anchors, num_classes, offs, cfg, dir_offset=0.0,
                            dir_limit_offset=1.0, hw_transposed=False, want_candidates=False):

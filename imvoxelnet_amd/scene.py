@@ -68,6 +68,18 @@ filled with 1, depths with 0 (no measurement) -- and a slot reused by a view wit
 nothing further, because maps travel with slots and are per view, not per voxel.  depth_gate=None (the default) refuses depth maps; a plain session
 refuses both.  A session that never passes a map calls the ops it called before.
 
+View coverage and the keyframe gate (SceneSession.coverage(extrinsics) / SceneBatch.coverage(extrinsics, scene); add_views(..., min_novelty=m)).  Every
+frame that reaches add_views pays for the 2-D trunk, and most frames of a 30 Hz camera look at voxels the scene has fused already.  Whether a pose adds
+anything depends on the geometry and on the scene's state only, so it is counted before the trunk runs: coverage returns, per candidate pose, how many
+voxels the lift would count the view at (seen) and how many of those hold less than fresh_below of evidence (fresh) -- the view count of a plain
+session, the weight sum of a fading one, the valid mask of a windowed one -- in one small integer launch (ops.view_coverage, ivx_view_coverage_fwd;
+include/imvoxel.h has the definition) whose validity decision is the lift's own, bit for bit, with the confidence map and the gated depth when they
+are given.  add_views(..., min_novelty=m) with m in (0, 1] admits a view iff seen > 0 and fresh / seen >= m, tested against the state BEFORE the call
+(the views of one call do not see each other; a fading scene's coming fade is not anticipated), and drops the rejected views with their images,
+extrinsics, weights and maps before the trunk; a call whose views are all rejected launches nothing more and changes nothing -- no tick on a fading
+session, an untouched scene in a batch -- and last_admitted holds the verdicts (None after an ungated call).  min_novelty=None runs the code it ran
+before.
+
 How the module is laid out.  Every host rule is written once.  _SceneRecord is the host state of ONE scene (meta, view list, ids, stale flag, image
 size, window, decay, threshold) with the rules that need no device: the checks of meta / window / fading, reset, view_ids, remove_views, which slots
 of a range [base, base + W) a windowed add frees and fills, the id-to-slot lookup, the body of reweight.  The argument checks of an add (images,
@@ -76,7 +88,8 @@ record plus its own buffers and launches; a SceneBatch HOLDS N records (_scenes)
 the two, for a measured reason (profiles/scene_batch.md: the listed lift at one row is about 20 us slower than the plain one), so they stay in
 the classes, and nothing shared asks which class called it: wording that differs in a noun is passed in.
 
-Out of scope: decay on windowed scenes; resizing pixel maps through the add_views_u8 pipeline, a soft (ramp) or signed-distance gate, maps for plain
+Out of scope: a gate in which the views of one call see each other (sequential gating), anticipating a fading scene's next decay in coverage(),
+choosing which kept view of a window to evict; decay on windowed scenes; resizing pixel maps through the add_views_u8 pipeline, a soft (ramp) or signed-distance gate, maps for plain
 sessions and for simple_test; scrolling by a fraction of a voxel or by a rotation (both would resample the state);
 scrolling a model with an Anchor3DHead (its boxes would have to be translated); scene batches across ranks; a model-level C handle for sessions
 (the state lives here, over the op-level ABI and the handle's sub-range calls).
@@ -207,6 +220,57 @@ def _maps_at(maps, hw, p0, strided=True):
     """The checked maps of an add (pixel_weights, depths) at the resolution of the trunk's output p0 [V,1,FH,FW,C], on its device, contiguous."""
     fhw = tuple(int(v) for v in p0.shape[-3:-1])
     return tuple(None if t is None else pick_map(t, name, hw, fhw, strided).to(p0.device).contiguous() for t, name in zip(maps, MAP_FILL))
+
+
+# ------------------------------------------------------------------ view coverage and the keyframe gate: the host rules
+def _check_novelty(min_novelty, fresh_below, alone=False):
+    """The gate arguments of an add or of coverage() -> (min_novelty as a float or None, fresh_below as a float; None means 1.0: less than one
+    full-weight view's worth of evidence).  min_novelty must lie in (0, 1]; fresh_below must be finite and > 0 and, in an add (alone=False),
+    needs min_novelty."""
+    if fresh_below is not None and min_novelty is None and not alone:
+        raise ValueError('fresh_below belongs to the gate: give min_novelty with it')
+    if fresh_below is not None and (isinstance(fresh_below, bool) or not isinstance(fresh_below, (int, float, np.integer, np.floating))
+                                    or not (math.isfinite(fresh_below) and fresh_below > 0)):
+        raise ValueError(f'fresh_below must be None or a finite number > 0, got {fresh_below!r}')
+    if min_novelty is not None and (isinstance(min_novelty, bool) or not isinstance(min_novelty, (int, float, np.integer, np.floating))
+                                    or not 0 < min_novelty <= 1):
+        raise ValueError(f'min_novelty must be None or a number in (0, 1], got {min_novelty!r}')
+    return (None if min_novelty is None else float(min_novelty)), (1.0 if fresh_below is None else float(fresh_below))
+
+
+def admitted(counts, min_novelty):
+    """The gate's rule on coverage counts [K,2] (seen, fresh): view k is admitted iff seen > 0 and fresh / seen >= min_novelty, in Python
+    floats -> list of K bools."""
+    return [bool(int(s) > 0 and int(f) / int(s) >= min_novelty) for s, f in np.asarray(counts).reshape(-1, 2).tolist()]
+
+
+def _kept(keep, seq):
+    """The entries of a per-view argument of an add that the gate admitted: a list stays a list, a tensor is indexed along its first axis on
+    its own device, None stays None."""
+    idx = [i for i, k in enumerate(keep) if k]
+    if seq is None:
+        return None
+    if isinstance(seq, torch.Tensor):
+        return seq[torch.tensor(idx, dtype=torch.int64).to(seq.device)].contiguous()
+    return [seq[i] for i in idx]
+
+
+def _coverage_fhw(hw, meta):
+    """The feature-map size (FH, FW) coverage clamps the crop to and reads maps at, before any feature exists: the scene's known padded image
+    size // 4 (the stride of FPN level 0), else the meta's pad_shape // 4."""
+    if hw is None:
+        if 'pad_shape' not in meta:
+            raise ValueError('coverage before the first view needs the padded image size: give the scene meta a pad_shape (add_views_u8 fills it)')
+        hw = tuple(int(v) for v in meta['pad_shape'][:2])
+    return hw, (hw[0] // 4, hw[1] // 4)
+
+
+def _scene_device(model, *tensors):
+    """Where a scene's launches go before it has features: the device of a buffer it holds, else the model's, else the current HIP device."""
+    for t in tensors:
+        if t is not None:
+            return t.device
+    return model._prepared_device if model._prepared_device is not None else torch.device('cuda', torch.cuda.current_device())
 
 
 # ------------------------------------------------------------------ scrolling: the host rules
@@ -450,6 +514,7 @@ class SceneSession(_SceneRecord):
         # window=W: the rings, and the host ring of the slots' weights, None until a weight is given.  decay=lam: a weight sum beside sum / count
         self._ring = self._pring = self._wring = self._wsum = None
         self._mring = self._dring = None          # window=W: the device rings of the slots' pixel-weight / depth maps [W,FH,FW], each None until a map is given
+        self.last_admitted = None                 # the gate's verdict per view of the last add_views(..., min_novelty=) call; None after an ungated one
 
     # ------------------------------------------------------------------ state
     def _check_open(self):
@@ -471,8 +536,13 @@ class SceneSession(_SceneRecord):
     def _features(self, img):
         return _trunk(self._model, img)
 
-    def add_views(self, img, extrinsics, emit=True, weights=None, pixel_weights=None, depths=None):
+    def add_views(self, img, extrinsics, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None):
         """img [V,3,H,W] float32 on the device (normalised and padded as for simple_test), extrinsics: V float32 4x4 matrices.
+        min_novelty in (0, 1] (None: no gate, the code as it was): a keyframe gate.  Each view of the call is tested by coverage() against the
+        state BEFORE the call -- the views of one call do not see each other -- and is admitted iff seen > 0 and fresh / seen >= min_novelty
+        (Python floats; fresh_below as for coverage(), only together with min_novelty).  Rejected views are dropped before the trunk runs, with
+        their images, extrinsics, weights and maps; if none is admitted nothing is launched after the count and nothing changes (no tick on a
+        fading session).  last_admitted holds the verdicts, one bool per view of the call (None after an ungated call).
         emit=False skips the store of the mean volume (detect() / volume() then compute it once from the sums): for callers that add
         many chunks between two detections.  Views count in the order they are added.  On a windowed session (window=W) the views go
         into free slots of the ring, the oldest views leaving first when the window is full; more than W views in one call raise
@@ -484,11 +554,13 @@ class SceneSession(_SceneRecord):
         (pick_map); other shapes raise ValueError.  A view's weight at a voxel is its weight times the confidence of the pixel the voxel
         projects to; a pixel with a measured depth D lets the view count only at voxels of depth D - front .. D + behind (the module docstring,
         "Pixel maps")."""
-        return self._add_views(img, extrinsics, emit, {}, weights, (pixel_weights, depths))
+        return self._add_views(img, extrinsics, emit, {}, weights, (pixel_weights, depths), gate=_check_novelty(min_novelty, fresh_below))
 
-    def _add_views(self, img, extrinsics, emit, shapes, weights=None, maps=(None, None), strided=True):
+    def _add_views(self, img, extrinsics, emit, shapes, weights=None, maps=(None, None), strided=True, gate=(None, 1.0), verdict=None):
         """add_views with the img_shape / ori_shape / pad_shape of these views (add_views_u8); the session changes only when the
-        views are in: a call that raises leaves meta, state and n_views as they were."""
+        views are in: a call that raises leaves meta, state and n_views as they were.  gate = (min_novelty, fresh_below) as _check_novelty
+        returns them; verdict: the gate has run already (add_views_u8, before its pipeline), these views are the ones it admitted and this is
+        what last_admitted becomes."""
         self._check_open()
         V, H, W = _check_images(img, 'V')
         E = _check_extrinsics(extrinsics, V)
@@ -502,6 +574,13 @@ class SceneSession(_SceneRecord):
         if not img.is_cuda:
             raise RuntimeError('img must be a device (HIP) tensor; the MI355X path has no CPU fallback')
         m = self._model
+        if gate[0] is not None:                   # the keyframe gate: against the state before the call, before the trunk
+            verdict = admitted(self._coverage(E, maps, (H, W), meta, gate[1], strided, img.device), gate[0])
+            if not any(verdict):
+                self.last_admitted = verdict
+                return self
+            if not all(verdict):
+                img, E, weights, maps = _kept(verdict, img), _kept(verdict, E), _kept(verdict, weights), tuple(_kept(verdict, t) for t in maps)
         if m._prepared_device is None:
             m.prepare(img.device)
         p0 = self._features(img.contiguous())
@@ -517,7 +596,57 @@ class SceneSession(_SceneRecord):
             self._add_unbounded(p0, proj, origin, crop, E, (H, W), weights, emit, maps)
         self._origin, self._crop = origin, crop
         self.meta.update(shapes)
+        self.last_admitted = verdict
         return self
+
+    # ------------------------------------------------------------------ view coverage
+    def coverage(self, extrinsics, pixel_weights=None, depths=None, fresh_below=None):
+        """What would these K candidate views add?  extrinsics: K float32 4x4 matrices -> np.ndarray [K,2] int64, columns (seen, fresh): the
+        number of voxels of the scene's grid the lift would count the view at, and how many of those hold less than fresh_below of evidence
+        (None: 1.0, less than one full-weight view's worth).  One small launch and one device-to-host read, no trunk, no image
+        (ops.view_coverage, ivx_view_coverage_fwd): the decision is the lift's own, bit for bit, at the scene's origin and crop, by the model's
+        projection rule.  The evidence is the view count of a plain session, the weight sum of a fading one and the valid mask of a windowed
+        one (a kept view of weight 0 leaves its voxels fresh); an empty scene has none, so fresh == seen.  A fading session's state is read as
+        it is stored: the fade of its next tick is not anticipated.  A stale windowed scene refreshes first, with its one gathered lift -- the
+        only thing the call may change; views, state and meta stay as they are.
+        pixel_weights, depths: as for add_views ([K,FH,FW], or [K,H,W] at the input size through pick_map), accepted on every kind of
+        session because nothing is fused; depths need depth_gate= at open.  The feature-map size is the scene's image size // 4, before the
+        first view the meta's pad_shape // 4 (ValueError without one); the meta needs img_shape and ori_shape as in add_views."""
+        self._check_open()
+        extrinsics = list(extrinsics)
+        E = _check_extrinsics(extrinsics, len(extrinsics))
+        if not E:
+            raise ValueError('coverage needs at least one candidate view')
+        maps = tuple(_check_map(t, name, len(E)) for t, name in zip((pixel_weights, depths), MAP_FILL))
+        if maps[1] is not None and self._gate is None:
+            raise ValueError('this session was opened without depth_gate and takes no depths: open it with depth_gate=(behind, front)')
+        if 'img_shape' not in self.meta or 'ori_shape' not in self.meta:
+            raise ValueError('the scene meta needs img_shape and ori_shape (add_views_u8 fills them from its frames)')
+        return self._coverage(E, maps, self._hw, self.meta, _check_novelty(None, fresh_below, alone=True)[1])
+
+    def _coverage(self, E, maps, hw, meta, fresh_below, strided=True, dev=None):
+        """coverage() of checked arguments on the meta of the call (add_views_u8 brings shapes the scene's meta does not have yet); hw: the
+        padded image size, None: from the meta."""
+        m = self._model
+        hw, fhw = _coverage_fhw(hw, meta)
+        dev = _scene_device(m, self._origin, self._count, self._valid) if dev is None else dev
+        view_meta = dict(meta, lidar2img=dict(meta['lidar2img'], extrinsic=E))
+        if self._origin is None:
+            proj, origin, crop = m._camera_setup([view_meta], 4, dev)
+            proj = proj[0]
+        else:
+            proj, origin, crop = m._compute_projection(view_meta, 4).contiguous().to(dev), self._origin, self._crop
+        pw, dp = (None if t is None else pick_map(t, name, hw, fhw, strided).to(dev).contiguous() for t, name in zip(maps, MAP_FILL))
+        state = None
+        if self.n_views and self._window is not None:     # the evidence: the mask of the kept views (refreshed when stale) ...
+            self.volume()
+            state = self._valid
+        elif self.n_views:                                # ... or the weight sum / the view count of the running state
+            state = self._wsum if self._decay is not None else self._count
+        n = ops.MAX_COVERAGE_VIEWS
+        out = [ops.view_coverage(proj[k:k + n].contiguous(), [list(range(min(n, len(E) - k)))], [0], origin, crop, m.voxel_size, m.n_voxels, fhw, state, fresh_below,
+                                 None if pw is None else pw[k:k + n], None if dp is None else dp[k:k + n], self._gate)[0] for k in range(0, len(E), n)]
+        return (out[0] if len(out) == 1 else torch.cat(out)).cpu().numpy().astype(np.int64)
 
     def _add_unbounded(self, p0, proj, origin, crop, E, hw, weights, emit, maps=(None, None)):
         """The new views' maps p0 [V,1,FH,FW,C] added to the running (sum, count) state in one launch: the plain lift, or one tick of the
@@ -613,11 +742,14 @@ class SceneSession(_SceneRecord):
             self.scroll(s)
         return tuple(s)
 
-    def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, **pipeline_kw):
+    def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None,
+                     **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
         (data.prepare_images_device; pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device) and fills img_shape / ori_shape /
         pad_shape of the scene meta.  Later frames must come out at the same shapes.  weights as for add_views; pixel_weights and depths at
-        feature resolution [V,FH,FW] only (the frames are resized on the device; resizing maps with them is out of scope)."""
+        feature resolution [V,FH,FW] only (the frames are resized on the device; resizing maps with them is out of scope).  min_novelty /
+        fresh_below as for add_views: once the scene knows its shapes (it has had views) the gate runs before the pipeline, so a rejected
+        frame is not even resized; on the first call it runs after the pipeline, which is what tells the shapes."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
@@ -625,9 +757,17 @@ class SceneSession(_SceneRecord):
         self._check_fits(len(frames))
         weights = self._take_weights(weights, len(frames), 'session')
         maps = self._take_maps(pixel_weights, depths, len(frames), 'session')
+        gate, verdict = _check_novelty(min_novelty, fresh_below), None
+        if gate[0] is not None and self._hw is not None and 'img_shape' in self.meta and 'ori_shape' in self.meta:
+            verdict = admitted(self._coverage(E, maps, self._hw, self.meta, gate[1], strided=False), gate[0])
+            if not any(verdict):
+                self.last_admitted = verdict
+                return self
+            frames, E, weights, maps = _kept(verdict, frames), _kept(verdict, E), _kept(verdict, weights), tuple(_kept(verdict, t) for t in maps)
+            gate = (None, gate[1])
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)       # one multi-view sample
         self._check_shapes(shapes[0], self.n_views, 'scene')
-        return self._add_views(img[0], E, emit, shapes[0], weights, maps, strided=False)
+        return self._add_views(img[0], E, emit, shapes[0], weights, maps, strided=False, gate=gate, verdict=verdict)
 
     # ------------------------------------------------------------------ reading the scene
     def volume(self):
@@ -715,6 +855,7 @@ class SceneBatch:
         self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
         self._hw, self._closed = None, False
         self._cam = [None] * self._N              # per scene: host (new_origin [3], crop [2]) of its last add
+        self.last_admitted = None                 # the gate's verdict per view of the last add_views(..., min_novelty=) call; None after an ungated one
 
     # ------------------------------------------------------------------ state
     def _check_open(self):
@@ -806,17 +947,22 @@ class SceneBatch:
     def _features(self, img):
         return _trunk(self._model, img)
 
-    def add_views(self, img, extrinsics, scene, emit=True, weights=None, pixel_weights=None, depths=None):
+    def add_views(self, img, extrinsics, scene, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None):
         """img [T,3,H,W] float32 on the device, extrinsics: T float32 4x4 matrices, scene: T scene indices -- view t belongs to scene
         scene[t]; the views of one scene count in the order given.  emit=False skips the store of the means (computed when asked).
         Windowed batch: more than W views for one scene in a call raise ValueError; emit has no effect.
         weights: one finite float >= 0 per view, on a batch opened with decay= or window=.  Fading batch: one tick for the touched scenes only.
-        pixel_weights, depths: one float32 tensor [T,FH,FW] or [T,H,W] each, as for SceneSession.add_views (row t is view t's map)."""
-        return self._add_views(img, extrinsics, scene, emit, {}, weights=weights, maps=(pixel_weights, depths))
+        pixel_weights, depths: one float32 tensor [T,FH,FW] or [T,H,W] each, as for SceneSession.add_views (row t is view t's map).
+        min_novelty in (0, 1] / fresh_below: the keyframe gate of SceneSession.add_views, ONE coverage launch for all the T views against their
+        scenes' states before the call; rejected views are dropped before the trunk, a scene whose views are all rejected is untouched (and
+        does not fade), and last_admitted holds the T verdicts (None after an ungated call)."""
+        return self._add_views(img, extrinsics, scene, emit, {}, weights=weights, maps=(pixel_weights, depths), gate=_check_novelty(min_novelty, fresh_below))
 
-    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, **pipeline_kw):
+    def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None,
+                     fresh_below=None, **pipeline_kw):
         """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
-        ori_shape / pad_shape of every scene's meta, which later frames must reproduce.  Pixel maps at feature resolution only."""
+        ori_shape / pad_shape of every scene's meta, which later frames must reproduce.  Pixel maps at feature resolution only.  The gate
+        runs before the pipeline once the batch knows its shapes, after it on the first call."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
@@ -824,23 +970,87 @@ class SceneBatch:
         groups = self._groups(scene, len(frames))
         weights = self._scenes[0]._take_weights(weights, len(frames), 'batch')
         maps = self._scenes[0]._take_maps(pixel_weights, depths, len(frames), 'batch')
+        gate, verdict = _check_novelty(min_novelty, fresh_below), None
+        if gate[0] is not None and self._hw is not None and all('img_shape' in self._scenes[s].meta and 'ori_shape' in self._scenes[s].meta for s in groups):
+            verdict = admitted(self._coverage(E, groups, maps, self._hw, {}, gate[1], strided=False), gate[0])
+            if not any(verdict):
+                self.last_admitted = verdict
+                return self
+            frames, E, scene, weights = _kept(verdict, frames), _kept(verdict, E), _kept(verdict, list(scene)), _kept(verdict, weights)
+            maps, groups, gate = tuple(_kept(verdict, t) for t in maps), self._groups(scene, len(frames)), (None, gate[1])
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
         for r in self._scenes:
             r._check_shapes(shapes[0], any(self.n_views), 'batch')
-        return self._add_views(img[0], E, scene, emit, shapes[0], groups, weights, maps, strided=False)
+        return self._add_views(img[0], E, scene, emit, shapes[0], groups, weights, maps, strided=False, gate=gate, verdict=verdict)
 
-    def _groups(self, scene, T):
-        """scene (T indices) -> {scene: [t, ...]} in first-touch order; the checks that need no device."""
+    def _groups(self, scene, T, fit=True):
+        """scene (T indices) -> {scene: [t, ...]} in first-touch order; the checks that need no device (fit: the views are to be added, so
+        those of one scene must fit its window)."""
         if isinstance(scene, torch.Tensor) or not hasattr(scene, '__len__') or len(scene) != T:
             raise ValueError(f'scene must list one scene index per view: {T} views, got {scene!r}')
         groups = {}
         for t, s in enumerate(scene):
             groups.setdefault(self._scene_index(s), []).append(t)
         for s, ts in groups.items():
-            self._scenes[s]._check_fits(len(ts), f' of scene {s}')
+            if fit:
+                self._scenes[s]._check_fits(len(ts), f' of scene {s}')
         return groups
 
-    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None, weights=None, maps=(None, None), strided=True):
+    def coverage(self, extrinsics, scene, pixel_weights=None, depths=None, fresh_below=None):
+        """SceneSession.coverage for T candidate views of any subset of the scenes: extrinsics: T float32 4x4 matrices, scene: T scene indices
+        -> np.ndarray [T,2] int64 (seen, fresh) in the order of the call's views.  ONE launch (ops.view_coverage: ragged lists per scene,
+        rows equal to the scene indices) and one device-to-host read.  The evidence is the scenes' rows of the count pool (plain batch), of the
+        weight-sum pool (fading) or of the valid pool (windowed; the stale ones among the named scenes are lifted again first, in one launch);
+        a scene without views has none.  pixel_weights / depths: [T,FH,FW] or [T,H,W], row t is view t's map."""
+        self._check_open()
+        extrinsics = list(extrinsics)
+        E = _check_extrinsics(extrinsics, len(extrinsics))
+        if not E:
+            raise ValueError('coverage needs at least one candidate view')
+        groups = self._groups(scene, len(E), fit=False)
+        maps = tuple(_check_map(t, name, len(E)) for t, name in zip((pixel_weights, depths), MAP_FILL))
+        if maps[1] is not None and self._scenes[0]._gate is None:
+            raise ValueError('this batch was opened without depth_gate and takes no depths: open it with depth_gate=(behind, front)')
+        return self._coverage(E, groups, maps, self._hw, {}, _check_novelty(None, fresh_below, alone=True)[1])
+
+    def _coverage(self, E, groups, maps, hw, shapes, fresh_below, strided=True, dev=None):
+        """coverage() of checked arguments: groups {scene: [t, ...]} of the T views, shapes: the img_shape / ori_shape / pad_shape of frames that
+        are not in the metas yet (add_views_u8), hw: the padded image size, None: from the first named scene's meta."""
+        m, touched, T = self._model, sorted(groups), len(E)
+        metas = {s: dict(self._scenes[s].meta, **shapes) for s in touched}
+        for s in touched:
+            if 'img_shape' not in metas[s] or 'ori_shape' not in metas[s]:
+                raise ValueError('every scene meta needs img_shape and ori_shape (add_views_u8 fills them from its frames)')
+        hw, fhw = _coverage_fhw(hw, metas[touched[0]])
+        if max(len(groups[s]) for s in touched) > ops.MAX_COVERAGE_VIEWS:
+            raise ValueError(f'more than {ops.MAX_COVERAGE_VIEWS} candidate views of one scene in one call')
+        dev = _scene_device(m, self._count, self._valid) if dev is None else dev
+        cpu = torch.device('cpu')
+        proj_h, cams = torch.empty((T, 3, 4), dtype=torch.float32), []
+        for s in touched:                         # the host camera set-up of _add_views: rows of proj in the order of the T views
+            view_meta = dict(metas[s], lidar2img=dict(metas[s]['lidar2img'], extrinsic=[E[t] for t in groups[s]]))
+            p, origin, crop = m._camera_setup([view_meta], 4, cpu)
+            proj_h[torch.tensor(groups[s])] = p[0]
+            cams.append(self._cam[s] if self._cam[s] is not None else (origin[0], crop[0]))
+        proj, origin, crop = self._upload(dev, proj_h, cams)
+        pw, dp = (None if t is None else pick_map(t, name, hw, fhw, strided).to(dev).contiguous() for t, name in zip(maps, MAP_FILL))
+        with_views = [s for s in touched if self._scenes[s].n_views]
+        state = None
+        if with_views:                            # the evidence pool; the rows of named scenes without views hold nothing yet: zero is what they mean
+            if self._window is not None:
+                self._refresh(with_views)
+            state = self._valid if self._window is not None else self._wsum if self._fading else self._count
+            for s in touched:
+                if not self._scenes[s].n_views:
+                    state[s].zero_()
+        out =ops.view_coverage(proj, [groups[s] for s in touched], touched, origin, crop, m.voxel_size, m.n_voxels, fhw, state, fresh_below, pw, dp,
+                                self._scenes[0]._gate).cpu().numpy().astype(np.int64)
+        counts = np.zeros((T, 2), np.int64)
+        for i, s in enumerate(touched):
+            counts[groups[s]] = out[i, :len(groups[s])]
+        return counts
+
+    def _add_views(self, img, extrinsics, scene, emit, shapes, groups=None, weights=None, maps=(None, None), strided=True, gate=(None, 1.0), verdict=None):
         self._check_open()
         T, H, W = _check_images(img, 'T')
         E = _check_extrinsics(extrinsics, T)
@@ -857,6 +1067,15 @@ class SceneBatch:
         if not img.is_cuda:
             raise RuntimeError('img must be a device (HIP) tensor; the MI355X path has no CPU fallback')
         m = self._model
+        if gate[0] is not None:                   # the keyframe gate: ONE coverage launch against the states before the call, before the trunk
+            verdict = admitted(self._coverage(E, groups, maps, (H, W), shapes, gate[1], strided, img.device), gate[0])
+            if not any(verdict):
+                self.last_admitted = verdict
+                return self
+            if not all(verdict):
+                img, E, weights, maps = _kept(verdict, img), _kept(verdict, E), _kept(verdict, weights), tuple(_kept(verdict, t) for t in maps)
+                groups = self._groups(_kept(verdict, list(scene)), len(E))
+                T, touched = len(E), sorted(groups)
         if m._prepared_device is None:
             m.prepare(img.device)
         p0 = self._features(img.contiguous())                      # ONE trunk call over the T views of this tick
@@ -881,6 +1100,7 @@ class SceneBatch:
             r.meta.update(shapes)
         for s in touched:
             self._cam[s] = cam[s]
+        self.last_admitted = verdict
         return self
 
     @staticmethod

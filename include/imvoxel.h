@@ -44,7 +44,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * batches of scenes and ragged batches; 480 = 0.4.8: ivx_backproject_weighted_fwd / ivx_volume_wmean_fwd, the listed lift with per-view weights,
  * per-sample decay and a forgetting threshold, for fading scenes; 490 = 0.4.9: ivx_volume_scroll_fwd, the in-place voxel shift of rows of the state
  * pools, for scrolling scenes; 500 = 0.5.0: ivx_backproject_mapped_fwd, the weighted lift with a per-pixel confidence map and a gated depth map
- * per view) and the message of the last failing call on this thread (never NULL). */
+ * per view; 501 = 0.5.1: ivx_view_coverage_fwd, the integer count of the voxels a candidate view would see and of those the scene has no evidence
+ * for yet, before its trunk runs) and the message of the last failing call on this thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
 
@@ -787,6 +788,63 @@ int ivx_backproject_mapped_fwd(const ivx_backproject_desc *d, const ivx_lift_lis
  * Z or C; C % 4 != 0; X*Y*Z at or beyond 2^31; a row outside [0, R); two samples on one row (they would race).                                  */
 int ivx_volume_scroll_fwd(int32_t B, const int32_t *row /*host [B]*/, const int32_t *shift /*host [B,3]*/, int32_t R, int32_t X, int32_t Y, int32_t Z,
                           int32_t C, float *volume_sum, int32_t *count, float *wsum /*or NULL*/, ivx_stream_t stream);
+
+/* (0.5.1) View coverage: what would a candidate view add to a scene?  Every frame that reaches a streaming scene pays for the 2-D trunk, and
+ * most frames of a 30 Hz camera look at voxels the scene has already fused.  Whether a pose adds anything depends only on the geometry and on
+ * the scene's state, not on the image, so it is counted here, in integers, by one small launch BEFORE the trunk runs (a keyframe gate:
+ * scene.py, SceneSession.coverage / add_views(..., min_novelty=)).  The decision "view v sees voxel n" is the lift's own, bit for bit, depth
+ * gate and confidence map included, so the gate cannot disagree with the lift at the frustum's edges.  Like the bilinear rule, fading,
+ * scrolling and pixel maps it lies outside the reference-parity claims; it is pinned with == to a numpy restatement of the definition below
+ * (tests/ref_view_coverage.py) and to the lift's own mask.
+ *
+ * Definition.  For sample b (a scene): its state row r = row[b] (NULL: b), its grid new_origin[b], crop_hw[b], d->X, d->Y, d->Z, d->voxel_size,
+ * and candidate view v with slot = view_slot[b*V + v] into proj_pool [S,3,4].  Over all voxels n = (i*Y + j)*Z + k of the grid:
+ *   sees(b,v,n)   step 3 of ivx_backproject_mapped_fwd with view weight 1, decided exactly as that step decides it:
+ *                 the point  float(idx) * voxel_size + new_origin  (an fp32 product, an fp32 sum), the projection chain  P0 * x, fma(P1, y, .),
+ *                 fma(P2, z, .), fma(P3, 1, .)  per row, (xr, yr) = (rint(u / d), rint(v / d)) of the two IEEE quotients, and
+ *                 0 <= xr < min(crop_w, FW) && 0 <= yr < min(crop_h, FH) && d > 0, tested on the rounded floats.
+ *                 depth != NULL: with D = depth[slot, yr, xr], if D > 0 && D < inf (a measurement) also  d <= D + behind && d >= D - front,
+ *                 the sum and the difference each rounded once; any other D gates nothing.
+ *                 pixel_weight != NULL: w = pixel_weight[slot, yr, xr] must pass  w > 0 && w < inf  (1 * w is w: the lift's rounded product).
+ *                 A slot outside [0, S) sees nothing (-1 pads ragged rows, anywhere in a row).  The map addresses are formed from slot and
+ *                 pixel only after the validity test has passed, and no address depends on a map's value.
+ *   den(b,n)      the evidence the scene already holds at the voxel, by state_kind:
+ *                 IVX_STATE_NONE   state == NULL, an empty scene: den = 0
+ *                 IVX_STATE_COUNT  state int32 [R,X,Y,Z], the view counts of a (sum, count) scene: den = (float)count
+ *                 IVX_STATE_WSUM   state fp32  [R,X,Y,Z], the weight sums of a fading scene:      den = wsum
+ *                 IVX_STATE_MASK   state uint8 [R,X,Y,Z], the valid mask of a windowed scene:     den = valid ? 1 : 0
+ *   fresh(b,n)    !(den >= fresh_below) -- the form of the forgetting rule: a NaN evidence is fresh, equality is not.
+ *   out [B,V,2] int32:  out[b,v,0] = #{n : sees},  out[b,v,1] = #{n : sees && fresh}.  A padded slot gives (0, 0).
+ * The entry zeroes out on the stream itself (hipMemsetAsync), so a reused buffer does not accumulate.  The kernel adds with integer atomics
+ * only: the result does not depend on the order of arrival.
+ *
+ * d           the descriptor of ivx_backproject_fwd_ex: B, V (the length of a row of view_slot), FH, FW (the size of the maps and the clamp of
+ *             the crop), X, Y, Z and voxel_size are read; C, feat_dtype, mode, sampling and first are IGNORED (there are no features here)
+ * l           S (slots of proj_pool and of the maps), R (rows of state), view_slot DEVICE [B,V], row DEVICE [B] or NULL (= b; then R >= B);
+ *             l->first must be NULL.  A row outside [0, R) makes sample b count nothing (tested per workgroup before any address is formed).
+ *             Rows need not be distinct: nothing is written to the state.
+ * m           the maps of ivx_backproject_mapped_fwd, [S,FH,FW] fp32 each, and the gate; NULL, or both pointers NULL: no maps
+ * proj_pool   DEVICE [S,3,4] fp32; new_origin DEVICE [B,3] fp32; crop_hw DEVICE [B,2] int32: per SAMPLE, as for the listed lifts
+ * state, state_kind   as above; the pointer and the kind must agree
+ * fresh_below finite and > 0 (1: "less than one full-weight view's worth of evidence")
+ * out         DEVICE [B,V,2] int32
+ *
+ * Properties that follow from the definition.
+ *   Same as the lift.  out[b,v,0] equals the number of set bytes of `valid` of ivx_backproject_mapped_fwd (mean mode) over the single view v with
+ *                 unit weight and the same maps, on the same grid.
+ *   Bounds.       0 <= fresh <= seen <= X*Y*Z; with IVX_STATE_NONE fresh == seen; fresh is monotone in fresh_below.
+ *   Read only.    Nothing but out is written.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names this entry: a null d, l, proj_pool, l->view_slot, new_origin, crop_hw or out;
+ * non-positive B, V, S, R, FH, FW, X, Y or Z; X*Y*Z, S*FH*FW or B*V at or beyond 2^31; B > 65535; V > 256; R < B with no row list; an unknown
+ * state_kind; a state pointer that contradicts it (NULL with a kind other than IVX_STATE_NONE, non-NULL with IVX_STATE_NONE); a fresh_below that
+ * is not finite or not > 0; l->first != NULL; depth != NULL with a behind or front that is negative or NaN.                                  */
+#define IVX_STATE_NONE 0
+#define IVX_STATE_COUNT 1
+#define IVX_STATE_WSUM 2
+#define IVX_STATE_MASK 3
+int ivx_view_coverage_fwd(const ivx_backproject_desc *d, const ivx_lift_lists *l, const ivx_lift_maps *m /*or NULL*/, const float *proj_pool,
+                          const float *new_origin /*[B,3]*/, const int32_t *crop_hw /*[B,2]*/, const void *state /*or NULL*/, int32_t state_kind,
+                          float fresh_below, int32_t *out /*[B,V,2]*/, ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Anchor3DHead tail -- replaces Anchor3DHead.get_bboxes_single
