@@ -138,10 +138,16 @@ struct fp8_t { unsigned char v; };       // storage element of the fp8 instantia
 typedef long i64_t;
 
 __device__ __forceinline__ float fp8_to_f32(unsigned char b) { return __builtin_amdgcn_cvt_f32_fp8((int)b, 0); }
-// saturating e4m3 conversion of two floats -> low / high byte pair (NaN stays NaN)
+// saturating e4m3 conversion of two floats -> low / high byte pair; +-inf saturates, NaN stays NaN.  The clamp alone does not keep a
+// NaN: fminf(fmaxf(x, -448), 448) compiles to a median of three, which returns the smaller of the other two for a NaN operand, and the
+// byte stored was 0xFE (-448) -- so a value that is not equal to itself goes to the conversion unclamped.
+__device__ __forceinline__ float fp8_clamp(float x) {
+  const float c = __builtin_fminf(__builtin_fmaxf(x, -448.f), 448.f);
+  return x != x ? x : c;
+}
 __device__ __forceinline__ unsigned int f32x2_to_fp8(float a, float b) {
-  a = __builtin_fminf(__builtin_fmaxf(a, -448.f), 448.f);
-  b = __builtin_fminf(__builtin_fmaxf(b, -448.f), 448.f);
+  a = fp8_clamp(a);
+  b = fp8_clamp(b);
   return (unsigned int)__builtin_amdgcn_cvt_pk_fp8_f32(a, b, 0, false) & 0xffffu;
 }
 

@@ -110,7 +110,9 @@ typedef struct ivx_conv_desc {
   float res_scale;       /* multiplier of the residual before it is added, 0 or 1 = none.  IVX_FP8 tensors are e4m3 bytes with a
                             per-tensor scale kept by the caller (x = byte_value * s_x): the caller folds s_in * s_wgt[co] / s_out
                             into scale[], 1 / s_out into shift[] and passes res_scale = s_res / s_out; the store saturates at
-                            +-448 and rounds to nearest even.  fp8 input needs Cin % 16 == 0 (wgt_layout 1: Cin % 128 == 0). */
+                            +-448 (+-inf included) and rounds to nearest even; a NaN is stored as a NaN byte (0x7F / 0xFF), and one
+                            that reaches the ReLU as 0, as in every epilogue (v > 0 ? v : 0).  fp8 input needs Cin % 16 == 0
+                            (wgt_layout 1: Cin % 128 == 0). */
   int32_t wino_operands; /* ivx_conv_winograd_* only (in / out stay fp32): operand type of the transformed-domain GEMMs.  IVX_F32 (0,
                             default): fp32 MFMA, exact fp32 arithmetic.  IVX_F16_PAIR: the input / filter transforms write V and U as
                             fp16 (hi, lo) pairs (power-of-two scales taken from max |in| / max |U| on the device, undone exactly by the
