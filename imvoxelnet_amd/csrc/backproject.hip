@@ -14,27 +14,36 @@
 // lane per LPV views instead of one per lane per view.
 //
 // Arithmetic parity (measured against the imported reference, tests/golden/backproject_cases.npz):
-//   point   = float(idx) * voxel_size + new_origin                (fp32 mul, fp32 add, no FMA)
-//   (u,v,w) = fma(P3,1, fma(P2,z, fma(P1,y, P0*x)))               (what torch.bmm does on CPU)
-//   x = rint(u / w), y = rint(v / w)                               (IEEE divide, round-half-even)
-//   valid   = 0 <= x < w_crop  &&  0 <= y < h_crop  &&  w > 0      (tested on the rounded floats:
-//             NaN/inf fail, as do the INT64_MIN values the reference's .long() produces for them)
-//   mean    = (sum over valid views in view order) / float(count)  (IEEE divide), 0 if count == 0
+//   point, (u,v,d), xf, yf, xr, yr, valid: lift_geometry.h, the one statement of the geometry chain; both kernels below call it
+//   mean    = (sum over valid views in view order) / float(count)  (IEEE divide), 0 if count == 0   (bp_divides below)
 // This file is compiled with -ffp-contract=off.
 //
 // Optional bilinear sampling (BP_BILINEAR, ivx_backproject_fwd_ex; an extra mode outside the reference-parity claims, defined in
 // include/imvoxel.h and pinned to the fp64 reference of tests/ref_unproject.py).  Validity, mask and count are the nearest rule's; with
-// xf = u / w, yf = v / w as above:
+// the unrounded quotients xf, yf of lift_project:
 //   x0 = floor(xf), x1 = x0 + 1, y0 = floor(yf), y1 = y0 + 1, each clamped to the crop (border rule)
 //   ax = xf - floor(xf), ay = yf - floor(yf), bx = 1 - ax, by = 1 - ay                         (__fsub_rn)
 //   w00 = bx * by, w10 = ax * by, w01 = bx * ay, w11 = ax * ay                                 (__fmul_rn)
 //   sample = fma(w11, f11, fma(w01, f01, fma(w10, f10, w00 * f00)))                            (__fmul_rn, then three __fmaf_rn)
 // (bp_bilinear_sample below, the one function every mode and element type calls), then the same view sum and division.
 #include "ivx_common.h"
+#include "lift_geometry.h"
 #include <stdlib.h>
 #include <type_traits>
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+// The mean of a sum over the evidence it was gathered with, a view count (int) or a weight sum (float): sum / (float)evidence where bp_divides,
+// else 0; the mask is bp_seen.  Stated once for the lift's stores and for volume_normalize_kernel.  A count divides when it is != 0 and is seen
+// when it is > 0; a weight sum divides and is seen when it is > 0 (NaN: neither).  The guarded division itself stays a conditional expression in
+// the two kernels: inside a helper the compiler turns it into a division on every path and a select (profiles/lift_one_geometry.md).
+template <typename E>
+__device__ __forceinline__ bool bp_divides(const E ev) {
+  if constexpr (std::is_floating_point_v<E>) return ev > 0.f;
+  else return ev != 0;
+}
+template <typename E>
+__device__ __forceinline__ bool bp_seen(const E ev) { return ev > 0; }
 
 struct BpParams {
   const float *feat;        // [B*V, FH, FW, C]
@@ -139,8 +148,8 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
   static_assert(!ROWS || (GATHER && VEC == 4 && MODE != BP_SUM), "the ROWS forms are the gathered mean / accumulate kernels");
   static_assert(!WEIGHTED || ROWS, "the WEIGHTED forms are ROWS forms");
   static_assert(!MAPPED || WEIGHTED, "the MAPPED forms are WEIGHTED forms");
+  static_assert(VEC == 4 || MODE == BP_MEAN, "VEC 1 is the fp32 mean of a view stack");
   typedef T tv4 __attribute__((ext_vector_type(4)));
-  constexpr bool MEAN = MODE == BP_MEAN;
   const int b = blockIdx.y;
   int r = b;                               // the row of the state / outputs of this sample
   int first = p.first;
@@ -171,15 +180,10 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
   const bool active = n < p.N;
   const int nn = active ? n : p.N - 1;
 
-  // voxel coordinates: n = (i*Y + j)*Z + k
-  const int k = nn % p.Z;
-  const int t = nn / p.Z;
-  const int j = t % p.Y;
-  const int i = t / p.Y;
+  int i, j, k;
+  lift_voxel(nn, p.Y, p.Z, i, j, k);
   const float *no = p.new_origin + b * 3;
-  const float px = __fadd_rn(__fmul_rn((float)i, p.vs0), no[0]);
-  const float py = __fadd_rn(__fmul_rn((float)j, p.vs1), no[1]);
-  const float pz = __fadd_rn(__fmul_rn((float)k, p.vs2), no[2]);
+  const float px = lift_point(i, p.vs0, no[0]), py = lift_point(j, p.vs1, no[1]), pz = lift_point(k, p.vs2, no[2]);
   const int hc = min(p.crop_hw[b * 2 + 0], p.FH), wc = min(p.crop_hw[b * 2 + 1], p.FW);   // slice semantics (detectors/imvoxelnet.py:69): clamped to the map
 
   constexpr int MAXCH = 4;  // channel chunks per lane when ceil(C/VEC) > 64 lanes (C up to 1024 for VEC 4)
@@ -243,42 +247,27 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
       if (listed && p.view_weight) wt = p.view_weight[slot];
     }
     if (listed) {
-      const float *P = p.proj + (GATHER ? (size_t)slot : (size_t)b * p.V + v) * 12;
-      float u = __fmul_rn(P[0], px);
-      u = __fmaf_rn(P[1], py, u);
-      u = __fmaf_rn(P[2], pz, u);
-      u = __fmaf_rn(P[3], 1.0f, u);
-      float w_ = __fmul_rn(P[4], px);
-      w_ = __fmaf_rn(P[5], py, w_);
-      w_ = __fmaf_rn(P[6], pz, w_);
-      w_ = __fmaf_rn(P[7], 1.0f, w_);
-      float d = __fmul_rn(P[8], px);
-      d = __fmaf_rn(P[9], py, d);
-      d = __fmaf_rn(P[10], pz, d);
-      d = __fmaf_rn(P[11], 1.0f, d);
-      const float xr = rintf(__fdiv_rn(u, d));
-      const float yr = rintf(__fdiv_rn(w_, d));
-      bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
-      if constexpr (WEIGHTED) ok = ok && wt > 0.f && wt < __builtin_inff();     // NaN, 0, negative and inf: an unseen view (off stays -1)
+      LiftPixel h;
+      bool ok = lift_project(p.proj + (GATHER ? (size_t)slot : (size_t)b * p.V + v) * 12, px, py, pz, hc, wc, h);
+      if constexpr (WEIGHTED) ok = ok && lift_weight_counts(wt);     // NaN, 0, negative and inf: an unseen view (off stays -1)
       if constexpr (MAPPED) {
         if (ok) {                 // the nearest pixel is inside the crop, hence inside the map: slot in [0, S), (int)yr in [0, FH), (int)xr in [0, FW)
-          const int pix = (slot * p.FH + (int)yr) * p.FW + (int)xr;
+          const int pix = (slot * p.FH + (int)h.yr) * p.FW + (int)h.xr;
           const float D = p.depth ? p.depth[pix] : 0.f;
           const float pw = p.pixel_weight ? p.pixel_weight[pix] : 1.0f;
-          if (D > 0.f && D < __builtin_inff()) ok = d <= __fadd_rn(D, p.behind) && d >= __fsub_rn(D, p.front);     // 0, negative, NaN, +inf: no measurement, no gate
+          ok = lift_gate(D, h.d, p.behind, p.front);
           if (p.pixel_weight) {
             wt = __fmul_rn(wt, pw);
-            ok = ok && wt > 0.f && wt < __builtin_inff();
+            ok = ok && lift_weight_counts(wt);
           }
         }
       }
-      if (ok) off = (((GATHER ? slot : b * p.V + v) * p.FH + (int)yr) * p.FW + (int)xr);
+      if (ok) off = (((GATHER ? slot : b * p.V + v) * p.FH + (int)h.yr) * p.FW + (int)h.xr);
       if constexpr (SAMP == BP_BILINEAR) {
         if (ok) {               // a valid sample: xf in [-0.5, wc - 0.5], so the floors are in [-1, wc - 1] and fit an int
-          const float xf = __fdiv_rn(u, d), yf = __fdiv_rn(w_, d);
-          const float fx = floorf(xf), fy = floorf(yf);
-          ax = __fsub_rn(xf, fx);
-          ay = __fsub_rn(yf, fy);
+          const float fx = floorf(h.xf), fy = floorf(h.yf);
+          ax = __fsub_rn(h.xf, fx);
+          ay = __fsub_rn(h.yf, fy);
           const int x0 = max((int)fx, 0), x1 = min((int)fx + 1, wc - 1);     // x0 <= wc - 1 and x1 >= 0 already
           const int y0 = max((int)fy, 0), y1 = min((int)fy + 1, hc - 1);
           step = (x1 - x0) | ((y1 - y0) << 1);
@@ -339,116 +328,57 @@ __global__ __launch_bounds__(256) void backproject_mean_kernel(
   }
 
   if (!active) return;
-  if constexpr (WEIGHTED) {            // the stores of the WEIGHTED forms: the mean divides by the weight sum, seen means W > 0 (VEC 4, BP_MEAN / BP_ACCUM)
-    const bool seen = wacc > 0.f;
-    float *run = MODE == BP_ACCUM ? p.volume + ((size_t)r * p.N + n) * p.C : nullptr;
-    T *mean = MODE == BP_ACCUM ? (p.mean_out ? reinterpret_cast<T *>(p.mean_out) + ((size_t)r * p.N + n) * p.C : nullptr)
-                               : reinterpret_cast<T *>(p.volume) + ((size_t)r * p.N + n) * p.C;
-#pragma unroll
-    for (int q = 0; q < MAXCH; ++q) {
-      const int ch = g + q * lpv;
-      if (ch < p.nchunk) {
-        f32x4 s;
-        tv4 y;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          s[e] = acc[q][e];
-          y[e] = (T)(seen ? __fdiv_rn(acc[q][e], wacc) : 0.f);
-        }
-        if (run) *reinterpret_cast<f32x4 *>(run + ch * 4) = s;
-        if (mean) *reinterpret_cast<tv4 *>(mean + ch * 4) = y;
-      }
-    }
-    if (g == 0) {
-      if constexpr (MODE == BP_ACCUM) {
-        p.count[(size_t)r * p.N + n] = cnt;
-        p.wsum[(size_t)r * p.N + n] = wacc;
-      }
-      if (mean) p.valid[(size_t)r * p.N + n] = seen ? 1 : 0;
-    }
-    return;
-  }
-  const float dn = (float)cnt;
-  if constexpr (MODE == BP_ACCUM) {
-    float *run = p.volume + ((size_t)r * p.N + n) * p.C;
-    T *mean = p.mean_out ? reinterpret_cast<T *>(p.mean_out) + ((size_t)r * p.N + n) * p.C : nullptr;
-#pragma unroll
-    for (int q = 0; q < MAXCH; ++q) {
-      const int ch = g + q * lpv;
-      if (ch < p.nchunk) {
-        f32x4 s;
-        tv4 y;
-#pragma unroll
-        for (int e = 0; e < VEC; ++e) {
-          s[e] = acc[q][e];
-          y[e] = (T)(cnt ? __fdiv_rn(acc[q][e], dn) : 0.f);
-        }
-        *reinterpret_cast<f32x4 *>(run + ch * 4) = s;
-        if (mean) *reinterpret_cast<tv4 *>(mean + ch * 4) = y;
-      }
-    }
-    if (g == 0) {
-      p.count[(size_t)r * p.N + n] = cnt;
-      if (mean) p.valid[(size_t)r * p.N + n] = cnt > 0 ? 1 : 0;
-    }
-    return;
-  }
-  T *dst = reinterpret_cast<T *>(p.volume) + ((size_t)r * p.N + n) * p.C;
+  // The stores of every form.  The evidence of the voxel is its weight sum (WEIGHTED) or its view count; `run` is the fp32 state of BP_ACCUM
+  // (stored as it stands: a list of unseen views puts the loaded bits back, no arithmetic), `out` the volume in the feature type: the mean of
+  // BP_MEAN and of BP_ACCUM with mean_out, the raw sum of BP_SUM.
+  std::conditional_t<WEIGHTED, float, int> ev;
+  if constexpr (WEIGHTED) ev = wacc;
+  else ev = cnt;
+  const float den = (float)ev;
+  const size_t at = (size_t)r * p.N + n;
+  float *run = p.volume + at * p.C;
+  T *out = MODE != BP_ACCUM ? reinterpret_cast<T *>(p.volume) + at * p.C : p.mean_out ? reinterpret_cast<T *>(p.mean_out) + at * p.C : nullptr;
+  const bool has_out = MODE != BP_ACCUM || out;     // BP_ACCUM without mean_out updates the state alone
 #pragma unroll
   for (int q = 0; q < MAXCH; ++q) {
     const int ch = g + q * lpv;
     if (ch < p.nchunk) {
-      if constexpr (VEC == 4) {
-        tv4 y;
+      f32x4 s;
+      tv4 y;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) y[e] = (T)(MEAN ? (cnt ? __fdiv_rn(acc[q][e], dn) : 0.f) : acc[q][e]);
-        *reinterpret_cast<tv4 *>(dst + ch * 4) = y;
-      } else {
-        dst[ch] = (T)(MEAN ? (cnt ? __fdiv_rn(acc[q][0], dn) : 0.f) : acc[q][0]);
+      for (int e = 0; e < VEC; ++e) {
+        s[e] = acc[q][e];
+        y[e] = (T)(MODE == BP_SUM ? acc[q][e] : bp_divides(ev) ? __fdiv_rn(acc[q][e], den) : 0.f);
       }
+      if constexpr (MODE == BP_ACCUM) *reinterpret_cast<f32x4 *>(run + ch * 4) = s;
+      if constexpr (VEC == 1) out[ch] = y[0];
+      else if (has_out) *reinterpret_cast<tv4 *>(out + ch * 4) = y;
     }
   }
   if (g == 0) {
-    if (MEAN)
-      p.valid[(size_t)r * p.N + n] = cnt > 0 ? 1 : 0;
-    else
-      p.count[(size_t)r * p.N + n] = cnt;
+    if constexpr (MODE != BP_MEAN) p.count[at] = cnt;
+    if constexpr (WEIGHTED && MODE == BP_ACCUM) p.wsum[at] = wacc;
+    if (MODE != BP_SUM && has_out) p.valid[at] = bp_seen(ev) ? 1 : 0;
   }
 }
 
-// out[b,n,:] = count ? sum / count : 0, valid = count > 0 (detectors/imvoxelnet.py:70-74 after the all-reduce of the
-// per-rank partial sums, or on the running sums of a streaming scene).  out == sum: in place (ivx_volume_normalize_fwd); otherwise
-// the sums stay intact and T may be __bf16 (one rounding at the store).  One float4 of sums per thread.
-template <typename T>
-__global__ __launch_bounds__(256) void volume_normalize_kernel(const float *sum, T *out, const int *count, uint8_t *valid, long long total4, int C4) {
+// The mean of a stored state, by the lift's own division and mask: out[n,:] = bp_divides(evidence[n]) ? sum[n,:] / evidence[n] : 0, valid =
+// bp_seen(evidence[n]).  E = int: a (sum, count) state (detectors/imvoxelnet.py:70-74 after the all-reduce of the per-rank partial sums, or the
+// running sums of a streaming scene); E = float: a (sum, weight sum) state (ivx_volume_wmean_fwd).  out == sum: in place (ivx_volume_normalize_fwd); otherwise the sums stay intact
+// and T may be __bf16 (one rounding at the store).  One float4 of sums per thread.
+template <typename T, typename E>
+__global__ __launch_bounds__(256) void volume_normalize_kernel(const float *sum, T *out, const E *evidence, uint8_t *valid, long long total4, int C4) {
   typedef T tv4 __attribute__((ext_vector_type(4)));
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
     const long long vox = i / C4;
-    const int cnt = count[vox];
+    const E ev = evidence[vox];
     const f32x4 x = *reinterpret_cast<const f32x4 *>(sum + i * 4);
-    const float dn = (float)cnt;
+    const float den = (float)ev;
     tv4 y;
 #pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = (T)(cnt ? __fdiv_rn(x[e], dn) : 0.f);
+    for (int e = 0; e < 4; ++e) y[e] = (T)(bp_divides(ev) ? __fdiv_rn(x[e], den) : 0.f);
     *reinterpret_cast<tv4 *>(out + i * 4) = y;
-    if (i % C4 == 0) valid[vox] = cnt > 0 ? 1 : 0;
-  }
-}
-
-// out[n,:] = W > 0 ? sum / W : 0, valid = W > 0: the mean of a (sum, weight sum) state (ivx_volume_wmean_fwd), the division and the mask of the
-// WEIGHTED accumulate kernel's mean_out.  Out of place only; T may be __bf16 (one rounding at the store).
-template <typename T>
-__global__ __launch_bounds__(256) void volume_wmean_kernel(const float *sum, T *out, const float *wsum, uint8_t *valid, long long total4, int C4) {
-  typedef T tv4 __attribute__((ext_vector_type(4)));
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
-    const long long vox = i / C4;
-    const float W = wsum[vox];
-    const f32x4 x = *reinterpret_cast<const f32x4 *>(sum + i * 4);
-    tv4 y;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) y[e] = (T)(W > 0.f ? __fdiv_rn(x[e], W) : 0.f);
-    *reinterpret_cast<tv4 *>(out + i * 4) = y;
-    if (i % C4 == 0) valid[vox] = W > 0.f ? 1 : 0;
+    if (i % C4 == 0) valid[vox] = bp_seen(ev) ? 1 : 0;
   }
 }
 
@@ -469,32 +399,14 @@ __global__ __launch_bounds__(256) void backproject_single_view_kernel(const BpPa
   const long long n = n0 + g;
   int off = -1;
   if (n < p.N) {
-    const int k = (int)(n % p.Z);
-    const int t = (int)(n / p.Z);
-    const int j = t % p.Y;
-    const int i = t / p.Y;
+    int i, j, k;
+    lift_voxel(n, p.Y, p.Z, i, j, k);
     const float *no = p.new_origin + b * 3;
-    const float px = __fadd_rn(__fmul_rn((float)i, p.vs0), no[0]);
-    const float py = __fadd_rn(__fmul_rn((float)j, p.vs1), no[1]);
-    const float pz = __fadd_rn(__fmul_rn((float)k, p.vs2), no[2]);
+    const float px = lift_point(i, p.vs0, no[0]), py = lift_point(j, p.vs1, no[1]), pz = lift_point(k, p.vs2, no[2]);
     const int hc = min(p.crop_hw[b * 2 + 0], p.FH), wc = min(p.crop_hw[b * 2 + 1], p.FW);   // slice semantics (detectors/imvoxelnet.py:69): clamped to the map
-    const float *P = p.proj + (size_t)b * 12;
-    float u = __fmul_rn(P[0], px);
-    u = __fmaf_rn(P[1], py, u);
-    u = __fmaf_rn(P[2], pz, u);
-    u = __fmaf_rn(P[3], 1.0f, u);
-    float w_ = __fmul_rn(P[4], px);
-    w_ = __fmaf_rn(P[5], py, w_);
-    w_ = __fmaf_rn(P[6], pz, w_);
-    w_ = __fmaf_rn(P[7], 1.0f, w_);
-    float d = __fmul_rn(P[8], px);
-    d = __fmaf_rn(P[9], py, d);
-    d = __fmaf_rn(P[10], pz, d);
-    d = __fmaf_rn(P[11], 1.0f, d);
-    const float xr = rintf(__fdiv_rn(u, d));
-    const float yr = rintf(__fdiv_rn(w_, d));
-    const bool ok = (xr >= 0.f) && (yr >= 0.f) && (xr < (float)wc) && (yr < (float)hc) && (d > 0.f);
-    if (ok) off = ((b * p.FH + (int)yr) * p.FW + (int)xr);
+    LiftPixel h;
+    const bool ok = lift_project(p.proj + (size_t)b * 12, px, py, pz, hc, wc, h);
+    if (ok) off = ((b * p.FH + (int)h.yr) * p.FW + (int)h.xr);
     p.valid[(size_t)b * p.N + n] = ok ? 1 : 0;
   }
   const int nvox = (p.N - n0) < lpv ? (int)(p.N - n0) : lpv;   // group-uniform; <= 0 for groups past the end
@@ -668,7 +580,14 @@ static BpMapParams bp_fill(const BpCall &c, dim3 *grid) {
   return p;
 }
 
-// The selection table: every instantiation of the two lift kernels is launched from exactly one line below.
+// Both feature types of one VEC 4 form of the multi-view kernel: the helper of the table below for the forms that exist for float and __bf16.
+template <int MODE, int SAMP, bool GATHER = false, bool ROWS = false, bool WEIGHTED = false, bool MAPPED = false, typename P>
+static void bp_launch_t(const bool bf16, const dim3 grid, hipStream_t st, const P &p) {
+  if (bf16) hipLaunchKernelGGL((backproject_mean_kernel<4, MODE, __bf16, SAMP, GATHER, ROWS, WEIGHTED, MAPPED>), grid, dim3(256), 0, st, p);
+  else      hipLaunchKernelGGL((backproject_mean_kernel<4, MODE, float, SAMP, GATHER, ROWS, WEIGHTED, MAPPED>), grid, dim3(256), 0, st, p);
+}
+
+// The selection table: every instantiation of the two lift kernels is launched from exactly one line below (a bp_launch_t line: both types).
 static int bp_launch(const BpCall &c, const BpMapParams &m, const dim3 grid) {
   const ivx_backproject_desc &d = *c.d;
   const BpWeightParams &w = m;
@@ -681,54 +600,36 @@ static int bp_launch(const BpCall &c, const BpMapParams &m, const dim3 grid) {
   const dim3 block(256);
   hipStream_t st = (hipStream_t)c.stream;
   if (c.mapped) {                                   // pixel maps: the WEIGHTED forms with a confidence and / or a gated depth per pixel
-    if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
-    else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
-    else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
-    else if (mode == BP_ACCUM)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
-    else if (bilinear && bf16)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
-    else if (bilinear)                         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true, true, true, true>), grid, block, 0, st, m);
-    else if (bf16)                             hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
-    else                                       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true, true, true, true>), grid, block, 0, st, m);
+    if (mode == BP_ACCUM && bilinear)  bp_launch_t<BP_ACCUM, BP_BILINEAR, true, true, true, true>(bf16, grid, st, m);
+    else if (mode == BP_ACCUM)         bp_launch_t<BP_ACCUM, BP_NEAREST, true, true, true, true>(bf16, grid, st, m);
+    else if (bilinear)                 bp_launch_t<BP_MEAN, BP_BILINEAR, true, true, true, true>(bf16, grid, st, m);
+    else                               bp_launch_t<BP_MEAN, BP_NEAREST, true, true, true, true>(bf16, grid, st, m);
   } else if (c.weighted) {                          // weights, decay and weight sums: the ROWS forms, with or without a row list
-    if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
-    else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
-    else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
-    else if (mode == BP_ACCUM)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
-    else if (bilinear && bf16)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
-    else if (bilinear)                         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true, true, true>), grid, block, 0, st, w);
-    else if (bf16)                             hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
-    else                                       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true, true, true>), grid, block, 0, st, w);
+    if (mode == BP_ACCUM && bilinear)  bp_launch_t<BP_ACCUM, BP_BILINEAR, true, true, true>(bf16, grid, st, w);
+    else if (mode == BP_ACCUM)         bp_launch_t<BP_ACCUM, BP_NEAREST, true, true, true>(bf16, grid, st, w);
+    else if (bilinear)                 bp_launch_t<BP_MEAN, BP_BILINEAR, true, true, true>(bf16, grid, st, w);
+    else                               bp_launch_t<BP_MEAN, BP_NEAREST, true, true, true>(bf16, grid, st, w);
   } else if (c.listed && (mode == BP_ACCUM || l.row)) {    // rows of a state / output pool: MEAN and ACCUM, VEC 4 only (a listed mean with no row list is the gathered launch below)
-    if (mode == BP_ACCUM && bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR, true, true>), grid, block, 0, st, l);
-    else if (mode == BP_ACCUM && bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR, true, true>), grid, block, 0, st, l);
-    else if (mode == BP_ACCUM && bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_NEAREST, true, true>), grid, block, 0, st, l);
-    else if (mode == BP_ACCUM)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_NEAREST, true, true>), grid, block, 0, st, l);
-    else if (bilinear && bf16)                 hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true, true>), grid, block, 0, st, l);
-    else if (bilinear)                         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true, true>), grid, block, 0, st, l);
-    else if (bf16)                             hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true, true>), grid, block, 0, st, l);
-    else                                       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true, true>), grid, block, 0, st, l);
+    if (mode == BP_ACCUM && bilinear)  bp_launch_t<BP_ACCUM, BP_BILINEAR, true, true>(bf16, grid, st, l);
+    else if (mode == BP_ACCUM)         bp_launch_t<BP_ACCUM, BP_NEAREST, true, true>(bf16, grid, st, l);
+    else if (bilinear)                 bp_launch_t<BP_MEAN, BP_BILINEAR, true, true>(bf16, grid, st, l);
+    else                               bp_launch_t<BP_MEAN, BP_NEAREST, true, true>(bf16, grid, st, l);
   } else if (c.gather) {                            // MEAN only, VEC 4 only, one listed view too
-    if (bilinear && bf16)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR, true>), grid, block, 0, st, g);
-    else if (bilinear)     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR, true>), grid, block, 0, st, g);
-    else if (bf16)         hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_NEAREST, true>), grid, block, 0, st, g);
-    else                   hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_NEAREST, true>), grid, block, 0, st, g);
+    if (bilinear)  bp_launch_t<BP_MEAN, BP_BILINEAR, true>(bf16, grid, st, g);
+    else           bp_launch_t<BP_MEAN, BP_NEAREST, true>(bf16, grid, st, g);
   } else if (bilinear) {                            // one view too: the blend is arithmetic, not a copy
-    if (mode == BP_MEAN && bf16)       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
-    else if (mode == BP_MEAN && vec4)  hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
-    else if (mode == BP_MEAN)          hipLaunchKernelGGL((backproject_mean_kernel<1, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
-    else if (mode == BP_SUM)           hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM, float, BP_BILINEAR>), grid, block, 0, st, p);
-    else if (bf16)                     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16, BP_BILINEAR>), grid, block, 0, st, p);
-    else                               hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float, BP_BILINEAR>), grid, block, 0, st, p);
+    if (mode == BP_MEAN && vec4)  bp_launch_t<BP_MEAN, BP_BILINEAR>(bf16, grid, st, p);
+    else if (mode == BP_MEAN)     hipLaunchKernelGGL((backproject_mean_kernel<1, BP_MEAN, float, BP_BILINEAR>), grid, block, 0, st, p);
+    else if (mode == BP_SUM)      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM, float, BP_BILINEAR>), grid, block, 0, st, p);
+    else                          bp_launch_t<BP_ACCUM, BP_BILINEAR>(bf16, grid, st, p);
   } else if (bp_single_view_copy(c)) {              // nearest fp32 mean of one view: the copy kernel (a bf16 view is not: its mean converts)
     if (vec4)  hipLaunchKernelGGL(backproject_single_view_kernel<4>, grid, block, 0, st, p);
     else       hipLaunchKernelGGL(backproject_single_view_kernel<1>, grid, block, 0, st, p);
   } else {
-    if (mode == BP_MEAN && bf16)       hipLaunchKernelGGL((backproject_mean_kernel<4, BP_MEAN, __bf16>), grid, block, 0, st, p);
-    else if (mode == BP_MEAN && vec4)  hipLaunchKernelGGL(backproject_mean_kernel<4>, grid, block, 0, st, p);
-    else if (mode == BP_MEAN)          hipLaunchKernelGGL(backproject_mean_kernel<1>, grid, block, 0, st, p);
-    else if (mode == BP_SUM)           hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM>), grid, block, 0, st, p);
-    else if (bf16)                     hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, __bf16>), grid, block, 0, st, p);
-    else                               hipLaunchKernelGGL((backproject_mean_kernel<4, BP_ACCUM, float>), grid, block, 0, st, p);
+    if (mode == BP_MEAN && vec4)  bp_launch_t<BP_MEAN, BP_NEAREST>(bf16, grid, st, p);
+    else if (mode == BP_MEAN)     hipLaunchKernelGGL(backproject_mean_kernel<1>, grid, block, 0, st, p);
+    else if (mode == BP_SUM)      hipLaunchKernelGGL((backproject_mean_kernel<4, BP_SUM>), grid, block, 0, st, p);
+    else                          bp_launch_t<BP_ACCUM, BP_NEAREST>(bf16, grid, st, p);
   }
   IVX_CHECK_LAUNCH(c.what);
   return IVX_OK;
@@ -837,9 +738,10 @@ extern "C" int ivx_backproject_mapped_fwd(const ivx_backproject_desc *d, const i
                  nullptr, true, l ? l->view_slot : nullptr, l ? l->S : 0, true, l, true, w, mapped, mapped ? m : nullptr});
 }
 
-// ------------------------------------------------------------------ mean of a (sum, count) volume
-// out == sum: in place (ivx_volume_normalize_fwd).  Otherwise the sums stay intact and out may be bf16 (ivx_volume_mean_fwd).
-static int volume_normalize_launch(const char *what, const float *sum, void *out, int32_t out_dtype, const int32_t *count, int64_t n_voxels, int32_t C,
+// ------------------------------------------------------------------ mean of a (sum, count) or (sum, weight sum) volume
+// out == sum: in place (ivx_volume_normalize_fwd).  Otherwise the sums stay intact and out may be bf16 (ivx_volume_mean_fwd, ivx_volume_wmean_fwd).
+template <typename E>
+static int volume_normalize_launch(const char *what, const float *sum, void *out, int32_t out_dtype, const E *evidence, int64_t n_voxels, int32_t C,
                                    uint8_t *valid, ivx_stream_t stream) {
   IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "%s: bad dims (C %% 4 must be 0)", what);
   IVX_REQUIRE(out_dtype == IVX_F32 || out_dtype == IVX_BF16, "%s: out_dtype must be IVX_F32 or IVX_BF16", what);
@@ -847,9 +749,9 @@ static int volume_normalize_launch(const char *what, const float *sum, void *out
   long long blocks = (total4 + 255) / 256;
   if (blocks > 256 * 64) blocks = 256 * 64;
   if (out_dtype == IVX_BF16)
-    hipLaunchKernelGGL(volume_normalize_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, (__bf16 *)out, count, valid, total4, C / 4);
+    hipLaunchKernelGGL((volume_normalize_kernel<__bf16, E>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, (__bf16 *)out, evidence, valid, total4, C / 4);
   else
-    hipLaunchKernelGGL(volume_normalize_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, (float *)out, count, valid, total4, C / 4);
+    hipLaunchKernelGGL((volume_normalize_kernel<float, E>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, sum, (float *)out, evidence, valid, total4, C / 4);
   IVX_CHECK_LAUNCH(what);
   return IVX_OK;
 }
@@ -872,15 +774,5 @@ extern "C" int ivx_volume_wmean_fwd(const float *volume_sum, const float *wsum, 
   const char *what = "ivx_volume_wmean_fwd";
   IVX_REQUIRE(volume_sum && wsum && out && valid, "%s: null argument", what);
   IVX_REQUIRE((const void *)volume_sum != out, "%s: out must not be volume_sum", what);
-  IVX_REQUIRE(n_voxels > 0 && C > 0 && C % 4 == 0, "%s: bad dims (C %% 4 must be 0)", what);
-  IVX_REQUIRE(out_dtype == IVX_F32 || out_dtype == IVX_BF16, "%s: out_dtype must be IVX_F32 or IVX_BF16", what);
-  const long long total4 = (long long)n_voxels * (C / 4);
-  long long blocks = (total4 + 255) / 256;
-  if (blocks > 256 * 64) blocks = 256 * 64;
-  if (out_dtype == IVX_BF16)
-    hipLaunchKernelGGL(volume_wmean_kernel<__bf16>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (__bf16 *)out, wsum, valid, total4, C / 4);
-  else
-    hipLaunchKernelGGL(volume_wmean_kernel<float>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, volume_sum, (float *)out, wsum, valid, total4, C / 4);
-  IVX_CHECK_LAUNCH(what);
-  return IVX_OK;
+  return volume_normalize_launch(what, volume_sum, out, out_dtype, wsum, n_voxels, C, valid, stream);
 }

@@ -85,23 +85,21 @@ __global__ __launch_bounds__(IVX_COVERAGE_WG) void view_coverage_kernel(const Co
     const int n = blk * IVX_COVERAGE_WG + (int)threadIdx.x;
     const bool active = n < p.N;
     const int nn = active ? n : p.N - 1;
-    const int k = nn % p.Z;
-    const int t = nn / p.Z;
-    const int j = t % p.Y;
-    const int i = t / p.Y;
+    int i, j, k;
+    lift_voxel(nn, p.Y, p.Z, i, j, k);
     const float px = lift_point(i, p.vs0, o0), py = lift_point(j, p.vs1, o1), pz = lift_point(k, p.vs2, o2);
     const float den = cov_den<KIND>(p.state, (size_t)r * p.N + nn);
     const bool fresh = !(den >= p.fresh_below);  // a NaN evidence is fresh; equality is not
     for (int v = 0; v < p.V; ++v) {
       const int slot = slots[v];                 // uniform
       if (slot < 0 || slot >= p.S) continue;     // a padded or unknown slot sees nothing: no address of it is formed
-      float xr, yr, d;
-      bool ok = active && lift_project(p.proj_pool + (size_t)slot * 12, px, py, pz, hc, wc, xr, yr, d);
+      LiftPixel h;
+      bool ok = active && lift_project(p.proj_pool + (size_t)slot * 12, px, py, pz, hc, wc, h);
       if (ok && (p.depth || p.pixel_weight)) {   // inside the crop, hence inside the map: (int)yr in [0, FH), (int)xr in [0, FW), slot in [0, S)
-        const int pix = (slot * p.FH + (int)yr) * p.FW + (int)xr;
+        const int pix = (slot * p.FH + (int)h.yr) * p.FW + (int)h.xr;
         const float D = p.depth ? p.depth[pix] : 0.f;
         const float pw = p.pixel_weight ? p.pixel_weight[pix] : 1.0f;
-        ok = lift_gate(D, d, p.behind, p.front) && lift_weight_counts(pw);
+        ok = lift_gate(D, h.d, p.behind, p.front) && lift_weight_counts(pw);
       }
       const unsigned long long seen = __ballot(ok), novel = __ballot(ok && fresh);
       if (lane == 0 && seen) {

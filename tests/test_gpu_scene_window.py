@@ -122,7 +122,7 @@ def test_gathered_lift_follows_the_list_order(ia, circle, order):
 
 # ------------------------------------------------------------------ width, batch, element types, sampling rule
 WIDE = [(256, torch.float32, 'nearest'), (512, torch.float32, 'nearest'), (256, torch.bfloat16, 'nearest'), (256, torch.float32, 'bilinear'),
-        (8, torch.float32, 'bilinear')]
+        (8, torch.float32, 'bilinear'), (8, torch.bfloat16, 'bilinear')]
 
 
 @pytest.mark.parametrize('C,dtype,sampling', WIDE, ids=[f'C{c}-{str(d).split(".")[1]}-{s}' for c, d, s in WIDE])

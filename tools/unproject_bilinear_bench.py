@@ -47,6 +47,7 @@ def main():
     rows, notes = [], []
     for name, nv, vs, Cn, hw, metas in shapes:
         cam = types.SimpleNamespace(n_voxels=nv, voxel_size=vs, _compute_projection=ia.ImVoxelNet._compute_projection)
+        cam._new_origin = lambda origin, cam=cam: ia.ImVoxelNet._new_origin(cam, origin)      # the camera set-up asks its model for the grid's corner
         proj, no, crop = ia.ImVoxelNet._camera_setup(cam, metas, 4, 'cuda')
         B, V = proj.shape[0], proj.shape[1]
         FH, FW = hw[0] // 4, hw[1] // 4
