@@ -29,6 +29,7 @@ SOURCES = [
     ('preprocess.hip', ['-ffp-contract=off']),
     ('dcn.hip', []),
     ('ubench.hip', []),
+    ('conv_plan.cpp', []),
     ('api_common.cpp', []),
     ('kitti_eval.cpp', []),
     ('model.cpp', ['-ffp-contract=off']),
@@ -51,8 +52,8 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, 'ivx_common.h'), os.path.join(CSRC, 'lift_geometry.h'),
-               os.path.join(os.path.dirname(os.path.dirname(CSRC)), 'include', 'imvoxel.h')]
+    headers = [os.path.join(CSRC, h) for h in ('ivx_common.h', 'lift_geometry.h', 'conv_shared.h', 'conv_tiles.h', 'conv_plan.h')] + \
+              [os.path.join(os.path.dirname(os.path.dirname(CSRC)), 'include', h) for h in ('imvoxel.h', 'imvoxel_lab.h')]
     objs, jobs = [], []
     for entry in SOURCES:
         src, extra = entry[0], entry[1]

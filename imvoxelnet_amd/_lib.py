@@ -155,6 +155,13 @@ class ImagePrepDesc(C.Structure):
                [('mean', C.c_float * 3), ('std', C.c_float * 3)]
 
 
+class ConvPlanRec(C.Structure):
+    """ivx_conv_plan_rec (include/imvoxel_lab.h): what the conv planner answers for a descriptor (ivx_conv_plan_query)."""
+    _fields_ = [('slice_samples', C.c_int32), ('n_slices', C.c_int32)] + \
+               [(n, C.c_int32 * 2) for n in ('samples', 'cfg', 'ksplit', 'tail_ks', 'q_total', 'qa', 'bm')] + \
+               [('slice_ws', C.c_int64 * 2), ('ws_bytes', C.c_int64)] + [(n, C.c_int32) for n in ('halo_cfg', 'grouped_tile', 'tile_matches', 'rows_dev_ok')]
+
+
 def declare_plan_view(L):
     """Argument types of the read-only plan view, on libimvoxel_hip.so or on the CPU restatement of the same ABI (tests)."""
     key = [C.c_void_p, C.c_char_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32]
@@ -163,7 +170,7 @@ def declare_plan_view(L):
     L.ivx_model_plan_tensor.argtypes = key + [C.c_int32, C.POINTER(PlanTensor)]
 
 
-EXPORTS = ['ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor', 'ivx_bottleneck_proj_supported', 'ivx_bottleneck_proj_pack', 'ivx_bottleneck_proj_fwd_pio', 'ivx_anchor_head_decode', 'ivx_fcos3d_head_decode', 'ivx_nms_rotated_bev', 'ivx_nms_aligned3d', 'ivx_bottleneck_supported', 'ivx_bottleneck_fwd_pio', 'ivx_amax_f32', 'ivx_stem_pool_filter_bytes', 'ivx_stem_pool_pack_filters', 'ivx_stem_pool_out_dims', 'ivx_stem_pool_fwd_pair', 'ivx_conv_winograd_set_variant', 'ivx_ubench_mfma', 'ivx_ubench_copy', 'ivx_version', 'ivx_last_error', 'ivx_conv_out_dims', 'ivx_conv_fwd', 'ivx_conv_fwd_naive', 'ivx_conv_set_tile_override', 'ivx_conv_set_epilogue_mode', 'ivx_conv_set_plan_mode', 'ivx_topk_set_mode', 'ivx_conv_workspace_bytes', 'ivx_conv_fwd_ws', 'ivx_conv_set_halo_mode', 'ivx_bf16_pair_split', 'ivx_f16_pair_split', 'ivx_conv_pair_supported', 'ivx_bf16_pair_pack_filters', 'ivx_conv_route', 'ivx_conv_pio_workspace_bytes', 'ivx_conv_fwd_pio', 'ivx_conv_fwd_pio_naive', 'ivx_pair_pack_filters', 'ivx_nchw_to_nhwc_amax', 'ivx_maxpool2d_fwd_pair', 'ivx_f16_pair_merge', 'ivx_model_calibrate_fp8', 'ivx_model_calibrate_fp8_ex', 'ivx_amax_bf16', 'ivx_conv_winograd_output_blocks', 'ivx_conv_winograd_issued_fraction', 'ivx_conv_winograd_output_amax', 'ivx_conv_winograd_input_amax', 'ivx_conv_winograd_fused_supported', 'ivx_conv_winograd_fused_blocks', 'ivx_conv_winograd_gemm_output_amax',
+EXPORTS = ['ivx_conv_plan_query', 'ivx_conv_tile_info', 'ivx_model_plan_info', 'ivx_model_plan_step', 'ivx_model_plan_tensor', 'ivx_bottleneck_proj_supported', 'ivx_bottleneck_proj_pack', 'ivx_bottleneck_proj_fwd_pio', 'ivx_anchor_head_decode', 'ivx_fcos3d_head_decode', 'ivx_nms_rotated_bev', 'ivx_nms_aligned3d', 'ivx_bottleneck_supported', 'ivx_bottleneck_fwd_pio', 'ivx_amax_f32', 'ivx_stem_pool_filter_bytes', 'ivx_stem_pool_pack_filters', 'ivx_stem_pool_out_dims', 'ivx_stem_pool_fwd_pair', 'ivx_conv_winograd_set_variant', 'ivx_ubench_mfma', 'ivx_ubench_copy', 'ivx_version', 'ivx_last_error', 'ivx_conv_out_dims', 'ivx_conv_fwd', 'ivx_conv_fwd_naive', 'ivx_conv_set_tile_override', 'ivx_conv_set_epilogue_mode', 'ivx_conv_set_plan_mode', 'ivx_topk_set_mode', 'ivx_conv_workspace_bytes', 'ivx_conv_fwd_ws', 'ivx_conv_set_halo_mode', 'ivx_bf16_pair_split', 'ivx_f16_pair_split', 'ivx_conv_pair_supported', 'ivx_bf16_pair_pack_filters', 'ivx_conv_route', 'ivx_conv_pio_workspace_bytes', 'ivx_conv_fwd_pio', 'ivx_conv_fwd_pio_naive', 'ivx_pair_pack_filters', 'ivx_nchw_to_nhwc_amax', 'ivx_maxpool2d_fwd_pair', 'ivx_f16_pair_merge', 'ivx_model_calibrate_fp8', 'ivx_model_calibrate_fp8_ex', 'ivx_amax_bf16', 'ivx_conv_winograd_output_blocks', 'ivx_conv_winograd_issued_fraction', 'ivx_conv_winograd_output_amax', 'ivx_conv_winograd_input_amax', 'ivx_conv_winograd_fused_supported', 'ivx_conv_winograd_fused_blocks', 'ivx_conv_winograd_gemm_output_amax',
            'ivx_conv_winograd_bg_supported', 'ivx_conv_winograd_bg_bytes', 'ivx_conv_winograd_bg_layer_offset', 'ivx_conv_winograd_bg_plan',
            'ivx_conv_winograd_input_bg', 'ivx_conv_winograd_gemm_bg', 'ivx_conv_winograd_output_bg',
            'ivx_conv_winograd_supported', 'ivx_conv_winograd_weight_elems', 'ivx_conv_winograd_weights', 'ivx_conv_winograd_workspace_bytes',
@@ -228,6 +235,8 @@ def lib():
     L.ivx_bf16_pair_pack_filters.argtypes = [vp, i32, i32, i32, i32, vp]
     L.ivx_conv_route.argtypes = [C.POINTER(ConvDesc), i32, C.POINTER(ConvRouteOpts), C.POINTER(ConvRoute)]
     L.ivx_conv_pio_workspace_bytes.argtypes = [C.POINTER(ConvDesc), C.POINTER(PairIO)]
+    L.ivx_conv_plan_query.argtypes = [C.POINTER(ConvDesc), C.POINTER(PairIO), C.c_int, C.c_int, C.POINTER(ConvPlanRec)]
+    L.ivx_conv_tile_info.argtypes = [C.c_int, C.POINTER(i32)]
     L.ivx_conv_pio_workspace_bytes.restype = i64
     L.ivx_amax_f32.argtypes = [vp, i64, vp, vp]
     L.ivx_stem_pool_filter_bytes.restype = i64

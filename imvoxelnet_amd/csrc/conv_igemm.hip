@@ -19,89 +19,24 @@
 //               M tiles so halo re-reads hit its own L2).
 //
 // Reference call sites replaced: see include/imvoxel.h (ivx_conv_fwd).
-#include "ivx_common.h"
-#include <stdlib.h>
+#include "conv_plan.h"      // ConvParams / ConvPlan and the cross-unit prototypes (conv_shared.h), the tile table (conv_tiles.h), the planner
+#include "../../include/imvoxel_lab.h"
+#include <string.h>
 
 // This file is compiled six times (imvoxelnet_amd/_build.py), each translation unit instantiating one family of the LDS-DMA kernel, so that
 // the families build in parallel:  IVX_CONV_TU 0 = the host side, the generic / naive / reduce kernels;  1 = fp32;  2 = bf16 and e4m3;
 // 3 = bf16 (hi, lo) pair operands;  4 = fp16 pair operands;  5 = the z-halo kernel (conv_wino_halo_kernel).
+// Which tile number is which instantiation: conv_tiles.h (every launch switch below expands its rows).  Which number a launch takes:
+// conv_plan.cpp (host only); TU 0 keeps fill_params, run_conv, conv_dispatch and the entry points.
 #ifndef IVX_CONV_TU
 #define IVX_CONV_TU 0
 #endif
-struct ConvParams;
-struct ConvPlan;
-int ivx_conv_launch_f32(ConvParams &p, const ConvPlan &pl, hipStream_t st);
-int ivx_conv_launch_lowp(ConvParams &p, const ConvPlan &pl, hipStream_t st);
-int ivx_conv_launch_pair_bf16(ConvParams &p, const ConvPlan &pl, hipStream_t st);
-int ivx_conv_launch_pair_f16(ConvParams &p, const ConvPlan &pl, hipStream_t st);
-int ivx_conv_launch_halo(ConvParams &p, int cfg, hipStream_t st);    // TU 5: the z-halo kernel of the Winograd-domain GEMMs (pair operands)
-int ivx_conv_launch_fold4(ConvParams &p, const IvxWinoFold &f, int n2, hipStream_t st);    // TU 5: GEMM + output transform of F(4x4,3x3) fused
-int ivx_conv_fold4_blocks(long long M, int Cout);
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-struct ConvParams {
-  const float *in, *wgt, *scale, *shift, *res;
-  float *out;
-  int B, D, H, W, Cin;
-  int Cout, KD, KH, KW;
-  int sd, sh, sw, pd, ph, pw;
-  int Do, Ho, Wo;
-  int M, K;
-  int relu, res_mode, rH, rW;
-  int kmode;  // 0: k = tap*Cin + ci   1: k = (ci/32)*taps*32 + tap*32 + ci%32
-  int out_mode;       // 1: ConvTranspose(k2,s2) scatter: column n = tap*Cr + co goes to output voxel 2*(d,h,w) + tap
-  int Cr;             // real output channels (Cout / 8 when out_mode == 1, else Cout)
-  int res_after_act;  // add the residual after the activation (skip connections of the U-shaped necks)
-  float post_scale;   // final multiplier (Atlas neck (x + y) / 2); 1 = none
-  int ksplit;         // > 1: split-K, grid.y = slice; raw partial sums go to `partial` [ksplit][8*q_count*BM][Cout]
-  float *partial;
-  // M-tile range of this launch (LDS-DMA kernel): XCD x owns tiles [x*q_total, (x+1)*q_total); this launch covers the
-  // q_count tiles starting at q_begin inside every XCD's range.  Whole problem: q_begin 0, q_count q_total.
-  int q_total, q_begin, q_count, bm;
-  int in_bf16;        // in / wgt are bf16 (LDS-DMA kernel only); accumulation is always fp32
-  int out_bf16;       // out / res are bf16 (converted round-to-nearest-even in the epilogue)
-  // grouped launch (LDS-DMA kernel, grid.z = group; the Winograd-domain GEMMs): group g reads in + g*g_in, wgt + g*g_w
-  // and writes out + g*g_out (element strides; all 0 for an ordinary convolution)
-  long long g_in, g_w, g_out;
-  int groups;
-  int narrow_epilogue;  // A/B knob: 1 = the one-channel-per-lane epilogue everywhere (ivx_conv_set_epilogue_mode)
-  int in_fp8;         // in / wgt are OCP e4m3 bytes (v_mfma_f32_32x32x16_fp8_fp8); dequantisation is folded into scale[]
-  int out_fp8;        // out / res are e4m3 bytes (saturating round-to-nearest-even at the store)
-  float res_scale;    // multiplier of the residual (fp8 storage: res_scale_of_tensor / out_scale); 1 otherwise
-  int in_pair;        // 1 / 2: in / wgt hold every fp32 value as a (hi, lo) bf16 / fp16 pair, 16-channel groups [hi16 | lo16] (IVX_*_PAIR); Cin and K
-                      // count bf16 elements (2 per real channel); the K loop issues hi*hi + hi*lo + lo*hi per group
-  // fp16-pair ACTIVATIONS with device-side power-of-two scales (ivx_pair_io, include/imvoxel.h): the 2-D trunk chained on the 16-bit
-  // matrix cores without split passes -- the producing epilogue writes the operand its consumer reads.
-  int pio;                       // any of the fields below is in use (in_pair == 2 kernels, the split-K reduction, the validation kernel)
-  const float *in_scale_p;       // device: the scale the pair input was written with (NULL: 1); the accumulator is divided by it
-  int out_pair, res_pair;        // out / res are IVX_F16_PAIR tensors [.., 2*Cout] (independently of each other)
-  const float *res_scale_p;      // device: scale of the pair residual
-  float *out_scale_p;            // device: receives the scale chosen for the output
-  const unsigned *amax_in, *amax_res;   // device, IVX_AMAX_SLOTS words: bits of max |in| / max |res| (true values); out_pair only
-  unsigned *amax_out;            // device, IVX_AMAX_SLOTS words the epilogue accumulates max |out| into (atomic max), or NULL
-  float wbound, sbound;          // |out| <= amax_in * wbound + sbound (+ amax_res): max_co |scale[co]| * sum_k |w[co][k]| and max_co |shift[co]|
-  // one device word copied by workgroup 0 of the launch (grouped Winograd-domain GEMMs: the filter scale travels to the workspace header
-  // the output transform reads -- was a 4-byte hipMemcpyAsync, i.e. one more launch per neck layer); NULL = none
-  const unsigned *cp_src;
-  unsigned *cp_dst;
-  // Row count of the launch on the DEVICE (conv_wino_halo_kernel / conv_wino_zblk_kernel: the compacted Winograd-domain GEMMs of a neck
-  // whose background tiles are computed once, winograd.hip): *m_dev <= M rows are computed; the grid keeps the size of M rows and the
-  // surplus workgroups return before their first barrier.  NULL = M.
-  const int *m_dev;
-  // Phase stagger of the first round of workgroups (pair-IO launches with a residual epilogue, run_conv): workgroups whose XCD-local index q has bit
-  // stagger_shift set and q < stagger_first wait stagger_ticks (100 MHz) before their first request, so that the K loops of one half of the resident
-  // workgroups overlap the epilogues of the other half for the rest of the launch.  0 ticks = off.
-  int stagger_ticks, stagger_shift, stagger_first;
-#ifdef IVX_CONV_TIMELINE
-  unsigned long long *tl;        // debug build only (tools/conv_timeline.py): 8 words per workgroup of conv_igemm_v4_kernel's pair-IO path --
-                                 // s_memrealtime (100 MHz) at entry, after the prologue barrier, after the K loop, at the end; HW_ID; XCC_ID
-#endif
-};
 
 // What a wave needs of the pair-IO state: multipliers of the accumulator / the residual (exact: powers of two) and the output scale.
 struct PairIO { float inv_in, inv_res, s_out; bool sat; float post; };      // post = ConvParams::post_scale (carried here: see conv_igemm_v4_kernel)
@@ -1385,20 +1320,6 @@ __global__ __launch_bounds__(256) void conv_naive_f32_kernel(const ConvParams p)
 static unsigned long long *g_timeline = nullptr;
 extern "C" int ivx_conv_set_timeline(void *buf) { g_timeline = (unsigned long long *)buf; return 0; }
 #endif
-static thread_local int g_plan_mode = 0;
-// Tuning knob (A/B; per calling thread): 1 = the round-1 tile rule of plan_conv, 0 (default) = the scored choice.
-extern "C" int ivx_conv_set_plan_mode(int mode) {
-  g_plan_mode = mode;
-  return IVX_OK;
-}
-
-static thread_local int g_narrow_epilogue = 0;
-// Tuning knob (A/B experiments; per calling thread): 1 = one-channel-per-lane epilogue stores in the LDS-DMA kernel,
-// 0 (default) = the LDS-transposed wide-store epilogue where it applies.
-extern "C" int ivx_conv_set_epilogue_mode(int narrow) {
-  g_narrow_epilogue = narrow ? 1 : 0;
-  return IVX_OK;
-}
 
 static int fill_params(const ivx_conv_desc *d, const void *in, const void *wgt, const float *scale,
                        const float *shift, const void *res, void *out, ConvParams *p, const ivx_pair_io *io = nullptr) {
@@ -1457,7 +1378,7 @@ static int fill_params(const ivx_conv_desc *d, const void *in, const void *wgt, 
   p->ksplit = 1; p->partial = nullptr; p->q_total = 0; p->q_begin = 0; p->q_count = 0; p->bm = 0;
   p->stagger_ticks = 0; p->stagger_shift = 0; p->stagger_first = 0;
   p->groups = 1; p->g_in = p->g_w = p->g_out = 0;
-  p->narrow_epilogue = g_narrow_epilogue;
+  p->narrow_epilogue = conv_lab().narrow_epilogue;
 #ifdef IVX_CONV_TIMELINE
   p->tl = g_timeline;
 #endif
@@ -1527,361 +1448,32 @@ static void launch_v4(ConvParams &p, hipStream_t st) {
 }
 
 
-
-struct ConvPlan {
-  int cfg;       // tile / kernel selector (see launch_one)
-  int ksplit;    // > 1: split K over the whole problem (small outputs)
-  int tail_ks;   // > 1: the last partial round of M-tiles runs as a second launch with K split tail_ks ways
-  int q_total;   // M-tiles per XCD (LDS-DMA kernels)
-  int qa;        // M-tiles per XCD covered by the first launch when tail_ks > 1
-  int bm;        // tile rows of the chosen config
-  int64_t ws_bytes;
-};
-
-
-#if IVX_CONV_TU == 0
-static thread_local int g_halo_mode = -1;   // A/B knob (ivx_conv_set_halo_mode): -1 default rule | 0 never | 1 .. 14 / 30 .. 34 force that z-halo config of the stride-1 layers, 21 .. 24 / 41 .. 45 of the z-stride-2 layers
-extern "C" int ivx_conv_set_halo_mode(int mode) {
-  g_halo_mode = mode;
-  return IVX_OK;
-}
-static thread_local int g_tile_override = 0;
-// Tuning knob (A/B experiments, tools/conv_bench.py; per calling thread): 0 = automatic choice, else force a tile
-// config of launch_one (1..7 generic kernel, 41..53 LDS-DMA fp32, 61..73 LDS-DMA bf16).
-extern "C" int ivx_conv_set_tile_override(int cfg) {
-  g_tile_override = cfg;
-  return IVX_OK;
-}
-
-struct TileInfo { int bm, bn, bk, wg_per_cu; };
-static bool tile_info(int cfg, TileInfo *t) {
+// The launch switch of an LDS-DMA translation unit: the rows of conv_tiles.h that name the operand family FAM, on the element type T.
+// false: FAM has no instantiation of `cfg`.
+template <typename T, int FAM, int PAIR = 0>
+static bool launch_tile(ConvParams &p, int cfg, hipStream_t st) {
   switch (cfg) {
-    case 41: *t = {128, 128, 32, 2}; return true;
-    case 43: *t = {128, 64, 32, 3}; return true;
-    case 44: *t = {128, 32, 32, 4}; return true;
-    case 46: *t = {64, 64, 32, 5}; return true;
-    case 51: *t = {128, 128, 16, 3}; return true;
-    case 53: *t = {128, 64, 16, 5}; return true;
-    case 52: *t = {256, 64, 16, 3}; return true;
-    case 54: *t = {128, 128, 16, 4}; return true;
-    case 55: *t = {128, 128, 16, 5}; return true;
-    case 56: *t = {128, 64, 16, 6}; return true;
-    case 57: *t = {256, 64, 16, 4}; return true;
-    case 58: *t = {256, 128, 16, 2}; return true;
-    case 59: *t = {128, 256, 16, 2}; return true;
-    case 47: *t = {64, 64, 16, 6}; return true;
-    case 48: *t = {64, 128, 16, 5}; return true;
-    case 49: *t = {128, 64, 16, 5}; return true;
-    case 74: *t = {128, 128, 32, 4}; return true;
-    case 91: *t = {128, 128, 64, 4}; return true;
-    case 92: *t = {128, 64, 64, 5}; return true;
-    case 93: *t = {64, 64, 64, 6}; return true;
-    case 94: *t = {128, 128, 128, 2}; return true;
-    case 81: *t = {256, 128, 32, 2}; return true;
-    case 82: *t = {256, 256, 32, 1}; return true;
-    case 83: *t = {256, 128, 64, 1}; return true;
-    // bf16 (cfg + 20: same tile, same LDS bytes, BK counts bf16 elements)
-    case 61: *t = {128, 128, 64, 2}; return true;
-    case 63: *t = {128, 64, 64, 3}; return true;
-    case 64: *t = {128, 32, 64, 4}; return true;
-    case 66: *t = {64, 64, 64, 5}; return true;
-    case 67: *t = {64, 64, 32, 6}; return true;
-    case 71: *t = {128, 128, 32, 3}; return true;
-    case 73: *t = {128, 64, 32, 5}; return true;
-    case 75: *t = {128, 64, 32, 5}; return true;
-    case 76: *t = {256, 64, 32, 4}; return true;
-    case 85: *t = {128, 256, 32, 2}; return true;
-    case 72: *t = {256, 64, 32, 3}; return true;
-    // deep-ring forms of 66 / 74 (pair operands): NB = 4 -> 64 KB of LDS, two workgroups per CU; NB = 3 -> 48 KB, three
-    case 166: *t = {64, 64, 64, 2}; return true;
-    case 174: *t = {128, 128, 32, 2}; return true;
-    case 474: *t = {128, 128, 32, 3}; return true;
-    case 475: *t = {128, 128, 32, 2}; return true;
-    case 574: *t = {128, 128, 32, 2}; return true;
-    case 177: *t = {128, 128, 32, 2}; return true;
-    case 179: *t = {128, 128, 64, 1}; return true;
-    case 77: *t = {128, 128, 32, 2}; return true;
-    case 183: *t = {256, 256, 32, 1}; return true;
+#define IVX_ROW(n, fam, TM, TN, WR, WC, BK, WPE, NB, RPF, WG) \
+    case n: if constexpr ((IVX_FAM_##fam & FAM) != 0) { launch_v4<T, TM, TN, WR, WC, BK, WPE, PAIR, NB, RPF>(p, st); return true; } else return false;
+    IVX_CONV_TILES(IVX_ROW)
+#undef IVX_ROW
     default: return false;
   }
 }
 
-static bool dma_applicable(const ConvParams &p) {
-  const int el = p.in_fp8 ? 1 : (p.in_bf16 ? 2 : 4);
-  const int64_t in_b = (int64_t)p.B * p.D * p.H * p.W * p.Cin * el, w_b = (int64_t)p.Cout * p.K * el;
-  return in_b < (1LL << 31) && w_b < (1LL << 31) && p.KD <= 8 && p.KH <= 8 && p.KW <= 8;
-}
-
-// Kernel / tile / split-K choice (measured per layer on MI355X with tools/conv_bench.py).
-//  * Big problems want the 128-row tiles with the best MFMA : staging ratio; BK 16 keeps LDS at 32 KB and the
-//    128 x 128 kernel is compiled for <= 128 registers (launch bound 4 waves/SIMD), so four workgroups share a CU
-//    (+2.5 % per layer over three; measured).  When 128 x 128 tiles would not fill the workgroup slots several
-//    times over -- every ResNet/FPN layer at KITTI resolution, the indoor necks -- 64 x 64 tiles win by occupancy.
-//  * When even 64 x 64 tiles leave most of the 256 CUs idle and K is long (ResNet stage 4, FPN laterals on C5, the
-//    coarse levels of the indoor necks), K is split across grid.y and a second pass sums the slices.
-//  * Grid tail: with uniform tiles the last partial round costs a whole workgroup time on a few CUs while the rest
-//    idle (measured: 10 044 tiles on 768 slots = 13.08 rounds runs 4 % slower per tile than exactly 13 rounds).
-//    When the remainder is at most half a round, the full rounds run as one launch and the remainder as a second
-//    launch with K split so that it fills every slot once (needs the caller's workspace: ivx_conv_fwd_ws).
-//  * The LDS-DMA kernel (cfg 4x/5x fp32, 6x/7x bf16) is used whenever its preconditions hold, else the same tile on
-//    the generic kernel (cfg 1..7).
-static int conv_skinny_rule() {
-  static const int v = getenv("IVX_CONV_SKINNY") ? atoi(getenv("IVX_CONV_SKINNY")) : 1;
-  return v;
-}
-static ConvPlan plan_conv(const ConvParams &p, bool allow_ws) {
-  ConvPlan pl = {g_tile_override, 1, 1, 0, 0, 0, 0};
-  const bool dma_ok = dma_applicable(p);
-  bool small = false;
-  if (pl.cfg == 0 && dma_ok && !p.in_bf16 && p.Cout > 32 && g_plan_mode == 0) {
-    // fp32 LDS-DMA kernel: score the three tile shapes by (tile efficiency) x (useful fraction of the padded tile grid) x (fill
-    // of the last round of workgroup slots) and take the best.  The round-1 rule (128 x 128 from 2500 tiles on, else 64 x 64)
-    // left the mid-sized layers of the 2-D trunk -- 900 .. 2500 big tiles, i.e. 0.9 .. 2.4 rounds of 1024 slots -- on 64 x 64
-    // tiles at ~0.8 of the big tile's rate, or on a half-empty second round; 128 x 64 at five per CU sits in between.
-    // Efficiencies are the measured per-tile rates on long layers relative to 128 x 128 (141 / 131 / 113 TFLOP/s).
-    // Short K (the 1x1 layers up to 512 input channels): one or two K slabs per tile, the tile's time is its epilogue and the
-    // latency of its loads, and six 128 x 64 workgroups per CU (56) overlap those better than four 128 x 128: interleaved A/B
-    // at 50 views (tools/conv_ab.py, profiles/r02_conv_ab_f32.log) 64->256 0.547 vs 0.640 ms, 128->512 0.378 vs 0.417,
-    // 256->1024 0.293 vs 0.310, 512->2048 0.269 vs 0.290; from K = 1024 on the 128 x 128 tile is ahead again.
-    const bool short_k = p.K <= 512;
-    const int c64 = p.K <= 640 ? 47 : 46;
-    const int cand[3] = {54, short_k ? 56 : 49, c64};
-    const double eff[3] = {short_k ? 0.93 : 1.00, short_k ? 1.00 : 0.93, short_k ? 0.85 : 0.80};
-    double best = -1.0;
-    for (int i = 0; i < 3; ++i) {
-      TileInfo ti;
-      tile_info(cand[i], &ti);
-      const double tiles = (double)((p.M + ti.bm - 1) / ti.bm) * ((p.Cout + ti.bn - 1) / ti.bn);
-      const double util = (double)p.M * p.Cout / (tiles * ti.bm * ti.bn);
-      const double rounds = tiles / (256.0 * ti.wg_per_cu);
-      const double fill = rounds >= 1.0 ? rounds / (double)(long long)(rounds + 0.999999) : rounds;
-      const double score = eff[i] * util * fill;
-      if (score > best) { best = score; pl.cfg = cand[i]; }
-    }
-    small = pl.cfg == c64;
-    // (Round 6, measured and not adopted -- profiles/r06_skinny_convs.md: 128 x 128 / 256 x 128 tiles + split K for the layers of a few hundred rows
-    // under a K loop of 13824 .. 27648 (512 -> 512 at 10 x 10 x 4): 0.084 -> 0.140 / 0.243 ms per launch.  These launches are bound by the number of
-    // slabs a workgroup runs one after the other, not by L2 -> LDS bytes: 64 x 64 tiles with K split 27 ways stay.)
-  }
-  if (pl.cfg == 0) {
-    const long long nblk = (long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-    if (p.Cout <= 32) {
-      pl.cfg = dma_ok ? 44 : 4;
-      // the head convs of the indoor configs (Cout = 25) on the coarse levels: 4 .. 25 row tiles under a K loop of 54 .. 108 slabs ran as that
-      // many workgroups, one slab after the other (89 us for 69 MFLOP at 10 x 10 x 4); K is split as for every other small layer
-      // (IVX_CONV_SKINNY=0: the round-5 rule, for A/B)
-      small = dma_ok && !p.in_bf16 && !p.in_fp8 && conv_skinny_rule() != 0;
-    } else if (nblk >= 2500) {
-      pl.cfg = p.Cout > 64 ? (dma_ok ? 54 : 1) : (dma_ok ? (p.K <= 640 ? 49 : 56) : 3);   // 49: the stem
-    } else {
-      // short-K layers (1x1 convolutions, 3x3 on 64 channels, the stem) are staging/latency-bound: the 64-byte-row
-      // variant at six workgroups per CU keeps more loads in flight; long-K layers prefer the 128-byte rows
-      pl.cfg = dma_ok ? (p.K <= 640 ? 47 : 46) : 6;
-      small = true;
-    }
-  }
-  if (p.in_fp8) {
-    // e4m3 storage (2-D trunk of the bf16 + fp8 mode): HBM / latency-bound like the bf16 trunk, same rule: 128 x 128 at four per
-    // CU, 128 x 64 for Cout <= 64, 64 x 64 (+ split K) when the tiles would not fill the workgroup slots
-    if (g_tile_override >= 91 && g_tile_override <= 94) {
-      pl.cfg = g_tile_override;
-    } else {
-      const long long t128 = (long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-      if (p.Cout <= 64) pl.cfg = ((long long)((p.M + 127) / 128) * 2 > 256 * 5) ? 92 : 93;
-      else pl.cfg = t128 * 2 > 1024 ? 91 : 93;
-      small = pl.cfg == 93;
-    }
-  }
-  if (p.in_bf16 && g_tile_override == 0 && dma_ok && p.Cout > 32 && g_plan_mode == 0) {
-    // bf16: interleaved A/B over the layers of the 2-D trunk at 50 views (tools/conv_ab.py, profiles/r02_conv_ab_bf16.log).
-    // At 8x the MFMA rate every 1x1 layer and most 3x3 layers are bound by HBM / staging latency, and what matters is how
-    // many workgroups a CU holds to overlap one tile's epilogue with another's loads: 128 x 128 with 64-byte LDS rows at four
-    // per CU (74) is the best or within 5 % of it on all of them (the 1 / 2 per CU of 82 / 81 / 61 lose 20-40 % on short K);
-    // Cout <= 64 takes 128 x 64 (63).  The 8- / 16-wave tiles keep the long-K layers with many tiles (the 3-D necks), and
-    // layers that would leave most workgroup slots empty keep the 64 x 64 + split-K path below.
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-    if (p.Cout <= 64) {
-      if ((long long)((p.M + 127) / 128) * 2 > 256 * 3) pl.cfg = 63;
-    } else if (t128 * 2 > 1024 && !(t128 >= 2500 && p.K >= 1024)) {
-      pl.cfg = 74;
-    }
-    if (pl.cfg == 63 || pl.cfg == 74) small = false;
-  }
-  if (p.in_bf16 && pl.cfg >= 41 && pl.cfg <= 57) {
-    // same tile, bf16 instantiation -- except for the big layers: at 8x the MFMA rate the kernel is bound by the
-    // L2 -> LDS staging traffic (ablation: +33 % without the loads), so the 256 x 128 / 256 x 256 workgroups of 8 / 16
-    // waves, which move 25 % / 50 % fewer bytes per flop, win there (measured, tools/conv_bench.py --dtype bf16)
-    if (g_tile_override == 0 && pl.cfg == 54) pl.cfg = p.Cout > 128 ? 82 : 81;   // 16 / 8 waves: less L2->LDS traffic per flop
-    else if (pl.cfg == 54 || pl.cfg == 55) pl.cfg = 74;
-    else if (pl.cfg == 48) pl.cfg = 66;
-    else if (pl.cfg == 49 || pl.cfg == 56) pl.cfg = 73;
-    else if (pl.cfg == 57) pl.cfg = 72;
-    else if (pl.cfg <= 53) pl.cfg += 20;   // 41..47, 51..53 -> 61..67, 71..73
-  }
-  if (p.in_pair && g_tile_override == 0) {   // pair operands are instantiated for a subset of the bf16 tiles
-    if (pl.cfg == 64) pl.cfg = 67;
-    else if (pl.cfg == 71) pl.cfg = 74;
-    else if (pl.cfg == 72) pl.cfg = 73;
-  }
-  static const int pio_rule = getenv("IVX_PIO_RULE") ? atoi(getenv("IVX_PIO_RULE")) : 1;        // A/B knobs of the round-4 measurements
-  static const int pio_splitk = getenv("IVX_PIO_SPLITK") ? atoi(getenv("IVX_PIO_SPLITK")) : 1;
-  if (p.in_pair == 2 && p.pio && g_tile_override == 0 && dma_ok && pio_rule) {
-    // Chained fp16-pair activations (the 2-D trunk): interleaved A/B of every pair tile on the trunk's layer shapes at KITTI batch 4 and at
-    // 50 views (tools/pio_ab.py, profiles/r04_pio_ab_*.md).  128 x 128 with 64-byte LDS rows at four per CU (74) is the best or within
-    // 5-10 % of it wherever it fills the chip, also for Cout = 64 at KITTI size (half of its B tile is zero fill, and it still beats
-    // 128 x 64 / 256 x 64: 43 vs 50 / 47 us); the 50-view maps of 64 output channels take 256 x 64 (76); layers with few tiles take
-    // 64 x 64 with 128-byte rows (66: 63 vs 90 us on 256 -> 256 3x3 at 24 x 80 x 4, 49 vs 58 on 1024 -> 256) + split K.
-    const long long t128 = (long long)((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-    if (p.Cout <= 64) pl.cfg = p.M >= 400000 ? 76 : (p.M >= 60000 ? 74 : 66);
-    else pl.cfg = t128 >= 200 ? 74 : 66;
-    small = pl.cfg == 66 && pio_splitk;
-    // Round 5: a launch with fewer tiles than the chip has workgroup slots (every /8 .. /32 layer of the trunk at KITTI's batch of 4: 240 - 480
-    // tiles) cannot hide its slab latency behind other resident workgroups; it takes the deep-ring form of its tile (166 / 174: FOUR slabs
-    // in flight per workgroup, raw barriers; bit-identical results) unless the split-K rule below takes it.  Measured (profiles/
-    // r05_trunk_deep_ring.md): trunk span 3.85 -> 3.39 ms at KITTI; tiles <= 512 is the best threshold (1024 / 2048 / all: 3.61 -- above one
-    // tile per slot the 64 KB workgroups lose more occupancy than the depth returns).  The first form of the deep ring kept __syncthreads(),
-    // whose fence waits for vmcnt(0): no effect in the model and +25 us per launch in isolation.  IVX_PIO_DEEP=0 turns the rule off (A/B).
-    static const int pio_deep = getenv("IVX_PIO_DEEP") ? atoi(getenv("IVX_PIO_DEEP")) : 4;
-    if (pio_deep == 4) {
-      TileInfo td;
-      tile_info(pl.cfg, &td);
-      const long long tl = (long long)((p.M + td.bm - 1) / td.bm) * ((p.Cout + td.bn - 1) / td.bn);
-      const int Sd = (p.K + td.bk - 1) / td.bk;
-      static const long long split_tiles = getenv("IVX_PIO_SPLIT_TILES") ? atoll(getenv("IVX_PIO_SPLIT_TILES")) : 320;
-      const bool will_split = small && allow_ws && Sd >= 16 && tl <= split_tiles && (tl <= 100 || Sd >= 48);      // (the rule of the split-K block below)
-      static const long long deep_tiles = getenv("IVX_PIO_DEEP_TILES") ? atoll(getenv("IVX_PIO_DEEP_TILES")) : 512;
-      static const int deep_slabs = getenv("IVX_PIO_DEEP_SLABS") ? atoi(getenv("IVX_PIO_DEEP_SLABS")) : 6;
-      if (!will_split && p.kmode == 1 && Sd >= deep_slabs && tl <= deep_tiles && (pl.cfg == 66 || pl.cfg == 74)) {      // (only these two have a deep-ring form)
-        pl.cfg += 100;       // 66 -> 166, 74 -> 174
-        // ... and the 128 x 128 tile runs on MORE WAVES where the launch leaves SIMDs idle: 16 waves (179: wave tile 32 x 32, 128-byte rows, 128 KB, one
-        // workgroup per CU) up to one tile per CU, 8 waves (177: wave tile 64 x 32) up to two.  A slab's LDS-DMA requests, fragment reads, barriers
-        // and the epilogue are issued by 4x / 2x the waves (workgroup timelines, profiles/r05_trunk_wg_timeline.md: 512 -> 128 at 48 x 160 x 4
-        // 27.1 -> 23.1 -> 20.2 us, 128 -> 128 3x3 46.8 -> 41.1 -> 34.9, 512 -> 2048 + residual at 12 x 40 33.5 -> 26.9 -> 21.9).  Same products in
-        // the same order per output: bit-identical.
-        static const long long w16_tiles = getenv("IVX_PIO_W16_TILES") ? atoll(getenv("IVX_PIO_W16_TILES")) : 256;
-        static const long long w8_tiles = getenv("IVX_PIO_W8_TILES") ? atoll(getenv("IVX_PIO_W8_TILES")) : 512;
-        if (pl.cfg == 174) pl.cfg = tl <= w16_tiles ? 179 : (tl <= w8_tiles ? 177 : 174);
-        small = false;
-      }
-    }
-    // Round 6: the 256 x 256 tile on 16 waves (183: three-buffer ring, one workgroup per CU; built for the neck's last layer) for the wide layers of the
-    // multi-view maps -- half the L2 -> LDS bytes per product of the 128 x 128 tile.  It wins where its tiles fill the 256 CUs in whole rounds: interleaved
-    // A/B over the trunk's layers at 50 / 20 ScanNet views, nuScenes and KITTI (tools/pio_ab.py --cfgs 0,74,81,82,183; profiles/r06_tile183_trunk.md):
-    // 235 - 1876 tiles at 50 views -5 .. -19 % per launch (1024 -> 256 0.141 -> 0.114 ms, 256 -> 256 3x3 0.239 -> 0.202, 256 -> 1024 + residual 0.225 -> 0.215),
-    // 272 tiles (1.06 rounds) +4 .. +10 %, 94 - 136 tiles +30 %; the nearest-upsampled FPN laterals lose 4 %.  Rule: last-round fill of the 256 x 256 grid
-    // >= 0.7.  Same products in the same order per output: bit-identical.  IVX_PIO_T183=0 turns it off (A/B).
-    static const int pio_t183 = getenv("IVX_PIO_T183") ? atoi(getenv("IVX_PIO_T183")) : 1;
-    if (pio_t183 && pl.cfg == 74 && p.in_pair == 2 && p.kmode == 1 && p.res_mode != 2 && p.Cout >= 256 && p.Cout % 256 == 0) {
-      const long long t256 = (long long)((p.M + 255) / 256) * (p.Cout / 256);
-      const long long rounds = (t256 + 255) / 256;
-      if (t256 * 10 >= rounds * 256 * 7) {
-        pl.cfg = 183;
-        small = false;
-      }
-    }
-  }
-  TileInfo t;
-  if (!tile_info(pl.cfg, &t) || !dma_ok) return pl;
-  const long long Mt = (p.M + t.bm - 1) / t.bm, Nt = (p.Cout + t.bn - 1) / t.bn;
-  pl.q_total = (int)((Mt + 7) / 8);
-  pl.bm = t.bm;
-  if (!allow_ws || g_tile_override != 0) return pl;
-  const int S = (p.K + t.bk - 1) / t.bk;
-  if (small) {
-    const long long tiles = Mt * Nt;
-    const long long slots = 256LL * t.wg_per_cu;           // resident workgroups on the chip
-    static const long long pio_split_tiles = getenv("IVX_PIO_SPLIT_TILES") ? atoll(getenv("IVX_PIO_SPLIT_TILES")) : 320;
-    // Pair IO: at 16-bit MFMA rates a tile is short and a split costs a second launch plus the partial sums' round trip, so it pays only
-    // below about one tile per CU, and for the mid-sized layers only when the K loop is long.  Measured through bench.py's trunk span
-    // (profiles/r04_pio_split_rule.md): KITTI 4.24 ms with the fp32 rule (2 * tiles <= slots), 4.01 without any split, 3.88 with
-    // tiles <= 320; single-view SUN RGB-D 2.42 without, 2.06 with tiles <= 320, 1.86 with tiles <= 100 (its 150 / 160-tile layers have
-    // K loops of 16 .. 36 slabs and lose from the split; KITTI's 240-tile layers have 64 .. 144 and gain).
-    const bool pio_split = tiles <= pio_split_tiles && (tiles <= 100 || S >= 48);
-    if ((p.pio ? pio_split : 2 * tiles <= slots) && S >= 16) {     // under half a round: split K until the slots are filled once
-      long long ks = (slots + tiles - 1) / tiles;
-      if (ks > S / 8) ks = S / 8;
-      if (ks > 32) ks = 32;
-      if (ks >= 2) {
-        pl.ksplit = (int)ks;
-        pl.ws_bytes = ivx_align_up((int64_t)ks * 8 * pl.q_total * t.bm * p.Cout * 4, 256);
-      }
-    }
-    return pl;
-  }
-  // tail plan
-  // (Round 6: not for pair IO.  At 16-bit MFMA rates a tile is short: the second launch + the partial sums' round trip + the reduction cost more than
-  // the idle slots of the last round -- the same layers run 5 - 12 % faster as ONE launch (tools/pio_ab.py, cfg 0 vs the same tile forced:
-  // nuScenes 512 -> 1024 s2 0.177 -> 0.156 ms, 256 -> 512 s2 0.215 -> 0.195, 256 -> 128 0.257 -> 0.235; profiles/r06_tile183_trunk.md (c)).  IVX_PIO_TAIL=1 restores it.)
-  static const int pio_tail = getenv("IVX_PIO_TAIL") ? atoi(getenv("IVX_PIO_TAIL")) : 0;
-  if (p.pio && !pio_tail) return pl;
-  const long long spx = 32LL * t.wg_per_cu;              // workgroup slots per XCD
-  const long long bpx = (long long)pl.q_total * Nt;      // workgroups per XCD
-  const long long fr = bpx / spx, rem = bpx - fr * spx;
-  if (fr >= 2 && rem > 0 && 2 * rem <= spx && (fr * spx) % Nt == 0) {
-    long long ks = spx / rem;
-    if (ks > S / 8) ks = S / 8;
-    if (ks > 16) ks = 16;
-    if (ks >= 2) {
-      pl.tail_ks = (int)ks;
-      pl.qa = (int)(fr * spx / Nt);
-      pl.ws_bytes = ivx_align_up((int64_t)ks * 8 * (pl.q_total - pl.qa) * t.bm * p.Cout * 4, 256);
-    }
-  }
-  return pl;
-}
-
-#endif   // IVX_CONV_TU == 0
-
-// pair operands (IVX_BF16_PAIR / IVX_F16_PAIR): the bf16 tiles with the three-product K loop
 #if IVX_CONV_TU == 3 || IVX_CONV_TU == 4
-template <int PAIR>
-static int launch_pair(ConvParams &p, const ConvPlan &pl, hipStream_t st) {
-  switch (pl.cfg) {
-    case 63: launch_v4<__bf16, 2, 1, 2, 2, 64, 1, PAIR>(p, st); break;
-    case 66: launch_v4<__bf16, 1, 1, 2, 2, 64, 1, PAIR>(p, st); break;
-    case 67: launch_v4<__bf16, 1, 1, 2, 2, 32, 6, PAIR>(p, st); break;
-    case 73: launch_v4<__bf16, 2, 1, 2, 2, 32, 1, PAIR>(p, st); break;
-    case 75: launch_v4<__bf16, 2, 1, 2, 2, 32, 5, PAIR>(p, st); break;   // 73 at five workgroups per CU
-    case 74: launch_v4<__bf16, 2, 2, 2, 2, 32, 4, PAIR>(p, st); break;
-    case 61: launch_v4<__bf16, 2, 2, 2, 2, 64, 1, PAIR>(p, st); break;
-    case 81: launch_v4<__bf16, 2, 2, 4, 2, 32, 4, PAIR>(p, st); break;
-    case 82: launch_v4<__bf16, 2, 2, 4, 4, 32, 4, PAIR>(p, st); break;
-    case 83: launch_v4<__bf16, 2, 2, 4, 2, 64, 2, PAIR>(p, st); break;
-    // larger wave tiles: fewer LDS fragment reads per product (the pair loop reads 4 fragments for 3 products; at 16x the fp32 MFMA rate
-    // the LDS port, shared by the DMA writes and the fragment reads, is as busy as the matrix pipe)
-    case 76: launch_v4<__bf16, 2, 2, 4, 1, 32, 4, PAIR>(p, st); break;   // 256 x 64, wave tile 64 x 64
-    // deep LDS rings (NB = 4: four slabs in flight per workgroup, raw barriers): 64 KB, two per CU -- the rule's choice for launches of at
-    // most 512 tiles (plan_conv; profiles/r05_trunk_deep_ring.md)
-    case 166: launch_v4<__bf16, 1, 1, 2, 2, 64, 2, PAIR, 4>(p, st); break;   // 66 (64 x 64, 128-byte rows)
-    case 174: launch_v4<__bf16, 2, 2, 2, 2, 32, 2, PAIR, 4>(p, st); break;   // 74 (128 x 128, 64-byte rows)
-    // residual prefetch (RPF; fp16 pairs only): 74 at three / two workgroups per CU, 174
-    case 474: if constexpr (PAIR == 2) { launch_v4<__bf16, 2, 2, 2, 2, 32, 3, PAIR, 2, 1>(p, st); break; } else return IVX_ERR_INVALID_ARG;
-    case 475: if constexpr (PAIR == 2) { launch_v4<__bf16, 2, 2, 2, 2, 32, 2, PAIR, 2, 1>(p, st); break; } else return IVX_ERR_INVALID_ARG;
-    case 574: if constexpr (PAIR == 2) { launch_v4<__bf16, 2, 2, 2, 2, 32, 2, PAIR, 4, 1>(p, st); break; } else return IVX_ERR_INVALID_ARG;
-    // the 128 x 128 tile of 174 on 8 / 16 waves (wave tile 64 x 32 / 32 x 32): more waves issue the slab's LDS-DMA requests and barriers in parallel
-    case 177: launch_v4<__bf16, 2, 1, 2, 4, 32, 2, PAIR, 4>(p, st); break;
-    case 179: launch_v4<__bf16, 1, 1, 4, 4, 64, 1, PAIR, 4>(p, st); break;
-    case 77: launch_v4<__bf16, 2, 1, 2, 4, 32, 2, PAIR>(p, st); break;
-    case 183: launch_v4<__bf16, 2, 2, 4, 4, 32, 1, PAIR, 3>(p, st); break;   // 82 (256 x 256, 16 waves) with a three-buffer ring: 96 KB
-    // (round 5, measured and removed -- profiles/r05_trunk_deep_ring.md (e): rings of six / eight buffers (96 / 128 KB): trunk 3.40 -> 3.9 / 4.05 ms,
-    // and 3.43 / 3.47 when only launches of at most one tile per CU take them; a slab-level software pipeline of the four-buffer loop (next slab's
-    // fragments read and the next DMA issued in front of the slab's last eight MFMAs): -0.09 us per slab in a long K loop, but 3.42 -> 3.45 ms)
-    // (measured and removed, profiles/r05_trunk_deep_ring.md: 74 with three buffers for launches of 513 .. 4096 tiles: trunk 3.44 -> 3.57 ms; on the
-    // last neck layer's grouped GEMM 81 / 76 / 74 with three or four buffers: 0.66 / 0.67 / 0.74 / 0.62 ms against 0.57 of tile 82)
-    case 85: launch_v4<__bf16, 2, 4, 2, 2, 32, 2, PAIR>(p, st); break;   // 128 x 256, 4 waves, wave tile 64 x 128: no gain over 81 / 82, so the
-                                                                         // fragment reads are not what limits the loop (TM = 4 variants: the
-                                                                         // compiler keeps the accumulators in scratch, 10x slower; removed)
-    default:
-      ivx_set_error("ivx_conv_fwd: tile %d has no pair-operand instantiation (61, 63, 66, 67, 73 .. 77, 81 .. 83, 85, 166, 174, 177, 179, 183; fp16 pairs also 474, 475, 574)", pl.cfg);
-      return IVX_ERR_INVALID_ARG;
-  }
-  return IVX_OK;
+static int no_pair_tile(int cfg) {
+  ivx_set_error("ivx_conv_fwd: tile %d has no instantiation for these pair operands (conv_tiles.h)", cfg);
+  return IVX_ERR_INVALID_ARG;
 }
-
 #if IVX_CONV_TU == 3
-int ivx_conv_launch_pair_bf16(ConvParams &p, const ConvPlan &pl, hipStream_t st) { return launch_pair<1>(p, pl, st); }
+int ivx_conv_launch_pair_bf16(ConvParams &p, const ConvPlan &pl, hipStream_t st) {
+  return launch_tile<__bf16, IVX_FAM_PAIR_BF16, 1>(p, pl.cfg, st) ? IVX_OK : no_pair_tile(pl.cfg);
+}
 #else
-int ivx_conv_launch_pair_f16(ConvParams &p, const ConvPlan &pl, hipStream_t st) { return launch_pair<2>(p, pl, st); }
+int ivx_conv_launch_pair_f16(ConvParams &p, const ConvPlan &pl, hipStream_t st) {
+  return launch_tile<__bf16, IVX_FAM_PAIR_F16, 2>(p, pl.cfg, st) ? IVX_OK : no_pair_tile(pl.cfg);
+}
 #endif
 #endif
 
@@ -2337,56 +1929,17 @@ int ivx_conv_launch_halo(ConvParams &p, int cfg, hipStream_t st) {
     ivx_set_error("ivx_conv_launch_halo: fp16 pair operands only");
     return IVX_ERR_INVALID_ARG;
   }
-  switch (cfg) {
-    case 1: launch_halo<2, 2, 4, 1, 2, 2, 2>(p, st); break;   // 256 x 64, 4 waves, 2 buffers: 58 KB, two workgroups per CU
-    case 2: launch_halo<2, 2, 2, 2, 2, 2, 2>(p, st); break;   // 128 x 128, 4 waves, 2 buffers: 66 KB
-    case 3: launch_halo<2, 2, 4, 2, 1, 2, 2>(p, st); break;   // 256 x 128, 8 waves, 2 buffers: 82 KB
-    case 4: launch_halo<2, 1, 2, 2, 3, 2, 2>(p, st); break;   // 128 x 64, 4 waves, 2 buffers: 42 KB, three per CU
-    case 5: launch_halo<2, 2, 4, 4, 1, 2, 2>(p, st); break;   // 256 x 256, 16 waves, 2 buffers: 130 KB
-    case 6: launch_halo<2, 2, 4, 2, 1, 2, 3>(p, st); break;   // 256 x 128, 8 waves, 3 buffers: 123 KB
-    case 7: launch_halo<2, 1, 2, 2, 2, 2, 3>(p, st); break;   // 128 x 64, 4 waves, 3 buffers: 63 KB, two per CU
-    case 8: launch_halo<2, 2, 4, 1, 1, 2, 3>(p, st); break;   // 256 x 64, 4 waves, 3 buffers: 87 KB
-    case 9: launch_halo<2, 2, 2, 2, 1, 2, 3>(p, st); break;   // 128 x 128, 4 waves, 3 buffers: 99 KB
-    case 10: launch_halo<2, 1, 2, 2, 4, 2, 2, 0>(p, st); break;  // 126 (of 128) x 64, overlapping tiles, 40 KB: four per CU
-    case 11: launch_halo<2, 2, 4, 1, 2, 2, 2, 0>(p, st); break;  // 254 x 64, overlapping tiles, 56 KB: two per CU
-    case 12: launch_halo<2, 2, 4, 4, 1, 2, 2, 0>(p, st); break;  // 254 x 256, 16 waves, overlapping tiles, 128 KB
-    case 13: launch_halo<2, 2, 4, 2, 1, 2, 2, 0>(p, st); break;  // 254 x 128, 8 waves, overlapping tiles, 80 KB: two per CU
-    case 14: launch_halo<2, 2, 2, 2, 2, 2, 2, 0>(p, st); break;  // 126 x 128, 4 waves, overlapping tiles, 64 KB: two per CU
-    // z stride 2 (p.W == 2 * p.Wo): 2 BM staged rows
-    case 21: launch_halo<2, 1, 2, 2, 2, 2, 2, 0, 2>(p, st); break;  // 127 x 64, 4 waves: 56 KB, two per CU
-    case 22: launch_halo<2, 2, 2, 2, 2, 2, 2, 0, 2>(p, st); break;  // 127 x 128, 4 waves: 80 KB, two per CU
-    case 23: launch_halo<2, 2, 4, 2, 1, 2, 2, 0, 2>(p, st); break;  // 255 x 128, 8 waves: 112 KB, one per CU
-    case 24: launch_halo<1, 2, 4, 1, 2, 2, 2, 0, 2>(p, st); break;  // 127 x 64, 4 waves in M (wave tile 32 x 64): 56 KB
-    // ZR: masked taps read a zero row (10 / 13 / 14 / 11 / 22 / 21 with the fragment address selected instead of the fragment zeroed)
-    case 30: launch_halo<2, 1, 2, 2, 4, 2, 2, 0, 1, 1>(p, st); break;  // 125 x 64
-    // (round 5, with the raw barrier that makes a third buffer a real prefetch distance of two groups -- measured and removed, profiles/
-    // r05_fused_gemm_output.md: 125 x 64 with three / four buffers 0.535 / 0.600 ms against 0.493 (64 channels); 253 x 128 with three 0.806
-    // against 0.659 (128) and 1.314 against 1.171 (256): on these launches resident workgroups DO hide the latency better than depth)
-    case 31: launch_halo<2, 2, 4, 1, 2, 2, 2, 0, 1, 1>(p, st); break;  // 253 x 64
-    case 33: launch_halo<2, 2, 4, 2, 1, 2, 2, 0, 1, 1>(p, st); break;  // 253 x 128, 8 waves
-    case 34: launch_halo<2, 2, 2, 2, 2, 2, 2, 0, 1, 1>(p, st); break;  // 125 x 128
-    case 41: launch_halo<2, 1, 2, 2, 2, 2, 2, 0, 2, 1>(p, st); break;  // stride 2: 127 x 64
-    case 42: launch_halo<2, 2, 2, 2, 2, 2, 2, 0, 2, 1>(p, st); break;  // stride 2: 127 x 128
-    case 43: launch_halo<2, 2, 2, 2, 2, 2, 2, 0, 2, 1, 1>(p, st); break;  // 42 with de-interleaved staging
-    case 44: launch_halo<2, 1, 2, 2, 2, 2, 2, 0, 2, 1, 1>(p, st); break;  // 41 with de-interleaved staging
-    case 45: launch_halo<2, 2, 2, 2, 2, 2, 2, 0, 2, 0, 1>(p, st); break;  // 22 with de-interleaved staging
-    // round 5 (A/B): the tile of 42 on twice the waves (wave tile 64 x 32 instead of 64 x 64) -- 0.520 / 0.807 ms against 0.519 / 0.802: unlike the
-    // trunk's one-wave-per-SIMD launches these kernels are not bound by what a single wave issues
-    case 46: launch_halo<2, 1, 2, 4, 2, 2, 2, 0, 2, 1>(p, st); break;  // stride 2: 127 x 128, 8 waves, 80 KB, two per CU
-    // z-blocked tiles (conv_wino_zblk_kernel; Wo = 3 or 6 only): 50 / 51 = 8 / 16 waves at Z = 3, 60 at Z = 6.  Measured and not kept as
-    // instantiations (profiles/r04_zblk_ab.md): 384 x 64 (8 waves) 1.04, 192 x 64 (4 waves) 1.07, 192 x 256 (16 waves) 1.05, 96 x 128 1.22 ms at
-    // Z = 3 (50: 0.99); at Z = 6: 192 x 64 0.675, 192 x 256 1.08, 384 x 128 0.67 (60: 0.63-0.65); z stride 2: 6 -> 3 slices 64 columns 0.874, 12 -> 6 0.578
-    // (the halo form 42: 0.785 / 0.507)
-    case 50: if (p.Wo != 3) return zblk_wrong_z(3, p.Wo); launch_zblk<3, 2, 4, 4>(p, st); return IVX_OK;   // 192 rows (64 columns) x 128: 72 KB, two per CU
-    case 51: if (p.Wo != 3) return zblk_wrong_z(3, p.Wo); launch_zblk<3, 4, 4, 4>(p, st); return IVX_OK;   // 384 rows x 128, 16 waves: 96 KB, one per CU
-    case 60: if (p.Wo != 6) return zblk_wrong_z(6, p.Wo); launch_zblk<6, 1, 4, 4>(p, st); return IVX_OK;   // 192 rows (32 columns) x 128
-    // z stride 2 (p.W == 2 p.Wo), 6 -> 3 slices: 0.818 ms against 0.785 of the halo form 42 -- an A/B point, not the rule
-    case 71: if (p.Wo != 3 || p.W != 6) return zblk_wrong_z(3, p.Wo); launch_zblk<3, 1, 4, 2, 2>(p, st); return IVX_OK;   // 32 columns x 128 (two waves per SIMD)
+  switch (cfg) {       // the rows of IVX_CONV_HALO_CFGS (conv_tiles.h)
+#define IVX_H(n, TM, TN, WR, WC, WPE, PAIR, NBUF, TAIL, SW, ZR, DI) case n: launch_halo<TM, TN, WR, WC, WPE, PAIR, NBUF, TAIL, SW, ZR, DI>(p, st); return IVX_OK;
+#define IVX_Z(n, ZD, WCOL, WN, WPE, SW) \
+    case n: if (p.Wo != ZD || (SW > 1 && p.W != SW * ZD)) return zblk_wrong_z(ZD, p.Wo); launch_zblk<ZD, WCOL, WN, WPE, SW>(p, st); return IVX_OK;
+    IVX_CONV_HALO_CFGS(IVX_H, IVX_Z)
+#undef IVX_H
+#undef IVX_Z
     default:
       ivx_set_error("ivx_conv_launch_halo: unknown config %d", cfg);
       return IVX_ERR_INVALID_ARG;
   }
-  return IVX_OK;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2719,75 +2272,39 @@ int ivx_conv_launch_fold4(ConvParams &p, const IvxWinoFold &f, int n2, hipStream
 
 #if IVX_CONV_TU == 1
 int ivx_conv_launch_f32(ConvParams &p, const ConvPlan &pl, hipStream_t st) {
-  switch (pl.cfg) {
-    case 41: launch_v4<float, 2, 2, 2, 2, 32>(p, st); break;   // LDS-DMA: 128 x 128, 128-byte LDS rows
-    case 43: launch_v4<float, 2, 1, 2, 2, 32>(p, st); break;   //          128 x 64
-    case 44: launch_v4<float, 1, 1, 4, 1, 32>(p, st); break;   //          128 x 32
-    case 46: launch_v4<float, 1, 1, 2, 2, 32>(p, st); break;   //          64 x 64
-    case 51: launch_v4<float, 2, 2, 2, 2, 16>(p, st); break;   //          128 x 128, 64-byte rows: 32 KB LDS, 3 workgroups/CU
-    case 53: launch_v4<float, 2, 1, 2, 2, 16>(p, st); break;
-    case 52: launch_v4<float, 2, 2, 4, 1, 16>(p, st); break;   //          256 x 64, 64-byte rows: 40 KB LDS
-    case 54: launch_v4<float, 2, 2, 2, 2, 16, 4>(p, st); break;  // 51 squeezed to 128 registers: 4 workgroups/CU
-    case 55: launch_v4<float, 2, 2, 2, 2, 16, 5>(p, st); break;  //    ... to 102 registers: 5 workgroups/CU (all 160 KB of LDS)
-    case 56: launch_v4<float, 2, 1, 2, 2, 16, 6>(p, st); break;  // 53 at 6 workgroups/CU
-    case 57: launch_v4<float, 2, 2, 4, 1, 16, 4>(p, st); break;  // 52 at 4 workgroups/CU
-    case 58: launch_v4<float, 2, 2, 4, 2, 16, 4>(p, st); break;  // 8 waves, 256 x 128: two workgroups per CU, half the tiles per FLOP
-    case 59: launch_v4<float, 2, 2, 2, 4, 16, 4>(p, st); break;  // 8 waves, 128 x 256
-    case 47: launch_v4<float, 1, 1, 2, 2, 16, 6>(p, st); break;  // 64 x 64, 64-byte rows: 16 KB LDS, 6 workgroups/CU
-    case 48: launch_v4<float, 1, 2, 2, 2, 16, 5>(p, st); break;  // 64 x 128
-    case 49: launch_v4<float, 2, 1, 2, 2, 16, 5>(p, st); break;  // 128 x 64 at 5 workgroups/CU
-    default:
-      ivx_set_error("ivx_conv_fwd: tile %d is not an fp32 LDS-DMA tile", pl.cfg);
-      return IVX_ERR_INVALID_ARG;
-  }
-  return IVX_OK;
+  if (launch_tile<float, IVX_FAM_F32>(p, pl.cfg, st)) return IVX_OK;
+  ivx_set_error("ivx_conv_fwd: tile %d is not an fp32 LDS-DMA tile", pl.cfg);
+  return IVX_ERR_INVALID_ARG;
 }
 #endif
 
 #if IVX_CONV_TU == 2
 int ivx_conv_launch_lowp(ConvParams &p, const ConvPlan &pl, hipStream_t st) {
-  switch (pl.cfg) {
-    case 74: launch_v4<__bf16, 2, 2, 2, 2, 32, 4>(p, st); break; // 71 at 4 workgroups/CU
-    case 91: launch_v4<fp8_t, 2, 2, 2, 2, 64, 4>(p, st); break;  // e4m3 operands, v_mfma_f32_32x32x16_fp8_fp8: 128 x 128, 64-byte rows
-    case 92: launch_v4<fp8_t, 2, 1, 2, 2, 64, 5>(p, st); break;  //   128 x 64
-    case 93: launch_v4<fp8_t, 1, 1, 2, 2, 64, 6>(p, st); break;  //   64 x 64
-    case 94: launch_v4<fp8_t, 2, 2, 2, 2, 128, 2>(p, st); break; //   128 x 128, 128-byte rows
-    case 81: launch_v4<__bf16, 2, 2, 4, 2, 32, 4>(p, st); break; // 8 waves, 256 x 128: 25 % less L2->LDS traffic per flop
-    case 82: launch_v4<__bf16, 2, 2, 4, 4, 32, 4>(p, st); break; // 16 waves, 256 x 256: half the traffic per flop
-    case 83: launch_v4<__bf16, 2, 2, 4, 2, 64, 2>(p, st); break; // 8 waves, 256 x 128, 128-byte rows
-    case 61: launch_v4<__bf16, 2, 2, 2, 2, 64>(p, st); break;  // bf16 operands, v_mfma_f32_32x32x16_bf16
-    case 63: launch_v4<__bf16, 2, 1, 2, 2, 64>(p, st); break;
-    case 64: launch_v4<__bf16, 1, 1, 4, 1, 64>(p, st); break;
-    case 66: launch_v4<__bf16, 1, 1, 2, 2, 64>(p, st); break;
-    case 67: launch_v4<__bf16, 1, 1, 2, 2, 32, 6>(p, st); break;
-    case 71: launch_v4<__bf16, 2, 2, 2, 2, 32>(p, st); break;
-    case 73: launch_v4<__bf16, 2, 1, 2, 2, 32>(p, st); break;
-    case 72: launch_v4<__bf16, 2, 2, 4, 1, 32>(p, st); break;
-    default:
-      ivx_set_error("ivx_conv_fwd: tile %d is not a bf16 / e4m3 LDS-DMA tile", pl.cfg);
-      return IVX_ERR_INVALID_ARG;
-  }
-  return IVX_OK;
+  if (p.in_fp8 ? launch_tile<fp8_t, IVX_FAM_E4M3>(p, pl.cfg, st) : launch_tile<__bf16, IVX_FAM_BF16>(p, pl.cfg, st)) return IVX_OK;
+  ivx_set_error("ivx_conv_fwd: tile %d is not a bf16 / e4m3 LDS-DMA tile", pl.cfg);
+  return IVX_ERR_INVALID_ARG;
 }
 #endif
 
 #if IVX_CONV_TU == 0
+// (a template, as launch_tile is, so that the rows of the other families are discarded before they instantiate a kernel)
+template <int FAM>
+static bool launch_generic_tile(const ConvParams &p, int cfg, hipStream_t st) {
+  switch (cfg) {
+#define IVX_ROW(n, fam, TM, TN, WR, WC, BK, WPE, NB, RPF, WG) \
+    case n: if constexpr ((IVX_FAM_##fam & FAM) != 0) { launch_cfg<TM, TN, WR, WC>(p, st); return true; } else return false;
+    IVX_CONV_TILES(IVX_ROW)
+#undef IVX_ROW
+    default: return false;
+  }
+}
+
 static int launch_one(ConvParams &p, const ConvPlan &pl, hipStream_t st) {
   if (p.in_pair) return p.in_pair == 2 ? ivx_conv_launch_pair_f16(p, pl, st) : ivx_conv_launch_pair_bf16(p, pl, st);
   if (pl.cfg >= 40) return (p.in_bf16 || p.in_fp8) ? ivx_conv_launch_lowp(p, pl, st) : ivx_conv_launch_f32(p, pl, st);
-  switch (pl.cfg) {
-    case 1: launch_cfg<2, 2, 2, 2>(p, st); break;  // 128 x 128, 2 workgroups/CU
-    case 2: launch_cfg<2, 2, 4, 1>(p, st); break;  // 256 x 64, 1 workgroup/CU
-    case 3: launch_cfg<2, 1, 2, 2>(p, st); break;  // 128 x 64
-    case 4: launch_cfg<1, 1, 4, 1>(p, st); break;  // 128 x 32
-    case 5: launch_cfg<1, 2, 4, 1>(p, st); break;  // 128 x 64 (wave 32 x 64)
-    case 6: launch_cfg<1, 1, 2, 2>(p, st); break;  // 64 x 64
-    case 7: launch_cfg<1, 2, 2, 2>(p, st); break;  // 64 x 128
-    default:
-      ivx_set_error("ivx_conv_fwd: unknown tile override %d", pl.cfg);
-      return IVX_ERR_INVALID_ARG;
-  }
-  return IVX_OK;
+  if (launch_generic_tile<IVX_FAM_GENERIC>(p, pl.cfg, st)) return IVX_OK;
+  ivx_set_error("ivx_conv_fwd: unknown tile override %d", pl.cfg);
+  return IVX_ERR_INVALID_ARG;
 }
 
 static void launch_reduce(const ConvParams &p, hipStream_t st) {
@@ -2809,7 +2326,7 @@ static int run_conv(ConvParams &p, const ConvPlan &pl, void *workspace, hipStrea
     ivx_set_error("ivx_conv_fwd: fp8 input is only implemented by the LDS-DMA kernel (tensor < 2 GiB, kernel extents <= 8)");
     return IVX_ERR_UNSUPPORTED;
   }
-  const bool deep_cfg = pl.cfg == 166 || pl.cfg == 174 || pl.cfg == 474 || pl.cfg == 475 || pl.cfg == 574 || pl.cfg == 177 || pl.cfg == 179 || pl.cfg == 183;      // deep-ring pair tiles
+  const bool deep_cfg = tile_deep_form(pl.cfg);      // deep-ring / residual-prefetch pair tiles
   if (p.in_bf16 && (!dma_applicable(p) || !(tile_info(pl.cfg, &ti) && ((pl.cfg >= 61 && pl.cfg < 91) || (deep_cfg && p.in_pair))))) {
     ivx_set_error("ivx_conv_fwd: bf16 input is only implemented by the LDS-DMA kernel (tensor < 2 GiB, kernel extents <= 8)");
     return IVX_ERR_UNSUPPORTED;
@@ -2821,8 +2338,7 @@ static int run_conv(ConvParams &p, const ConvPlan &pl, void *workspace, hipStrea
   p.stagger_ticks = 0;
   if (p.pio && p.res_mode == 1 && pl.ksplit <= 1 && pl.tail_ks <= 1 && tile_info(pl.cfg, &ti)) {
     // (experiment, default off: IVX_PIO_STAGGER_US = delay in us, IVX_PIO_STAGGER_SHIFT = which bit of the XCD-local workgroup index picks the late half)
-    static const int st_us = getenv("IVX_PIO_STAGGER_US") ? atoi(getenv("IVX_PIO_STAGGER_US")) : 0;
-    static const int st_sh = getenv("IVX_PIO_STAGGER_SHIFT") ? atoi(getenv("IVX_PIO_STAGGER_SHIFT")) : 0;
+    const int st_us = (int)conv_env().pio_stagger_us, st_sh = (int)conv_env().pio_stagger_shift;
     const long long tiles = (long long)((p.M + ti.bm - 1) / ti.bm) * ((p.Cout + ti.bn - 1) / ti.bn);
     if (st_us > 0 && tiles >= 2LL * 256 * ti.wg_per_cu) {
       p.stagger_ticks = st_us * 100;
@@ -2850,44 +2366,22 @@ static int run_conv(ConvParams &p, const ConvPlan &pl, void *workspace, hipStrea
   return IVX_OK;
 }
 
-// Batch slicing: the LDS-DMA kernel addresses its operands with 31-bit buffer offsets.  When the input of a launch
-// reaches 2 GiB (e.g. the first KITTI neck layers from batch 13 up) the batch is cut into the largest slices that fit
-// and the slices run back to back on the stream, sharing the workspace; B is the outermost dimension, so a slice is a
-// pointer offset.  Returns the number of samples per slice (B = no slicing needed or not possible).
-static int conv_batch_slice(const ConvParams &p) {
-  if (dma_applicable(p) || p.B == 1 || p.KD > 8 || p.KH > 8 || p.KW > 8) return p.B;
-  const int el = p.in_fp8 ? 1 : (p.in_bf16 ? 2 : 4);
-  const int64_t in_s = (int64_t)p.D * p.H * p.W * p.Cin * el;
-  if ((int64_t)p.Cout * p.K * el >= (1LL << 31) || in_s >= (1LL << 31)) return p.B;
-  const int64_t nb = ((1LL << 31) - 1) / in_s;
-  return (int)(nb < p.B ? nb : p.B);
-}
-
-static ConvParams conv_slice_params(const ConvParams &p, int b0, int nb) {
-  ConvParams q = p;
-  const size_t in_el = p.in_fp8 ? 1 : (p.in_bf16 ? 2 : 4), out_el = p.out_fp8 ? 1 : (p.out_bf16 ? 2 : 4);
-  const size_t in_s = (size_t)p.D * p.H * p.W * p.Cin;
-  const size_t out_s = p.out_mode == 1 ? (size_t)8 * p.D * p.H * p.W * p.Cr : (size_t)p.Do * p.Ho * p.Wo * p.Cout;
-  q.B = nb;
-  q.M = nb * p.Do * p.Ho * p.Wo;
-  q.in = (const float *)((const char *)p.in + (size_t)b0 * in_s * in_el);
-  q.out = (float *)((char *)p.out + (size_t)b0 * out_s * out_el);
-  if (p.res) {
-    const size_t res_s = p.res_mode == 2 ? (size_t)p.rH * p.rW * p.Cout : out_s;
-    q.res = (const float *)((const char *)p.res + (size_t)b0 * res_s * out_el);
-  }
-  return q;
-}
-
-// Plan (and with `launch`, run) the whole problem: one call, or one call per batch slice.  *need = workspace bytes.
+// Plan (and with `launch`, run) the whole problem: one call, or one call per batch slice.  *need = workspace bytes.  rec: the plans of the
+// distinct slices are written there (ivx_conv_plan_query).
 static int conv_dispatch(const ConvParams &p, bool allow_ws, bool launch, void *workspace, int64_t workspace_bytes, hipStream_t st,
-                         int64_t *need, const char *who) {
+                         int64_t *need, const char *who, ivx_conv_plan_rec *rec = nullptr) {
   const int nb = conv_batch_slice(p);
+  if (rec) rec->slice_samples = nb;
   *need = 0;
   for (int b0 = 0; b0 < p.B; b0 += nb) {
     ConvParams q = nb == p.B ? p : conv_slice_params(p, b0, (p.B - b0) < nb ? (p.B - b0) : nb);
     const ConvPlan pl = plan_conv(q, allow_ws);
     if (pl.ws_bytes > *need) *need = pl.ws_bytes;
+    if (rec && rec->n_slices < 2 && (rec->n_slices == 0 || rec->samples[rec->n_slices - 1] != q.B)) {
+      const int i = rec->n_slices++;
+      rec->samples[i] = q.B; rec->cfg[i] = pl.cfg; rec->ksplit[i] = pl.ksplit; rec->tail_ks[i] = pl.tail_ks; rec->q_total[i] = pl.q_total;
+      rec->qa[i] = pl.qa; rec->bm[i] = pl.bm; rec->slice_ws[i] = pl.ws_bytes;
+    }
     if (!launch) continue;
     if (pl.ws_bytes > 0 && (!workspace || workspace_bytes < pl.ws_bytes)) {
       ivx_set_error("%s: workspace too small (%lld < %lld); size it with ivx_conv_workspace_bytes", who, (long long)workspace_bytes,
@@ -2912,52 +2406,6 @@ extern "C" int ivx_conv_fwd(const ivx_conv_desc *d, const void *in, const void *
   return IVX_OK;
 }
 
-// Internal (winograd.hip): `groups` independent convolutions of the same shape in ONE launch of the LDS-DMA kernel
-// (grid.z = group), identity epilogue.  `d` describes one group; operands of group g start g*stride elements further.
-// the default rule takes the z-blocked tile (conv_wino_zblk_kernel, config 50) for 3-slice columns with more than 64 output channels
-static bool zblk_rule(const ConvParams &p) { return p.Wo == 3 && p.W == 3 && p.Cout > 64; }
-
-// Fraction of the 3 Z tap-slices a stride-1, pad-1 Winograd-domain GEMM issues under the default rule (for FLOP accounting: the z-blocked
-// tile skips the taps outside the column, the halo tile multiplies zeros there).  d: the LAYER descriptor (W = slices, KW = 3).
-extern "C" float ivx_conv_winograd_issued_fraction(const ivx_conv_desc *d) {
-  if (!d || d->wino_operands != IVX_F16_PAIR || d->KW != 3 || d->sw != 1 || d->pw != 1 || d->W != 3 || d->Cin % 64 || d->Cout <= 64 || d->wgt_layout != 1 ||
-      g_halo_mode >= 0 || g_tile_override != 0)
-    return 1.0f;
-  return 7.0f / 9.0f;
-}
-
-// The z-halo / z-blocked config (ivx_conv_launch_halo) the library's rule gives one xi convolution of a grouped launch, 0 = another kernel.
-static int grouped_halo_cfg(const ConvParams &p, const ivx_conv_desc *d, int groups) {
-  // z-halo kernel (TU 5): 1x1x3 along z, stride 1, pad 1, chunk-major fp16 pairs -- the ResModule layers of the stack necks
-  if (p.in_pair == 2 && p.kmode == 1 && d->KD == 1 && d->KH == 1 && d->KW == 3 && d->sw == 2 && d->pw == 1 && p.W == 2 * p.Wo && p.Cin % 64 == 0 &&
-      ((g_halo_mode >= 21 && g_halo_mode < 30) || (g_halo_mode >= 40 && g_halo_mode < 50) || g_halo_mode >= 70 || (g_halo_mode < 0 && g_tile_override == 0))) {
-    // (round 4, tools/halo_ab.py, profiles/r04_halo_ab.md: the zero-row form 42 vs 22: 0.494 / 0.790 vs 0.492 / 0.811 ms; de-interleaved staging
-    // 43 / 45: equal -- neither the masks nor the bank conflicts are what this kernel waits for)
-    return g_halo_mode >= 21 ? g_halo_mode : 42;
-  }
-  if (p.in_pair == 2 && p.kmode == 1 && d->KD == 1 && d->KH == 1 && d->KW == 3 && d->sw == 1 && d->pw == 1 && p.Cin % 64 == 0 &&
-      ((g_halo_mode > 0 && g_halo_mode < 21) || (g_halo_mode >= 30 && g_halo_mode < 40) || (g_halo_mode >= 50 && g_halo_mode < 70) ||
-       (g_halo_mode < 0 && g_tile_override == 0))) {
-    // measured (tools/pair_ab.py --halo N, profiles/r03b_pair_ab_halo.log; generic kernel 0.73 / 0.90 / 1.41 ms for Cout 64 / 128 / 256):
-    // with the 16-row tail pass: 128 x 64 at three per CU 0.57 / 0.84 / 1.44, 256 x 64 0.60-0.64 / 0.83 / 1.33, 256 x 128 0.99 / 0.84 / 1.37,
-    // 256 x 256 (16 waves) 1.40-1.44 / 1.19 / 1.24-1.27; every three-buffer ring is slower than its two-buffer form (resident workgroups
-    // hide the load latency better than depth does).  Overlapping tiles without the tail pass: 126 x 64 at FOUR per CU 0.49 / 0.74 / 1.35,
-    // 254 x 64 0.51 / 0.72 / 1.23, 254 x 128 (8 waves, two per CU) 0.65 / 0.64 / 1.15, 254 x 256 1.19 / 1.10 / 1.20
-    // round 4: the zero-row forms (30 / 33: the fragment ADDRESS of a masked tap selected once per tile instead of 32 v_cndmask per group):
-    // 125 x 64 0.487 / 0.756 / 1.410 (= 10), 253 x 128 0.597 / 0.644 / 1.144 (13: 0.607 / 0.653 / 1.167); bit-identical results
-    // round 4, z-blocked tiles for 3-slice columns (50: a tap outside the column is skipped instead of multiplied by zeros: 7 of 9
-    // tap-slices): 256 -> 256 at 216 x 248 x 3 0.99 vs 1.135-1.15 ms, bit-identical; at 6 slices (60) 0.626-0.651 vs 0.637-0.650: a wash
-    // round 6: small volumes (the indoor necks: 200 .. 1600 rows per Winograd position).  The 253 x 128 tile on 8 waves leaves most CUs idle there --
-    // 72 workgroups for 256 -> 256 at 20 x 20 x 8 -- and the 125 x 64 tile at four per CU wins for every Cout: 0.073 -> 0.050 ms (12 launches per ScanNet v1
-    // step), 512 -> 512 0.208 -> 0.163, 128 -> 128 at 40 x 40 x 16 0.037 -> 0.033 (tools/neck_halo_ab.py, profiles/r06_halo_small_volumes.md); bit-identical
-    // results.  Rule: fewer workgroups of the 253 x 128 tile than the chip has slots for them (512).  IVX_HALO_SMALL=0 turns it off (A/B).
-    static const int halo_small = getenv("IVX_HALO_SMALL") ? atoi(getenv("IVX_HALO_SMALL")) : 1;
-    const bool few = halo_small && p.Cout > 64 && !zblk_rule(p) && (long long)((p.M + 252) / 253) * ((p.Cout + 127) / 128) * groups < 512;
-    return g_halo_mode > 0 ? g_halo_mode : ((p.Cout <= 64 || few) ? 30 : (zblk_rule(p) ? 50 : 33));
-  }
-  return 0;
-}
-
 // Internal (winograd.hip): can the grouped launch of `d` take its row count from the device (ConvParams::m_dev)?  Only the z-halo and
 // z-blocked kernels read it.
 int ivx_conv_grouped_rows_dev_ok(const ivx_conv_desc *d, int groups) {
@@ -2967,6 +2415,8 @@ int ivx_conv_grouped_rows_dev_ok(const ivx_conv_desc *d, int groups) {
   return grouped_halo_cfg(p, d, groups) != 0;
 }
 
+// Internal (winograd.hip): `groups` independent convolutions of the same shape in ONE launch of the LDS-DMA kernel
+// (grid.z = group), identity epilogue.  `d` describes one group; operands of group g start g*stride elements further.
 int ivx_conv_grouped_launch(const ivx_conv_desc *d, int groups, const float *in, long long g_in, const float *wgt, long long g_w,
                             float *out, long long g_out, hipStream_t st, const unsigned *cp_src, unsigned *cp_dst, const int *m_dev) {
   ConvParams p;
@@ -2996,37 +2446,7 @@ int ivx_conv_grouped_launch(const ivx_conv_desc *d, int groups, const float *in,
     ivx_set_error("ivx_conv_grouped_launch: only the z-halo and z-blocked kernels take a device-side row count");
     return IVX_ERR_UNSUPPORTED;
   }
-  ConvPlan pl = {g_tile_override, 1, 1, 0, 0, 0, 0};
-  if (pl.cfg == 0 && p.in_pair) {
-    // pair operands: three bf16-rate products per staged operand pair; 8- / 16-wave workgroups stage the fewest bytes per product
-    // (tools/gemm_ab.py --pair, profiles/r03_gemm_ab_pair.log)
-    // measured on the KITTI neck (tools/pair_ab.py, profiles/r03_pair_ab.log): Cout 64: 256 x 64 at four per CU 0.69 ms (128 x 64: 0.74-0.84);
-    // Cout 128: 256 x 128 8 waves 0.60 / 0.88 (128 x 128: 0.63 / 0.89); Cout 256: 256 x 256 16 waves 0.87 / 1.39 (8 waves: 0.91 / 1.41)
-    // round 5: the 256 x 256 tile with a THREE-buffer ring behind raw barriers (183; one workgroup of 16 waves per CU either way): the last KITTI
-    // neck layer (256 -> 256, z 3 -> 1: a dense GEMM with K = 3 Cin, 48 slabs of 1.9 us for 0.64 us of matrix work) 0.633 -> 0.579 ms (four
-    // buffers 0.582; tools/l9_ab.py); same products in the same order
-    pl.cfg = p.Cout <= 64 ? 76 : (p.Cout <= 128 ? 81 : (p.in_pair == 2 && p.kmode == 1 ? 183 : 82));
-    // few tiles (the 2-D 3x3 layers of the trunk at KITTI size, the indoor necks): the 8- / 16-wave tiles would leave most CUs idle
-    const long long nblk = (long long)groups * ((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-    if (nblk < 2500) pl.cfg = 67;
-  }
-  if (pl.cfg == 0) {
-    const long long nblk = (long long)groups * ((p.M + 127) / 128) * ((p.Cout + 127) / 128);
-    if (p.Cout <= 32) pl.cfg = 44;
-    // measured on the Winograd-domain GEMMs of the KITTI neck (tools/conv_bench.py --winograd --wcfgs ...): K is only
-    // KW*Cin here (192 .. 768), so a workgroup's prologue and epilogue weigh more than in the direct form and one more
-    // resident workgroup per CU pays: 128 x 64 at six per CU for Cout <= 64 (1.51 vs 1.85 ms at five), 128 x 128 at five
-    // per CU up to K = 512 (2.50 vs 2.90 ms at four); at K = 768 four and five tie
-    // re-measured with the LDS-transposed epilogue, configs interleaved inside one process (tools/gemm_ab.py,
-    // profiles/r02_gemm_ab.log; run-to-run spread exceeds most tile effects otherwise): the shorter epilogue removes the
-    // advantage of a fifth / sixth resident workgroup -- 128 x 128 at four per CU wins for every Cout >= 128 layer
-    // (K = 192: 1.05 vs 1.12 ms at five; K = 384: 1.79 vs 1.86; K = 768: 3.37 vs 3.40), 128 x 64 at five for Cout <= 64
-    // (1.08 vs 1.09 at six, 1.14 for 256 x 64)
-    // round 3, same tool with the 8-wave 256 x 128 tile added: it wins only the 128 -> 128 layers (K = 384: 1.838 vs
-    // 1.903 ms, spreads disjoint) and ties at K = 192 / 768 (profiles/r03_gemm_ab.log)
-    else if (nblk >= 2500) pl.cfg = p.Cout > 64 ? (p.Cout == 128 && p.K == 384 ? 58 : 54) : 49;
-    else pl.cfg = p.K <= 640 ? 47 : 46;
-  }
+  const ConvPlan pl = grouped_tile_plan(p, groups);
   TileInfo t;
   if (!tile_info(pl.cfg, &t) || (pl.cfg >= 61) != (p.in_pair != 0)) {
     ivx_set_error("ivx_conv_grouped_launch: tile %d does not match the operand type", pl.cfg);
@@ -3126,6 +2546,38 @@ extern "C" int ivx_conv_fwd_naive(const ivx_conv_desc *d, const void *in, const 
   if (blocks > 65536 * 8) blocks = 65536 * 8;
   hipLaunchKernelGGL(conv_naive_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
   IVX_CHECK_LAUNCH("ivx_conv_fwd_naive");
+  return IVX_OK;
+}
+// Lab (include/imvoxel_lab.h): what the planner answers, from the functions the launchers above call.  No launch, no device call.
+extern "C" int ivx_conv_tile_info(int cfg, int32_t *v) {
+  TileInfo t;
+  if (!v || !tile_info(cfg, &t)) return 0;
+  v[0] = t.bm; v[1] = t.bn; v[2] = t.bk; v[3] = t.wg_per_cu;
+  return 1;
+}
+
+extern "C" int ivx_conv_plan_query(const ivx_conv_desc *d, const ivx_pair_io *io, int allow_ws, int groups, ivx_conv_plan_rec *out) {
+  IVX_REQUIRE(out && groups >= 0, "ivx_conv_plan_query: null record or negative group count");
+  memset(out, 0, sizeof(*out));
+  ConvParams p;
+  float dummy;
+  if (groups == 0) {
+    int rc = fill_params(d, &dummy, &dummy, nullptr, nullptr, d && d->res_mode ? &dummy : nullptr, &dummy, &p, io);
+    if (rc != IVX_OK) return rc;
+    return conv_dispatch(p, allow_ws != 0, false, nullptr, 0, nullptr, &out->ws_bytes, "ivx_conv_plan_query", out);
+  }
+  int rc = fill_params(d, &dummy, &dummy, nullptr, nullptr, nullptr, &dummy, &p);
+  if (rc != IVX_OK) return rc;
+  if (!dma_applicable(p)) {
+    ivx_set_error("ivx_conv_plan_query: one group must stay below 2 GiB");
+    return IVX_ERR_UNSUPPORTED;
+  }
+  out->rows_dev_ok = ivx_conv_grouped_rows_dev_ok(d, groups);
+  out->halo_cfg = grouped_halo_cfg(p, d, groups);
+  if (out->halo_cfg) return IVX_OK;
+  TileInfo t;
+  out->grouped_tile = grouped_tile_plan(p, groups).cfg;
+  out->tile_matches = tile_info(out->grouped_tile, &t) && (out->grouped_tile >= 61) == (p.in_pair != 0);
   return IVX_OK;
 }
 #endif   // IVX_CONV_TU == 0

@@ -17,16 +17,8 @@
 // by fp32 rounding only: measured max deviation from the direct MFMA kernel on the KITTI neck layers, as a fraction of the
 // output range: m = 2 up to 4e-6, m = 4 up to 2.4e-5, m = 6 up to 4e-5 (profiles/r01_conv_layers.log).
 #include "ivx_common.h"
+#include "conv_shared.h"
 #include <stdlib.h>
-int ivx_conv_launch_fold4w(const _Float16 *V, long long vs, const _Float16 *U, long long us, int M, int Cin_stored, int Cout, int Z, const IvxWinoFold &f,
-                           hipStream_t st);
-
-int ivx_conv_grouped_launch(const ivx_conv_desc *d, int groups, const float *in, long long g_in, const float *wgt, long long g_w,
-                            float *out, long long g_out, hipStream_t st, const unsigned *cp_src, unsigned *cp_dst, const int *m_dev);
-int ivx_conv_grouped_rows_dev_ok(const ivx_conv_desc *d, int groups);
-int ivx_conv_grouped_fold4(const ivx_conv_desc *d, int groups, const float *in, long long g_in, const float *wgt, long long g_w, const IvxWinoFold *f,
-                           hipStream_t st);
-int ivx_conv_fold4_blocks(long long M, int Cout);
 
 namespace {
 

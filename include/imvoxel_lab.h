@@ -25,6 +25,21 @@ int ivx_conv_winograd_set_variant(int32_t output_variant, int32_t input_variant)
 int ivx_conv_set_epilogue_mode(int narrow);
 /* Per calling thread, A/B only: 1 = the round-1 tile rule of the direct convolution planner, 0 (default) = scored choice. */
 int ivx_conv_set_plan_mode(int mode);
+/* What the conv planner answers for `d` under the calling thread's knobs, from the functions the launchers call.  Host code only: no launch, no
+ * device call.  groups == 0: the direct path (ivx_conv_fwd / _ws with allow_ws, ivx_conv_fwd_pio with `io`) -- per distinct batch slice (the
+ * full slices, then the shorter last one if there is one) the plan's fields; ws_bytes is what ivx_conv_workspace_bytes /
+ * ivx_conv_pio_workspace_bytes return.  groups > 0: one Winograd-domain convolution of a grouped launch -- the z-halo / z-blocked config, or 0 and
+ * the tile of the LDS-DMA kernel (tile_matches 0: the launch refuses it for these operands). */
+typedef struct ivx_conv_plan_rec {
+  int32_t slice_samples, n_slices;    /* samples per batch slice (B: not sliced); distinct slices below (1 or 2) */
+  int32_t samples[2], cfg[2], ksplit[2], tail_ks[2], q_total[2], qa[2], bm[2];
+  int64_t slice_ws[2];
+  int64_t ws_bytes;                   /* maximum over the slices */
+  int32_t halo_cfg, grouped_tile, tile_matches, rows_dev_ok;
+} ivx_conv_plan_rec;
+/* The planner's figures of an LDS-DMA tile: v = {rows, columns, K slab, workgroups per CU}; returns 1, or 0 for a number that is no such tile. */
+int ivx_conv_tile_info(int cfg, int32_t *v);
+int ivx_conv_plan_query(const ivx_conv_desc *d, const ivx_pair_io *io_or_null, int allow_ws, int groups, ivx_conv_plan_rec *out);
 /* Per calling thread, A/B and tests only: 1 = the candidate top-k of the detection tails (ivx_anchor_head_get_bboxes,
  * ivx_fcos_head_level_candidates) always runs as the one-workgroup radix select; 0 (default) = lists of >= 16 384 scores take
  * the chip-wide histogram / compaction form.  Both return the same indices in the same order. */

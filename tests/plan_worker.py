@@ -12,7 +12,11 @@ restatement of the same ABI (--lib cpu):
   routes record tests/golden/conv_routes.json: which form every convolution takes (direct, Winograd with which tile and operands, split-operand).
          Section `layers` (no GPU) asks the FusedConv queries on a grid of layers, shapes and switches; section `plans` (GPU, planning only)
          reads the conv steps of every family's detect plan at the BASELINE shapes.  Run it at the commit whose rule is to be the reference,
-         BEFORE the rule is touched: tests/test_conv_route.py and tests/test_gpu_plan_switches.py hold every later commit to the file."""
+         BEFORE the rule is touched: tests/test_conv_route.py and tests/test_gpu_plan_switches.py hold every later commit to the file.
+  convplans record tests/golden/conv_plans.json: what the conv planner answers one level below the route (ivx_conv_plan_query: tile, K split,
+         grid-tail plan, workspace, batch slices; for the grouped launches the z-halo / z-blocked config or the tile) on the grids below, under
+         every lab knob, and -- one child process per switch, since they are read once -- under every environment switch.  No GPU.  Run it on a
+         library built from the commit whose rules are the reference (IVX_LIB_PATH): tests/test_host_conv_plan.py holds later commits to the file."""
 import argparse
 import ctypes as C
 import json
@@ -423,17 +427,195 @@ def job_routes(args):
     print(json.dumps({k: (v if k == 'commit' else {k2: len(v2) for k2, v2 in v.items()} if k == 'layers' else len(v)) for k, v in out.items()}))
 
 
+# ------------------------------------------------------------------------------------------------- job: convplans
+PLANS_FILE = os.path.join(HERE, 'golden', 'conv_plans.json')
+# the grid of the direct path: the route grid's layers and shapes, plus a 9x9 kernel (no LDS-DMA form: the generic 64 x 64 tile), a wide 1x1 layer
+# (the 8- / 16-wave tiles, the 256 x 256 tile of the trunk) and the shapes that put the pair-IO rule on both sides of its tile counts
+PLAN_LAYERS = ROUTE_LAYERS + [(64, 16, (9, 9), (1, 1), 4, 2, None), (1024, 256, (1, 1), (1, 1), 0, 2, None), (256, 1024, (1, 1), (1, 1), 0, 2, None)]
+PLAN_SHAPES_3D = ROUTE_SHAPES_3D
+PLAN_SHAPES_2D = ROUTE_SHAPES_2D + [(4, 1, 48, 160), (4, 1, 24, 80), (6, 1, 116, 200), (4, 1, 96, 320)]
+# operand modes: (in_dtype, out_dtype, ivx_pair_io?, 128-byte channel chunk of wgt_layout 1 in channels)
+PLAN_MODES_CONV = [(0, 0, False, 32), (1, 1, False, 64), (2, 2, False, 128), (3, 0, False, 32), (4, 0, False, 32), (4, 4, True, 32)]
+# per (layer, shape, mode): (allow_ws, plan mode, res_mode); a residual in the modes whose rules read it (fp32, pair IO), res_mode 2 on the 2-D shapes only
+PLAN_CALLS = [(0, 0, 0), (1, 0, 0), (1, 1, 0), (1, 0, 1), (1, 0, 2), (0, 0, 1)]
+# tile override: every row of csrc/conv_tiles.h (0 is the rest of the grid) on two layers at one shape each, every operand mode
+PLAN_TILES = [1, 2, 3, 4, 5, 6, 7, 41, 43, 44, 46, 47, 48, 49, 51, 52, 53, 54, 55, 56, 57, 58, 59, 61, 63, 64, 66, 67, 71, 72, 73, 74, 75, 76, 77, 81, 82, 83, 85,
+              91, 92, 93, 94, 166, 174, 177, 179, 183, 474, 475, 574] + [8, 45, 65, 90, 175]       # ... and numbers in no row
+PLAN_TILE_CASES = [((256, 256, (3, 3), (1, 1), 1, 2, None), (50, 1, 50, 80)), ((128, 64, (1, 1, 1), (1, 1, 1), 0, 3, None), (1, 40, 40, 16))]
+# grouped launches (one xi convolution of a Winograd-domain GEMM: 1x1xKW along z on `rows` tile columns): (Cout, Cin), (KW, stride, pad), slices, rows,
+# groups, operands
+PLAN_G_CH = [(64, 64), (128, 128), (256, 256), (32, 32), (128, 64), (512, 512), (48, 48)]
+PLAN_G_K = [(3, 1, 1), (3, 2, 1), (3, 1, 0), (1, 1, 0)]
+PLAN_G_Z = [3, 6, 12, 16]
+PLAN_G_ROWS = [100, 1600, 13392]
+PLAN_G_GROUPS = [16, 36]
+PLAN_G_DTYPES = [0, 3, 4]
+# halo mode: default, never, every row of IVX_CONV_HALO_CFGS and numbers in no row -- on the f16-pair layers of both z strides
+PLAN_HALO_MODES = [-1, 0] + list(range(1, 15)) + [21, 22, 23, 24, 30, 31, 33, 34, 41, 42, 43, 44, 45, 46, 50, 51, 60, 71] + [25, 99, 15, 70]
+PLAN_HALO_CASES = [(ch, k, z, 1600, 36) for ch in ((64, 64), (256, 256)) for k in PLAN_G_K[:3] for z in (3, 6)]
+# environment switches, each at one value that is not its default (csrc/conv_plan.h IVX_CONV_ENV)
+PLAN_ENV = dict(IVX_CONV_SKINNY=0, IVX_PIO_RULE=0, IVX_PIO_SPLITK=0, IVX_PIO_SPLIT_TILES=100, IVX_PIO_DEEP=0, IVX_PIO_DEEP_TILES=128, IVX_PIO_DEEP_SLABS=40,
+                IVX_PIO_W16_TILES=0, IVX_PIO_W8_TILES=0, IVX_PIO_T183=0, IVX_PIO_TAIL=1, IVX_PIO_STAGGER_US=5, IVX_PIO_STAGGER_SHIFT=1, IVX_HALO_SMALL=0)
+
+
+def plan_desc(spec, shape, mode, res_mode=0):
+    """(ivx_conv_desc, ivx_pair_io or None) of a PLAN_LAYERS entry on the input `shape` (B, D, H, W) in an operand mode."""
+    from imvoxelnet_amd._lib import ConvDesc, PairIO
+    co, ci, k, st, pad, dims, _ = spec
+    k, st = ((1,) + tuple(k), (1,) + tuple(st)) if dims == 2 else (tuple(k), tuple(st))
+    pd = (0, pad, pad) if dims == 2 else (pad, pad, pad)
+    ci = (ci + 3) // 4 * 4
+    out = [(shape[1 + i] + 2 * pd[i] - k[i]) // st[i] + 1 for i in range(3)]
+    in_dt, out_dt, pio, ck = mode
+    d = ConvDesc(*shape, ci, co, *k, *st, *pd, 1, res_mode, (out[1] + 1) // 2 if res_mode == 2 else 0, (out[2] + 1) // 2 if res_mode == 2 else 0,
+                 1 if ci % ck == 0 else 0, 0, 0, 1.0, in_dt, out_dt, 1.0, 0)
+    some = C.c_void_p(64)           # (never read: the query makes no device call)
+    return d, (PairIO(some, some, IVX_F16_PAIR, some, some, some, some, 1.0, 1.0) if pio else None)
+
+
+def grouped_desc(ch, k, z, rows, dtype):
+    from imvoxelnet_amd._lib import ConvDesc
+    return ConvDesc(1, 1, rows, z, ch[1], ch[0], 1, 1, k[0], 1, 1, k[1], 0, 0, k[2], 0, 0, 0, 0, 1 if ch[1] % 32 == 0 else 0, 0, 0, 1.0, dtype, 0, 1.0, 0)
+
+
+def plan_row(L, d, io, allow_ws, groups=0):
+    """The answer of ivx_conv_plan_query as a list of integers: [rc] when it refuses; direct [samples per slice, then per distinct slice samples, cfg,
+    ksplit, tail_ks, q_total, qa, bm, ws_bytes; ws_bytes of the call]; grouped [halo_cfg, tile, tile_matches, rows_dev_ok]."""
+    from imvoxelnet_amd._lib import ConvPlanRec
+    r = ConvPlanRec()
+    rc = L.ivx_conv_plan_query(C.byref(d), C.byref(io) if io is not None else None, allow_ws, groups, C.byref(r))
+    if rc != 0:
+        return [rc]
+    if groups:
+        return [r.halo_cfg, r.grouped_tile, r.tile_matches, r.rows_dev_ok]
+    row = [r.slice_samples]
+    for i in range(r.n_slices):
+        row += [r.samples[i], r.cfg[i], r.ksplit[i], r.tail_ks[i], r.q_total[i], r.qa[i], r.bm[i], r.slice_ws[i]]
+    return row + [r.ws_bytes]
+
+
+def plan_workspace(L, d, io):
+    """What the two workspace entry points say (the query with allow_ws = 1 must agree)."""
+    L.ivx_conv_workspace_bytes.restype = L.ivx_conv_pio_workspace_bytes.restype = C.c_int64
+    return L.ivx_conv_pio_workspace_bytes(C.byref(d), C.byref(io)) if io is not None else L.ivx_conv_workspace_bytes(C.byref(d))
+
+
+def plan_shapes(spec):
+    return PLAN_SHAPES_3D if spec[5] == 3 else PLAN_SHAPES_2D
+
+
+def plan_section(L, name, check=None):
+    """The rows of a section of the fixture, in the order of its loops (the keys are not stored).  check(d, io, row): called on the direct rows asked
+    with allow_ws = 1."""
+    rows = []
+
+    def direct(spec, shape, mode, allow_ws, pm, res):
+        d, io = plan_desc(spec, shape, mode, res)
+        L.ivx_conv_set_plan_mode(pm)
+        rows.append(plan_row(L, d, io, allow_ws))
+        if check and allow_ws:
+            check(d, io, rows[-1])
+        L.ivx_conv_set_plan_mode(0)
+
+    if name == 'direct':
+        for spec in PLAN_LAYERS:
+            for shape in plan_shapes(spec):
+                for mode in PLAN_MODES_CONV:
+                    for aw, pm, res in PLAN_CALLS:
+                        if res == 0 or (mode in (PLAN_MODES_CONV[0], PLAN_MODES_CONV[5]) and (res != 2 or spec[5] == 2)):
+                            direct(spec, shape, mode, aw, pm, res)
+    elif name == 'tiles':
+        for spec, shape in PLAN_TILE_CASES:
+            for mode in PLAN_MODES_CONV:
+                for t in PLAN_TILES:
+                    L.ivx_conv_set_tile_override(t)
+                    direct(spec, shape, mode, 1, 0, 0)
+        for t in PLAN_TILES:
+            L.ivx_conv_set_tile_override(t)
+            for dt in PLAN_G_DTYPES:
+                rows.append(plan_row(L, grouped_desc((128, 128), PLAN_G_K[2], 3, 13392, dt), None, 0, 36))
+        L.ivx_conv_set_tile_override(0)
+    elif name == 'grouped':
+        for ch in PLAN_G_CH:
+            for k in PLAN_G_K:
+                for z in PLAN_G_Z:
+                    for n in PLAN_G_ROWS:
+                        for g in PLAN_G_GROUPS:
+                            for dt in PLAN_G_DTYPES:
+                                rows.append(plan_row(L, grouped_desc(ch, k, z, n, dt), None, 0, g))
+    elif name == 'halo':
+        for hm in PLAN_HALO_MODES:
+            L.ivx_conv_set_halo_mode(hm)
+            for ch, k, z, n, g in PLAN_HALO_CASES:
+                rows.append(plan_row(L, grouped_desc(ch, k, z, n, IVX_F16_PAIR), None, 0, g))
+        L.ivx_conv_set_halo_mode(-1)
+    elif name == 'env':                     # the reduced grid every environment child answers: what the switches bear on
+        for spec in PLAN_LAYERS:
+            for shape in plan_shapes(spec):
+                for mode in (PLAN_MODES_CONV[5],) if spec[5] == 2 else (PLAN_MODES_CONV[0],) if spec[0] <= 32 else ():
+                    for aw, pm, res in PLAN_CALLS[:2] + PLAN_CALLS[3:4]:
+                        direct(spec, shape, mode, aw, pm, res)
+        for ch in PLAN_G_CH[:3]:
+            for z in PLAN_G_Z:
+                for n in PLAN_G_ROWS:
+                    rows.append(plan_row(L, grouped_desc(ch, PLAN_G_K[0], z, n, IVX_F16_PAIR), None, 0, 36))
+    else:
+        raise KeyError(name)
+    return rows
+
+
+def plan_tile_infos(L):
+    """{number: [bm, bn, bk, wg_per_cu]} of every number the planner knows as an LDS-DMA tile (asked for 0 .. 999)."""
+    out = {}
+    v = (C.c_int32 * 4)()
+    for t in range(1000):
+        if L.ivx_conv_tile_info(t, v):
+            out[str(t)] = list(v)
+    return out
+
+
+def plan_env_child(name, value):
+    """The `env` section as a fresh process answers it with the switch `name` set (the switches are read once per process)."""
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if not k.startswith('IVX_') or k == 'IVX_LIB_PATH'}
+    env[name] = str(value)
+    r = subprocess.run([sys.executable, os.path.abspath(__file__), 'convplans', '--section', 'env'], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, f'{name}={value}: {r.stderr[-2000:]}'
+    return json.loads(r.stdout.strip().splitlines()[-1])
+
+
+def plan_env_diff(base, rows):
+    """[[index, row]] of the rows that differ from the section under the default environment"""
+    assert len(base) == len(rows)
+    return [[i, r] for i, (b, r) in enumerate(zip(base, rows)) if b != r]
+
+
+def job_convplans(args):
+    from imvoxelnet_amd import _lib
+    L = _lib.lib()
+    if args.section == 'env':                # a child of plan_env_child
+        print(json.dumps(plan_section(L, 'env'), separators=(',', ':')))
+        return
+    out = {'commit': args.commit, 'tile_info': plan_tile_infos(L)}
+    for name in ('direct', 'tiles', 'grouped', 'halo', 'env'):
+        out[name] = plan_section(L, name)
+    out['env_switches'] = {k: plan_env_diff(out['env'], plan_env_child(k, v)) for k, v in PLAN_ENV.items()}
+    with open(args.out or PLANS_FILE, 'w') as fh:
+        fh.write('{\n' + ',\n'.join(f' {json.dumps(k)}: {json.dumps(v, separators=(",", ":"))}' for k, v in out.items()) + '\n}\n')
+    print(json.dumps({k: (v if k == 'commit' else len(v)) for k, v in out.items()}))
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument('job', choices=['plans', 'run', 'routes'])
+    ap.add_argument('job', choices=['plans', 'run', 'routes', 'convplans'])
     ap.add_argument('--lib', choices=['cpu', 'hip'], default='cpu')
     ap.add_argument('--config', default='kitti_small')
     ap.add_argument('--phases', default='0', help='comma-separated trace levels; the four steps run once per level')
     ap.add_argument('--out', default=None)
-    ap.add_argument('--section', choices=['layers', 'plans', 'all'], default='all', help='routes: the section(s) to record; the other is kept')
+    ap.add_argument('--section', choices=['layers', 'plans', 'all', 'env'], default='all', help='routes: the section(s) to record; the other is kept')
     ap.add_argument('--commit', default='', help='routes: short hash of the commit whose rule is recorded')
     args = ap.parse_args()
-    {'plans': job_plans, 'run': job_run, 'routes': job_routes}[args.job](args)
+    {'plans': job_plans, 'run': job_run, 'routes': job_routes, 'convplans': job_convplans}[args.job](args)
 
 
 if __name__ == '__main__':

@@ -11,11 +11,12 @@ mkdir -p "$TMP" "$ROOT/tools/bin"
 for tu in 0 4 5; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$CSRC/conv_igemm.hip" -o "$TMP/tu$tu.o" -DIVX_CONV_TU=$tu -DIVX_CONV_TIMELINE &
 done
+/opt/rocm/bin/hipcc -O2 -std=c++17 -fPIC -c "$CSRC/conv_plan.cpp" -o "$TMP/conv_plan.o" -DIVX_CONV_TIMELINE &      # (the planner copies ConvParams: same layout as TU 0)
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$CSRC/bottleneck.hip" -o "$TMP/bottleneck.o" -DIVX_CONV_TIMELINE &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$CSRC/stem.hip" -o "$TMP/stem.o" -DIVX_CONV_TIMELINE &
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -c "$CSRC/winograd.hip" -o "$TMP/winograd.o" -DIVX_CONV_TIMELINE &
 wait
 cd "$CSRC"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/bin/libimvoxel_hip_tl.so" "$TMP/tu0.o" conv_igemm_f32.o conv_igemm_lowp.o \
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$ROOT/tools/bin/libimvoxel_hip_tl.so" "$TMP/tu0.o" "$TMP/conv_plan.o" conv_igemm_f32.o conv_igemm_lowp.o \
   conv_igemm_pair_bf16.o "$TMP/tu4.o" "$TMP/tu5.o" "$TMP/bottleneck.o" "$TMP/stem.o" "$TMP/winograd.o" pool_layout.o backproject.o anchor_tail.o dcn.o fold4w.o ubench.o api_common.o kitti_eval.o model.o
 echo "$ROOT/tools/bin/libimvoxel_hip_tl.so"
