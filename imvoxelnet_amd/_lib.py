@@ -155,6 +155,16 @@ class ImagePrepDesc(C.Structure):
                [('mean', C.c_float * 3), ('std', C.c_float * 3)]
 
 
+LENS_BROWN, LENS_FISHEYE = 0, 1      # ivx_lens.model: OpenCV's 5-coefficient model (k1, k2, p1, p2, k3) | its equidistant fisheye model (k1..k4)
+MAP_F32, MAP_U16 = 0, 1              # the element type of a source-size map of ivx_map_prep_lens
+
+
+class Lens(C.Structure):
+    """ivx_lens: a real camera (K, distortion) and the ideal pinhole camera the network input shows (ivx_image_prep_lens_u8 / ivx_map_prep_lens)."""
+    _fields_ = [('model', C.c_int32)] + [(n, C.c_double) for n in ('fx', 'fy', 'cx', 'cy')] + [('coef', C.c_double * 5)] + \
+               [(n, C.c_double) for n in ('new_fx', 'new_fy', 'new_cx', 'new_cy', 'r2_max')]
+
+
 class ConvPlanRec(C.Structure):
     """ivx_conv_plan_rec (include/imvoxel_lab.h): what the conv planner answers for a descriptor (ivx_conv_plan_query)."""
     _fields_ = [('slice_samples', C.c_int32), ('n_slices', C.c_int32)] + \
@@ -189,7 +199,7 @@ EXPORTS = ['ivx_conv_plan_query', 'ivx_conv_tile_info', 'ivx_model_plan_info', '
            'ivx_model_trace', 'ivx_model_trace_count', 'ivx_model_trace_read',
            'ivx_model_detect_workspace_bytes', 'ivx_model_max_detections', 'ivx_model_detect', 'ivx_layout_head_decode', 'ivx_layout_extrinsics',
            'ivx_indoor_tail_workspace_bytes', 'ivx_indoor_tail_get_bboxes',
-           'ivx_rescale_size', 'ivx_image_prep_u8',
+           'ivx_rescale_size', 'ivx_image_prep_u8', 'ivx_image_prep_lens_u8', 'ivx_map_prep_lens',
            'ivx_kitti_image_box_overlap', 'ivx_kitti_compute_statistics', 'ivx_kitti_collect_scores', 'ivx_kitti_fused_statistics']
 
 
@@ -307,6 +317,9 @@ def lib():
                                                  vp, vp]
     if hasattr(L, 'ivx_view_coverage_fwd'):        # (0.5.1; an older build still loads: ops.view_coverage and the scenes' coverage() / min_novelty= then refuse)
         L.ivx_view_coverage_fwd.argtypes = [C.POINTER(BackprojectDesc), C.POINTER(LiftLists), C.POINTER(LiftMaps), vp, vp, vp, vp, i32, f32, vp, vp]
+    if hasattr(L, 'ivx_image_prep_lens_u8'):       # (0.5.2; an older build still loads: ops.image_prep_lens_u8 / map_prep_lens and the scenes' lens= / depth_frames= then refuse)
+        L.ivx_image_prep_lens_u8.argtypes = [C.POINTER(ImagePrepDesc), C.POINTER(Lens), vp, i64, i32, vp, vp]
+        L.ivx_map_prep_lens.argtypes = [C.POINTER(ImagePrepDesc), C.POINTER(Lens), vp, i32, i64, i64, f32, i32, i32, vp, vp]
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -1,6 +1,7 @@
 """Input side of the path: checkpoint loading, the test-time image pipeline and the
 on-disk calibration -> `lidar2img` adapters.  Host-side numpy/torch, except prepare_images_device, which runs the image pipeline
-of prepare_image on the device (ops.image_prep_u8) and is held to prepare_image bit for bit.
+of prepare_image on the device (ops.image_prep_u8) and is held to prepare_image bit for bit; with lens= (a Lens record: a real camera's
+intrinsic and distortion) it undistorts in the same launch (ops.image_prep_lens_u8), held to an fp64 reference within a derived bound.
 
 Reference: configs/imvoxelnet/imvoxelnet_kitti.py:66,94-105 (Resize keep_ratio -> Normalize -> Pad(size_divisor=32)),
 mmdet3d/datasets/{kitti,nuscenes,scannet,sunrgbd}_monocular_dataset.py (lidar2img), pipelines/multi_view.py:45-53
@@ -138,7 +139,86 @@ def _pipeline_shapes(ori_hw, img_scale, size_divisor, keep_ratio):
     return (nh, nw), ((nh + size_divisor - 1) // size_divisor * size_divisor, (nw + size_divisor - 1) // size_divisor * size_divisor)
 
 
-def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor=32, keep_ratio=True, device='cuda'):
+class Lens:
+    """A real camera and the ideal one its undistorted image shows (include/imvoxel.h, ivx_lens): a small checked record.
+    model: 'brown' (OpenCV's 5-coefficient model, coef = (k1, k2, p1, p2, k3); four coefficients mean k3 = 0) or 'fisheye' (OpenCV's
+    equidistant model, coef = (k1, k2, k3, k4)).  K: the real camera's intrinsic, at least 3x3, zero skew, in pixels of the SOURCE frame.
+    new_K: the ideal pinhole camera of the undistorted image at the source size (None: K) -- what the lidar2img intrinsic of the metas must
+    describe.  r2_max: the normalised radius squared beyond which the polynomial is not trusted (> 0; inf: no limit); pixels beyond it are
+    border.  Immutable; `key` is hashable and equal for equal lenses, so frames group by it and scenes cache by it."""
+    MODELS = {'brown': 0, 'fisheye': 1}
+
+    def __init__(self, model, K, coef, new_K=None, r2_max=float('inf')):
+        if model not in self.MODELS:
+            raise ValueError(f"model must be 'brown' or 'fisheye', got {model!r}")
+        cams = []
+        for name, M in (('K', K), ('new_K', K if new_K is None else new_K)):
+            M = np.asarray(M, np.float64)
+            if M.ndim != 2 or M.shape[0] < 3 or M.shape[1] < 3:
+                raise ValueError(f'{name} must be at least 3x3, got {M.shape}')
+            fx, fy, cx, cy = float(M[0, 0]), float(M[1, 1]), float(M[0, 2]), float(M[1, 2])
+            if not all(np.isfinite(v) for v in (fx, fy, cx, cy)) or fx == 0 or fy == 0:
+                raise ValueError(f'{name} must hold finite entries and non-zero focal lengths, got fx {fx}, fy {fy}, cx {cx}, cy {cy}')
+            if M[0, 1] != 0 or M[1, 0] != 0 or M[2, 0] != 0 or M[2, 1] != 0 or M[2, 2] != 1:
+                raise ValueError(f'{name} must be a pinhole intrinsic without skew ([[fx,0,cx],[0,fy,cy],[0,0,1]])')
+            cams.append((fx, fy, cx, cy))
+        c = [float(v) for v in np.asarray(coef, np.float64).reshape(-1)]
+        want = (4, 5) if model == 'brown' else (4,)
+        if len(c) not in want:
+            raise ValueError(f'a {model} lens takes {" or ".join(str(n) for n in want)} coefficients, got {len(c)}')
+        if not all(np.isfinite(v) for v in c):
+            raise ValueError(f'coefficients must be finite, got {c}')
+        r2_max = float(r2_max)
+        if not r2_max > 0:
+            raise ValueError(f'r2_max must be > 0 (inf: no limit), got {r2_max}')
+        self._key = (model, cams[0], tuple(c + [0.0] * (5 - len(c))), cams[1], r2_max)
+
+    model = property(lambda self: self._key[0])
+    coef = property(lambda self: self._key[2])
+    r2_max = property(lambda self: self._key[4])
+    key = property(lambda self: self._key)
+
+    @staticmethod
+    def _matrix(cam):
+        fx, fy, cx, cy = cam
+        return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], np.float64)
+
+    K = property(lambda self: self._matrix(self._key[1]))
+    new_K = property(lambda self: self._matrix(self._key[3]))
+
+    def __eq__(self, other):
+        return isinstance(other, Lens) and self._key == other._key
+
+    def __hash__(self):
+        return hash(self._key)
+
+    def __repr__(self):
+        return f'Lens{self._key!r}'
+
+    def struct(self):
+        """The ivx_lens of this record."""
+        import ctypes
+        from ._lib import Lens as CLens
+        model, k, c, nk, r2 = self._key
+        return CLens(self.MODELS[model], *k, (ctypes.c_double * 5)(*c), *nk, r2)
+
+
+def _check_lenses(lens, n):
+    """lens of prepare_images_device -> None (no lens anywhere) or a list of n entries, each a Lens or None."""
+    if lens is None:
+        return None
+    if isinstance(lens, Lens):
+        return [lens] * n
+    lens = list(lens)
+    if len(lens) != n:
+        raise ValueError(f'{len(lens)} lenses for {n} frames (one Lens for all, or one entry per frame)')
+    for l in lens:
+        if l is not None and not isinstance(l, Lens):
+            raise TypeError(f'every lens entry must be a data.Lens or None, got {type(l).__name__}')
+    return lens
+
+
+def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor=32, keep_ratio=True, device='cuda', lens=None):
     """prepare_image for a whole batch on the device (ops.image_prep_u8, csrc/preprocess.hip): the uint8 frames cross to the
     device as they are (a quarter of the bytes of the fp32 tensor) and ONE launch per group of same-sized frames resizes, normalises
     and pads them -- bit-identical to prepare_image per frame.
@@ -148,7 +228,11 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
     whose plane is the LARGEST pad shape of the batch (zero filled below / right of each image, what mmdet's collate does); a
     group whose frames are not adjacent in the batch takes one launch per run of adjacent frames.
     Returns (img [N,3,Hp,Wp] or [B,V,3,Hp,Wp] fp32 on `device`, list of per-sample dicts img_shape / ori_shape / pad_shape equal to
-    prepare_image's; for a multi-view sample the dict of its LAST view, as MultiViewPipeline)."""
+    prepare_image's; for a multi-view sample the dict of its LAST view, as MultiViewPipeline).
+    lens: None (ideal cameras: the call as it was), one Lens for every frame, or a list with one entry per frame in batch order, each a
+    Lens or None (a rig).  Frames with a lens go through ops.image_prep_lens_u8 (csrc/lens_prep.hip: undistortion in the same launch, ONE
+    bilinear interpolation in fp32 instead of cv2's integer resize, border pixels zero); frames are then grouped by (source shape, lens),
+    a run of adjacent frames of one group still taking one launch.  The image shows the lens's new_K scaled by the resize."""
     from . import ops
     device = torch.device(device)
     views = None
@@ -171,15 +255,16 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
     for f in flat:
         if f.ndim != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
             raise TypeError(f'frames must be (H,W,3) uint8, got {tuple(f.shape)} {f.dtype}')
-    groups = {}                                                  # source (h, w) -> indices, in batch order
+    lenses = _check_lenses(lens, len(flat))
+    groups = {}                                                  # source (h, w) [, lens] -> indices, in batch order
     for i, f in enumerate(flat):
-        groups.setdefault((int(f.shape[0]), int(f.shape[1])), []).append(i)
-    shapes = {hw: _pipeline_shapes(hw, img_scale, size_divisor, keep_ratio) for hw in groups}
+        groups.setdefault((int(f.shape[0]), int(f.shape[1])) + (() if lenses is None else (lenses[i],)), []).append(i)
+    shapes = {hw: _pipeline_shapes(hw[:2], img_scale, size_divisor, keep_ratio) for hw in groups}
     Hp, Wp = max(s[1][0] for s in shapes.values()), max(s[1][1] for s in shapes.values())
     out = torch.empty((len(flat), 3, Hp, Wp), device=device, dtype=torch.float32)
     mean, std, to_rgb = img_norm_cfg['mean'], img_norm_cfg['std'], img_norm_cfg.get('to_rgb', True)
     for hw, idx in groups.items():
-        if stacked is not None:                                  # one group by construction
+        if stacked is not None and len(groups) == 1:             # one group (by construction without lenses)
             src = torch.from_numpy(np.ascontiguousarray(stacked)) if isinstance(stacked, np.ndarray) else stacked
         elif all(isinstance(flat[i], np.ndarray) for i in idx):
             src = torch.from_numpy(np.stack([flat[i] for i in idx]))
@@ -192,12 +277,15 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
             b = a + 1
             while b < len(idx) and idx[b] == idx[b - 1] + 1:
                 b += 1
-            ops.image_prep_u8(src[a:b], shapes[hw][0], (Hp, Wp), mean, std, to_rgb, out=out[idx[a]:idx[a] + b - a])
+            if len(hw) == 2 or hw[2] is None:
+                ops.image_prep_u8(src[a:b], shapes[hw][0], (Hp, Wp), mean, std, to_rgb, out=out[idx[a]:idx[a] + b - a])
+            else:
+                ops.image_prep_lens_u8(src[a:b], hw[2], shapes[hw][0], (Hp, Wp), mean, std, to_rgb, out=out[idx[a]:idx[a] + b - a])
             a = b
     metas = []
     for f in flat:
         hw = (int(f.shape[0]), int(f.shape[1]))
-        (nh, nw), (ph, pw) = shapes[hw]
+        (nh, nw), (ph, pw) = _pipeline_shapes(hw, img_scale, size_divisor, keep_ratio) if lenses is not None else shapes[hw]
         metas.append(dict(img_shape=(nh, nw, 3), ori_shape=(hw[0], hw[1], 3), pad_shape=(ph, pw, 3)))
     if views is not None:
         return out.view(len(flat) // views, views, 3, Hp, Wp), metas[views - 1::views]

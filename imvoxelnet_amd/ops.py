@@ -81,6 +81,102 @@ def image_prep_u8(src, size_hw, pad_hw, mean, std, to_rgb=True, out=None):
     return out
 
 
+def _lens_entry(name):
+    """The 0.5.2 entry `name` of the loaded library; an older build of the ABI refuses here."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise _lib.IvxError(f'{name} is not in the loaded libimvoxel_hip.so (version {L.ivx_version()} < 502): the lens-aware image pipeline needs 0.5.2')
+    return getattr(L, name)
+
+
+def _lens_struct(lens, name='lens'):
+    """A data.Lens (anything with .struct()) -> _lib.Lens."""
+    if not hasattr(lens, 'struct'):
+        raise TypeError(f'{name} must be a data.Lens, got {type(lens).__name__}')
+    return lens.struct()
+
+
+def image_prep_lens_u8(src, lens, size_hw, pad_hw, mean, std, to_rgb=True, out=None):
+    """image_prep_u8 for the frames of a real camera: Undistort -> Resize -> Normalize -> zero Pad in one launch and ONE interpolation
+    (ivx_image_prep_lens_u8; include/imvoxel.h has the definition of the map G and of the fp32 bilinear blend).  lens: a data.Lens, one for
+    all n frames; the output shows the ideal camera lens.new_K (at the source size), and pixels that G sends outside the frame or beyond
+    r2_max are border: +0.0f, like the pad.  Everything else as image_prep_u8."""
+    fn = _lens_entry('ivx_image_prep_lens_u8')
+    ls = _lens_struct(lens)
+    if not isinstance(src, torch.Tensor):
+        raise TypeError('src must be a torch.Tensor')
+    if not src.is_cuda:
+        raise RuntimeError('src must be a device (HIP) tensor; the MI355X path has no CPU fallback')
+    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
+        raise TypeError(f'src must be uint8 [n,H,W,3], got {src.dtype} {tuple(src.shape)}')
+    n, H, W, _ = src.shape
+    if n < 1:
+        raise ValueError('src holds no frame')
+    row = src.stride(1) if H > 1 else 3 * W                  # (the stride of an extent-1 axis is arbitrary)
+    if src.stride(3) != 1 or (W > 1 and src.stride(2) != 3) or row < 3 * W or (n > 1 and src.stride(0) < H * row):
+        raise ValueError(f'src rows must be dense HWC (strides (>= H * row, >= 3 * W, 3, 1)), got {tuple(src.stride())}')
+    (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
+    if out is None:
+        out = torch.empty((n, 3, ph, pw), device=src.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != (n, 3, ph, pw) or out.device != src.device:
+            raise ValueError(f'out must be [{n},3,{ph},{pw}] on {src.device}, got {tuple(out.shape)} on {out.device}')
+    d = _lib.ImagePrepDesc(H, W, row, nh, nw, ph, pw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
+                           (C.c_float * 3)(*[float(v) for v in std]))
+    check(fn(C.byref(d), C.byref(ls), _ptr(src), src.stride(0), n, _ptr(out), _stream()), 'ivx_image_prep_lens_u8')
+    return out
+
+
+_MAP_DT = {torch.float32: (_lib.MAP_F32, 4), torch.uint16: (_lib.MAP_U16, 2)}
+
+
+def map_prep_lens(size_hw, pad_hw, src_hw, lens=None, src=None, scale=1.0, stride=4, n=1, out=None, device=None):
+    """The feature-resolution maps of the geometry of image_prep_lens_u8 (ivx_map_prep_lens): [n, ceil(pad_h / stride), ceil(pad_w / stride)]
+    fp32, feature pixel (i, j) being input pixel (stride * i, stride * j) of the pipeline src_hw -> size_hw -> pad_hw (scene.pick_map's rule).
+    src=None: the cover map, 1 where that input pixel shows the frame and 0 where it is border (pad, outside the frame, beyond r2_max); n
+    copies; on `device` (None: the current HIP device).  src: device maps [n,H,W] at the source size src_hw, float32 or uint16 (a depth
+    frame), rows dense: scale * the value at the nearest source pixel, 0 at border pixels (the lifts' "no measurement").  lens=None is the
+    ideal camera, which takes depth frames through the plain pipeline.  out: a contiguous fp32 tensor of the result's shape to write into."""
+    fn = _lens_entry('ivx_map_prep_lens')
+    ls = None if lens is None else _lens_struct(lens)
+    (nh, nw), (ph, pw), (H, W) = (int(v) for v in size_hw), (int(v) for v in pad_hw), (int(v) for v in src_hw)
+    if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
+        raise ValueError(f'stride must be an integer >= 1, got {stride!r}')
+    row = plane = dt = 0
+    if src is not None:
+        if not isinstance(src, torch.Tensor):
+            raise TypeError('src must be None or a torch.Tensor')
+        if not src.is_cuda:
+            raise RuntimeError('src must be a device (HIP) tensor; the MI355X path has no CPU fallback')
+        if src.dtype not in _MAP_DT or src.dim() != 3 or tuple(src.shape[1:]) != (H, W):
+            raise TypeError(f'src must be float32 or uint16 [n,{H},{W}] at the source size, got {src.dtype} {tuple(src.shape)}')
+        n = int(src.shape[0])
+        if n < 1:
+            raise ValueError('src holds no map')
+        dt, es = _MAP_DT[src.dtype]
+        rs = src.stride(1) if H > 1 else W
+        if (W > 1 and src.stride(2) != 1) or rs < W or (n > 1 and src.stride(0) < H * rs):
+            raise ValueError(f'src rows must be dense (strides (>= H * row, >= W, 1)), got {tuple(src.stride())}')
+        row, plane = rs * es, src.stride(0) * es
+        device = src.device
+    elif isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f'n must be an integer >= 1, got {n!r}')
+    if min(ph, pw) < 1:
+        raise ValueError(f'pad_hw must be positive, got {(ph, pw)}')
+    shape = (n, (ph - 1) // stride + 1, (pw - 1) // stride + 1)
+    if out is None:
+        out = torch.empty(shape, device=torch.device('cuda', torch.cuda.current_device()) if device is None else device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != shape or (src is not None and out.device != src.device):
+            raise ValueError(f'out must be {list(shape)}' + (f' on {src.device}' if src is not None else '') + f', got {tuple(out.shape)} on {out.device}')
+    d = _lib.ImagePrepDesc(H, W, 3 * W, nh, nw, ph, pw, 0, (C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1, 1, 1))
+    check(fn(C.byref(d), None if ls is None else C.byref(ls), _ptr(src), dt, row, plane, float(scale), stride, n, _ptr(out), _stream()),
+          'ivx_map_prep_lens')
+    return out
+
+
 def to_channels_last(x, pad_to=None):
     """[B,C,*spatial] (reference layout) -> [B,D,H,W,Cpad] channels-last (D=1 for 2-D input)."""
     _chk(x, 'x')

@@ -61,7 +61,8 @@ fixed at open, lets the view count at a voxel only where the voxel's depth d lie
 or a truncation band; a pixel with no measurement -- 0, negative, NaN, inf -- gates nothing).  Both are read at the nearest pixel the voxel projects
 to, in the same single launch (ops.backproject_mapped_accum_ / _mean_, ivx_backproject_mapped_fwd; include/imvoxel.h has the definition).  Each map
 is one float32 tensor [V,FH,FW], host or device, or [V,H,W] at the padded input size, which is reduced by the strided pick map[:, ::s, ::s] with
-s = H // FH (pick_map: feature pixel (x, y) is input pixel (s*x, s*y), as in the projection rule; exact); add_views_u8 takes feature resolution only.
+s = H // FH (pick_map: feature pixel (x, y) is input pixel (s*x, s*y), as in the projection rule; exact); add_views_u8 takes feature resolution only,
+and depth frames at the source size through depth_frames= (below).
 Fading scenes consume the maps in the tick's launch and keep nothing.  Windowed scenes keep two device rings beside the feature ring ([W,FH,FW] fp32
 each, 77 KB per slot at 480 x 640; [N*W,FH,FW] in a batch, scene s owning slots s*W .. s*W+W-1), each allocated when its first map is given -- weights
 filled with 1, depths with 0 (no measurement) -- and a slot reused by a view without a map goes back to 1 / 0; eviction, remove_views and scroll need
@@ -80,6 +81,15 @@ extrinsics, weights and maps before the trunk; a call whose views are all reject
 session, an untouched scene in a batch -- and last_admitted holds the verdicts (None after an ungated call).  min_novelty=None runs the code it ran
 before.
 
+Lenses and depth frames (add_views_u8(..., lens=, depth_frames=, depth_scale=)).  The cameras scenes are built for have radial distortion, and the
+black border after undistortion is the first use of a confidence map.  One geometric map from a pixel of the network input back to the raw frame
+(include/imvoxel.h, the map G of ivx_image_prep_lens_u8) gives all three things such a camera needs, on the device: the undistorted, resized,
+normalised image in the pipeline's own launch and in ONE interpolation (data.prepare_images_device(lens=)); the cover map at feature resolution
+(ops.map_prep_lens: 1 where the input pixel shows the frame), which multiplies the view's confidence on sessions that take maps and which the
+keyframe gate sees as well; and the depth frame of an RGB-D camera, picked at the nearest source pixel of each feature pixel by the same rule.
+The cover depends on (lens, source shape, pipeline shapes) only and is cached on the scene or batch.  The meta's intrinsic must be the lens's
+new_K.  A scene that never passes lens or depth_frames calls what it called before.
+
 How the module is laid out.  Every host rule is written once.  _SceneRecord is the host state of ONE scene (meta, view list, ids, stale flag, image
 size, window, decay, threshold) with the rules that need no device: the checks of meta / window / fading, reset, view_ids, remove_views, which slots
 of a range [base, base + W) a windowed add frees and fills, the id-to-slot lookup, the body of reweight.  The argument checks of an add (images,
@@ -89,7 +99,7 @@ the two, for a measured reason (profiles/scene_batch.md: the listed lift at one 
 the classes, and nothing shared asks which class called it: wording that differs in a noun is passed in.
 
 Out of scope: a gate in which the views of one call see each other (sequential gating), anticipating a fading scene's next decay in coverage(),
-choosing which kept view of a window to evict; decay on windowed scenes; resizing pixel maps through the add_views_u8 pipeline, a soft (ramp) or signed-distance gate, maps for plain
+choosing which kept view of a window to evict; decay on windowed scenes; confidence maps at the source size through the add_views_u8 pipeline, a soft (ramp) or signed-distance gate, maps for plain
 sessions and for simple_test; scrolling by a fraction of a voxel or by a rotation (both would resample the state);
 scrolling a model with an Anchor3DHead (its boxes would have to be translated); scene batches across ranks; a model-level C handle for sessions
 (the state lives here, over the op-level ABI and the handle's sub-range calls).
@@ -220,6 +230,90 @@ def _maps_at(maps, hw, p0, strided=True):
     """The checked maps of an add (pixel_weights, depths) at the resolution of the trunk's output p0 [V,1,FH,FW,C], on its device, contiguous."""
     fhw = tuple(int(v) for v in p0.shape[-3:-1])
     return tuple(None if t is None else pick_map(t, name, hw, fhw, strided).to(p0.device).contiguous() for t, name in zip(maps, MAP_FILL))
+
+
+# ------------------------------------------------------------------ lenses and depth frames of add_views_u8: the host rules and the two small launches
+def _check_depth_frames(t, V):
+    """depth_frames of an add_views_u8 call: None, or one [V,H,W] uint16 / float32 array or tensor at the source size (host or device) -> tensor."""
+    if t is None:
+        return None
+    if isinstance(t, np.ndarray):
+        t = torch.from_numpy(np.ascontiguousarray(t))
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f'depth_frames must be None or one [V,H,W] uint16 / float32 array or tensor, got {type(t).__name__}')
+    if t.dtype not in (torch.uint16, torch.float32):
+        raise TypeError(f'depth_frames must be uint16 or float32, got {t.dtype}')
+    if t.dim() != 3 or t.shape[0] != V:
+        raise ValueError(f'depth_frames must be [V,H,W] at the source size for the {V} frames of this call, got {tuple(t.shape)}')
+    return t
+
+
+def _check_intrinsic(meta, lens):
+    """The lift projects with the meta's intrinsic, the undistorted image shows lens.new_K: the two must be one camera (an identity intrinsic --
+    a meta whose extrinsics carry the whole projection -- is not judged).  More than 1e-6 relative apart raises ValueError."""
+    K = np.asarray(meta['lidar2img']['intrinsic'], np.float64)[:3, :3]
+    if np.array_equal(K, np.eye(3)) or np.allclose(K, lens.new_K, rtol=1e-6, atol=0.0):
+        return
+    raise ValueError(f"the scene meta's intrinsic {K.tolist()} is not the lens's new_K {lens.new_K.tolist()}: the lift would project with another "
+                     'camera than the undistorted image shows (build the intrinsic from lens.new_K)')
+
+
+def _lens_maps(records, cache, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, what):
+    """What lens= / depth_frames= of an add_views_u8 call add to its checked pixel maps, before the gate and the pipeline run: -> (one lens
+    entry per frame or None, (pixel_weights, depths) at feature resolution).  records: the _SceneRecords the call touches (their metas must
+    agree with the lenses); cache: the owner's cover cache {(lens, source shape, resized shape, padded shape, device): cover [FH,FW]}.
+    On a scene that takes maps a lens makes the cover map (ops.map_prep_lens: 1 where the input pixel shows the frame, 0 on the border)
+    part of the view's confidence -- pixel_weights * cover, or the cover alone; a frame whose entry is None keeps its weights -- and
+    depth_frames go through the same geometry to feature resolution (one launch per run of frames of one lens).  A plain scene gets the
+    undistorted image and no mask."""
+    from .data import _check_lenses, _pipeline_shapes
+    V, rec = len(frames), records[0]
+    lenses = _check_lenses(lens, V)
+    dframes = _check_depth_frames(depth_frames, V)
+    takes_maps = rec._window is not None or rec._decay is not None
+    if dframes is not None:
+        if not takes_maps:
+            raise ValueError(f'this {what} was opened plain and takes no depth frames: open it with decay=1.0 (weights, nothing fades) or with window=W')
+        if rec._gate is None:
+            raise ValueError(f'this {what} was opened without depth_gate and takes no depth frames: open it with depth_gate=(behind, front)')
+        if maps[1] is not None:
+            raise ValueError('depth_frames (at the source size) and depths (at feature resolution) exclude each other')
+        if isinstance(depth_scale, bool) or not isinstance(depth_scale, (int, float, np.integer, np.floating)) or not math.isfinite(depth_scale):
+            raise ValueError(f'depth_scale must be a finite number, got {depth_scale!r}')
+    src = {(int(f.shape[0]), int(f.shape[1])) for f in frames}
+    if len(src) != 1:
+        raise ValueError(f'frames that come with a lens or with depth frames must share one source size in a call, got {sorted(src)}')
+    src_hw = src.pop()
+    if dframes is not None and tuple(dframes.shape[1:]) != src_hw:
+        raise ValueError(f'depth_frames must be at the source size {src_hw} of the frames, got {tuple(dframes.shape[1:])}')
+    distinct = [] if lenses is None else [l for l in dict.fromkeys(lenses) if l is not None]
+    for l in distinct:
+        for r in records:
+            _check_intrinsic(r.meta, l)
+    if not takes_maps:
+        return lenses, maps
+    size_hw, pad_hw = _pipeline_shapes(src_hw, img_scale, pipeline_kw.get('size_divisor', 32), pipeline_kw.get('keep_ratio', True))
+    dev = torch.device(pipeline_kw.get('device', 'cuda'))
+    pw, dp = maps
+    if distinct:
+        for l in distinct:
+            key = (l, src_hw, size_hw, pad_hw, str(dev))
+            if key not in cache:
+                cache[key] = ops.map_prep_lens(size_hw, pad_hw, src_hw, lens=l, stride=4, device=dev)[0]
+        covers = {l: cache[(l, src_hw, size_hw, pad_hw, str(dev))] for l in distinct}
+        cover = torch.stack([covers[l] if l is not None else torch.ones_like(covers[distinct[0]]) for l in lenses])
+        pw = cover if pw is None else pick_map(pw, 'pixel_weights', pad_hw, tuple(cover.shape[1:]), strided=False).to(dev) * cover
+    if dframes is not None:
+        dframes, ls = dframes.to(dev), lenses if lenses is not None else [None] * V
+        dp = torch.empty((V, (pad_hw[0] - 1) // 4 + 1, (pad_hw[1] - 1) // 4 + 1), device=dev, dtype=torch.float32)
+        a = 0
+        while a < V:                              # runs of frames of one lens: one launch each
+            b = a + 1
+            while b < V and ls[b] == ls[a]:
+                b += 1
+            ops.map_prep_lens(size_hw, pad_hw, src_hw, lens=ls[a], src=dframes[a:b], scale=float(depth_scale), stride=4, out=dp[a:b])
+            a = b
+    return lenses, (pw, dp)
 
 
 # ------------------------------------------------------------------ view coverage and the keyframe gate: the host rules
@@ -514,6 +608,7 @@ class SceneSession(_SceneRecord):
         # window=W: the rings, and the host ring of the slots' weights, None until a weight is given.  decay=lam: a weight sum beside sum / count
         self._ring = self._pring = self._wring = self._wsum = None
         self._mring = self._dring = None          # window=W: the device rings of the slots' pixel-weight / depth maps [W,FH,FW], each None until a map is given
+        self._covers = {}                         # add_views_u8(lens=): the cover maps [FH,FW] by (lens, source shape, pipeline shapes, device)
         self.last_admitted = None                 # the gate's verdict per view of the last add_views(..., min_novelty=) call; None after an ungated one
 
     # ------------------------------------------------------------------ state
@@ -530,6 +625,7 @@ class SceneSession(_SceneRecord):
     def close(self):
         self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
         self._ring = self._pring = self._wsum = self._wring = self._mring = self._dring = None
+        self._covers = {}
         self._closed = True
 
     # ------------------------------------------------------------------ adding views
@@ -743,13 +839,26 @@ class SceneSession(_SceneRecord):
         return tuple(s)
 
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None,
-                     **pipeline_kw):
+                     lens=None, depth_frames=None, depth_scale=0.001, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
         (data.prepare_images_device; pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device) and fills img_shape / ori_shape /
         pad_shape of the scene meta.  Later frames must come out at the same shapes.  weights as for add_views; pixel_weights and depths at
-        feature resolution [V,FH,FW] only (the frames are resized on the device; resizing maps with them is out of scope).  min_novelty /
+        feature resolution [V,FH,FW] only (the frames are resized on the device; confidence maps at the source size are out of scope).  min_novelty /
         fresh_below as for add_views: once the scene knows its shapes (it has had views) the gate runs before the pipeline, so a rejected
-        frame is not even resized; on the first call it runs after the pipeline, which is what tells the shapes."""
+        frame is not even resized; on the first call it runs after the pipeline, which is what tells the shapes.
+        lens: a data.Lens for every frame of the call, or one entry (a Lens or None) per frame (a rig): the frames of a real camera are
+        undistorted in the pipeline's own launch (ops.image_prep_lens_u8, one interpolation), and the scene meta's intrinsic must describe the
+        lens's new_K (ValueError when it is not the identity and differs by more than 1e-6 relative).  On a session that takes maps (decay= or
+        window=) the cover map of the lens -- 1 where an input pixel shows the frame, 0 on the black border after undistortion -- becomes
+        part of each view's confidence: pixel_weights * cover, or the cover alone.  It depends on (lens, source shape, pipeline shapes)
+        only, is computed once by ops.map_prep_lens and cached on the scene; the gate sees it too, so coverage still equals the lift's
+        mask.  A plain session takes the undistorted image and, refusing maps as before, no mask: border pixels then enter as the mean
+        colour (zeros after normalisation).
+        depth_frames: [V,H,W] uint16 or float32 at the SOURCE size, host or device (a depth camera registered to the colour frame), in
+        units of depth_scale metres (0.001: millimetres); needs depth_gate= at open and excludes depths=.  They are taken to feature
+        resolution through the same geometry (ops.map_prep_lens with the frame's lens, or with none: the nearest source pixel of each
+        feature pixel, 0 -- no measurement -- on the border).  Frames that come with a lens or with depth frames must share one source size
+        in a call.  A scene that never passes lens or depth_frames calls what it called before."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
@@ -757,6 +866,8 @@ class SceneSession(_SceneRecord):
         self._check_fits(len(frames))
         weights = self._take_weights(weights, len(frames), 'session')
         maps = self._take_maps(pixel_weights, depths, len(frames), 'session')
+        if lens is not None or depth_frames is not None:
+            lens, maps = _lens_maps([self], self._covers, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, 'session')
         gate, verdict = _check_novelty(min_novelty, fresh_below), None
         if gate[0] is not None and self._hw is not None and 'img_shape' in self.meta and 'ori_shape' in self.meta:
             verdict = admitted(self._coverage(E, maps, self._hw, self.meta, gate[1], strided=False), gate[0])
@@ -764,7 +875,9 @@ class SceneSession(_SceneRecord):
                 self.last_admitted = verdict
                 return self
             frames, E, weights, maps = _kept(verdict, frames), _kept(verdict, E), _kept(verdict, weights), tuple(_kept(verdict, t) for t in maps)
-            gate = (None, gate[1])
+            gate, lens = (None, gate[1]), _kept(verdict, lens)
+        if lens is not None:
+            pipeline_kw = dict(pipeline_kw, lens=lens)
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)       # one multi-view sample
         self._check_shapes(shapes[0], self.n_views, 'scene')
         return self._add_views(img[0], E, emit, shapes[0], weights, maps, strided=False, gate=gate, verdict=verdict)
@@ -851,6 +964,7 @@ class SceneBatch:
         self._scenes = [_SceneRecord(model, meta, window, d, forget_below, depth_gate) for meta, d in zip(metas, decays)]      # checks every meta, window, decay, gate and head_2d
         self._fading, self._forget, self._wsum, self._wring = decays[0] is not None, self._scenes[0]._forget, None, None
         self._mring = self._dring = None          # windowed: the device rings of the slots' pixel maps [N*W,FH,FW], each None until a map is given
+        self._covers = {}                         # add_views_u8(lens=): the cover maps [FH,FW] by (lens, source shape, pipeline shapes, device)
         self._model, self._window, self._N = model, self._scenes[0]._window, len(metas)
         self._sum = self._count = self._mean = self._valid = self._ring = self._pring = None
         self._hw, self._closed = None, False
@@ -959,10 +1073,12 @@ class SceneBatch:
         return self._add_views(img, extrinsics, scene, emit, {}, weights=weights, maps=(pixel_weights, depths), gate=_check_novelty(min_novelty, fresh_below))
 
     def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None,
-                     fresh_below=None, **pipeline_kw):
+                     fresh_below=None, lens=None, depth_frames=None, depth_scale=0.001, **pipeline_kw):
         """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
         ori_shape / pad_shape of every scene's meta, which later frames must reproduce.  Pixel maps at feature resolution only.  The gate
-        runs before the pipeline once the batch knows its shapes, after it on the first call."""
+        runs before the pipeline once the batch knows its shapes, after it on the first call.  lens / depth_frames / depth_scale as for
+        SceneSession.add_views_u8 (entry t belongs to frame t; the metas of the touched scenes must agree with the lenses; the cover
+        cache is the batch's)."""
         from .data import prepare_images_device
         self._check_open()
         frames = list(frames)
@@ -970,6 +1086,8 @@ class SceneBatch:
         groups = self._groups(scene, len(frames))
         weights = self._scenes[0]._take_weights(weights, len(frames), 'batch')
         maps = self._scenes[0]._take_maps(pixel_weights, depths, len(frames), 'batch')
+        if lens is not None or depth_frames is not None:
+            lens, maps = _lens_maps([self._scenes[s] for s in groups], self._covers, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, 'batch')
         gate, verdict = _check_novelty(min_novelty, fresh_below), None
         if gate[0] is not None and self._hw is not None and all('img_shape' in self._scenes[s].meta and 'ori_shape' in self._scenes[s].meta for s in groups):
             verdict = admitted(self._coverage(E, groups, maps, self._hw, {}, gate[1], strided=False), gate[0])
@@ -977,7 +1095,9 @@ class SceneBatch:
                 self.last_admitted = verdict
                 return self
             frames, E, scene, weights = _kept(verdict, frames), _kept(verdict, E), _kept(verdict, list(scene)), _kept(verdict, weights)
-            maps, groups, gate = tuple(_kept(verdict, t) for t in maps), self._groups(scene, len(frames)), (None, gate[1])
+            maps, groups, gate, lens = tuple(_kept(verdict, t) for t in maps), self._groups(scene, len(frames)), (None, gate[1]), _kept(verdict, lens)
+        if lens is not None:
+            pipeline_kw = dict(pipeline_kw, lens=lens)
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
         for r in self._scenes:
             r._check_shapes(shapes[0], any(self.n_views), 'batch')

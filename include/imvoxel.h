@@ -45,7 +45,9 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * per-sample decay and a forgetting threshold, for fading scenes; 490 = 0.4.9: ivx_volume_scroll_fwd, the in-place voxel shift of rows of the state
  * pools, for scrolling scenes; 500 = 0.5.0: ivx_backproject_mapped_fwd, the weighted lift with a per-pixel confidence map and a gated depth map
  * per view; 501 = 0.5.1: ivx_view_coverage_fwd, the integer count of the voxels a candidate view would see and of those the scene has no evidence
- * for yet, before its trunk runs) and the message of the last failing call on this thread (never NULL). */
+ * for yet, before its trunk runs; 502 = 0.5.2: ivx_image_prep_lens_u8 / ivx_map_prep_lens, the image pipeline through a lens model (undistortion
+ * in the prep launch) and the cover / depth maps of the same geometry at feature resolution) and the message of the last failing call on this
+ * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
 
@@ -455,6 +457,74 @@ int ivx_rescale_size(int32_t src_h, int32_t src_w, int32_t scale_a, int32_t scal
  * zero or not finite, n <= 0, src_image_bytes < src_h * src_row_bytes with n > 1, an extent or n above the limits. */
 int ivx_image_prep_u8(const ivx_image_prep_desc *d, const void *src, int64_t src_image_bytes,
                       int32_t n, float *out, ivx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Lens-aware device image pipeline (0.5.2) -- Undistort -> Resize -> Normalize -> Pad in the one launch that reads the raw frame
+ * (csrc/lens_prep.hip), and the feature-resolution maps of the same geometry.  ivx_image_prep_u8 assumes an ideal pinhole camera; a real
+ * one (handheld RGB-D scanners, wide-angle and fisheye heads) has radial distortion, and undistorting on the host costs a second
+ * interpolation, a host pass per frame and the uint8 path.  Here ONE geometric map G takes a pixel of the network input back to the raw
+ * frame; the image is sampled through it once, and the border mask and the depth frame at feature resolution follow from the same rule.
+ *
+ * The lens (all double, in pixels of the SOURCE frame): */
+#define IVX_LENS_BROWN 0   /* OpenCV's 5-coefficient model: coef = (k1, k2, p1, p2, k3) */
+#define IVX_LENS_FISHEYE 1 /* OpenCV's equidistant fisheye model: coef = (k1, k2, k3, k4), coef[4] unused (must be finite) */
+typedef struct ivx_lens {
+  int32_t model;                           /* IVX_LENS_BROWN | IVX_LENS_FISHEYE (the doubles that follow are 8-byte aligned) */
+  double fx, fy, cx, cy;                   /* the real camera */
+  double coef[5];                          /* the distortion coefficients */
+  double new_fx, new_fy, new_cx, new_cy;   /* the ideal pinhole camera the network input shows, at the source size: what the
+                                              caller's lidar2img intrinsic must describe */
+  double r2_max;                           /* normalised radius squared beyond which the polynomial is not trusted; +inf: no limit */
+} ivx_lens;
+/* The map G.  For the input pixel (x, y), 0 <= x < dst_w, 0 <= y < dst_h, every step in fp64, each operation rounded on its own (no
+ * fused multiply-add), in exactly this order (k1.. / p1, p2 name the entries of coef by the model's list above):
+ *   px = (x + 0.5) * (double(src_w) / double(dst_w)) - 0.5 ;  py = (y + 0.5) * (double(src_h) / double(dst_h)) - 0.5
+ *   xn = (px - new_cx) / new_fx ;  yn = (py - new_cy) / new_fy ;  r2 = xn * xn + yn * yn
+ *   BROWN:    rad = 1 + r2 * (k1 + r2 * (k2 + r2 * k3))
+ *             xd  = (xn * rad + ((2 * p1) * xn) * yn) + p2 * (r2 + (2 * xn) * xn)
+ *             yd  = (yn * rad + p1 * (r2 + (2 * yn) * yn)) + ((2 * p2) * xn) * yn
+ *   FISHEYE:  r = sqrt(r2) ;  th = atan(r) ;  t2 = th * th
+ *             thd = th * (1 + t2 * (k1 + t2 * (k2 + t2 * (k3 + t2 * k4))))
+ *             s = r > 0 ? thd / r : 1 ;  xd = xn * s ;  yd = yn * s
+ *   u = fx * xd + cx ;  v = fy * yd + cy
+ *   inside = r2 <= r2_max  and  -0.5 <= u <= src_w - 0.5  and  -0.5 <= v <= src_h - 0.5        (false when anything is NaN)
+ * Pixels of the pad region (x >= dst_w or y >= dst_h) and pixels with inside == false are BORDER.  lens == NULL (the map entry only)
+ * is the ideal camera: u = px, v = py, inside by the same range test.
+ *
+ * ivx_image_prep_lens_u8: ivx_image_prep_u8 through G, reusing ivx_image_prep_desc unchanged.  An inside pixel is the bilinear blend
+ * of the four source bytes around (u, v), taps clamped to the frame (replicate):
+ *   iu = floor(u), iv = floor(v) ;  fu = float32(u - iu), fv = float32(v - iv)       (the fractions rounded ONCE to fp32)
+ *   x0 = max(iu, 0), x1 = min(iu + 1, src_w - 1) ;  y0 = max(iv, 0), y1 = min(iv + 1, src_h - 1)
+ *   a = S[y0][x0], b = S[y0][x1], c = S[y1][x0], d = S[y1][x1] as fp32 ;  then, every operation in fp32 and rounded on its own:
+ *   top = a + fu * (b - a) ;  bot = c + fu * (d - c) ;  val = top + fv * (bot - top)
+ *   out = (val - mean[c]) / std[c]                 (one subtract, one IEEE divide, as the plain entry; NO rounding to uint8)
+ * Border and pad pixels are written as +0.0f; to_rgb as in the plain entry; one lens per call; every element of out is written.
+ * The same work split as the plain kernel: 4 consecutive x of one row per thread, three 16-byte stores (scalar stores when
+ * pad_w % 4 != 0 or out is not 16-byte aligned; same bits).  Error against the exact blend at the exact (u, v):
+ * at most 8 * 2^-24 * 255 / |std[c]| plus the divide's own rounding (tests/test_gpu_lens_prep.py counts the operations).
+ * IVX_ERR_INVALID_ARG (before any launch): everything ivx_image_prep_u8 refuses, a null lens, an unknown model, fx / fy / new_fx /
+ * new_fy zero or not finite, cx / cy / new_cx / new_cy or a coefficient not finite, r2_max that is neither > 0 nor +inf (NaN refused). */
+int ivx_image_prep_lens_u8(const ivx_image_prep_desc *d, const ivx_lens *lens, const void *src, int64_t src_image_bytes,
+                           int32_t n, float *out, ivx_stream_t stream);
+
+/* The feature-resolution maps of the same geometry.  out is [n, ceil(pad_h / stride), ceil(pad_w / stride)] fp32; feature pixel
+ * (i, j) is input pixel (y, x) = (stride * i, stride * j) -- the strided pick rule of the scenes' pixel maps.  Of `d` only src_h,
+ * src_w, dst_h, dst_w, pad_h, pad_w are read (the sizes of the image pipeline this map belongs to).
+ *   src == NULL   the COVER map: 1.0f where that input pixel is inside, 0.0f where it is border; every one of the n planes is written
+ *                 (src_dtype, src_row_bytes, src_map_bytes and scale are ignored).
+ *   src != NULL   n maps at the SOURCE size, src + i * src_map_bytes, rows src_row_bytes apart, IVX_MAP_F32 or IVX_MAP_U16 elements
+ *                 (a depth frame in millimetres): out = scale * float32(value at the nearest source pixel (floor(u + 0.5),
+ *                 floor(v + 0.5)), clamped to the frame) -- one fp32 multiply -- and 0.0f at border pixels: the lifts' "no measurement".
+ * lens == NULL is the ideal camera, which takes depth frames through the plain pipeline as well.
+ * IVX_ERR_INVALID_ARG (before any launch): null d / out, the size rules of ivx_image_prep_u8 (positive sizes, pad >= dst, extents and
+ * n within the limits), stride < 1, an invalid lens (as above), and with src: an unknown src_dtype, src_row_bytes below src_w elements
+ * or not a multiple of the element size, a misaligned src or src_map_bytes, src_map_bytes < src_h * src_row_bytes with n > 1, a scale
+ * that is not finite. */
+#define IVX_MAP_F32 0
+#define IVX_MAP_U16 1
+int ivx_map_prep_lens(const ivx_image_prep_desc *d, const ivx_lens *lens_or_null, const void *src_or_null, int32_t src_dtype,
+                      int64_t src_row_bytes, int64_t src_map_bytes, float scale, int32_t stride, int32_t n, float *out,
+                      ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused image-to-voxel unprojection -- replaces the per-sample Python loop
