@@ -24,8 +24,8 @@ from .scene import SceneSession, SceneBatch, scrolled_origin                    
 from .params import randomize_                                              # noqa: F401
 
 from .data import (load_checkpoint, prepare_image, MultiViewPipeline, KittiSetOrigin, SunRgbdSetOrigin,  # noqa: F401
-                   imresize_cv2_linear, prepare_images_device, rescale_size, Lens)
-from .ops import image_prep_u8, image_prep_lens_u8, map_prep_lens           # noqa: F401
+                   imresize_cv2_linear, prepare_images_device, rescale_size, Lens, FrameFormat, to_bgr_u8)
+from .ops import image_prep_u8, image_prep_lens_u8, map_prep_lens, image_prep_fmt_u8   # noqa: F401
 from .registry import maybe_register_into_mmdet as _reg_mmdet, register_into_mmdet  # noqa: F401
 
 _reg_mmdet()          # opt-in (IVX_REGISTER_MMDET=1); otherwise call register_into_mmdet() explicitly

@@ -165,6 +165,12 @@ class Lens(C.Structure):
                [(n, C.c_double) for n in ('new_fx', 'new_fy', 'new_cx', 'new_cy', 'r2_max')]
 
 
+class FrameFormat(C.Structure):
+    """ivx_frame_format: the pixel layout of a source frame and, for the YUV layouts, the integer matrix (ivx_image_prep_fmt_u8)."""
+    _fields_ = [('layout', C.c_int32), ('plane1_row_bytes', C.c_int32), ('plane1_offset', C.c_int64)] + \
+               [(n, C.c_int32) for n in ('y_off', 'cy', 'cub', 'cug', 'cvg', 'cvr')]
+
+
 class ConvPlanRec(C.Structure):
     """ivx_conv_plan_rec (include/imvoxel_lab.h): what the conv planner answers for a descriptor (ivx_conv_plan_query)."""
     _fields_ = [('slice_samples', C.c_int32), ('n_slices', C.c_int32)] + \
@@ -199,7 +205,7 @@ EXPORTS = ['ivx_conv_plan_query', 'ivx_conv_tile_info', 'ivx_model_plan_info', '
            'ivx_model_trace', 'ivx_model_trace_count', 'ivx_model_trace_read',
            'ivx_model_detect_workspace_bytes', 'ivx_model_max_detections', 'ivx_model_detect', 'ivx_layout_head_decode', 'ivx_layout_extrinsics',
            'ivx_indoor_tail_workspace_bytes', 'ivx_indoor_tail_get_bboxes',
-           'ivx_rescale_size', 'ivx_image_prep_u8', 'ivx_image_prep_lens_u8', 'ivx_map_prep_lens',
+           'ivx_rescale_size', 'ivx_image_prep_u8', 'ivx_image_prep_lens_u8', 'ivx_map_prep_lens', 'ivx_image_prep_fmt_u8', 'ivx_yuv_matrix',
            'ivx_kitti_image_box_overlap', 'ivx_kitti_compute_statistics', 'ivx_kitti_collect_scores', 'ivx_kitti_fused_statistics']
 
 
@@ -320,6 +326,9 @@ def lib():
     if hasattr(L, 'ivx_image_prep_lens_u8'):       # (0.5.2; an older build still loads: ops.image_prep_lens_u8 / map_prep_lens and the scenes' lens= / depth_frames= then refuse)
         L.ivx_image_prep_lens_u8.argtypes = [C.POINTER(ImagePrepDesc), C.POINTER(Lens), vp, i64, i32, vp, vp]
         L.ivx_map_prep_lens.argtypes = [C.POINTER(ImagePrepDesc), C.POINTER(Lens), vp, i32, i64, i64, f32, i32, i32, vp, vp]
+    if hasattr(L, 'ivx_image_prep_fmt_u8'):        # (0.5.3; an older build still loads: ops.image_prep_fmt_u8 and format= then refuse; data.FrameFormat computes its named matrices itself)
+        L.ivx_image_prep_fmt_u8.argtypes = [C.POINTER(ImagePrepDesc), C.POINTER(FrameFormat), C.POINTER(Lens), vp, i64, i32, vp, vp]
+        L.ivx_yuv_matrix.argtypes = [i32, i32, C.POINTER(FrameFormat)]
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

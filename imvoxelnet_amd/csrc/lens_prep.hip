@@ -14,16 +14,13 @@
 // (G is smooth), so a wavefront's taps fall into a few source rows and the cache lines are shared as in the plain kernel.
 // Map kernel: one lane per feature pixel; tiny and launch-bound.  No LDS, no atomics, plain vector stores.
 #include "ivx_common.h"
+#include "pixel_fetch.h"
 
 #include <math.h>
 
 namespace {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int kPrepMaxDim = 32768;       // every extent (include/imvoxel.h IVX_IMAGE_PREP_MAX_DIM)
-constexpr int kPrepMaxFrames = 1 << 20;
-constexpr int kPrepGridCap = 2048;       // 256 CUs x 8 workgroups; larger batches stride
 
 struct LensG {                           // what G needs: the lens (model < 0: the ideal camera) and the resize
   int model;
@@ -38,7 +35,7 @@ struct LensPrepP {
   const uint8_t *src;
   float *out;
   long long src_image_bytes, total;      // total = n * pad_h * qw work items
-  int row_bytes, dst_h, dst_w, pad_h, pad_w, qw;
+  int dst_h, dst_w, pad_h, pad_w, qw;       // (the source geometry is PixSrc's)
   int swap;                              // to_rgb: output channel c reads source channel 2 - c
   float mean[3], std[3];
 };
@@ -82,8 +79,12 @@ __device__ __forceinline__ bool lens_map(const LensG &g, const double px, const 
   return r2 <= g.r2_max && u >= -0.5 && u <= g.u_hi && v >= -0.5 && v <= g.v_hi;      // every comparison is false for NaN
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(256) void image_prep_lens_u8_kernel(const LensPrepP p) {
+// The image kernel, for every pixel layout (0.5.3): the four taps are fetched through a policy of pixel_fetch.h -- each tap is fetched (and, for
+// the YUV layouts, converted to its three BGR bytes) once -- and blended in fp32 in the header's order.  ivx_image_prep_lens_u8 launches the
+// BGR8 instantiation (same bits as the kernel it had before, tests/golden/image_prep_bgr_0_5_2.npz; 0.79 .. 0.89 of its time).
+template <int L, bool VEC>
+__global__ __launch_bounds__(256) void image_prep_fmt_lens_u8_kernel(const LensPrepP p, const PixSrc f) {
+  typedef PixFetch<L> F;
   const long long stride = (long long)gridDim.x * blockDim.x;
   const int per_img = p.pad_h * p.qw;
   const long long plane = (long long)p.pad_h * p.pad_w;
@@ -91,10 +92,14 @@ __global__ __launch_bounds__(256) void image_prep_lens_u8_kernel(const LensPrepP
     const int img = (int)(idx / per_img);
     const int rem = (int)(idx - (long long)img * per_img);
     const int y = rem / p.qw, x0 = (rem - y * p.qw) * 4;
-    float val[3][4];                      // blended values [output channel][x]
+    float val[4][3];                      // blended values [x][BGR]
     bool in[4];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) in[j] = false;
+    for (int j = 0; j < 4; ++j) {
+      in[j] = false;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) val[j][k] = 0.f;
+    }
     if (y < p.dst_h && x0 < p.dst_w) {
       const uint8_t *s = p.src + (long long)img * p.src_image_bytes;
       const double py = centre(y, p.g.scale_y);
@@ -106,15 +111,18 @@ __global__ __launch_bounds__(256) void image_prep_lens_u8_kernel(const LensPrepP
           const double fu_d = floor(u), fv_d = floor(v);
           const int iu = (int)fu_d, iv = (int)fv_d;
           const float fu = (float)(u - fu_d), fv = (float)(v - fv_d);
-          const int xa = max(iu, 0) * 3, xb = min(iu + 1, p.g.src_w - 1) * 3;
-          const uint8_t *r0 = s + (long long)max(iv, 0) * p.row_bytes, *r1 = s + (long long)min(iv + 1, p.g.src_h - 1) * p.row_bytes;
+          const int xa = max(iu, 0), xb = min(iu + 1, p.g.src_w - 1), ya = max(iv, 0), yb = min(iv + 1, p.g.src_h - 1);
+          int ta[3], tb[3], tc[3], td[3];
+          F::px(f, s, xa, ya, ta);
+          F::px(f, s, xb, ya, tb);
+          F::px(f, s, xa, yb, tc);
+          F::px(f, s, xb, yb, td);
 #pragma unroll
-          for (int c = 0; c < 3; ++c) {
-            const int k = p.swap ? 2 - c : c;
-            const float a = (float)r0[xa + k], b = (float)r0[xb + k], cc = (float)r1[xa + k], d = (float)r1[xb + k];
+          for (int k = 0; k < 3; ++k) {
+            const float a = (float)ta[k], b = (float)tb[k], cc = (float)tc[k], d = (float)td[k];
             const float top = __fadd_rn(a, __fmul_rn(fu, __fsub_rn(b, a)));
             const float bot = __fadd_rn(cc, __fmul_rn(fu, __fsub_rn(d, cc)));
-            val[c][j] = __fadd_rn(top, __fmul_rn(fv, __fsub_rn(bot, top)));
+            val[j][k] = __fadd_rn(top, __fmul_rn(fv, __fsub_rn(bot, top)));
           }
         }
       }
@@ -125,7 +133,7 @@ __global__ __launch_bounds__(256) void image_prep_lens_u8_kernel(const LensPrepP
       const float m = p.mean[c], sd = p.std[c];
       f32x4 r;
 #pragma unroll
-      for (int j = 0; j < 4; ++j) r[j] = in[j] ? __fsub_rn(val[c][j], m) / sd : 0.f;
+      for (int j = 0; j < 4; ++j) r[j] = in[j] ? __fsub_rn(p.swap ? val[j][2 - c] : val[j][c], m) / sd : 0.f;
       if (VEC) {
         *reinterpret_cast<f32x4 *>(o + c * plane) = r;
       } else {
@@ -163,18 +171,6 @@ __global__ __launch_bounds__(256) void map_prep_lens_kernel(const LensMapP p) {
 
 bool finite_nz(const double v) { return isfinite(v) && v != 0.0; }
 
-// the size rules both entries share with ivx_image_prep_u8 (what: the entry's name)
-int check_sizes(const ivx_image_prep_desc *d, const int32_t n, const char *what) {
-  IVX_REQUIRE(d->src_h > 0 && d->src_w > 0 && d->dst_h > 0 && d->dst_w > 0, "%s: sizes must be positive (src %d x %d, dst %d x %d)", what, d->src_h,
-              d->src_w, d->dst_h, d->dst_w);
-  IVX_REQUIRE(d->pad_h >= d->dst_h && d->pad_w >= d->dst_w, "%s: pad %d x %d is smaller than dst %d x %d", what, d->pad_h, d->pad_w, d->dst_h,
-              d->dst_w);
-  IVX_REQUIRE(d->src_h <= kPrepMaxDim && d->src_w <= kPrepMaxDim && d->pad_h <= kPrepMaxDim && d->pad_w <= kPrepMaxDim,
-              "%s: extents above %d are not supported (src %d x %d, pad %d x %d)", what, kPrepMaxDim, d->src_h, d->src_w, d->pad_h, d->pad_w);
-  IVX_REQUIRE(n > 0 && n <= kPrepMaxFrames, "%s: n = %d must be in 1 .. %d", what, n, kPrepMaxFrames);
-  return IVX_OK;
-}
-
 int check_lens(const ivx_lens *l, const char *what) {
   IVX_REQUIRE(l->model == IVX_LENS_BROWN || l->model == IVX_LENS_FISHEYE, "%s: unknown lens model %d (IVX_LENS_BROWN = 0, IVX_LENS_FISHEYE = 1)", what,
               l->model);
@@ -207,25 +203,15 @@ void fill_geometry(LensG &g, const ivx_image_prep_desc *d, const ivx_lens *l) {
 
 }  // namespace
 
-extern "C" int ivx_image_prep_lens_u8(const ivx_image_prep_desc *d, const ivx_lens *lens, const void *src, int64_t src_image_bytes, int32_t n,
-                                      float *out, ivx_stream_t stream) {
-  static const char *const what = "ivx_image_prep_lens_u8";
-  IVX_REQUIRE(d && lens && src && out, "ivx_image_prep_lens_u8: null argument");
-  if (int e = check_sizes(d, n, what)) return e;
-  IVX_REQUIRE((int64_t)d->src_row_bytes >= 3 * (int64_t)d->src_w, "ivx_image_prep_lens_u8: src_row_bytes %d is below 3 * src_w = %d", d->src_row_bytes,
-              3 * d->src_w);
-  for (int c = 0; c < 3; ++c)
-    IVX_REQUIRE(isfinite(d->std[c]) && d->std[c] != 0.f, "ivx_image_prep_lens_u8: std[%d] = %g must be finite and non-zero", c, (double)d->std[c]);
-  IVX_REQUIRE(n == 1 || src_image_bytes >= (int64_t)d->src_h * d->src_row_bytes,
-              "ivx_image_prep_lens_u8: src_image_bytes %lld is below src_h * src_row_bytes = %lld", (long long)src_image_bytes,
-              (long long)d->src_h * d->src_row_bytes);
+// Check the lens, fill the kernel's parameters from a checked call and launch the layout's instantiation (declared in pixel_fetch.h)
+int ivx_image_prep_lens_launch(const ivx_image_prep_desc *d, int32_t layout, const PixSrc &f, const ivx_lens *lens, const void *src,
+                               int64_t src_image_bytes, int32_t n, float *out, ivx_stream_t stream, const char *what) {
   if (int e = check_lens(lens, what)) return e;
   LensPrepP p;
   fill_geometry(p.g, d, lens);
   p.src = (const uint8_t *)src;
   p.out = out;
   p.src_image_bytes = n == 1 ? 0 : src_image_bytes;
-  p.row_bytes = d->src_row_bytes;
   p.dst_h = d->dst_h, p.dst_w = d->dst_w, p.pad_h = d->pad_h, p.pad_w = d->pad_w;
   p.qw = (d->pad_w + 3) / 4;
   p.total = (long long)n * d->pad_h * p.qw;
@@ -237,17 +223,32 @@ extern "C" int ivx_image_prep_lens_u8(const ivx_image_prep_desc *d, const ivx_le
   long long blocks = (p.total + 255) / 256;
   if (blocks > kPrepGridCap) blocks = kPrepGridCap;
   const bool vec = d->pad_w % 4 == 0 && ((uintptr_t)out & 15) == 0;
-  if (vec) hipLaunchKernelGGL(image_prep_lens_u8_kernel<true>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  else hipLaunchKernelGGL(image_prep_lens_u8_kernel<false>, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p);
-  IVX_CHECK_LAUNCH("ivx_image_prep_lens_u8");
+#define IVX_LENS_LAUNCH(L)                                                                                                              \
+  if (vec) hipLaunchKernelGGL((image_prep_fmt_lens_u8_kernel<L, true>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, f); \
+  else hipLaunchKernelGGL((image_prep_fmt_lens_u8_kernel<L, false>), dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, p, f)
+  IVX_PIX_DISPATCH(layout, IVX_LENS_LAUNCH)
+#undef IVX_LENS_LAUNCH
+  IVX_CHECK_LAUNCH(what);
   return IVX_OK;
+}
+
+extern "C" int ivx_image_prep_lens_u8(const ivx_image_prep_desc *d, const ivx_lens *lens, const void *src, int64_t src_image_bytes, int32_t n,
+                                      float *out, ivx_stream_t stream) {
+  static const char *const what = "ivx_image_prep_lens_u8";
+  IVX_REQUIRE(d && lens && src && out, "ivx_image_prep_lens_u8: null argument");
+  if (int e = prep_check_sizes(d, n, what)) return e;
+  if (int e = prep_check_rows(d, IVX_PIX_BGR8, what)) return e;
+  IVX_REQUIRE(n == 1 || src_image_bytes >= (int64_t)d->src_h * d->src_row_bytes,
+              "ivx_image_prep_lens_u8: src_image_bytes %lld is below src_h * src_row_bytes = %lld", (long long)src_image_bytes,
+              (long long)d->src_h * d->src_row_bytes);
+  return ivx_image_prep_lens_launch(d, IVX_PIX_BGR8, pix_src_bgr8(d), lens, src, src_image_bytes, n, out, stream, what);
 }
 
 extern "C" int ivx_map_prep_lens(const ivx_image_prep_desc *d, const ivx_lens *lens, const void *src, int32_t src_dtype, int64_t src_row_bytes,
                                  int64_t src_map_bytes, float scale, int32_t stride, int32_t n, float *out, ivx_stream_t stream) {
   static const char *const what = "ivx_map_prep_lens";
   IVX_REQUIRE(d && out, "ivx_map_prep_lens: null argument");
-  if (int e = check_sizes(d, n, what)) return e;
+  if (int e = prep_check_sizes(d, n, what)) return e;
   IVX_REQUIRE(stride >= 1, "ivx_map_prep_lens: stride = %d must be >= 1", stride);
   if (lens)
     if (int e = check_lens(lens, what)) return e;

@@ -218,7 +218,149 @@ def _check_lenses(lens, n):
     return lens
 
 
-def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor=32, keep_ratio=True, device='cuda', lens=None):
+def _yuv_rows():
+    """The named integer matrices of ivx_yuv_matrix (include/imvoxel.h): (y_off, cy, cub, cug, cvg, cvr) by (standard, full_range).  BT.601
+    limited range is OpenCV's table by value; the others are the exact matrix times 2^20 rounded half to even (Fraction arithmetic;
+    Python's round() on a Fraction rounds half to even)."""
+    from fractions import Fraction as Fr
+    rows = {}
+    for std, (kr, kb) in (('bt601', (Fr(299, 1000), Fr(114, 1000))), ('bt709', (Fr(2126, 10000), Fr(722, 10000)))):
+        kg = 1 - kr - kb
+        for full in (False, True):
+            cy, s, y_off = (Fr(1), Fr(1), 0) if full else (Fr(255, 219), Fr(255, 224), 16)
+            m = (cy, 2 * s * (1 - kb), -2 * s * kb * (1 - kb) / kg, -2 * s * kr * (1 - kr) / kg, 2 * s * (1 - kr))
+            rows[(std, full)] = (y_off,) + tuple(int(round(v * (1 << 20))) for v in m)
+    rows[('bt601', False)] = (16, 1220542, 2116026, -409993, -852492, 1673527)
+    return rows
+
+
+class FrameFormat:
+    """The pixel format of a source frame (include/imvoxel.h, ivx_frame_format): a small checked record.
+    layout: 'bgr' | 'rgb' (3 bytes / pixel), 'bgra' | 'rgba' (4 bytes, byte 3 ignored), 'gray' (1 byte), 'nv12' (a Y plane and an interleaved
+    half-resolution UV plane), 'yuyv' (packed 4:2:2).  yuv (YUV layouts only): 'bt601' | 'bt709' with full_range, or the six integers
+    (y_off, cy, cub, cug, cvg, cvr) of another standard, 20 fractional bits, |coefficient| <= 3 << 20 and 0 <= y_off <= 255.
+    Immutable; `key` is hashable and equal for equal formats, so frames group by it.  The frame arrays of each layout: (H,W,3), (H,W,4),
+    (H,W) or (H,W,1), (H + ceil(H/2), W) with even W (the stacked NV12 array), (H,W,2) with even W."""
+    LAYOUTS = {'bgr': 0, 'rgb': 1, 'bgra': 2, 'rgba': 3, 'gray': 4, 'nv12': 5, 'yuyv': 6}
+    COEF_MAX = 3 << 20
+    _rows = None
+
+    def __init__(self, layout, yuv='bt601', full_range=False):
+        if isinstance(layout, FrameFormat):
+            layout, yuv = layout.layout, layout.matrix
+        if not isinstance(layout, str) or layout not in self.LAYOUTS:
+            raise ValueError(f'layout must be one of {sorted(self.LAYOUTS, key=self.LAYOUTS.get)}, got {layout!r}')
+        m = None
+        if layout in ('nv12', 'yuyv'):
+            if isinstance(yuv, str):
+                if FrameFormat._rows is None:
+                    FrameFormat._rows = _yuv_rows()
+                if (yuv, bool(full_range)) not in FrameFormat._rows:
+                    raise ValueError(f"yuv must be 'bt601', 'bt709' or six integers, got {yuv!r}")
+                m = FrameFormat._rows[(yuv, bool(full_range))]
+            else:
+                m = tuple(yuv)
+                if len(m) != 6 or any(isinstance(v, bool) or not isinstance(v, (int, np.integer)) for v in m):
+                    raise ValueError(f'a custom yuv matrix is six integers (y_off, cy, cub, cug, cvg, cvr), got {yuv!r}')
+                m = tuple(int(v) for v in m)
+                if not 0 <= m[0] <= 255:
+                    raise ValueError(f'y_off must be in 0 .. 255, got {m[0]}')
+                if any(abs(v) > self.COEF_MAX for v in m[1:]):
+                    raise ValueError(f'every coefficient magnitude must be <= 3 << 20 = {self.COEF_MAX}, got {m[1:]}')
+        self._key = (layout, m)
+
+    layout = property(lambda self: self._key[0])
+    matrix = property(lambda self: self._key[1])
+    key = property(lambda self: self._key)
+
+    def __eq__(self, other):
+        return isinstance(other, FrameFormat) and self._key == other._key
+
+    def __hash__(self):
+        return hash(self._key)
+
+    def __repr__(self):
+        return f'FrameFormat{self._key!r}'
+
+    def struct(self, plane1_offset=0, plane1_row_bytes=0):
+        """The ivx_frame_format of this record (the plane geometry of an NV12 surface is the call's, not the format's)."""
+        from ._lib import FrameFormat as CFormat
+        return CFormat(self.LAYOUTS[self.layout], int(plane1_row_bytes), int(plane1_offset), *(self.matrix or (0,) * 6))
+
+    def frame_hw(self, shape):
+        """(H, W) of the converted BGR frame of a frame array of this layout; TypeError when the shape is not the layout's."""
+        shape, lay = tuple(int(v) for v in shape), self.layout
+        if lay in ('bgr', 'rgb', 'bgra', 'rgba'):
+            ok = len(shape) == 3 and shape[2] == (3 if lay in ('bgr', 'rgb') else 4)
+        elif lay == 'gray':
+            ok = len(shape) == 2 or (len(shape) == 3 and shape[2] == 1)
+        elif lay == 'yuyv':
+            ok = len(shape) == 3 and shape[2] == 2 and shape[1] % 2 == 0
+        else:
+            ok = len(shape) == 2 and shape[1] % 2 == 0 and shape[0] % 3 != 1
+        if not ok or min(shape) < 1:
+            want = {'bgr': '(H,W,3)', 'rgb': '(H,W,3)', 'bgra': '(H,W,4)', 'rgba': '(H,W,4)', 'gray': '(H,W) or (H,W,1)', 'yuyv': '(H,W,2) with even W',
+                    'nv12': '(H + ceil(H/2), W) with even W'}[lay]
+            raise TypeError(f'{lay!r} frames must be {want} uint8, got {shape}')
+        if lay == 'nv12':
+            return ((2 * shape[0]) // 3 if shape[0] % 3 == 0 else (2 * shape[0] - 1) // 3), shape[1]
+        return shape[0], shape[1]
+
+
+def to_bgr_u8(frame, fmt, src_hw=None):
+    """The BGR frame that a frame in format `fmt` IS (include/imvoxel.h, the 0.5.3 definition), in numpy on the host: (H,W,3) uint8.  The host
+    sibling of the conversion inside ops.image_prep_fmt_u8, as prepare_image is of ops.image_prep_u8.  frame: the layout's array (see
+    FrameFormat); src_hw=(H, W) names an odd width, which the arrays of 'nv12' / 'yuyv' (2 * ceil(W/2) samples per row) cannot tell.
+    Chroma is the nearest sample (replicated); YUV -> BGR is the header's integer rule, every shift a floor."""
+    if not isinstance(fmt, FrameFormat):
+        fmt = FrameFormat(fmt)
+    a = frame.cpu().numpy() if isinstance(frame, torch.Tensor) else np.asarray(frame)
+    if a.dtype != np.uint8:
+        raise TypeError(f'frames must be uint8, got {a.dtype}')
+    H, W = fmt.frame_hw(a.shape)
+    if src_hw is not None:
+        h, w = (int(v) for v in src_hw)
+        if h != H or ((w + 1) // 2 * 2 != W if fmt.layout in ('nv12', 'yuyv') else w != W):
+            raise ValueError(f'src_hw {(h, w)} does not fit a {fmt.layout!r} frame of shape {a.shape}')
+        W = w
+    lay = fmt.layout
+    if lay == 'bgr':
+        return a.copy()
+    if lay == 'rgb':
+        return a[:, :, ::-1].copy()
+    if lay == 'bgra':
+        return a[:, :, :3].copy()
+    if lay == 'rgba':
+        return a[:, :, 2::-1].copy()
+    if lay == 'gray':
+        return np.repeat(a.reshape(H, W, 1), 3, axis=2)
+    xs = np.arange(W)
+    if lay == 'nv12':
+        Y = a[:H, :W].astype(np.int64)
+        uv = a[H:].reshape(-1, a.shape[1] // 2, 2).astype(np.int64)[np.arange(H) >> 1][:, xs >> 1]
+    else:
+        Y = a.reshape(H, -1)[:, 0::2][:, :W].astype(np.int64)
+        uv = a.reshape(H, -1, 4)[:, :, 1::2].astype(np.int64)[:, xs >> 1]
+    y_off, cy, cub, cug, cvg, cvr = fmt.matrix
+    yy = np.maximum(0, Y - y_off) * cy + (1 << 19)
+    u, v = uv[..., 0] - 128, uv[..., 1] - 128
+    bgr = np.stack([(yy + cub * u) >> 20, (yy + cvg * v + cug * u) >> 20, (yy + cvr * v) >> 20], axis=2)
+    return np.clip(bgr, 0, 255).astype(np.uint8)
+
+
+def _check_formats(format, n):
+    """format of prepare_images_device -> None (packed BGR everywhere: the call as it was) or a list of n FrameFormat."""
+    if format is None:
+        return None
+    if isinstance(format, (str, FrameFormat)):
+        return [FrameFormat(format)] * n
+    format = list(format)
+    if len(format) != n:
+        raise ValueError(f'{len(format)} formats for {n} frames (one format for all, or one entry per frame)')
+    return [FrameFormat(f) for f in format]
+
+
+def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor=32, keep_ratio=True, device='cuda', lens=None, format=None):
     """prepare_image for a whole batch on the device (ops.image_prep_u8, csrc/preprocess.hip): the uint8 frames cross to the
     device as they are (a quarter of the bytes of the fp32 tensor) and ONE launch per group of same-sized frames resizes, normalises
     and pads them -- bit-identical to prepare_image per frame.
@@ -232,12 +374,16 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
     lens: None (ideal cameras: the call as it was), one Lens for every frame, or a list with one entry per frame in batch order, each a
     Lens or None (a rig).  Frames with a lens go through ops.image_prep_lens_u8 (csrc/lens_prep.hip: undistortion in the same launch, ONE
     bilinear interpolation in fp32 instead of cv2's integer resize, border pixels zero); frames are then grouped by (source shape, lens),
-    a run of adjacent frames of one group still taking one launch.  The image shows the lens's new_K scaled by the resize."""
+    a run of adjacent frames of one group still taking one launch.  The image shows the lens's new_K scaled by the resize.
+    format: None (packed BGR frames: the call as it was), one FrameFormat or layout name for every frame, or one per frame: the frames are
+    a decoder's -- 'rgb', 'bgra', 'rgba', 'gray', 'nv12', 'yuyv'; FrameFormat lists the array of each layout -- and are converted inside the
+    same launch (ops.image_prep_fmt_u8), the result being the format=None call on to_bgr_u8 of each frame, bit for bit, with or without a
+    lens.  Frames are then grouped by (source shape, format, lens), and the returned shapes are those of the converted frame."""
     from . import ops
     device = torch.device(device)
     views = None
     if isinstance(frames, (np.ndarray, torch.Tensor)):
-        if frames.ndim != 4:
+        if frames.ndim != 4 and (format is None or frames.ndim != 3):
             raise TypeError(f'a stacked batch must be [N,H,W,3] uint8, got {tuple(frames.shape)}')
         flat = list(frames)
         stacked = frames
@@ -252,6 +398,9 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
             flat = frames
     if not flat:
         raise ValueError('no frames')
+    formats = _check_formats(format, len(flat))
+    if formats is not None:
+        return _prepare_images_fmt(flat, stacked, views, formats, _check_lenses(lens, len(flat)), img_scale, img_norm_cfg, size_divisor, keep_ratio, device)
     for f in flat:
         if f.ndim != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
             raise TypeError(f'frames must be (H,W,3) uint8, got {tuple(f.shape)} {f.dtype}')
@@ -286,6 +435,45 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
     for f in flat:
         hw = (int(f.shape[0]), int(f.shape[1]))
         (nh, nw), (ph, pw) = _pipeline_shapes(hw, img_scale, size_divisor, keep_ratio) if lenses is not None else shapes[hw]
+        metas.append(dict(img_shape=(nh, nw, 3), ori_shape=(hw[0], hw[1], 3), pad_shape=(ph, pw, 3)))
+    if views is not None:
+        return out.view(len(flat) // views, views, 3, Hp, Wp), metas[views - 1::views]
+    return out, metas
+
+
+def _prepare_images_fmt(flat, stacked, views, formats, lenses, img_scale, img_norm_cfg, size_divisor, keep_ratio, device):
+    """prepare_images_device with format=: frames grouped by (array shape, format, lens), one ops.image_prep_fmt_u8 launch per run of adjacent
+    frames of a group; the frame-shape checks are the layout's (FrameFormat.frame_hw) and the returned shapes those of the converted frame."""
+    from . import ops
+    groups, hws = {}, []
+    for i, f in enumerate(flat):
+        if f.dtype not in (np.uint8, torch.uint8):
+            raise TypeError(f'frames must be uint8, got {f.dtype}')
+        hws.append(formats[i].frame_hw(f.shape))
+        groups.setdefault((tuple(int(v) for v in f.shape), formats[i], None if lenses is None else lenses[i]), []).append(i)
+    shapes = {k: _pipeline_shapes(formats[idx[0]].frame_hw(k[0]), img_scale, size_divisor, keep_ratio) for k, idx in groups.items()}
+    Hp, Wp = max(s[1][0] for s in shapes.values()), max(s[1][1] for s in shapes.values())
+    out = torch.empty((len(flat), 3, Hp, Wp), device=device, dtype=torch.float32)
+    mean, std, to_rgb = img_norm_cfg['mean'], img_norm_cfg['std'], img_norm_cfg.get('to_rgb', True)
+    for k, idx in groups.items():
+        if stacked is not None and len(groups) == 1:
+            src = torch.from_numpy(np.ascontiguousarray(stacked)) if isinstance(stacked, np.ndarray) else stacked
+        elif all(isinstance(flat[i], np.ndarray) for i in idx):
+            src = torch.from_numpy(np.stack([flat[i] for i in idx]))
+        else:
+            fs = [torch.from_numpy(flat[i]) if isinstance(flat[i], np.ndarray) else flat[i] for i in idx]
+            src = torch.stack([f.to(device) for f in fs] if any(f.is_cuda for f in fs) else fs)
+        src = src.to(device)                                     # the one host-to-device copy of the group (no-op for device tensors)
+        a = 0
+        while a < len(idx):                                      # runs of adjacent frames: one launch each
+            b = a + 1
+            while b < len(idx) and idx[b] == idx[b - 1] + 1:
+                b += 1
+            ops.image_prep_fmt_u8(src[a:b], k[1], shapes[k][0], (Hp, Wp), mean, std, to_rgb, lens=k[2], out=out[idx[a]:idx[a] + b - a])
+            a = b
+    metas = []
+    for hw in hws:
+        (nh, nw), (ph, pw) = _pipeline_shapes(hw, img_scale, size_divisor, keep_ratio)
         metas.append(dict(img_shape=(nh, nw, 3), ori_shape=(hw[0], hw[1], 3), pad_shape=(ph, pw, 3)))
     if views is not None:
         return out.view(len(flat) // views, views, 3, Hp, Wp), metas[views - 1::views]

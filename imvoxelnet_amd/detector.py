@@ -339,17 +339,22 @@ class ImVoxelNet(nn.Module):
                 results[i]['layout'] = layouts[i]
         return results
 
-    def simple_test_u8(self, frames, img_metas, img_scale, lens=None, **pipeline_kw):
+    def simple_test_u8(self, frames, img_metas, img_scale, lens=None, format=None, **pipeline_kw):
         """simple_test from uint8 camera frames: the test pipeline (Resize -> Normalize -> Pad) runs on the device
         (data.prepare_images_device: a list of N frames -- one single-view sample each --, one [N,H,W,3] batch, or B lists of V
         views) and fills img_shape / ori_shape / pad_shape into a copy of every meta; the caller supplies lidar2img (and box_type_3d)
         as for simple_test.  pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device of prepare_images_device.
         lens: a data.Lens for every frame, or one entry (a Lens or None) per frame: the frames are undistorted in the same launch
         (prepare_images_device), and the metas' lidar2img intrinsic must then describe the lens's new_K; border pixels enter as the
-        mean colour (zeros after normalisation).  None: the call as it was."""
+        mean colour (zeros after normalisation).  None: the call as it was.
+        format: the pixel format of the frames -- a data.FrameFormat or layout name ('nv12', 'yuyv', 'bgra', ...) for all, or one per
+        frame: decoder frames are converted inside the same launch, and the result is that of the converted BGR frames bit for bit.
+        None: packed BGR, the call as it was."""
         from .data import prepare_images_device
         if lens is not None:
             pipeline_kw['lens'] = lens
+        if format is not None:
+            pipeline_kw['format'] = format
         img, shapes = prepare_images_device(frames, img_scale, **pipeline_kw)
         if len(shapes) != len(img_metas):
             raise ValueError(f'{len(img_metas)} img_metas for {len(shapes)} samples')

@@ -128,6 +128,124 @@ def image_prep_lens_u8(src, lens, size_hw, pad_hw, mean, std, to_rgb=True, out=N
     return out
 
 
+_PIX_BYTES = {'bgr': 3, 'rgb': 3, 'bgra': 4, 'rgba': 4, 'gray': 1}      # bytes per pixel of the packed one-sample-per-pixel layouts
+
+
+def _fmt_entry(name='ivx_image_prep_fmt_u8'):
+    """The 0.5.3 entry `name` of the loaded library; an older build of the ABI refuses here."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise _lib.IvxError(f'{name} is not in the loaded libimvoxel_hip.so (version {L.ivx_version()} < 503): decoder pixel formats in the image '
+                            'pipeline need 0.5.3')
+    return getattr(L, name)
+
+
+def image_prep_fmt_u8(src, fmt, size_hw, pad_hw, mean, std, to_rgb=True, lens=None, out=None, src_hw=None, row_bytes=None, plane1_offset=None,
+                      plane1_row_bytes=None):
+    """image_prep_u8 / image_prep_lens_u8 on frames in a decoder's pixel format (ivx_image_prep_fmt_u8; include/imvoxel.h has the integer
+    definition): the frame IS a BGR frame through data.to_bgr_u8's rule, converted inside the fetch of the same one launch, and the result
+    equals the BGR entry on the converted frames bit for bit.  fmt: a data.FrameFormat or a layout name.  src, a device uint8 tensor:
+      'bgr' | 'rgb' [n,H,W,3], 'bgra' | 'rgba' [n,H,W,4], 'gray' [n,H,W] or [n,H,W,1], 'yuyv' [n,H,2*ceil(W/2),2] -- pixels of a row
+          dense, a row stride above the row's bytes (a decoder pitch) and any frame stride are passed through, as for image_prep_u8;
+      'nv12' [n, H + ceil(H/2), 2*ceil(W/2)]: the usual stacked array, Y rows then UV rows at one pitch;
+      any layout, a raw surface: a 1-D tensor (one frame) or 2-D [n, bytes] (bytes dense) with src_hw=(H, W), row_bytes= and for NV12
+          plane1_offset= / plane1_row_bytes=: a decoder's pitched surface as it lies, without a copy.
+    src_hw: the frame size where the array cannot tell it (an odd W of 'yuyv' / 'nv12'; required for a raw surface).  lens: a data.Lens
+    (image_prep_lens_u8's rule) or None.  Everything else as image_prep_u8."""
+    fn = _fmt_entry()
+    from .data import FrameFormat
+    if not isinstance(fmt, FrameFormat):
+        fmt = FrameFormat(fmt)
+    ls = None if lens is None else _lens_struct(lens)
+    if not isinstance(src, torch.Tensor):
+        raise TypeError('src must be a torch.Tensor')
+    if not src.is_cuda:
+        raise RuntimeError('src must be a device (HIP) tensor; the MI355X path has no CPU fallback')
+    if src.dtype != torch.uint8:
+        raise TypeError(f'src must be uint8, got {src.dtype}')
+    lay = fmt.layout
+    hw = None if src_hw is None else tuple(int(v) for v in src_hw)
+    if hw is not None and (len(hw) != 2 or min(hw) < 1):
+        raise ValueError(f'src_hw must be a positive (H, W), got {src_hw!r}')
+    p1_off = p1_row = 0
+    if row_bytes is not None:                                    # a raw surface: the geometry is the caller's
+        if hw is None:
+            raise ValueError('a raw surface (row_bytes=) needs src_hw=(H, W)')
+        if src.dim() not in (1, 2) or src.stride(-1) != 1:
+            raise TypeError(f'a raw surface must be a 1-D tensor or [n, bytes] with dense bytes, got {tuple(src.shape)} strides {tuple(src.stride())}')
+        H, W = hw
+        n, size = (1, src.shape[0]) if src.dim() == 1 else (int(src.shape[0]), int(src.shape[1]))
+        step = src.stride(0) if src.dim() == 2 else size
+        row = int(row_bytes)
+        cw, ch = (W + 1) // 2, (H + 1) // 2
+        tight = 4 * cw if lay == 'yuyv' else W if lay == 'nv12' else _PIX_BYTES[lay] * W
+        if row < tight:
+            raise ValueError(f'row_bytes {row} is below the {tight} bytes of a {lay} row of {W} pixels')
+        end = (H - 1) * row + tight
+        if lay == 'nv12':
+            if plane1_offset is None or plane1_row_bytes is None:
+                raise ValueError('a raw NV12 surface needs plane1_offset= and plane1_row_bytes=')
+            p1_off, p1_row = int(plane1_offset), int(plane1_row_bytes)
+            if p1_row < 2 * cw or p1_off < H * row:
+                raise ValueError(f'plane1_row_bytes {p1_row} / plane1_offset {p1_off} are below 2 * ceil(W / 2) = {2 * cw} / H * row_bytes = {H * row}')
+            end = p1_off + (ch - 1) * p1_row + 2 * cw
+        elif plane1_offset is not None or plane1_row_bytes is not None:
+            raise ValueError(f"plane1_offset / plane1_row_bytes belong to 'nv12', not to {lay!r}")
+        if n < 1 or size < end:
+            raise ValueError(f'the surface holds {n} x {size} bytes, a frame of this geometry ends at byte {end}')
+    else:
+        if plane1_offset is not None or plane1_row_bytes is not None:
+            raise ValueError('plane1_offset / plane1_row_bytes describe a raw surface: pass row_bytes= and src_hw= with them')
+        if lay == 'nv12':
+            if src.dim() != 3:
+                raise TypeError(f"'nv12' frames must be [n, H + ceil(H/2), W] uint8 (or a raw surface with row_bytes=), got {tuple(src.shape)}")
+            n, R, We = (int(v) for v in src.shape)
+            if We % 2 or R % 3 == 1 or R < 2:
+                raise ValueError(f"a stacked 'nv12' array has an even width and H + ceil(H/2) rows, got {R} x {We}")
+            H, W = (2 * R) // 3 if R % 3 == 0 else (2 * R - 1) // 3, We
+            if hw is not None:
+                if hw[0] != H or (hw[1] + 1) // 2 * 2 != We:
+                    raise ValueError(f'src_hw {hw} does not fit a stacked nv12 array of {R} x {We}')
+                W = hw[1]
+            row = src.stride(1)
+            if (We > 1 and src.stride(2) != 1) or row < We or (n > 1 and src.stride(0) < R * row):
+                raise ValueError(f'src rows must be dense (strides (>= rows * row, >= W, 1)), got {tuple(src.stride())}')
+            p1_off, p1_row = H * row, row
+        else:
+            if lay == 'gray' and src.dim() == 3:
+                src = src.unsqueeze(3)
+            Cb = 2 if lay == 'yuyv' else _PIX_BYTES[lay]
+            if src.dim() != 4 or src.shape[3] != Cb:
+                raise TypeError(f'{lay!r} frames must be uint8 [n,H,W,{Cb}], got {tuple(src.shape)}')
+            n, H, We, _ = (int(v) for v in src.shape)
+            W = We
+            if lay == 'yuyv':
+                if We % 2:
+                    raise ValueError(f"a 'yuyv' array holds 2 * ceil(W/2) samples per row, got {We}")
+                if hw is not None:
+                    W = hw[1]
+            if hw is not None and (hw[0] != H or (hw[1] != We if lay != 'yuyv' else (hw[1] + 1) // 2 * 2 != We)):
+                raise ValueError(f'src_hw {hw} does not fit {lay!r} frames of shape {tuple(src.shape)}')
+            row = src.stride(1) if H > 1 else Cb * We            # (the stride of an extent-1 axis is arbitrary)
+            if (Cb > 1 and src.stride(3) != 1) or (We > 1 and src.stride(2) != Cb) or row < Cb * We or (n > 1 and src.stride(0) < H * row):
+                raise ValueError(f'src rows must be dense (strides (>= H * row, >= {Cb} * W, {Cb}, 1)), got {tuple(src.stride())}')
+        if n < 1:
+            raise ValueError('src holds no frame')
+        step = src.stride(0)
+    (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
+    if out is None:
+        out = torch.empty((n, 3, ph, pw), device=src.device, dtype=torch.float32)
+    else:
+        _chk(out, 'out')
+        if tuple(out.shape) != (n, 3, ph, pw) or out.device != src.device:
+            raise ValueError(f'out must be [{n},3,{ph},{pw}] on {src.device}, got {tuple(out.shape)} on {out.device}')
+    d = _lib.ImagePrepDesc(H, W, row, nh, nw, ph, pw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
+                           (C.c_float * 3)(*[float(v) for v in std]))
+    fs = fmt.struct(plane1_offset=p1_off, plane1_row_bytes=p1_row)
+    check(fn(C.byref(d), C.byref(fs), None if ls is None else C.byref(ls), _ptr(src), step, n, _ptr(out), _stream()), 'ivx_image_prep_fmt_u8')
+    return out
+
+
 _MAP_DT = {torch.float32: (_lib.MAP_F32, 4), torch.uint16: (_lib.MAP_U16, 2)}
 
 

@@ -258,7 +258,7 @@ def _check_intrinsic(meta, lens):
                      'camera than the undistorted image shows (build the intrinsic from lens.new_K)')
 
 
-def _lens_maps(records, cache, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, what):
+def _lens_maps(records, cache, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, what, format=None):
     """What lens= / depth_frames= of an add_views_u8 call add to its checked pixel maps, before the gate and the pipeline run: -> (one lens
     entry per frame or None, (pixel_weights, depths) at feature resolution).  records: the _SceneRecords the call touches (their metas must
     agree with the lenses); cache: the owner's cover cache {(lens, source shape, resized shape, padded shape, device): cover [FH,FW]}.
@@ -266,7 +266,7 @@ def _lens_maps(records, cache, frames, maps, lens, depth_frames, depth_scale, im
     part of the view's confidence -- pixel_weights * cover, or the cover alone; a frame whose entry is None keeps its weights -- and
     depth_frames go through the same geometry to feature resolution (one launch per run of frames of one lens).  A plain scene gets the
     undistorted image and no mask."""
-    from .data import _check_lenses, _pipeline_shapes
+    from .data import _check_lenses, _check_formats, _pipeline_shapes
     V, rec = len(frames), records[0]
     lenses = _check_lenses(lens, V)
     dframes = _check_depth_frames(depth_frames, V)
@@ -280,7 +280,8 @@ def _lens_maps(records, cache, frames, maps, lens, depth_frames, depth_scale, im
             raise ValueError('depth_frames (at the source size) and depths (at feature resolution) exclude each other')
         if isinstance(depth_scale, bool) or not isinstance(depth_scale, (int, float, np.integer, np.floating)) or not math.isfinite(depth_scale):
             raise ValueError(f'depth_scale must be a finite number, got {depth_scale!r}')
-    src = {(int(f.shape[0]), int(f.shape[1])) for f in frames}
+    formats = _check_formats(format, V)                  # (the source size is that of the converted frame)
+    src = {(int(f.shape[0]), int(f.shape[1])) if formats is None else formats[i].frame_hw(f.shape) for i, f in enumerate(frames)}
     if len(src) != 1:
         raise ValueError(f'frames that come with a lens or with depth frames must share one source size in a call, got {sorted(src)}')
     src_hw = src.pop()
@@ -839,7 +840,7 @@ class SceneSession(_SceneRecord):
         return tuple(s)
 
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None,
-                     lens=None, depth_frames=None, depth_scale=0.001, **pipeline_kw):
+                     lens=None, depth_frames=None, depth_scale=0.001, format=None, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
         (data.prepare_images_device; pipeline_kw: img_norm_cfg, size_divisor, keep_ratio, device) and fills img_shape / ori_shape /
         pad_shape of the scene meta.  Later frames must come out at the same shapes.  weights as for add_views; pixel_weights and depths at
@@ -858,8 +859,11 @@ class SceneSession(_SceneRecord):
         units of depth_scale metres (0.001: millimetres); needs depth_gate= at open and excludes depths=.  They are taken to feature
         resolution through the same geometry (ops.map_prep_lens with the frame's lens, or with none: the nearest source pixel of each
         feature pixel, 0 -- no measurement -- on the border).  Frames that come with a lens or with depth frames must share one source size
-        in a call.  A scene that never passes lens or depth_frames calls what it called before."""
-        from .data import prepare_images_device
+        in a call.  A scene that never passes lens or depth_frames calls what it called before.
+        format: the pixel format of the frames (a data.FrameFormat or layout name for all, or one per frame; data.prepare_images_device):
+        decoder frames -- NV12, YUYV, BGRA ... -- are converted inside the pipeline's launch, with or without a lens, and the scene is the
+        one the converted BGR frames give, bit for bit.  depth_frames, the cover map and the gate depend on geometry only."""
+        from .data import prepare_images_device, FrameFormat
         self._check_open()
         frames = list(frames)
         E = _check_extrinsics(extrinsics, len(frames))
@@ -867,7 +871,7 @@ class SceneSession(_SceneRecord):
         weights = self._take_weights(weights, len(frames), 'session')
         maps = self._take_maps(pixel_weights, depths, len(frames), 'session')
         if lens is not None or depth_frames is not None:
-            lens, maps = _lens_maps([self], self._covers, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, 'session')
+            lens, maps = _lens_maps([self], self._covers, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, 'session', format)
         gate, verdict = _check_novelty(min_novelty, fresh_below), None
         if gate[0] is not None and self._hw is not None and 'img_shape' in self.meta and 'ori_shape' in self.meta:
             verdict = admitted(self._coverage(E, maps, self._hw, self.meta, gate[1], strided=False), gate[0])
@@ -876,8 +880,11 @@ class SceneSession(_SceneRecord):
                 return self
             frames, E, weights, maps = _kept(verdict, frames), _kept(verdict, E), _kept(verdict, weights), tuple(_kept(verdict, t) for t in maps)
             gate, lens = (None, gate[1]), _kept(verdict, lens)
+            format = format if format is None or isinstance(format, (str, FrameFormat)) else _kept(verdict, list(format))
         if lens is not None:
             pipeline_kw = dict(pipeline_kw, lens=lens)
+        if format is not None:
+            pipeline_kw = dict(pipeline_kw, format=format)
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)       # one multi-view sample
         self._check_shapes(shapes[0], self.n_views, 'scene')
         return self._add_views(img[0], E, emit, shapes[0], weights, maps, strided=False, gate=gate, verdict=verdict)
@@ -1073,13 +1080,13 @@ class SceneBatch:
         return self._add_views(img, extrinsics, scene, emit, {}, weights=weights, maps=(pixel_weights, depths), gate=_check_novelty(min_novelty, fresh_below))
 
     def add_views_u8(self, frames, extrinsics, scene, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None,
-                     fresh_below=None, lens=None, depth_frames=None, depth_scale=0.001, **pipeline_kw):
+                     fresh_below=None, lens=None, depth_frames=None, depth_scale=0.001, format=None, **pipeline_kw):
         """add_views from uint8 camera frames through data.prepare_images_device (as SceneSession.add_views_u8); fills img_shape /
         ori_shape / pad_shape of every scene's meta, which later frames must reproduce.  Pixel maps at feature resolution only.  The gate
         runs before the pipeline once the batch knows its shapes, after it on the first call.  lens / depth_frames / depth_scale as for
         SceneSession.add_views_u8 (entry t belongs to frame t; the metas of the touched scenes must agree with the lenses; the cover
-        cache is the batch's)."""
-        from .data import prepare_images_device
+        cache is the batch's); format as for SceneSession.add_views_u8."""
+        from .data import prepare_images_device, FrameFormat
         self._check_open()
         frames = list(frames)
         E = _check_extrinsics(extrinsics, len(frames))
@@ -1087,7 +1094,7 @@ class SceneBatch:
         weights = self._scenes[0]._take_weights(weights, len(frames), 'batch')
         maps = self._scenes[0]._take_maps(pixel_weights, depths, len(frames), 'batch')
         if lens is not None or depth_frames is not None:
-            lens, maps = _lens_maps([self._scenes[s] for s in groups], self._covers, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, 'batch')
+            lens, maps = _lens_maps([self._scenes[s] for s in groups], self._covers, frames, maps, lens, depth_frames, depth_scale, img_scale, pipeline_kw, 'batch', format)
         gate, verdict = _check_novelty(min_novelty, fresh_below), None
         if gate[0] is not None and self._hw is not None and all('img_shape' in self._scenes[s].meta and 'ori_shape' in self._scenes[s].meta for s in groups):
             verdict = admitted(self._coverage(E, groups, maps, self._hw, {}, gate[1], strided=False), gate[0])
@@ -1096,8 +1103,11 @@ class SceneBatch:
                 return self
             frames, E, scene, weights = _kept(verdict, frames), _kept(verdict, E), _kept(verdict, list(scene)), _kept(verdict, weights)
             maps, groups, gate, lens = tuple(_kept(verdict, t) for t in maps), self._groups(scene, len(frames)), (None, gate[1]), _kept(verdict, lens)
+            format = format if format is None or isinstance(format, (str, FrameFormat)) else _kept(verdict, list(format))
         if lens is not None:
             pipeline_kw = dict(pipeline_kw, lens=lens)
+        if format is not None:
+            pipeline_kw = dict(pipeline_kw, format=format)
         img, shapes = prepare_images_device([frames], img_scale, **pipeline_kw)
         for r in self._scenes:
             r._check_shapes(shapes[0], any(self.n_views), 'batch')

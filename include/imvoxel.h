@@ -46,7 +46,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * pools, for scrolling scenes; 500 = 0.5.0: ivx_backproject_mapped_fwd, the weighted lift with a per-pixel confidence map and a gated depth map
  * per view; 501 = 0.5.1: ivx_view_coverage_fwd, the integer count of the voxels a candidate view would see and of those the scene has no evidence
  * for yet, before its trunk runs; 502 = 0.5.2: ivx_image_prep_lens_u8 / ivx_map_prep_lens, the image pipeline through a lens model (undistortion
- * in the prep launch) and the cover / depth maps of the same geometry at feature resolution) and the message of the last failing call on this
+ * in the prep launch) and the cover / depth maps of the same geometry at feature resolution; 503 = 0.5.3: ivx_image_prep_fmt_u8 / ivx_yuv_matrix, the image pipeline on decoder pixel
+ * formats (RGB, BGRA / RGBA, gray, NV12, YUYV) converted in the fetch of the prep launch) and the message of the last failing call on this
  * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -525,6 +526,71 @@ int ivx_image_prep_lens_u8(const ivx_image_prep_desc *d, const ivx_lens *lens, c
 int ivx_map_prep_lens(const ivx_image_prep_desc *d, const ivx_lens *lens_or_null, const void *src_or_null, int32_t src_dtype,
                       int64_t src_row_bytes, int64_t src_map_bytes, float scale, int32_t stride, int32_t n, float *out,
                       ivx_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------
+ * Decoder pixel formats in the device image pipeline (0.5.3) -- the two image entries above take packed 3-byte BGR, which no decoder or
+ * camera stack on the device side produces: a hardware video decoder hands out pitched NV12 surfaces, UVC cameras YUYV, compositors BGRA
+ * or RGBA, IR sensors 8-bit gray.  Here the colour conversion happens inside the fetch of the same one launch (csrc/pixel_fetch.h): no
+ * extra pass, no 3-byte intermediate frame, and ONE stated rounding rule.
+ *
+ * The definition.  A frame in any layout IS a BGR uint8 frame through the integer rule below, and the result of the pipeline is the
+ * existing entry applied to that BGR frame: nothing about the resize, the lens map G, the blend, the normalisation or the pad changes. */
+#define IVX_PIX_BGR8  0   /* 3 bytes / pixel: the input of ivx_image_prep_u8 */
+#define IVX_PIX_RGB8  1   /* 3 bytes / pixel */
+#define IVX_PIX_BGRA8 2   /* 4 bytes / pixel, byte 3 ignored */
+#define IVX_PIX_RGBA8 3   /* 4 bytes / pixel, byte 3 ignored */
+#define IVX_PIX_GRAY8 4   /* 1 byte / pixel, B = G = R = the byte */
+#define IVX_PIX_NV12  5   /* plane 0: Y [src_h][src_w]; plane 1: interleaved (U, V) [ceil(src_h/2)][ceil(src_w/2)][2] */
+#define IVX_PIX_YUYV  6   /* packed 4:2:2, macropixel (Y0, U, Y1, V) for pixels (2k, 2k+1); ceil(src_w/2) macropixels per row */
+typedef struct ivx_frame_format {
+  int32_t layout;            /* IVX_PIX_* */
+  int32_t plane1_row_bytes;  /* NV12 only: pitch of the UV plane, >= 2 * ceil(src_w / 2) */
+  int64_t plane1_offset;     /* NV12 only: bytes from the frame's first byte to its UV plane, >= src_h * src_row_bytes */
+  int32_t y_off, cy, cub, cug, cvg, cvr;   /* YUV layouts only: the integer matrix, 20 fractional bits */
+} ivx_frame_format;
+/* Geometry.  ivx_image_prep_desc is reused unchanged; its src_row_bytes is the pitch of plane 0, with a lower bound per layout (in the
+ * order of the list above): 3 * src_w, 3 * src_w, 4 * src_w, 4 * src_w, src_w, src_w, 4 * ceil(src_w / 2).  Odd src_w and src_h are
+ * legal for every layout.  Chroma is taken at the NEAREST sample -- replicated, as cv2.cvtColor does, never interpolated: for NV12 pixel
+ * (x, y) uses the (U, V) pair [y >> 1][x >> 1] of plane 1, for YUYV the pair of macropixel x >> 1 of its own row.  Fields that a layout
+ * does not use are not read.
+ *
+ * YUV -> BGR, per pixel, in integers (every >> is a floor; clamp(v, 0, 255) = min(max(v, 0), 255)):
+ *   yy = max(0, Y - y_off) * cy ;  u = U - 128 ;  v = V - 128
+ *   R = clamp((yy + (1 << 19) + cvr * v) >> 20, 0, 255)
+ *   G = clamp((yy + (1 << 19) + cvg * v + cug * u) >> 20, 0, 255)
+ *   B = clamp((yy + (1 << 19) + cub * u) >> 20, 0, 255)
+ * Every coefficient magnitude must be <= 3 << 20 and 0 <= y_off <= 255; then no intermediate leaves int32
+ * (255 * 3 * 2^20 + 2 * 128 * 3 * 2^20 + 2^19 < 2^31).  The entry refuses anything larger.
+ *
+ * The named matrices (host only): fills y_off, cy, cub, cug, cvg, cvr of *f and touches nothing else.  IVX_YUV_BT601 with
+ * full_range == 0 is OpenCV's table VERBATIM -- y_off 16, cy 1220542, cub 2116026, cug -409993, cvg -852492, cvr 1673527, the constants
+ * of cvtColor(COLOR_YUV2BGR_NV12 / _YUY2), which are rounded decimals and not the exact matrix; that row is therefore listed by value.
+ * The other three rows (BT.601 full range, BT.709 limited, BT.709 full) are the exact real matrix times 2^20 rounded half to even, with
+ * (Kr, Kb) = (0.299, 0.114) for BT.601 or (0.2126, 0.0722) for BT.709, Kg = 1 - Kr - Kb; limited range: y_off = 16, cy = 255/219,
+ * chroma scale s = 255/224; full range: y_off = 0, cy = 1, s = 1; cvr = 2s(1-Kr), cub = 2s(1-Kb), cug = -2s*Kb(1-Kb)/Kg,
+ * cvg = -2s*Kr(1-Kr)/Kg.  A caller with another standard writes the six integers themselves.  Parity with cv2 ITSELF is UNPINNED (as
+ * for the resize): the rule is held to an independent integer restatement, not to OpenCV.
+ * IVX_ERR_INVALID_ARG: a null f, an unknown standard. */
+#define IVX_YUV_BT601 0
+#define IVX_YUV_BT709 1
+int ivx_yuv_matrix(int32_t standard, int32_t full_range, ivx_frame_format *f);
+
+/* n frames of one geometry and one format, src + i * src_image_bytes (planes included: plane 1 of frame i is at
+ * src + i * src_image_bytes + plane1_offset); out [n,3,pad_h,pad_w] fp32; caller-owned buffers, no sync.
+ *   lens_or_null == NULL   the result equals ivx_image_prep_u8 on the converted BGR frames BIT FOR BIT: the three resize modes (copy,
+ *                          exact-half area, linear) and both store paths.
+ *   lens_or_null != NULL   the result equals ivx_image_prep_lens_u8 on the converted frames BIT FOR BIT: the four taps are converted
+ *                          bytes, the fp32 blend is the stated one.
+ * d->to_rgb keeps its meaning: swap channels 0 and 2 of the BGR frame defined above (IVX_PIX_RGB8 with to_rgb = 1 therefore reads its
+ * bytes straight through).  Every tap is converted once for its three channels; the (U, V) pair of NV12 is read with one 2-byte load and
+ * the macropixel of YUYV / the pixel of BGRA, RGBA with one 4-byte load when base, offset, pitches and frame stride make every such
+ * address aligned, with byte loads otherwise (same bits): no alignment is required of the caller.
+ * IVX_ERR_INVALID_ARG (before any launch): everything the two existing entries refuse, with the row-bytes bound taken per layout; a null
+ * fmt or an unknown layout; NV12 with plane1_row_bytes or plane1_offset below their bounds (or plane1_offset above 2^46); a coefficient
+ * or y_off out of range on a YUV layout; with n > 1 a src_image_bytes that does not cover the last plane.  ivx_image_prep_u8,
+ * ivx_image_prep_lens_u8 and ivx_map_prep_lens keep their signatures, messages and bits. */
+int ivx_image_prep_fmt_u8(const ivx_image_prep_desc *d, const ivx_frame_format *fmt, const ivx_lens *lens_or_null, const void *src,
+                          int64_t src_image_bytes, int32_t n, float *out, ivx_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------
  * Fused image-to-voxel unprojection -- replaces the per-sample Python loop
