@@ -26,8 +26,7 @@ SOURCES = [
     ('volume_scroll.hip', []),
     ('view_coverage.hip', ['-ffp-contract=off']),
     ('anchor_tail.hip', ['-ffp-contract=off']),
-    ('preprocess.hip', ['-ffp-contract=off']),
-    ('lens_prep.hip', ['-ffp-contract=off']),
+    ('image_prep.hip', ['-ffp-contract=off']),
     ('dcn.hip', []),
     ('ubench.hip', []),
     ('conv_plan.cpp', []),

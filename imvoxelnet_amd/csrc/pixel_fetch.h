@@ -1,6 +1,6 @@
 // Source access of the device image pipeline for the decoder pixel formats of include/imvoxel.h (0.5.3, ivx_frame_format): ONE place that
 // knows how the bytes of a frame lie.  A frame in any layout IS a BGR uint8 frame through the header's integer rule; a fetch policy
-// PixFetch<LAYOUT> returns the three bytes of pixel (x, y) in BGR order, and the kernels of csrc/preprocess.hip and csrc/lens_prep.hip are
+// PixFetch<LAYOUT> returns the three bytes of pixel (x, y) in BGR order, and the image kernel of csrc/image_prep.hip and its two samplers are
 // templated on it, so the resize, the lens map, the blend, the normalisation and the pad are written once and see BGR bytes only.
 //
 //   px(f, frame, x, y, bgr)              one pixel (the taps of the linear resize and of the lens gather: arbitrary columns)
@@ -18,98 +18,15 @@
 #pragma once
 #include "ivx_common.h"
 
-#include <math.h>
-
 #define IVX_PIX_COUNT 7
 #define IVX_YUV_COEF_MAX (3 << 20)
 
-struct PixSrc {                          // how the source frames lie (filled and checked on the host by pix_src_fill)
+struct PixSrc {                          // how the source frames lie (filled and checked on the host by csrc/image_prep.hip pix_src_fill)
   long long plane1_offset;               // NV12: bytes from a frame's first byte to its UV plane
   int src_h, src_w, row_bytes, plane1_row_bytes;
   int y_off, cy, cub, cug, cvg, cvr;     // YUV layouts: the integer matrix, 20 fractional bits
   int wide;                              // the 2- / 4-byte loads of the layout are aligned (checked on the host)
 };
-
-constexpr int kPrepMaxDim = 32768;       // every extent (include/imvoxel.h IVX_IMAGE_PREP_MAX_DIM)
-constexpr int kPrepMaxFrames = 1 << 20;
-constexpr int kPrepGridCap = 2048;       // 256 CUs x 8 workgroups; larger batches stride
-
-// The checks of an ivx_image_prep_desc that every entry of csrc/preprocess.hip and csrc/lens_prep.hip makes, with one text (what: the entry's
-// name): the size rules (the map entry stops here) ...
-static inline int prep_check_sizes(const ivx_image_prep_desc *d, const int32_t n, const char *what) {
-  IVX_REQUIRE(d->src_h > 0 && d->src_w > 0 && d->dst_h > 0 && d->dst_w > 0, "%s: sizes must be positive (src %d x %d, dst %d x %d)", what, d->src_h,
-              d->src_w, d->dst_h, d->dst_w);
-  IVX_REQUIRE(d->pad_h >= d->dst_h && d->pad_w >= d->dst_w, "%s: pad %d x %d is smaller than dst %d x %d", what, d->pad_h, d->pad_w, d->dst_h,
-              d->dst_w);
-  IVX_REQUIRE(d->src_h <= kPrepMaxDim && d->src_w <= kPrepMaxDim && d->pad_h <= kPrepMaxDim && d->pad_w <= kPrepMaxDim,
-              "%s: extents above %d are not supported (src %d x %d, pad %d x %d)", what, kPrepMaxDim, d->src_h, d->src_w, d->pad_h, d->pad_w);
-  IVX_REQUIRE(n > 0 && n <= kPrepMaxFrames, "%s: n = %d must be in 1 .. %d", what, n, kPrepMaxFrames);
-  return IVX_OK;
-}
-// ... and, for the image entries, the pitch of plane 0 against the layout's bound and the normalisation (sizes checked before)
-static inline int prep_check_rows(const ivx_image_prep_desc *d, const int layout, const char *what) {
-  const int64_t w = d->src_w, cw = (w + 1) / 2;
-  static const char *const rule[IVX_PIX_COUNT] = {"3 * src_w", "3 * src_w", "4 * src_w", "4 * src_w", "src_w", "src_w", "4 * ceil(src_w / 2)"};
-  const int64_t need[IVX_PIX_COUNT] = {3 * w, 3 * w, 4 * w, 4 * w, w, w, 4 * cw};
-  IVX_REQUIRE((int64_t)d->src_row_bytes >= need[layout], "%s: src_row_bytes %d is below %s = %lld", what, d->src_row_bytes, rule[layout],
-              (long long)need[layout]);
-  for (int c = 0; c < 3; ++c) IVX_REQUIRE(isfinite(d->std[c]) && d->std[c] != 0.f, "%s: std[%d] = %g must be finite and non-zero", what, c, (double)d->std[c]);
-  return IVX_OK;
-}
-
-// packed BGR as the entries before 0.5.3 take it: no second plane, no matrix, byte loads
-static inline PixSrc pix_src_bgr8(const ivx_image_prep_desc *d) {
-  PixSrc s = {};
-  s.src_h = d->src_h, s.src_w = d->src_w, s.row_bytes = d->src_row_bytes;
-  return s;
-}
-
-// The two launchers, each in the file of its kernel: fill the kernel's parameters from the CHECKED d / f / n, dispatch on the layout, launch.
-// what: the calling entry's name (the lens launcher checks the lens under it first).
-int ivx_image_prep_launch(const ivx_image_prep_desc *d, int32_t layout, const PixSrc &f, const void *src, int64_t src_image_bytes, int32_t n, float *out,
-                          ivx_stream_t stream, const char *what);
-int ivx_image_prep_lens_launch(const ivx_image_prep_desc *d, int32_t layout, const PixSrc &f, const ivx_lens *lens, const void *src,
-                               int64_t src_image_bytes, int32_t n, float *out, ivx_stream_t stream, const char *what);
-
-// the fmt entry's checks of a frame format (layout and row pitch checked before) and of the source geometry that depends on it; fills `s`
-static inline int pix_src_fill(PixSrc &s, const ivx_image_prep_desc *d, const ivx_frame_format *f, const void *src, const int64_t src_image_bytes,
-                               const int32_t n, const char *what) {
-  const int64_t w = d->src_w, cw = (w + 1) / 2, ch = ((int64_t)d->src_h + 1) / 2;
-  int64_t last = (int64_t)d->src_h * d->src_row_bytes;         // one past the last byte of the last plane
-  s.plane1_offset = 0;
-  s.plane1_row_bytes = 0;
-  if (f->layout == IVX_PIX_NV12) {
-    IVX_REQUIRE((int64_t)f->plane1_row_bytes >= 2 * cw, "%s: plane1_row_bytes %d is below 2 * ceil(src_w / 2) = %lld", what, f->plane1_row_bytes,
-                (long long)(2 * cw));
-    IVX_REQUIRE(f->plane1_offset >= last, "%s: plane1_offset %lld is below src_h * src_row_bytes = %lld", what, (long long)f->plane1_offset,
-                (long long)last);
-    IVX_REQUIRE(f->plane1_offset <= ((int64_t)1 << 46), "%s: plane1_offset %lld is above 2^46", what, (long long)f->plane1_offset);
-    s.plane1_offset = f->plane1_offset;
-    s.plane1_row_bytes = f->plane1_row_bytes;
-    last = f->plane1_offset + ch * f->plane1_row_bytes;
-  }
-  const bool yuv = f->layout == IVX_PIX_NV12 || f->layout == IVX_PIX_YUYV;
-  if (yuv) {
-    IVX_REQUIRE(f->y_off >= 0 && f->y_off <= 255, "%s: y_off = %d must be in 0 .. 255", what, f->y_off);
-    const int32_t c[5] = {f->cy, f->cub, f->cug, f->cvg, f->cvr};
-    static const char *const cn[5] = {"cy", "cub", "cug", "cvg", "cvr"};
-    for (int i = 0; i < 5; ++i)
-      IVX_REQUIRE(c[i] >= -IVX_YUV_COEF_MAX && c[i] <= IVX_YUV_COEF_MAX, "%s: coefficient %s = %d is outside +-(3 << 20) = +-%d", what, cn[i], c[i],
-                  IVX_YUV_COEF_MAX);
-  }
-  IVX_REQUIRE(n == 1 || src_image_bytes >= last, "%s: src_image_bytes %lld does not cover the last plane, which ends at byte %lld", what,
-              (long long)src_image_bytes, (long long)last);
-  s.src_h = d->src_h, s.src_w = d->src_w, s.row_bytes = d->src_row_bytes;
-  s.y_off = yuv ? f->y_off : 0;
-  s.cy = yuv ? f->cy : 0, s.cub = yuv ? f->cub : 0, s.cug = yuv ? f->cug : 0, s.cvg = yuv ? f->cvg : 0, s.cvr = yuv ? f->cvr : 0;
-  const uintptr_t base = (uintptr_t)src;
-  const int64_t step = n == 1 ? 0 : src_image_bytes;
-  if (f->layout == IVX_PIX_NV12) s.wide = ((base + (uintptr_t)f->plane1_offset) % 2 == 0) && f->plane1_row_bytes % 2 == 0 && step % 2 == 0;
-  else if (f->layout == IVX_PIX_YUYV || f->layout == IVX_PIX_BGRA8 || f->layout == IVX_PIX_RGBA8)
-    s.wide = base % 4 == 0 && d->src_row_bytes % 4 == 0 && step % 4 == 0;
-  else s.wide = 0;
-  return IVX_OK;
-}
 
 #if defined(__HIPCC__)
 __device__ __forceinline__ int pix_clamp(const int v) { return min(max(v, 0), 255); }
@@ -238,7 +155,7 @@ struct PixFetch<IVX_PIX_YUYV> {
   }
 };
 
-// LAUNCH(L) for the checked layout: both files dispatch the seven layouts the same way
+// LAUNCH(L) for the checked layout
 #define IVX_PIX_DISPATCH(layout, LAUNCH)                  \
   switch (layout) {                                       \
     case IVX_PIX_BGR8: LAUNCH(IVX_PIX_BGR8); break;       \

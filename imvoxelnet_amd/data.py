@@ -361,7 +361,7 @@ def _check_formats(format, n):
 
 
 def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_divisor=32, keep_ratio=True, device='cuda', lens=None, format=None):
-    """prepare_image for a whole batch on the device (ops.image_prep_u8, csrc/preprocess.hip): the uint8 frames cross to the
+    """prepare_image for a whole batch on the device (ops.image_prep_u8, csrc/image_prep.hip): the uint8 frames cross to the
     device as they are (a quarter of the bytes of the fp32 tensor) and ONE launch per group of same-sized frames resizes, normalises
     and pads them -- bit-identical to prepare_image per frame.
     frames: a list of (H,W,3) uint8 BGR arrays / tensors; one [N,H,W,3] uint8 array or tensor (host or device); or a list of B
@@ -372,7 +372,7 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
     Returns (img [N,3,Hp,Wp] or [B,V,3,Hp,Wp] fp32 on `device`, list of per-sample dicts img_shape / ori_shape / pad_shape equal to
     prepare_image's; for a multi-view sample the dict of its LAST view, as MultiViewPipeline).
     lens: None (ideal cameras: the call as it was), one Lens for every frame, or a list with one entry per frame in batch order, each a
-    Lens or None (a rig).  Frames with a lens go through ops.image_prep_lens_u8 (csrc/lens_prep.hip: undistortion in the same launch, ONE
+    Lens or None (a rig).  Frames with a lens go through ops.image_prep_lens_u8 (the lens sampler of csrc/image_prep.hip: undistortion in the same launch, ONE
     bilinear interpolation in fp32 instead of cv2's integer resize, border pixels zero); frames are then grouped by (source shape, lens),
     a run of adjacent frames of one group still taking one launch.  The image shows the lens's new_K scaled by the resize.
     format: None (packed BGR frames: the call as it was), one FrameFormat or layout name for every frame, or one per frame: the frames are
@@ -400,20 +400,28 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
         raise ValueError('no frames')
     formats = _check_formats(format, len(flat))
     if formats is not None:
-        return _prepare_images_fmt(flat, stacked, views, formats, _check_lenses(lens, len(flat)), img_scale, img_norm_cfg, size_divisor, keep_ratio, device)
-    for f in flat:
-        if f.ndim != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
-            raise TypeError(f'frames must be (H,W,3) uint8, got {tuple(f.shape)} {f.dtype}')
-    lenses = _check_lenses(lens, len(flat))
-    groups = {}                                                  # source (h, w) [, lens] -> indices, in batch order
+        lenses = _check_lenses(lens, len(flat))
+    groups, hws = {}, []                                         # (array shape, format or None, lens or None) -> indices, in batch order
     for i, f in enumerate(flat):
-        groups.setdefault((int(f.shape[0]), int(f.shape[1])) + (() if lenses is None else (lenses[i],)), []).append(i)
-    shapes = {hw: _pipeline_shapes(hw[:2], img_scale, size_divisor, keep_ratio) for hw in groups}
+        if formats is None:
+            if f.ndim != 3 or f.shape[2] != 3 or f.dtype not in (np.uint8, torch.uint8):
+                raise TypeError(f'frames must be (H,W,3) uint8, got {tuple(f.shape)} {f.dtype}')
+            hws.append((int(f.shape[0]), int(f.shape[1])))
+        else:                                                    # the frame-shape checks are the layout's
+            if f.dtype not in (np.uint8, torch.uint8):
+                raise TypeError(f'frames must be uint8, got {f.dtype}')
+            hws.append(formats[i].frame_hw(f.shape))
+    if formats is None:
+        lenses = _check_lenses(lens, len(flat))
+    for i, f in enumerate(flat):
+        key = (tuple(int(v) for v in f.shape), None if formats is None else formats[i], None if lenses is None else lenses[i])
+        groups.setdefault(key, []).append(i)
+    shapes = {k: _pipeline_shapes(hws[idx[0]], img_scale, size_divisor, keep_ratio) for k, idx in groups.items()}
     Hp, Wp = max(s[1][0] for s in shapes.values()), max(s[1][1] for s in shapes.values())
     out = torch.empty((len(flat), 3, Hp, Wp), device=device, dtype=torch.float32)
     mean, std, to_rgb = img_norm_cfg['mean'], img_norm_cfg['std'], img_norm_cfg.get('to_rgb', True)
-    for hw, idx in groups.items():
-        if stacked is not None and len(groups) == 1:             # one group (by construction without lenses)
+    for k, idx in groups.items():
+        if stacked is not None and len(groups) == 1:             # one group: the batch as it is
             src = torch.from_numpy(np.ascontiguousarray(stacked)) if isinstance(stacked, np.ndarray) else stacked
         elif all(isinstance(flat[i], np.ndarray) for i in idx):
             src = torch.from_numpy(np.stack([flat[i] for i in idx]))
@@ -426,50 +434,13 @@ def prepare_images_device(frames, img_scale, img_norm_cfg=IMG_NORM_CFG, size_div
             b = a + 1
             while b < len(idx) and idx[b] == idx[b - 1] + 1:
                 b += 1
-            if len(hw) == 2 or hw[2] is None:
-                ops.image_prep_u8(src[a:b], shapes[hw][0], (Hp, Wp), mean, std, to_rgb, out=out[idx[a]:idx[a] + b - a])
+            o = out[idx[a]:idx[a] + b - a]
+            if k[1] is not None:
+                ops.image_prep_fmt_u8(src[a:b], k[1], shapes[k][0], (Hp, Wp), mean, std, to_rgb, lens=k[2], out=o)
+            elif k[2] is not None:
+                ops.image_prep_lens_u8(src[a:b], k[2], shapes[k][0], (Hp, Wp), mean, std, to_rgb, out=o)
             else:
-                ops.image_prep_lens_u8(src[a:b], hw[2], shapes[hw][0], (Hp, Wp), mean, std, to_rgb, out=out[idx[a]:idx[a] + b - a])
-            a = b
-    metas = []
-    for f in flat:
-        hw = (int(f.shape[0]), int(f.shape[1]))
-        (nh, nw), (ph, pw) = _pipeline_shapes(hw, img_scale, size_divisor, keep_ratio) if lenses is not None else shapes[hw]
-        metas.append(dict(img_shape=(nh, nw, 3), ori_shape=(hw[0], hw[1], 3), pad_shape=(ph, pw, 3)))
-    if views is not None:
-        return out.view(len(flat) // views, views, 3, Hp, Wp), metas[views - 1::views]
-    return out, metas
-
-
-def _prepare_images_fmt(flat, stacked, views, formats, lenses, img_scale, img_norm_cfg, size_divisor, keep_ratio, device):
-    """prepare_images_device with format=: frames grouped by (array shape, format, lens), one ops.image_prep_fmt_u8 launch per run of adjacent
-    frames of a group; the frame-shape checks are the layout's (FrameFormat.frame_hw) and the returned shapes those of the converted frame."""
-    from . import ops
-    groups, hws = {}, []
-    for i, f in enumerate(flat):
-        if f.dtype not in (np.uint8, torch.uint8):
-            raise TypeError(f'frames must be uint8, got {f.dtype}')
-        hws.append(formats[i].frame_hw(f.shape))
-        groups.setdefault((tuple(int(v) for v in f.shape), formats[i], None if lenses is None else lenses[i]), []).append(i)
-    shapes = {k: _pipeline_shapes(formats[idx[0]].frame_hw(k[0]), img_scale, size_divisor, keep_ratio) for k, idx in groups.items()}
-    Hp, Wp = max(s[1][0] for s in shapes.values()), max(s[1][1] for s in shapes.values())
-    out = torch.empty((len(flat), 3, Hp, Wp), device=device, dtype=torch.float32)
-    mean, std, to_rgb = img_norm_cfg['mean'], img_norm_cfg['std'], img_norm_cfg.get('to_rgb', True)
-    for k, idx in groups.items():
-        if stacked is not None and len(groups) == 1:
-            src = torch.from_numpy(np.ascontiguousarray(stacked)) if isinstance(stacked, np.ndarray) else stacked
-        elif all(isinstance(flat[i], np.ndarray) for i in idx):
-            src = torch.from_numpy(np.stack([flat[i] for i in idx]))
-        else:
-            fs = [torch.from_numpy(flat[i]) if isinstance(flat[i], np.ndarray) else flat[i] for i in idx]
-            src = torch.stack([f.to(device) for f in fs] if any(f.is_cuda for f in fs) else fs)
-        src = src.to(device)                                     # the one host-to-device copy of the group (no-op for device tensors)
-        a = 0
-        while a < len(idx):                                      # runs of adjacent frames: one launch each
-            b = a + 1
-            while b < len(idx) and idx[b] == idx[b - 1] + 1:
-                b += 1
-            ops.image_prep_fmt_u8(src[a:b], k[1], shapes[k][0], (Hp, Wp), mean, std, to_rgb, lens=k[2], out=out[idx[a]:idx[a] + b - a])
+                ops.image_prep_u8(src[a:b], shapes[k][0], (Hp, Wp), mean, std, to_rgb, out=o)
             a = b
     metas = []
     for hw in hws:

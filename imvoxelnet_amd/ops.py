@@ -51,11 +51,20 @@ def image_s2d_bf16(img):
     return out
 
 
-def image_prep_u8(src, size_hw, pad_hw, mean, std, to_rgb=True, out=None):
-    """uint8 frames [n,H,W,3] (HWC, BGR as a decoder leaves them) -> Resize to size_hw -> Normalize -> zero Pad to pad_hw:
-    [n,3,pad_h,pad_w] fp32 in one launch (ivx_image_prep_u8), bit-identical to data.prepare_image per frame.  The pixels of a row
-    must be dense (strides (.., 3, 1)); a row stride above 3 * W (a decoder pitch) and any frame stride are passed through.
-    mean / std in output-channel order; out: a contiguous fp32 [n,3,pad_h,pad_w] view to write into (a slice of a batch tensor)."""
+def _entry(name, version, what):
+    """The entry `name` of the loaded library, which has it since `version`; an older build of the ABI refuses here."""
+    L = _lib.lib()
+    if not hasattr(L, name):
+        raise _lib.IvxError(f'{name} is not in the loaded libimvoxel_hip.so (version {L.ivx_version()} < {version}): {what}')
+    return getattr(L, name)
+
+
+_LENS_ABI = (502, 'the lens-aware image pipeline needs 0.5.2')
+_FMT_ABI = (503, 'decoder pixel formats in the image pipeline need 0.5.3')
+
+
+def _bgr_frames(src):
+    """The packed-BGR tensor rule of image_prep_u8 / image_prep_lens_u8 -> (n, H, W, row bytes)."""
     if not isinstance(src, torch.Tensor):
         raise TypeError('src must be a torch.Tensor')
     if not src.is_cuda:
@@ -68,25 +77,37 @@ def image_prep_u8(src, size_hw, pad_hw, mean, std, to_rgb=True, out=None):
     row = src.stride(1) if H > 1 else 3 * W                  # (the stride of an extent-1 axis is arbitrary)
     if src.stride(3) != 1 or (W > 1 and src.stride(2) != 3) or row < 3 * W or (n > 1 and src.stride(0) < H * row):
         raise ValueError(f'src rows must be dense HWC (strides (>= H * row, >= 3 * W, 3, 1)), got {tuple(src.stride())}')
-    (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
+    return n, H, W, row
+
+
+def _prep_out(out, shape, device, where=True):
+    """The `out` argument of the image ops: a new fp32 tensor of `shape` on `device`, or the caller's, checked (where: the message names the
+    device and the check asks for it)."""
     if out is None:
-        out = torch.empty((n, 3, ph, pw), device=src.device, dtype=torch.float32)
-    else:
-        _chk(out, 'out')
-        if tuple(out.shape) != (n, 3, ph, pw) or out.device != src.device:
-            raise ValueError(f'out must be [{n},3,{ph},{pw}] on {src.device}, got {tuple(out.shape)} on {out.device}')
-    d = _lib.ImagePrepDesc(H, W, row, nh, nw, ph, pw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
-                           (C.c_float * 3)(*[float(v) for v in std]))
-    check(_lib.lib().ivx_image_prep_u8(C.byref(d), _ptr(src), src.stride(0), n, _ptr(out), _stream()), 'ivx_image_prep_u8')
+        return torch.empty(shape, device=device, dtype=torch.float32)
+    _chk(out, 'out')
+    if tuple(out.shape) != tuple(shape) or (where and out.device != device):
+        want = f'[{",".join(str(v) for v in shape)}]' if len(shape) == 4 else f'{list(shape)}'
+        raise ValueError(f'out must be {want}' + (f' on {device}' if where else '') + f', got {tuple(out.shape)} on {out.device}')
     return out
 
 
-def _lens_entry(name):
-    """The 0.5.2 entry `name` of the loaded library; an older build of the ABI refuses here."""
-    L = _lib.lib()
-    if not hasattr(L, name):
-        raise _lib.IvxError(f'{name} is not in the loaded libimvoxel_hip.so (version {L.ivx_version()} < 502): the lens-aware image pipeline needs 0.5.2')
-    return getattr(L, name)
+def _prep_desc(H, W, row, size_hw, pad_hw, to_rgb=False, mean=(0, 0, 0), std=(1, 1, 1)):
+    return _lib.ImagePrepDesc(H, W, row, *size_hw, *pad_hw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
+                              (C.c_float * 3)(*[float(v) for v in std]))
+
+
+def image_prep_u8(src, size_hw, pad_hw, mean, std, to_rgb=True, out=None):
+    """uint8 frames [n,H,W,3] (HWC, BGR as a decoder leaves them) -> Resize to size_hw -> Normalize -> zero Pad to pad_hw:
+    [n,3,pad_h,pad_w] fp32 in one launch (ivx_image_prep_u8), bit-identical to data.prepare_image per frame.  The pixels of a row
+    must be dense (strides (.., 3, 1)); a row stride above 3 * W (a decoder pitch) and any frame stride are passed through.
+    mean / std in output-channel order; out: a contiguous fp32 [n,3,pad_h,pad_w] view to write into (a slice of a batch tensor)."""
+    n, H, W, row = _bgr_frames(src)
+    (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
+    out = _prep_out(out, (n, 3, ph, pw), src.device)
+    d = _prep_desc(H, W, row, (nh, nw), (ph, pw), to_rgb, mean, std)
+    check(_lib.lib().ivx_image_prep_u8(C.byref(d), _ptr(src), src.stride(0), n, _ptr(out), _stream()), 'ivx_image_prep_u8')
+    return out
 
 
 def _lens_struct(lens, name='lens'):
@@ -101,43 +122,17 @@ def image_prep_lens_u8(src, lens, size_hw, pad_hw, mean, std, to_rgb=True, out=N
     (ivx_image_prep_lens_u8; include/imvoxel.h has the definition of the map G and of the fp32 bilinear blend).  lens: a data.Lens, one for
     all n frames; the output shows the ideal camera lens.new_K (at the source size), and pixels that G sends outside the frame or beyond
     r2_max are border: +0.0f, like the pad.  Everything else as image_prep_u8."""
-    fn = _lens_entry('ivx_image_prep_lens_u8')
+    fn = _entry('ivx_image_prep_lens_u8', *_LENS_ABI)
     ls = _lens_struct(lens)
-    if not isinstance(src, torch.Tensor):
-        raise TypeError('src must be a torch.Tensor')
-    if not src.is_cuda:
-        raise RuntimeError('src must be a device (HIP) tensor; the MI355X path has no CPU fallback')
-    if src.dtype != torch.uint8 or src.dim() != 4 or src.shape[3] != 3:
-        raise TypeError(f'src must be uint8 [n,H,W,3], got {src.dtype} {tuple(src.shape)}')
-    n, H, W, _ = src.shape
-    if n < 1:
-        raise ValueError('src holds no frame')
-    row = src.stride(1) if H > 1 else 3 * W                  # (the stride of an extent-1 axis is arbitrary)
-    if src.stride(3) != 1 or (W > 1 and src.stride(2) != 3) or row < 3 * W or (n > 1 and src.stride(0) < H * row):
-        raise ValueError(f'src rows must be dense HWC (strides (>= H * row, >= 3 * W, 3, 1)), got {tuple(src.stride())}')
+    n, H, W, row = _bgr_frames(src)
     (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
-    if out is None:
-        out = torch.empty((n, 3, ph, pw), device=src.device, dtype=torch.float32)
-    else:
-        _chk(out, 'out')
-        if tuple(out.shape) != (n, 3, ph, pw) or out.device != src.device:
-            raise ValueError(f'out must be [{n},3,{ph},{pw}] on {src.device}, got {tuple(out.shape)} on {out.device}')
-    d = _lib.ImagePrepDesc(H, W, row, nh, nw, ph, pw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
-                           (C.c_float * 3)(*[float(v) for v in std]))
+    out = _prep_out(out, (n, 3, ph, pw), src.device)
+    d = _prep_desc(H, W, row, (nh, nw), (ph, pw), to_rgb, mean, std)
     check(fn(C.byref(d), C.byref(ls), _ptr(src), src.stride(0), n, _ptr(out), _stream()), 'ivx_image_prep_lens_u8')
     return out
 
 
 _PIX_BYTES = {'bgr': 3, 'rgb': 3, 'bgra': 4, 'rgba': 4, 'gray': 1}      # bytes per pixel of the packed one-sample-per-pixel layouts
-
-
-def _fmt_entry(name='ivx_image_prep_fmt_u8'):
-    """The 0.5.3 entry `name` of the loaded library; an older build of the ABI refuses here."""
-    L = _lib.lib()
-    if not hasattr(L, name):
-        raise _lib.IvxError(f'{name} is not in the loaded libimvoxel_hip.so (version {L.ivx_version()} < 503): decoder pixel formats in the image '
-                            'pipeline need 0.5.3')
-    return getattr(L, name)
 
 
 def image_prep_fmt_u8(src, fmt, size_hw, pad_hw, mean, std, to_rgb=True, lens=None, out=None, src_hw=None, row_bytes=None, plane1_offset=None,
@@ -152,7 +147,7 @@ def image_prep_fmt_u8(src, fmt, size_hw, pad_hw, mean, std, to_rgb=True, lens=No
           plane1_offset= / plane1_row_bytes=: a decoder's pitched surface as it lies, without a copy.
     src_hw: the frame size where the array cannot tell it (an odd W of 'yuyv' / 'nv12'; required for a raw surface).  lens: a data.Lens
     (image_prep_lens_u8's rule) or None.  Everything else as image_prep_u8."""
-    fn = _fmt_entry()
+    fn = _entry('ivx_image_prep_fmt_u8', *_FMT_ABI)
     from .data import FrameFormat
     if not isinstance(fmt, FrameFormat):
         fmt = FrameFormat(fmt)
@@ -233,14 +228,8 @@ def image_prep_fmt_u8(src, fmt, size_hw, pad_hw, mean, std, to_rgb=True, lens=No
             raise ValueError('src holds no frame')
         step = src.stride(0)
     (nh, nw), (ph, pw) = (int(v) for v in size_hw), (int(v) for v in pad_hw)
-    if out is None:
-        out = torch.empty((n, 3, ph, pw), device=src.device, dtype=torch.float32)
-    else:
-        _chk(out, 'out')
-        if tuple(out.shape) != (n, 3, ph, pw) or out.device != src.device:
-            raise ValueError(f'out must be [{n},3,{ph},{pw}] on {src.device}, got {tuple(out.shape)} on {out.device}')
-    d = _lib.ImagePrepDesc(H, W, row, nh, nw, ph, pw, int(bool(to_rgb)), (C.c_float * 3)(*[float(v) for v in mean]),
-                           (C.c_float * 3)(*[float(v) for v in std]))
+    out = _prep_out(out, (n, 3, ph, pw), src.device)
+    d = _prep_desc(H, W, row, (nh, nw), (ph, pw), to_rgb, mean, std)
     fs = fmt.struct(plane1_offset=p1_off, plane1_row_bytes=p1_row)
     check(fn(C.byref(d), C.byref(fs), None if ls is None else C.byref(ls), _ptr(src), step, n, _ptr(out), _stream()), 'ivx_image_prep_fmt_u8')
     return out
@@ -256,7 +245,7 @@ def map_prep_lens(size_hw, pad_hw, src_hw, lens=None, src=None, scale=1.0, strid
     copies; on `device` (None: the current HIP device).  src: device maps [n,H,W] at the source size src_hw, float32 or uint16 (a depth
     frame), rows dense: scale * the value at the nearest source pixel, 0 at border pixels (the lifts' "no measurement").  lens=None is the
     ideal camera, which takes depth frames through the plain pipeline.  out: a contiguous fp32 tensor of the result's shape to write into."""
-    fn = _lens_entry('ivx_map_prep_lens')
+    fn = _entry('ivx_map_prep_lens', *_LENS_ABI)
     ls = None if lens is None else _lens_struct(lens)
     (nh, nw), (ph, pw), (H, W) = (int(v) for v in size_hw), (int(v) for v in pad_hw), (int(v) for v in src_hw)
     if isinstance(stride, bool) or not isinstance(stride, int) or stride < 1:
@@ -283,13 +272,10 @@ def map_prep_lens(size_hw, pad_hw, src_hw, lens=None, src=None, scale=1.0, strid
     if min(ph, pw) < 1:
         raise ValueError(f'pad_hw must be positive, got {(ph, pw)}')
     shape = (n, (ph - 1) // stride + 1, (pw - 1) // stride + 1)
-    if out is None:
-        out = torch.empty(shape, device=torch.device('cuda', torch.cuda.current_device()) if device is None else device, dtype=torch.float32)
-    else:
-        _chk(out, 'out')
-        if tuple(out.shape) != shape or (src is not None and out.device != src.device):
-            raise ValueError(f'out must be {list(shape)}' + (f' on {src.device}' if src is not None else '') + f', got {tuple(out.shape)} on {out.device}')
-    d = _lib.ImagePrepDesc(H, W, 3 * W, nh, nw, ph, pw, 0, (C.c_float * 3)(0, 0, 0), (C.c_float * 3)(1, 1, 1))
+    if out is None and device is None:
+        device = torch.device('cuda', torch.cuda.current_device())
+    out = _prep_out(out, shape, device, where=src is not None)
+    d = _prep_desc(H, W, 3 * W, (nh, nw), (ph, pw))
     check(fn(C.byref(d), None if ls is None else C.byref(ls), _ptr(src), dt, row, plane, float(scale), stride, n, _ptr(out), _stream()),
           'ivx_map_prep_lens')
     return out

@@ -425,7 +425,7 @@ int ivx_nhwc_to_nchw(const float *in, int32_t B, int64_t S, int32_t C, float *ou
 /* ---------------------------------------------------------------------------------------
  * Device-side image pipeline (0.4.3) -- the Resize(keep_ratio) -> Normalize -> Pad(32) steps of the reference test pipelines
  * (configs/imvoxelnet/imvoxelnet_kitti.py:94-105) from uint8 HWC BGR frames to the fp32 NCHW input of the model, in one launch
- * (csrc/preprocess.hip).  The result is bit-identical to data.prepare_image of the Python package, zero pad region included:
+ * (csrc/image_prep.hip).  The result is bit-identical to data.prepare_image of the Python package, zero pad region included:
  *   resize     the integer restatement of cv2.resize(INTER_LINEAR) on uint8 held by data.imresize_cv2_linear / data._linear_tables:
  *              fx = float32((d + 0.5) * (double(src) / double(dst)) - 0.5) with the product and the difference in double, floor, both
  *              borders clamped, 11-bit weights rounded half to even; int32 horizontal pass S[sx] * a0 + S[sx1] * a1; vertical pass
@@ -461,7 +461,7 @@ int ivx_image_prep_u8(const ivx_image_prep_desc *d, const void *src, int64_t src
 
 /* ---------------------------------------------------------------------------------------
  * Lens-aware device image pipeline (0.5.2) -- Undistort -> Resize -> Normalize -> Pad in the one launch that reads the raw frame
- * (csrc/lens_prep.hip), and the feature-resolution maps of the same geometry.  ivx_image_prep_u8 assumes an ideal pinhole camera; a real
+ * (csrc/image_prep.hip), and the feature-resolution maps of the same geometry.  ivx_image_prep_u8 assumes an ideal pinhole camera; a real
  * one (handheld RGB-D scanners, wide-angle and fisheye heads) has radial distortion, and undistorting on the host costs a second
  * interpolation, a host pass per frame and the uint8 path.  Here ONE geometric map G takes a pixel of the network input back to the raw
  * frame; the image is sampled through it once, and the border mask and the depth frame at feature resolution follow from the same rule.

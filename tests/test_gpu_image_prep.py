@@ -1,4 +1,4 @@
-"""-m gpu: the device-side image pipeline (include/imvoxel.h ivx_image_prep_u8, csrc/preprocess.hip; ops.image_prep_u8,
+"""-m gpu: the device-side image pipeline (include/imvoxel.h ivx_image_prep_u8, csrc/image_prep.hip; ops.image_prep_u8,
 data.prepare_images_device, ImVoxelNet.simple_test_u8) against the host pipeline it restates: data.imresize_cv2_linear for the resize alone,
 data.prepare_image for Resize -> Normalize -> Pad.  Both are integer-exact restatements with one fp32 subtract and one IEEE divide per value,
 so every comparison is torch.equal / np.array_equal: NO tolerance.  The single exception is the independent fp64 bilinear check of one

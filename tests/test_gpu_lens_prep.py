@@ -1,4 +1,4 @@
-"""-m gpu: the lens-aware image pipeline (ops.image_prep_lens_u8 / ops.map_prep_lens, csrc/lens_prep.hip) against the numpy fp64 references of
+"""-m gpu: the lens-aware image pipeline (ops.image_prep_lens_u8 / ops.map_prep_lens, csrc/image_prep.hip) against the numpy fp64 references of
 tests/ref_lens.py, and the lens= / depth_frames= keywords of the streaming scenes against sessions that are handed the same images and maps.
 
 The image bound.  The header fixes the blend: fu, fv are fractions rounded once to fp32 (|error| <= 2^-25 each); top = a + fu * (b - a), bot likewise,

@@ -1,4 +1,4 @@
-"""-m gpu: decoder pixel formats in the device image pipeline (include/imvoxel.h 0.5.3 ivx_image_prep_fmt_u8, csrc/pixel_fetch.h;
+"""-m gpu: decoder pixel formats in the device image pipeline (include/imvoxel.h 0.5.3 ivx_image_prep_fmt_u8, csrc/image_prep.hip, csrc/pixel_fetch.h;
 ops.image_prep_fmt_u8, data.prepare_images_device(format=), the format= keyword of simple_test_u8 and of the scenes).  A frame in any layout IS
 a BGR frame through the header's integer rule (tests/ref_pixfmt.py restates it independently), and the result is the existing entry on that
 BGR frame: every comparison is torch.equal / ==, there is NO tolerance.  All inputs are uniform random bytes from fixed seeds; surfaces are

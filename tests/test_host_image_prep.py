@@ -1,4 +1,4 @@
-"""CPU-only tests of the device-side image pipeline's host surface (include/imvoxel.h ivx_rescale_size / ivx_image_prep_u8, csrc/preprocess.hip,
+"""CPU-only tests of the device-side image pipeline's host surface (include/imvoxel.h ivx_rescale_size / ivx_image_prep_u8, csrc/image_prep.hip,
 data.prepare_images_device): the size rule against data.rescale_size, argument validation before any launch, the ctypes layout, and the
 batching logic of prepare_images_device with ops.image_prep_u8 replaced by a host stand-in built from data.prepare_image.  The library loads
 without a device; nothing here launches a kernel."""

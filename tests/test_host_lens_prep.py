@@ -1,5 +1,5 @@
 """CPU-only tests of the lens-aware image pipeline's host surface (include/imvoxel.h ivx_lens / ivx_image_prep_lens_u8 / ivx_map_prep_lens,
-csrc/lens_prep.hip, data.Lens, data.prepare_images_device(lens=), the lens= / depth_frames= keywords of the scenes): argument validation before
+csrc/image_prep.hip, data.Lens, data.prepare_images_device(lens=), the lens= / depth_frames= keywords of the scenes): argument validation before
 any launch, the ctypes layout against the header text, the Lens record, the grouping and the launches of prepare_images_device with the ops
 replaced by stand-ins built from tests/ref_lens.py, the scene logic with stubbed ops, and the sanity of the fp64 reference itself against
 data.prepare_image.  The library loads without a device; nothing here launches a kernel."""

@@ -1,5 +1,5 @@
 """CPU-only tests of the decoder pixel formats of the image pipeline (include/imvoxel.h 0.5.3: ivx_frame_format / ivx_yuv_matrix /
-ivx_image_prep_fmt_u8, csrc/pixel_fetch.h; data.FrameFormat, data.to_bgr_u8, data.prepare_images_device(format=)): the host sibling of the
+ivx_image_prep_fmt_u8, csrc/image_prep.hip, csrc/pixel_fetch.h; data.FrameFormat, data.to_bgr_u8, data.prepare_images_device(format=)): the host sibling of the
 conversion against the independent restatement of tests/ref_pixfmt.py, the named matrices against Fraction arithmetic, the record, the
 grouping with the op replaced by a host stand-in, the refusals of the Python layer and of the entry, and an older library.  The library loads
 without a device; nothing here launches a kernel.  cv2 is not installed where this was written: parity with cv2.cvtColor is UNPINNED."""

@@ -1,4 +1,4 @@
-"""Measure the device-side image pipeline (ivx_image_prep_u8, csrc/preprocess.hip) on the GPU box.  python tools/image_prep_bench.py [--md out.md]
+"""Measure the device-side image pipeline (ivx_image_prep_u8, csrc/image_prep.hip) on the GPU box.  python tools/image_prep_bench.py [--md out.md]
 
 Per geometry (the four reference test pipelines at their benchmark batch sizes):
   kernel time    HIP events around one launch, warm-up first, median of --reps launches;

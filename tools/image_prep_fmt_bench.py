@@ -1,4 +1,4 @@
-"""Measure the image pipeline on decoder pixel formats (ivx_image_prep_fmt_u8, csrc/pixel_fetch.h) beside the unchanged BGR entries
+"""Measure the image pipeline on decoder pixel formats (ivx_image_prep_fmt_u8, csrc/image_prep.hip, csrc/pixel_fetch.h) beside the unchanged BGR entries
 (ivx_image_prep_u8 / ivx_image_prep_lens_u8) on the GPU box.  python tools/image_prep_fmt_bench.py [--md out.md]
 
 Per geometry (KITTI 375 x 1242 -> 384 x 1280, ScanNet 968 x 1296 -> 480 x 640, a 1080 x 1920 decoder frame -> the ScanNet input), plain and

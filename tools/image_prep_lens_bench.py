@@ -1,5 +1,5 @@
-"""Measure the lens-aware image pipeline (ivx_image_prep_lens_u8 / ivx_map_prep_lens, csrc/lens_prep.hip) beside the plain entry
-(ivx_image_prep_u8, csrc/preprocess.hip) on the GPU box.  python tools/image_prep_lens_bench.py [--md out.md]
+"""Measure the lens-aware image pipeline (ivx_image_prep_lens_u8 / ivx_map_prep_lens, csrc/image_prep.hip) beside the plain entry
+(ivx_image_prep_u8, csrc/image_prep.hip) on the GPU box.  python tools/image_prep_lens_bench.py [--md out.md]
 
 Per geometry (network input 480 x 640, 384 x 1280, 928 x 1600 from the frames of the ScanNet, KITTI and nuScenes pipelines), in ONE process, the
 three kernels alternating:
