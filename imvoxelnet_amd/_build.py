@@ -24,6 +24,7 @@ SOURCES = [
     ('pool_layout.hip', []),
     ('backproject.hip', ['-ffp-contract=off']),
     ('volume_scroll.hip', []),
+    ('volume_warp.hip', ['-ffp-contract=off']),
     ('view_coverage.hip', ['-ffp-contract=off']),
     ('anchor_tail.hip', ['-ffp-contract=off']),
     ('image_prep.hip', ['-ffp-contract=off']),

@@ -3,7 +3,8 @@
 // ivx_backproject_mapped_fwd step 3).
 //
 // Who uses it.  Both lift kernels of csrc/backproject.hip and the coverage kernel of csrc/view_coverage.hip (ivx_view_coverage_fwd): nothing
-// else in csrc/ splits a voxel index, projects a centre or decides validity.  tests/test_gpu_view_coverage.py still checks on the device that
+// else in csrc/ splits a voxel index, projects a centre or decides validity.  csrc/volume_warp.hip (ivx_volume_warp_fwd) takes the voxel of an
+// index, its centre and the row product from here for its rigid transform (no projection, no validity).  tests/test_gpu_view_coverage.py still checks on the device that
 // the coverage count of a view equals the lift's mask of that view: it guards the two callers (their crop, slot and map addressing), not two texts.
 // profiles/lift_one_geometry.md compares the code the lift kernels compile to with what their inline chain compiled to.
 //

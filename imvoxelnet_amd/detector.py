@@ -376,7 +376,8 @@ class ImVoxelNet(nn.Module):
         the pixel shows (scene.py, "Pixel maps").  depth_gate=None: depth maps are refused.  Every session answers coverage(extrinsics) --
         per candidate pose the voxels the lift would count it at and those of them the scene has no evidence for yet, one small launch, no
         trunk -- and add_views(..., min_novelty=m) uses it as a keyframe gate that drops redundant views before the trunk runs (scene.py,
-        "View coverage and the keyframe gate")."""
+        "View coverage and the keyframe gate").  Sessions opened with decay= or window= follow a platform that turns: warp(T) brings the
+        scene into the platform's current frame while the grid, and the anchors of an Anchor3DHead, stay put (scene.py, "Warping scenes")."""
         from .scene import SceneSession
         return SceneSession(self, meta, window=window, decay=decay, forget_below=forget_below, depth_gate=depth_gate)
 

@@ -1534,6 +1534,120 @@ def volume_scroll_(vol_sum, count, rows, shifts, wsum=None):
     return vol_sum, count
 
 
+RIGID_TOL = 1e-4             # a transform of volume_warp is rigid when max |R^T R - I| <= RIGID_TOL and det R > 0, in float64 (a float32 rotation: ~1e-7)
+
+
+def check_rigid(T, name='transform'):
+    """A rigid transform as a host 4x4 or 3x4 array (numpy, a host tensor, nested lists) -> float32 array [3,4].  Finite; a 4x4 must have the
+    last row (0, 0, 0, 1); R = T[:3,:3] must satisfy max |R^T R - I| <= RIGID_TOL and det R > 0, computed in float64: a scale, a shear and a
+    reflection raise ValueError."""
+    import numpy as np
+    if isinstance(T, torch.Tensor):
+        if T.is_cuda:
+            raise TypeError(f'{name} must be a host matrix (the transforms of a warp are checked and passed by value), got a device tensor')
+        T = T.detach().numpy()
+    try:
+        A = np.asarray(T, np.float64)
+    except (TypeError, ValueError):
+        raise TypeError(f'{name} must be a 4x4 or 3x4 matrix of numbers, got {type(T).__name__}') from None
+    if A.shape not in ((4, 4), (3, 4)):
+        raise ValueError(f'{name} must be 4x4 or 3x4, got {A.shape}')
+    if not np.isfinite(A).all():
+        raise ValueError(f'{name} must be finite')
+    if A.shape == (4, 4) and not np.array_equal(A[3], [0, 0, 0, 1]):
+        raise ValueError(f'{name}: the last row of a 4x4 must be (0, 0, 0, 1), got {A[3].tolist()}')
+    R = A[:3, :3]
+    off = float(np.abs(R.T @ R - np.eye(3)).max())
+    if not off <= RIGID_TOL:
+        raise ValueError(f'{name} is not rigid: max |R^T R - I| = {off:.3g} > {RIGID_TOL} (a scale or a shear would not keep the voxel size)')
+    if not np.linalg.det(R) > 0:
+        raise ValueError(f'{name} is not rigid: det R < 0 (a reflection)')
+    return np.ascontiguousarray(A[:3], np.float32)
+
+
+def volume_warp(vol_sum, wsum, count, rows, transforms, new_origin, voxel_size, out, out_rows=None, forget_below=0.0):
+    """Scenes that turn with their platform: resample rows of the state pools vol_sum [R,X,Y,Z,C] fp32 / wsum [R,X,Y,Z] fp32 / count [R,X,Y,Z]
+    int32 under rigid transforms into the pools out = (sum, wsum, count) of the same X, Y, Z, C (ivx_volume_warp_fwd; include/imvoxel.h has the
+    definition).  For sample b, row out_rows[b] of `out` (None: rows[b]) becomes the trilinear read of row rows[b] at x_old = T x_new with
+    T = transforms[b], a host 4x4 or 3x4 matrix (check_rigid; one matrix alone for one row) that maps a point of the NEW grid frame to the OLD one;
+    the grid itself -- new_origin [B,3] (or [3] for all; host floats, the device new_origin of the lifts) and voxel_size -- stays.  Sums and
+    weight sum take the same weights, count the maximum over the corners read; a voxel whose source lies outside the grid is unseen, and with
+    forget_below > 0 so is one whose new weight sum is below it.  Out of place: `out` must not share memory with the inputs.  rows: B host
+    integers in [0, R); out_rows: B distinct host integers.  Rows not named are neither read nor written.  Every check comes before the one C
+    call, so a call that raises changes nothing.  Returns out."""
+    import numpy as np
+    for t, name in ((vol_sum, 'vol_sum'), (wsum, 'wsum'), (count, 'count')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch.Tensor')
+    if not isinstance(out, (tuple, list)) or len(out) != 3 or any(not isinstance(t, torch.Tensor) for t in out):
+        raise TypeError('out must be a (sum, wsum, count) triple of torch.Tensors: the warp is out of place')
+    osum, owsum, ocount = out
+    if vol_sum.dim() != 5:
+        raise ValueError(f'vol_sum must be [R,X,Y,Z,C], got {tuple(vol_sum.shape)}')
+    R, X, Y, Z, Cn = (int(v) for v in vol_sum.shape)
+    rows = _host_ints(rows, 'rows')
+    if not rows:
+        raise ValueError('rows must name at least one row')
+    B = len(rows)
+    out_rows = list(rows) if out_rows is None else _host_ints(out_rows, 'out_rows', B)
+    if isinstance(transforms, (str, bytes)) or not hasattr(transforms, '__len__'):
+        raise TypeError('transforms must be a host list of 4x4 or 3x4 matrices')
+    if B == 1 and (transforms.dim() == 2 if isinstance(transforms, torch.Tensor) else
+                   len(transforms) in (3, 4) and all(hasattr(r, '__len__') and len(r) == 4 and not any(hasattr(v, '__len__') for v in r) for r in transforms)):
+        transforms = [transforms]                               # one matrix alone for one row
+    if len(transforms) != B:
+        raise ValueError(f'transforms must hold one matrix per row: {B} rows, got {len(transforms)}')
+    M = [check_rigid(T, f'transforms[{b}]') for b, T in enumerate(transforms)]
+    if isinstance(new_origin, torch.Tensor):
+        if new_origin.is_cuda:
+            raise TypeError('new_origin must be host floats [B,3] (it is checked and passed by value), got a device tensor')
+        new_origin = new_origin.detach().numpy()
+    try:
+        o = np.asarray(new_origin, np.float32)
+        vs = np.asarray([float(v) for v in voxel_size], np.float32)
+    except (TypeError, ValueError):
+        raise TypeError('new_origin must be host floats [B,3] and voxel_size three numbers') from None
+    if o.shape == (3,):
+        o = np.broadcast_to(o, (B, 3))
+    if o.shape != (B, 3) or vs.shape != (3,):
+        raise ValueError(f'new_origin must be [B,3] (or [3]) for {B} rows and voxel_size three numbers, got {o.shape} and {vs.shape}')
+    if not (np.isfinite(o).all() and np.isfinite(vs).all() and (vs > 0).all()):
+        raise ValueError(f'new_origin must be finite and voxel_size finite and > 0, got {o.tolist()} and {vs.tolist()}')
+    if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float)) or not (math.isfinite(forget_below) and forget_below >= 0):
+        raise ValueError(f'forget_below must be a finite number >= 0, got {forget_below!r}')
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}')
+    if osum.dim() != 5 or tuple(osum.shape[1:]) != (X, Y, Z, Cn):
+        raise ValueError(f'out[0] must be [R_out,{X},{Y},{Z},{Cn}] like vol_sum, got {tuple(osum.shape)}')
+    Ro = int(osum.shape[0])
+    if len(set(out_rows)) != B:
+        raise ValueError(f'out_rows must be distinct (two samples on one row race), got {out_rows}')
+    if any(not 0 <= r < Ro for r in out_rows):
+        raise ValueError(f'out_rows must be in [0, {Ro}), got {out_rows}')
+    if Cn % 4:
+        raise ValueError(f'vol_sum must have C % 4 == 0, got C = {Cn}')
+    for t, name, shape in ((wsum, 'wsum', (R, X, Y, Z)), (count, 'count', (R, X, Y, Z)), (owsum, 'out[1]', (Ro, X, Y, Z)), (ocount, 'out[2]', (Ro, X, Y, Z))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'{name} must be {list(shape)} beside its sums, got {tuple(t.shape)}')
+    for t, name, dt in ((vol_sum, 'vol_sum', torch.float32), (wsum, 'wsum', torch.float32), (count, 'count', torch.int32), (osum, 'out[0]', torch.float32),
+                        (owsum, 'out[1]', torch.float32), (ocount, 'out[2]', torch.int32)):
+        _chk(t, name, dt)
+        if t.device != vol_sum.device:
+            raise ValueError(f'{name} must be on the device of vol_sum')
+    for a, an in ((vol_sum, 'vol_sum'), (wsum, 'wsum'), (count, 'count')):
+        for t, tn in ((osum, 'out[0]'), (owsum, 'out[1]'), (ocount, 'out[2]')):
+            a0, t0 = a.data_ptr(), t.data_ptr()
+            if a0 < t0 + t.numel() * 4 and t0 < a0 + a.numel() * 4:
+                raise ValueError(f'{tn} shares memory with {an}: a resample cannot run in place')
+    fn = getattr(_lib.lib(), 'ivx_volume_warp_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_warp_fwd (needs version 0.5.4)')
+    flat = lambda a: (C.c_float * a.size)(*np.ascontiguousarray(a, np.float32).reshape(-1).tolist())     # noqa: E731
+    check(fn(B, (C.c_int32 * B)(*rows), (C.c_int32 * B)(*out_rows), flat(np.stack(M)), flat(o), flat(vs), float(forget_below), R, Ro, X, Y, Z, Cn,
+             _ptr(vol_sum), _ptr(wsum), _ptr(count), _ptr(osum), _ptr(owsum), _ptr(ocount), _stream()), 'ivx_volume_warp_fwd')
+    return out
+
+
 _STATE_KIND = {torch.int32: _lib.STATE_COUNT, torch.float32: _lib.STATE_WSUM, torch.uint8: _lib.STATE_MASK, torch.bool: _lib.STATE_MASK}
 MAX_COVERAGE_VIEWS = 256      # candidates per sample of one view_coverage call (the kernel's counters live in LDS)
 

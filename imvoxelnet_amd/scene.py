@@ -53,6 +53,22 @@ the new origin, so a scrolled scene is, bit for bit, a scene opened at the new o
 nothing fades.  Like bilinear sampling and fading it is an extra outside the reference-parity claims; a session that never scrolls runs the code
 it ran before.  Models with an Anchor3DHead refuse: their anchors are fixed in the LiDAR frame.
 
+Warping scenes (SceneSession.warp(T) / SceneBatch.warp(scenes, Ts); warped_extrinsic, frame).  scroll carries the grid along by whole voxels and
+moves the origin, which excludes the platforms that move most: a vehicle whose grid and anchors live in the vehicle frame needs the previous state
+in the CURRENT vehicle frame on every tick -- a rotation plus a fractional translation -- and a robot with a robot-aligned grid cannot turn.  warp is
+the one operation both need: T is a host 4x4 with x_old = T x_new (inv(world_from_old_ego) @ world_from_new_ego), the grid stays where the head
+expects it (origin, anchors and head code are untouched, so Anchor3DHead models warp like any other), and the state is resampled under T.  A fading
+scene already keeps the right state: a float weight sum resamples linearly beside the sums, both with the same trilinear weights, so the mean stays
+a convex combination of neighbouring means and evidence thins at the grid's border and at the edge of what was seen (ops.volume_warp,
+ivx_volume_warp_fwd, csrc/volume_warp.hip; include/imvoxel.h has the definition; out of place, into a twin state that a session keeps from its
+first warp on -- twice the state memory -- and a batch allocates per call for the rows it moves).  A windowed scene needs no kernel: it re-poses its
+kept views and lifts them again, which is exact.  Every extrinsic a scene holds follows ONE rule, warped_extrinsic(E, T) = float32(float64(E) @
+float64(T)), so `meta` stays a complete simple_test meta in the new frame; after a warp the caller's extrinsics and the returned boxes are in the
+grid's current frame, and `frame` (float64 4x4, the product of every T since open or reset()) takes a point of the current frame back to the
+opening one: x_opening = frame @ x_grid.  A warp is not a tick: nothing fades, but the session's forget_below applies to the thinned weight sums.
+A plain scene raises NotImplementedError -- integer view counts cannot be resampled; decay=1.0 fades nothing and can.  The identity launches
+nothing; a session that never warps runs the code it ran before.  scroll keeps its behaviour, its refusal for anchor heads included.
+
 Pixel maps (add_views(..., pixel_weights=..., depths=...); open_scene(meta, ..., depth_gate=(behind, front))).  A weight per view scales a whole
 frame, but a person walking through the scan, the robot's own arm, lens dirt and the black border after undistortion are properties of pixels, and
 an RGB-D camera knows which voxels on a pixel's ray lie behind the surface it shows.  Sessions that take weights (decay= or window=) take two
@@ -100,8 +116,9 @@ the classes, and nothing shared asks which class called it: wording that differs
 
 Out of scope: a gate in which the views of one call see each other (sequential gating), anticipating a fading scene's next decay in coverage(),
 choosing which kept view of a window to evict; decay on windowed scenes; confidence maps at the source size through the add_views_u8 pipeline, a soft (ramp) or signed-distance gate, maps for plain
-sessions and for simple_test; scrolling by a fraction of a voxel or by a rotation (both would resample the state);
-scrolling a model with an Anchor3DHead (its boxes would have to be translated); scene batches across ranks; a model-level C handle for sessions
+sessions and for simple_test; warping a plain session (integer view counts cannot be resampled: open it with decay=1.0); non-rigid transforms
+(a scale or a shear would not keep the voxel size; ops.check_rigid refuses them); scrolling by a fraction of a voxel (warp resamples instead);
+scrolling a model with an Anchor3DHead (its boxes would have to be translated; warp keeps the origin and needs no translation); scene batches across ranks; a model-level C handle for sessions
 (the state lives here, over the op-level ABI and the handle's sub-range calls).
 """
 import math
@@ -386,6 +403,27 @@ def _check_scroll(model, voxels):
     return s
 
 
+# ------------------------------------------------------------------ warping: the host rules
+def warped_extrinsic(E, T):
+    """The extrinsic of a view after a warp by T (x_old = T x_new):  float32(float64(E) @ float64(T))  -- the camera sees the same points, now
+    named in the new frame.  -> float32 array [4,4]."""
+    return (np.asarray(E, np.float64) @ np.asarray(T, np.float64)).astype(np.float32)
+
+
+def _check_warp(T):
+    """T of a warp -> float64 array [4,4]: a host 4x4 of numbers, finite, last row (0, 0, 0, 1), rigid by ops.check_rigid's rule."""
+    if isinstance(T, torch.Tensor) and not T.is_cuda:
+        T = T.detach().numpy()
+    if isinstance(T, torch.Tensor) or np.shape(T) != (4, 4):
+        raise ValueError(f'T must be a host 4x4 matrix with x_old = T x_new, got {type(T).__name__} of shape {tuple(np.shape(T)) if not isinstance(T, torch.Tensor) else tuple(T.shape)}')
+    ops.check_rigid(T, 'T')
+    return np.asarray(T, np.float64)
+
+
+_PLAIN_WARP = ('warp: a plain {what} keeps integer view counts, which cannot be resampled; open it with decay=1.0 (a weight sum beside the sums, '
+               'nothing fades) or with window=W')
+
+
 # ------------------------------------------------------------------ the two model calls around the lift
 def _trunk(m, img):
     """[V,3,H,W] -> FPN level 0 of these views.  The native handle's trunk sub-range is the same kernels with the same plans as
@@ -441,6 +479,7 @@ class _SceneRecord:
         self._window, self._views, self._next_id = window, [], 0
         self._decay, self._forget, self._gate = decay, forget_below, gate
         self._scrolled = (0, 0, 0)
+        self._frame = np.eye(4)
 
     @staticmethod
     def _check_fading(window, decay, forget_below):
@@ -469,6 +508,25 @@ class _SceneRecord:
         self.n_views, self._hw, self._stale = 0, None, False
         self._views, self._next_id = [], 0
         self._scrolled = (0, 0, 0)
+        self._frame = np.eye(4)
+
+    @property
+    def frame(self):
+        """float64 [4,4]: the product of every T warped by since the scene was opened or reset(), so that x_opening = frame @ x_grid -- a point named
+        in the grid's current frame, in the frame the scene was opened in.  A copy."""
+        return self._frame.copy()
+
+    def _warped(self, T):
+        """What a warp by T (float64 [4,4], x_old = T x_new) makes of the extrinsics this record holds -> (the meta's list, the windowed views):
+        warped_extrinsic of each.  Changes nothing."""
+        views = [(i, s, warped_extrinsic(e, T)) for i, s, e in self._views]
+        return ([v[2] for v in views] if self._window is not None else [warped_extrinsic(e, T) for e in self.meta['lidar2img']['extrinsic']]), views
+
+    def _warp(self, T, extrinsics, views):
+        """A warp by T is in: the extrinsics (_warped) replace the record's, frame takes T on the right, the mean of a scene with views is behind."""
+        self.meta['lidar2img']['extrinsic'], self._views = extrinsics, views
+        self._frame = self._frame @ T
+        self._stale = self._stale or self.n_views > 0
 
     @property
     def scrolled(self):
@@ -611,6 +669,7 @@ class SceneSession(_SceneRecord):
         self._mring = self._dring = None          # window=W: the device rings of the slots' pixel-weight / depth maps [W,FH,FW], each None until a map is given
         self._covers = {}                         # add_views_u8(lens=): the cover maps [FH,FW] by (lens, source shape, pipeline shapes, device)
         self.last_admitted = None                 # the gate's verdict per view of the last add_views(..., min_novelty=) call; None after an ungated one
+        self._twin = None                         # decay=lam: the (sum, wsum, count) buffers a warp writes into, None until the first warp
 
     # ------------------------------------------------------------------ state
     def _check_open(self):
@@ -625,7 +684,7 @@ class SceneSession(_SceneRecord):
 
     def close(self):
         self._sum = self._count = self._mean = self._valid = self._origin = self._crop = None
-        self._ring = self._pring = self._wsum = self._wring = self._mring = self._dring = None
+        self._ring = self._pring = self._wsum = self._wring = self._mring = self._dring = self._twin = None
         self._covers = {}
         self._closed = True
 
@@ -838,6 +897,40 @@ class SceneSession(_SceneRecord):
         if any(s):
             self.scroll(s)
         return tuple(s)
+
+    # ------------------------------------------------------------------ warping
+    def warp(self, T):
+        """Bring the scene into a frame that has turned and moved: T is a host float 4x4 with x_old = T x_new -- for a vehicle
+        inv(world_from_old_ego) @ world_from_new_ego.  The grid stays where the head expects it: origin, anchors and head code are untouched, so
+        models with an Anchor3DHead warp like any other.  After a warp the caller's extrinsics and the returned boxes are in the grid's current
+        frame; every extrinsic the session holds follows warped_extrinsic, so `meta` stays a complete simple_test meta in the new frame, and
+        `frame` accumulates T.
+        A fading session (decay=) resamples its state (sum, weight sum, count) in one ops.volume_warp (ivx_volume_warp_fwd) into a twin state and
+        swaps the two; the session's forget_below is passed through, nothing fades (a warp is not a tick) and the mean is recomputed when next
+        asked for.  The twin is allocated at the first warp and kept: a session that warps holds its state twice (ScanNet-fast 2 x 26.4 MB,
+        ScanNet-v1 2 x 54.1 MB).  A windowed session has no state to resample: its kept views are re-posed and the next volume() / detect() is the
+        gathered re-lift, bit for bit a fresh windowed scene given the same views with the warped extrinsics; maps and weights stay in their
+        slots.  A plain session raises NotImplementedError and goes on as before.  An empty scene only changes `frame`.  The identity changes
+        nothing and launches nothing.  A call that raises leaves the session as it was.  Returns self."""
+        self._check_open()
+        T = _check_warp(T)
+        if self._window is None and self._decay is None:
+            raise NotImplementedError(_PLAIN_WARP.format(what='session'))
+        if np.array_equal(T, np.eye(4)):
+            return self
+        m = self._model
+        extrinsics, views = self._warped(T)
+        if self.n_views and self._window is not None:     # the kept views' projection rows, by the rule their add used; the rings keep their slots
+            idx = torch.tensor([v[1] for v in views], dtype=torch.int64).to(self._pring.device)
+            rows = m._compute_projection(dict(self.meta, lidar2img=dict(self.meta['lidar2img'], extrinsic=extrinsics)), 4).contiguous().to(self._pring.device)
+            self._pring.index_copy_(0, idx, rows)
+        elif self.n_views:
+            state = (self._sum, self._wsum, self._count)
+            twin = self._twin if self._twin is not None else tuple(torch.empty_like(t) for t in state)
+            ops.volume_warp(*state, [0], [T], m._new_origin(self.meta['lidar2img']['origin']).numpy()[None], m.voxel_size, out=twin, forget_below=self._forget)
+            (self._sum, self._wsum, self._count), self._twin = twin, state
+        self._warp(T, extrinsics, views)
+        return self
 
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None,
                      lens=None, depth_frames=None, depth_scale=0.001, format=None, **pipeline_kw):
@@ -1062,6 +1155,50 @@ class SceneBatch:
             self._scenes[s]._scroll(v, origin)
             if self._cam[s] is not None:
                 self._cam[s] = (m._new_origin(origin), self._cam[s][1])
+        return self
+
+    def frame(self, scene):
+        """The product of every T one scene was warped by since it was opened or reset (SceneSession.frame)."""
+        self._check_open()
+        return self._scenes[self._scene_index(scene)].frame
+
+    def warp(self, scenes, Ts):
+        """SceneSession.warp for scenes of the batch: one scene index with one T, or a list of distinct indices with one T each.  A fading batch
+        warps the rows of all named scenes in ONE ops.volume_warp into a scratch pool of as many rows as scenes it has to move -- allocated for
+        the call, so the batch does not hold its state twice -- and copies those rows back; a windowed batch re-poses the kept views of the named
+        scenes (one index_copy_ of their projection rows).  Scenes not named are neither read nor written.  A plain batch raises
+        NotImplementedError.  A call that raises leaves every scene as it was."""
+        self._check_open()
+        if isinstance(scenes, (int, np.integer)) and not isinstance(scenes, bool):
+            scenes, Ts = [scenes], [Ts]
+        if isinstance(scenes, torch.Tensor) or not hasattr(scenes, '__len__') or (isinstance(Ts, torch.Tensor) and Ts.is_cuda) or not hasattr(Ts, '__len__') \
+                or len(scenes) != len(Ts):
+            raise ValueError(f'warp takes one scene index with one T, or lists of both of one length, got {scenes!r} and {len(Ts) if hasattr(Ts, "__len__") else Ts!r} transforms')
+        scenes = [self._scene_index(s) for s in scenes]
+        if len(set(scenes)) != len(scenes):
+            raise ValueError(f'a scene can be warped once per call, got {scenes}')
+        Ts = [_check_warp(T) for T in Ts]
+        if self._window is None and not self._fading:
+            raise NotImplementedError(_PLAIN_WARP.format(what='batch'))
+        m = self._model
+        moves = [(s, T) + self._scenes[s]._warped(T) for s, T in zip(scenes, Ts) if not np.array_equal(T, np.eye(4))]
+        rows = [mv for mv in moves if self._scenes[mv[0]].n_views]
+        if rows and self._window is not None:
+            dev = self._pring.device
+            idx = torch.tensor([v[1] for _, _, _, views in rows for v in views], dtype=torch.int64).to(dev)
+            proj = torch.cat([m._compute_projection(dict(self._scenes[s].meta, lidar2img=dict(self._scenes[s].meta['lidar2img'], extrinsic=ext)), 4)
+                              for s, _, ext, _ in rows])
+            self._pring.index_copy_(0, idx, proj.contiguous().to(dev))
+        elif rows:
+            named = [s for s, _, _, _ in rows]
+            scratch = tuple(torch.empty((len(named),) + tuple(t.shape[1:]), device=t.device, dtype=t.dtype) for t in (self._sum, self._wsum, self._count))
+            ops.volume_warp(self._sum, self._wsum, self._count, named, [T for _, T, _, _ in rows], torch.stack([self._cam[s][0] for s in named]).float().numpy(),
+                            m.voxel_size, out=scratch, out_rows=list(range(len(named))), forget_below=self._forget)
+            idx = torch.tensor(named, dtype=torch.int64).to(self._sum.device)
+            for pool, part in zip((self._sum, self._wsum, self._count), scratch):
+                pool.index_copy_(0, idx, part)
+        for s, T, ext, views in moves:
+            self._scenes[s]._warp(T, ext, views)
         return self
 
     # ------------------------------------------------------------------ adding views

@@ -47,7 +47,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * per view; 501 = 0.5.1: ivx_view_coverage_fwd, the integer count of the voxels a candidate view would see and of those the scene has no evidence
  * for yet, before its trunk runs; 502 = 0.5.2: ivx_image_prep_lens_u8 / ivx_map_prep_lens, the image pipeline through a lens model (undistortion
  * in the prep launch) and the cover / depth maps of the same geometry at feature resolution; 503 = 0.5.3: ivx_image_prep_fmt_u8 / ivx_yuv_matrix, the image pipeline on decoder pixel
- * formats (RGB, BGRA / RGBA, gray, NV12, YUYV) converted in the fetch of the prep launch) and the message of the last failing call on this
+ * formats (RGB, BGRA / RGBA, gray, NV12, YUYV) converted in the fetch of the prep launch; 540 = 0.5.4: ivx_volume_warp_fwd, the rigid out-of-place
+ * resample of rows of the state pools, for scenes that turn with their platform) and the message of the last failing call on this
  * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -926,6 +927,60 @@ int ivx_backproject_mapped_fwd(const ivx_backproject_desc *d, const ivx_lift_lis
  * Z or C; C % 4 != 0; X*Y*Z at or beyond 2^31; a row outside [0, R); two samples on one row (they would race).                                  */
 int ivx_volume_scroll_fwd(int32_t B, const int32_t *row /*host [B]*/, const int32_t *shift /*host [B,3]*/, int32_t R, int32_t X, int32_t Y, int32_t Z,
                           int32_t C, float *volume_sum, int32_t *count, float *wsum /*or NULL*/, ivx_stream_t stream);
+
+/* (0.5.4) Rigid resample of rows of the state pools: a scene's state is brought into a frame that has turned and moved by any amount while the grid
+ * stays where the head expects it (scenes that turn with their platform: scene.py, SceneSession.warp / SceneBatch.warp).  A fading state (sum,
+ * weight sum) resamples linearly: both take the same trilinear weights, so the mean stays a convex combination of neighbouring means.  Out of
+ * place, because a resample reads the neighbours of what it writes.  Like the bilinear rule, fading and scrolling it lies outside the
+ * reference-parity claims and is pinned to an fp64 reference written from the definition below (tests/ref_volume_warp.py).
+ *
+ * Definition.  Every operation is fp32, round-to-nearest, no contraction.  M = xform[b] [3,4] maps a point of the NEW grid frame to the OLD frame
+ * in which the state was written: x_old = R x_new + t.  For sample b and destination voxel (i,j,k) of row row_dst[b], reading row row_src[b]:
+ *   1. centre   p_a = float(idx_a) * voxel_size_a + new_origin_a                              (a product, a sum: the lift's voxel centre)
+ *   2. source   q_a = fma(M_a3, 1, fma(M_a2, p_z, fma(M_a1, p_y, M_a0 * p_x)))                (the lift's projection row)
+ *   3. grid     g_a = (q_a - new_origin_a) / voxel_size_a     one rounded difference, one IEEE division.  If !(g_a > -1 && g_a < N_a) on any
+ *               axis (N = X, Y, Z; NaN and inf fail too) the voxel becomes unseen -- sums +0, weight sum +0, count 0 -- and nothing is read.
+ *               Otherwise i0_a = floor(g_a) and f_a = g_a - i0_a, one rounded difference (exact for g_a >= 0; for g_a in (-2^-24, 0) it rounds
+ *               to 1, which puts the whole weight on index 0).
+ *   4. corners  The eight corners (i0_x + dx, i0_y + dy, i0_z + dz) in the order dx, dy, dz with dz fastest.  Axis weights: 1 - f_a (one
+ *               rounding) for d = 0, f_a for d = 1; corner weight w = (w_x * w_y) * w_z, two rounded products.  A corner outside the grid, or
+ *               with w == 0 exactly, is not read and contributes nothing.  Starting from +0, over the corners that are read:
+ *                   S'[c] = fma(w, S_corner[c], S'[c]) per channel,   W' = fma(w, W_corner, W'),   cnt' = max(cnt', cnt_corner).
+ *   5. forget   if forget_below > 0 && !(W' >= forget_below):  S' = +0, W' = +0, cnt' = 0     (the weighted lift's rule)
+ *   6. store    S', W', cnt' into row row_dst[b].  Every voxel of a named destination row is written.
+ *
+ * B            samples of this call
+ * row_src      HOST [B] int32: sample b reads row row_src[b] of the source pools (two samples may read one row)
+ * row_dst      HOST [B] int32: ... and writes row row_dst[b] of the destination pools; distinct
+ * xform        HOST [B,3,4] fp32, finite; rigidity is NOT required here (ops.volume_warp checks it)
+ * new_origin   HOST [B,3] fp32, finite: the grid's corner term, the new_origin of the lifts
+ * voxel_size   HOST [3] fp32, finite and > 0
+ * forget_below >= 0, finite
+ * R_src, R_dst, X, Y, Z, C   the source / destination pools have R_src / R_dst rows of X*Y*Z voxels; C % 4 == 0
+ * sum_src, wsum_src, count_src   DEVICE [R_src,X,Y,Z,C] fp32 (16-byte aligned), [R_src,X,Y,Z] fp32, [R_src,X,Y,Z] int32
+ * sum_dst, wsum_dst, count_dst   DEVICE the same with R_dst rows, written
+ * The lists are host lists, as for ivx_volume_scroll_fwd: everything is checked before any launch and nothing is uploaded (rows, transforms and
+ * origins reach the kernel by value, 32 samples per launch).
+ *
+ * Properties.
+ *   Untouched rows.  Rows named by no sample are neither read (source) nor written (destination).
+ *   Zero weights.    A corner of weight 0 is never read, so an unseen, NaN or inf cell there cannot leak.  Where g is an integer on all three axes
+ *                    a voxel has one corner, of weight 1: S' = fma(1, S, +0) is S with every bit (of a finite or infinite S; -0 becomes +0 and a NaN
+ *                    stays a NaN), W' and cnt' likewise.  A transform whose g is integer everywhere -- a whole-voxel translation on a grid where
+ *                    the chain above is exact, a quarter turn about the centre of a square one -- makes the call a permutation of the voxels, equal
+ *                    to ivx_volume_scroll_fwd for the translation.
+ *   Constant mean.   S / W == c on every read corner gives S' / W' == c within a few ulp.
+ *   Thinning.        At the grid's border and at the edge of what was seen both sums lose the same weights: evidence thins, and the mean S' / W'
+ *                    stays a convex combination of the neighbouring means.
+ *   Error.           Against the exact value of step 4 on the same i0 and f:  |S' - exact| <= 11 * 2^-24 * sum_corners |w S_corner| (+ 2^-126): one
+ *                    rounding in 1 - f, two in the products, eight accumulations (tests/ref_volume_warp.py derives it); the same for W'.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names this entry: a null pointer; a non-positive B, R_src, R_dst, X, Y, Z or C;
+ * C % 4 != 0; X*Y*Z at or beyond 2^31; a row outside its pool; two samples on one destination row; source and destination sum pools that overlap
+ * in memory (or are not 16-byte aligned); a non-finite xform, new_origin or voxel_size; voxel_size <= 0; a negative or non-finite forget_below. */
+int ivx_volume_warp_fwd(int32_t B, const int32_t *row_src /*host [B]*/, const int32_t *row_dst /*host [B]*/, const float *xform /*host [B,3,4]*/,
+                        const float *new_origin /*host [B,3]*/, const float *voxel_size /*host [3]*/, float forget_below, int32_t R_src, int32_t R_dst,
+                        int32_t X, int32_t Y, int32_t Z, int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src,
+                        float *sum_dst, float *wsum_dst, int32_t *count_dst, ivx_stream_t stream);
 
 /* (0.5.1) View coverage: what would a candidate view add to a scene?  Every frame that reaches a streaming scene pays for the 2-D trunk, and
  * most frames of a 30 Hz camera look at voxels the scene has already fused.  Whether a pose adds anything depends only on the geometry and on
