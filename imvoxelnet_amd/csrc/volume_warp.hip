@@ -1,4 +1,5 @@
-// Rigid resample of rows of the scene state pools (ivx_volume_warp_fwd, include/imvoxel.h): scenes that turn with their platform, scene.py.
+// Rigid resample of rows of the scene state pools (ivx_volume_warp_fwd, include/imvoxel.h): scenes that turn with their platform, scene.py -- and, as
+// a second instantiation of the same kernel, the rigid merge of one row into another (ivx_volume_merge_fwd): scenes that become one.
 //
 //   dst[i,j,k] = trilinear read of src at  g = (M * centre(i,j,k) - new_origin) / voxel_size,
 //
@@ -31,8 +32,18 @@
 // contiguous eighth of the row instead of every eighth workgroup (at VW = 16): 23 / 29 / 109 against 24 / 29 / 106 in the same run, no gain, not kept.
 // Not tried: every lane computing its own geometry.
 //
-// Samples travel by value in the kernel arguments (rows, the twelve numbers of M, new_origin), WARP_MAX_SAMPLES per launch: nothing is
-// uploaded, and every host list is checked before the first launch.
+// Merge (the kernel's MERGE flag; the header has the definition).  Geometry chain, corner weights, hand-off and tiling are the warp's, written once.
+// The instantiation adds: the SOURCE grid's origin in step 3; on the geometry lane the loads of the destination's own W_d and cnt_d (issued with the
+// corner loads), the merged decision W_s > 0, W' = fma(alpha, W_s, W_d), the saturating count, the forget decision and a conditional store; on the
+// sums lanes one more 16-byte load, S_d, issued with the corner loads, the one fma with alpha after the fold, and a conditional store.  The mask word
+// that travels to the sums lanes carries two bits beside the corners (MASK_STORE, MASK_FORGOT), because "not merged: store nothing" and "forgotten:
+// store zeros" are different and a mask of 0 alone cannot say which.  In place: a destination voxel reads only itself in the destination pools, and
+// the host refuses a row that is both a source and a destination.  Registers (hipcc -O3 -Rpass-analysis=kernel-resource-usage, gfx950): the warp
+// instantiation 58 VGPRs / 48 SGPRs / no scratch / 8 waves per SIMD, as before the template; the merge 62 / 50 / none / 8.
+//
+// Samples travel by value in the kernel arguments (rows, the twelve numbers of M, the two origins, alpha: 21 words), WARP_MAX_SAMPLES per launch --
+// 2784 bytes of arguments in all, under the 4 KB limit, so both instantiations carry 32: nothing is uploaded, and every host list is checked before
+// the first launch.
 #include <math.h>
 
 #include <algorithm>
@@ -51,11 +62,12 @@ static_assert(IVX_WARP_WG % 64 == 0 && IVX_WARP_WG >= 64 && IVX_WARP_WG <= 1024 
 
 namespace {
 
-constexpr int WARP_MAX_SAMPLES = 32;        // samples per launch: 17 words each in the kernel arguments
+constexpr int WARP_MAX_SAMPLES = 32;        // samples per launch: 21 words each in the kernel arguments
 
 struct WarpSample {
   int32_t row_src, row_dst;
-  float m[12], origin[3];                   // M [3,4] (new frame -> old frame) and the grid's new_origin
+  float m[12], origin[3];                   // M [3,4] (destination frame -> source frame) and the destination grid's new_origin (the warp's only grid)
+  float origin_src[3], alpha;               // the source grid's new_origin (the warp: == origin) and the weight of the source's evidence (MERGE only)
 };
 
 struct WarpArgs {
@@ -68,6 +80,11 @@ struct WarpArgs {
   long long nvox;
   WarpSample s[WARP_MAX_SAMPLES];           // blockIdx.y is the sample
 };
+static_assert(sizeof(WarpArgs) <= 4096, "the samples travel by value: the argument block must stay under the 4 KB kernel-argument limit");
+
+// MERGE only, beside the eight corner bits of a voxel's mask: what the sums lanes of a voxel do.  Neither: not merged, nothing is stored.  STORE with
+// corner bits: the sample is added to the destination's sums.  STORE | FORGOT (no corner bits): forgotten, zeros are stored and nothing is read.
+constexpr int MASK_STORE = 1 << 8, MASK_FORGOT = 1 << 9;
 
 // One axis of step 3: the grid coordinate g of the source point's coordinate q.  -> inside; i0 = floor(g), f = g - i0 (one rounded difference).
 __device__ __forceinline__ bool warp_axis(const float q, const float origin, const float vs, const int N, int &i0, float &f) {
@@ -85,6 +102,9 @@ __device__ __forceinline__ float warp_weight(const int c, const float fx, const 
   return __fmul_rn(__fmul_rn(wx, wy), wz);
 }
 
+// MERGE = false: ivx_volume_warp_fwd, the destination row is written whole.  MERGE = true: ivx_volume_merge_fwd, the sample is added in place to
+// the destination voxels that are merged (inside, W_s > 0) and no other voxel is written.
+template <bool MERGE>
 __global__ void __launch_bounds__(IVX_WARP_WG) volume_warp_kernel(const WarpArgs a) {
   const WarpSample &s = a.s[blockIdx.y];
   const int lane = threadIdx.x & 63;
@@ -96,6 +116,7 @@ __global__ void __launch_bounds__(IVX_WARP_WG) volume_warp_kernel(const WarpArgs
   // Y*Z + Z + 1 may pass 2^31, but the sum for a corner inside the grid is its flat index, below X*Y*Z < 2^31, and only those are addressed.
   const uint32_t uZ = (uint32_t)a.Z, uYZ = (uint32_t)YZ;
   const uint32_t corner_off[8] = {0u, 1u, uZ, uZ + 1u, uYZ, uYZ + 1u, uYZ + uZ, uYZ + uZ + 1u};
+  const float *og = MERGE ? s.origin_src : s.origin;                     // the grid that step 3 reads in
 
   // ---- geometry: lane l < VW owns voxel n0 + l
   uint32_t base = 0;
@@ -107,17 +128,18 @@ __global__ void __launch_bounds__(IVX_WARP_WG) volume_warp_kernel(const WarpArgs
     lift_voxel((int)n, a.Y, a.Z, i, j, k);                                // n < X*Y*Z < 2^31
     const float px = lift_point(i, a.vs[0], s.origin[0]), py = lift_point(j, a.vs[1], s.origin[1]), pz = lift_point(k, a.vs[2], s.origin[2]);
     const float qx = lift_row(s.m, px, py, pz), qy = lift_row(s.m + 4, px, py, pz), qz = lift_row(s.m + 8, px, py, pz);
-    bool in = warp_axis(qx, s.origin[0], a.vs[0], a.X, ix, fx);
-    in = warp_axis(qy, s.origin[1], a.vs[1], a.Y, iy, fy) && in;
-    in = warp_axis(qz, s.origin[2], a.vs[2], a.Z, iz, fz) && in;
+    bool in = warp_axis(qx, og[0], a.vs[0], a.X, ix, fx);
+    in = warp_axis(qy, og[1], a.vs[1], a.Y, iy, fy) && in;
+    in = warp_axis(qz, og[2], a.vs[2], a.Z, iz, fz) && in;
     float W = 0.f;
     int cnt = 0;
+    bool store = !MERGE;
     if (in) {
       base = ((uint32_t)ix * (uint32_t)a.Y + (uint32_t)iy) * uZ + (uint32_t)iz;
       const float *ws = a.wsum_src + (long long)s.row_src * a.nvox;
       const int32_t *cs = a.count_src + (long long)s.row_src * a.nvox;
-      float w[8], wv[8];
-      int cv[8];
+      float w[8], wv[8], wd = 0.f;
+      int cv[8], cd = 0;
 #pragma unroll
       for (int c = 0; c < 8; ++c) {
         const int cx = ix + (c >> 2), cy = iy + ((c >> 1) & 1), cz = iz + (c & 1);
@@ -130,16 +152,33 @@ __global__ void __launch_bounds__(IVX_WARP_WG) volume_warp_kernel(const WarpArgs
         wv[c] = rd ? ws[(uint32_t)(base + corner_off[c])] : 0.f;
         cv[c] = rd ? cs[(uint32_t)(base + corner_off[c])] : 0;
       }
+      if (MERGE) {                                                       // ... the destination's own two words among them
+        wd = a.wsum_dst[(long long)s.row_dst * a.nvox + n];
+        cd = a.count_dst[(long long)s.row_dst * a.nvox + n];
+      }
 #pragma unroll
       for (int c = 0; c < 8; ++c)
         if (mask >> c & 1) {
           W = __fmaf_rn(w[c], wv[c], W);
           cnt = max(cnt, cv[c]);
         }
-      if (a.forget_below > 0.f && !(W >= a.forget_below)) mask = 0, W = 0.f, cnt = 0;
+      if (MERGE) {
+        if (W > 0.f) {                                                   // merged: the state's own "seen" rule on the sample (a NaN W_s is not)
+          W = __fmaf_rn(s.alpha, W, wd);
+          cnt = (int)min((long long)cd + (long long)cnt, 2147483647ll);
+          mask |= MASK_STORE, store = true;
+          if (a.forget_below > 0.f && !(W >= a.forget_below)) mask = MASK_STORE | MASK_FORGOT, W = 0.f, cnt = 0;
+        } else {
+          mask = 0;
+        }
+      } else if (a.forget_below > 0.f && !(W >= a.forget_below)) {
+        mask = 0, W = 0.f, cnt = 0;
+      }
     }
-    a.wsum_dst[(long long)s.row_dst * a.nvox + n] = W;
-    a.count_dst[(long long)s.row_dst * a.nvox + n] = cnt;
+    if (store) {
+      a.wsum_dst[(long long)s.row_dst * a.nvox + n] = W;
+      a.count_dst[(long long)s.row_dst * a.nvox + n] = cnt;
+    }
   }
 
   // ---- sums: item e is channel word e % G of voxel n0 + e / G
@@ -152,21 +191,29 @@ __global__ void __launch_bounds__(IVX_WARP_WG) volume_warp_kernel(const WarpArgs
     const int vmask = __shfl(mask, v);
     const float vfx = __shfl(fx, v), vfy = __shfl(fy, v), vfz = __shfl(fz, v);
     if (e >= items || n0 + v >= a.nvox) continue;
-    float4 val[8];
+    if (MERGE && !(vmask & MASK_STORE)) continue;                        // not merged: this voxel's sums are neither read nor written
+    float4 val[8], acc = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 8; ++c)                                          // every load before the first use
       val[c] = vmask >> c & 1 ? src[(long long)(uint32_t)(vbase + corner_off[c]) * a.G + c4] : float4{0.f, 0.f, 0.f, 0.f};
-    float4 acc = {0.f, 0.f, 0.f, 0.f};
+    if (MERGE) acc = vmask & MASK_FORGOT ? float4{0.f, 0.f, 0.f, 0.f} : dst[(n0 + v) * a.G + c4];      // S_d, issued with the corner loads
+    float4 smp = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < 8; ++c)
       if (vmask >> c & 1) {
         const float w = warp_weight(c, vfx, vfy, vfz);
-        acc.x = __fmaf_rn(w, val[c].x, acc.x);
-        acc.y = __fmaf_rn(w, val[c].y, acc.y);
-        acc.z = __fmaf_rn(w, val[c].z, acc.z);
-        acc.w = __fmaf_rn(w, val[c].w, acc.w);
+        smp.x = __fmaf_rn(w, val[c].x, smp.x);
+        smp.y = __fmaf_rn(w, val[c].y, smp.y);
+        smp.z = __fmaf_rn(w, val[c].z, smp.z);
+        smp.w = __fmaf_rn(w, val[c].w, smp.w);
       }
-    dst[(n0 + v) * a.G + c4] = acc;
+    if (MERGE) {                                                         // (forgotten: no corner bits and no S_d, so fma(alpha, +0, +0) = +0)
+      smp.x = __fmaf_rn(s.alpha, smp.x, acc.x);
+      smp.y = __fmaf_rn(s.alpha, smp.y, acc.y);
+      smp.z = __fmaf_rn(s.alpha, smp.z, acc.z);
+      smp.w = __fmaf_rn(s.alpha, smp.w, acc.w);
+    }
+    dst[(n0 + v) * a.G + c4] = smp;
   }
 }
 
@@ -176,15 +223,18 @@ bool finite_all(const float *p, const int n) {
   return true;
 }
 
-}  // namespace
-
-extern "C" int ivx_volume_warp_fwd(int32_t B, const int32_t *row_src, const int32_t *row_dst, const float *xform, const float *new_origin,
-                                   const float *voxel_size, float forget_below, int32_t R_src, int32_t R_dst, int32_t X, int32_t Y, int32_t Z, int32_t C,
-                                   const float *sum_src, const float *wsum_src, const int32_t *count_src, float *sum_dst, float *wsum_dst,
-                                   int32_t *count_dst, ivx_stream_t stream) {
-  const char *what = "ivx_volume_warp_fwd";
-  IVX_REQUIRE(row_src && row_dst && xform && new_origin && voxel_size && sum_src && wsum_src && count_src && sum_dst && wsum_dst && count_dst,
-              "%s: null argument (the five host lists and the six pools are all required)", what);
+// Both entries: every check, then the launches.  merge: origin_src and alpha are given and the memory rule is the merge's; else origin_src is
+// origin_dst, alpha is NULL and the pools must not overlap.
+int resample(const bool merge, const char *what, int32_t B, const int32_t *row_src, const int32_t *row_dst, const float *xform, const float *origin_dst,
+             const float *origin_src, const float *alpha, const float *voxel_size, float forget_below, int32_t R_src, int32_t R_dst, int32_t X, int32_t Y,
+             int32_t Z, int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src, float *sum_dst, float *wsum_dst,
+             int32_t *count_dst, ivx_stream_t stream) {
+  if (merge)
+    IVX_REQUIRE(row_src && row_dst && xform && origin_dst && origin_src && alpha && voxel_size && sum_src && wsum_src && count_src && sum_dst && wsum_dst && count_dst,
+                "%s: null argument (the seven host lists and the six pools are all required)", what);
+  else
+    IVX_REQUIRE(row_src && row_dst && xform && origin_dst && voxel_size && sum_src && wsum_src && count_src && sum_dst && wsum_dst && count_dst,
+                "%s: null argument (the five host lists and the six pools are all required)", what);
   IVX_REQUIRE(B > 0 && R_src > 0 && R_dst > 0 && X > 0 && Y > 0 && Z > 0 && C > 0, "%s: bad dims (B, R_src, R_dst, X, Y, Z and C must be positive)", what);
   IVX_REQUIRE(C % 4 == 0, "%s: C %% 4 must be 0 (the sums are read and written as 16-byte words)", what);
   const long long nvox = (long long)X * Y * Z;
@@ -194,18 +244,33 @@ extern "C" int ivx_volume_warp_fwd(int32_t B, const int32_t *row_src, const int3
     IVX_REQUIRE(row_src[b] >= 0 && row_src[b] < R_src, "%s: row_src[%d] = %d is outside [0, %d)", what, b, row_src[b], R_src);
     IVX_REQUIRE(row_dst[b] >= 0 && row_dst[b] < R_dst, "%s: row_dst[%d] = %d is outside [0, %d)", what, b, row_dst[b], R_dst);
   }
+  std::vector<int32_t> sorted(row_dst, row_dst + B);
+  std::sort(sorted.begin(), sorted.end());
   {
-    std::vector<int32_t> sorted(row_dst, row_dst + B);
-    std::sort(sorted.begin(), sorted.end());
     const auto dup = std::adjacent_find(sorted.begin(), sorted.end());
     IVX_REQUIRE(dup == sorted.end(), "%s: destination rows must be distinct (two samples on row %d)", what, dup == sorted.end() ? 0 : *dup);
   }
   {
     const uintptr_t s0 = (uintptr_t)sum_src, s1 = s0 + (uintptr_t)R_src * nvox * C * 4, d0 = (uintptr_t)sum_dst, d1 = d0 + (uintptr_t)R_dst * nvox * C * 4;
-    IVX_REQUIRE(s1 <= d0 || d1 <= s0, "%s: the source and destination sum pools overlap in memory (a resample cannot run in place)", what);
+    if (!merge) {
+      IVX_REQUIRE(s1 <= d0 || d1 <= s0, "%s: the source and destination sum pools overlap in memory (a resample cannot run in place)", what);
+    } else if (!(s1 <= d0 || d1 <= s0)) {
+      IVX_REQUIRE(s0 == d0 && R_src == R_dst,
+                  "%s: the source and destination sum pools overlap in memory without being the same pool (the same base and R_src == R_dst)", what);
+      for (int b = 0; b < B; ++b)
+        IVX_REQUIRE(!std::binary_search(sorted.begin(), sorted.end(), row_src[b]),
+                    "%s: with one pool as source and destination, row %d is named both as a source and as a destination", what, row_src[b]);
+    }
   }
-  IVX_REQUIRE(finite_all(xform, 12 * B) && finite_all(new_origin, 3 * B) && finite_all(voxel_size, 3),
-              "%s: xform, new_origin and voxel_size must be finite", what);
+  if (merge) {
+    IVX_REQUIRE(finite_all(xform, 12 * B) && finite_all(origin_dst, 3 * B) && finite_all(origin_src, 3 * B) && finite_all(voxel_size, 3),
+                "%s: xform, origin_dst, origin_src and voxel_size must be finite", what);
+    for (int b = 0; b < B; ++b)
+      IVX_REQUIRE(std::isfinite(alpha[b]) && alpha[b] > 0, "%s: alpha[%d] = %g must be finite and > 0", what, b, (double)alpha[b]);
+  } else {
+    IVX_REQUIRE(finite_all(xform, 12 * B) && finite_all(origin_dst, 3 * B) && finite_all(voxel_size, 3),
+                "%s: xform, new_origin and voxel_size must be finite", what);
+  }
   IVX_REQUIRE(voxel_size[0] > 0 && voxel_size[1] > 0 && voxel_size[2] > 0, "%s: voxel_size must be positive", what);
   IVX_REQUIRE(std::isfinite(forget_below) && forget_below >= 0, "%s: forget_below must be finite and >= 0", what);
 
@@ -221,10 +286,33 @@ extern "C" int ivx_volume_warp_fwd(int32_t B, const int32_t *row_src, const int3
       WarpSample &s = a.s[b];
       s.row_src = row_src[b0 + b], s.row_dst = row_dst[b0 + b];
       std::copy(xform + 12 * (b0 + b), xform + 12 * (b0 + b + 1), s.m);
-      std::copy(new_origin + 3 * (b0 + b), new_origin + 3 * (b0 + b + 1), s.origin);
+      std::copy(origin_dst + 3 * (b0 + b), origin_dst + 3 * (b0 + b + 1), s.origin);
+      std::copy(origin_src + 3 * (b0 + b), origin_src + 3 * (b0 + b + 1), s.origin_src);
+      s.alpha = merge ? alpha[b0 + b] : 1.0f;
     }
-    hipLaunchKernelGGL(volume_warp_kernel, dim3((unsigned)wgs, (unsigned)n), dim3(IVX_WARP_WG), 0, (hipStream_t)stream, a);
+    if (merge)
+      hipLaunchKernelGGL(volume_warp_kernel<true>, dim3((unsigned)wgs, (unsigned)n), dim3(IVX_WARP_WG), 0, (hipStream_t)stream, a);
+    else
+      hipLaunchKernelGGL(volume_warp_kernel<false>, dim3((unsigned)wgs, (unsigned)n), dim3(IVX_WARP_WG), 0, (hipStream_t)stream, a);
     IVX_CHECK_LAUNCH(what);
   }
   return IVX_OK;
+}
+
+}  // namespace
+
+extern "C" int ivx_volume_warp_fwd(int32_t B, const int32_t *row_src, const int32_t *row_dst, const float *xform, const float *new_origin,
+                                   const float *voxel_size, float forget_below, int32_t R_src, int32_t R_dst, int32_t X, int32_t Y, int32_t Z, int32_t C,
+                                   const float *sum_src, const float *wsum_src, const int32_t *count_src, float *sum_dst, float *wsum_dst,
+                                   int32_t *count_dst, ivx_stream_t stream) {
+  return resample(false, "ivx_volume_warp_fwd", B, row_src, row_dst, xform, new_origin, new_origin, nullptr, voxel_size, forget_below, R_src, R_dst, X, Y, Z, C,
+                  sum_src, wsum_src, count_src, sum_dst, wsum_dst, count_dst, stream);
+}
+
+extern "C" int ivx_volume_merge_fwd(int32_t B, const int32_t *row_src, const int32_t *row_dst, const float *xform, const float *origin_dst,
+                                    const float *origin_src, const float *alpha, const float *voxel_size, float forget_below, int32_t R_src, int32_t R_dst,
+                                    int32_t X, int32_t Y, int32_t Z, int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src,
+                                    float *sum_dst, float *wsum_dst, int32_t *count_dst, ivx_stream_t stream) {
+  return resample(true, "ivx_volume_merge_fwd", B, row_src, row_dst, xform, origin_dst, origin_src, alpha, voxel_size, forget_below, R_src, R_dst, X, Y, Z, C,
+                  sum_src, wsum_src, count_src, sum_dst, wsum_dst, count_dst, stream);
 }

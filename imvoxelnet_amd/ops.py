@@ -1565,6 +1565,47 @@ def check_rigid(T, name='transform'):
     return np.ascontiguousarray(A[:3], np.float32)
 
 
+def _rigid_list(transforms, B):
+    """The transforms of a resample of B rows: a host list of B 4x4 or 3x4 matrices, or one matrix alone for one row -> B float32 [3,4] arrays
+    through check_rigid."""
+    if isinstance(transforms, (str, bytes)) or not hasattr(transforms, '__len__'):
+        raise TypeError('transforms must be a host list of 4x4 or 3x4 matrices')
+    if B == 1 and (transforms.dim() == 2 if isinstance(transforms, torch.Tensor) else
+                   len(transforms) in (3, 4) and all(hasattr(r, '__len__') and len(r) == 4 and not any(hasattr(v, '__len__') for v in r) for r in transforms)):
+        transforms = [transforms]                               # one matrix alone for one row
+    if len(transforms) != B:
+        raise ValueError(f'transforms must hold one matrix per row: {B} rows, got {len(transforms)}')
+    return [check_rigid(T, f'transforms[{b}]') for b, T in enumerate(transforms)]
+
+
+def _grid_floats(B, voxel_size, **origins):
+    """The host grid arguments of a resample of B rows: every named origin as host floats [B,3] (or [3] for all) and voxel_size as three numbers,
+    finite, voxel_size > 0 -> ([float32 [B,3] per origin], float32 [3])."""
+    import numpy as np
+    names = ' and '.join(origins)
+    for name, o in origins.items():
+        if isinstance(o, torch.Tensor):
+            if o.is_cuda:
+                raise TypeError(f'{name} must be host floats [B,3] (it is checked and passed by value), got a device tensor')
+            origins[name] = o.detach().numpy()
+    try:
+        os_ = [np.asarray(o, np.float32) for o in origins.values()]
+        vs = np.asarray([float(v) for v in voxel_size], np.float32)
+    except (TypeError, ValueError):
+        raise TypeError(f'{names} must be host floats [B,3] and voxel_size three numbers') from None
+    os_ = [np.broadcast_to(o, (B, 3)) if o.shape == (3,) else o for o in os_]
+    if any(o.shape != (B, 3) for o in os_) or vs.shape != (3,):
+        raise ValueError(f'{names} must be [B,3] (or [3]) for {B} rows and voxel_size three numbers, got {", ".join(str(o.shape) for o in os_)} and {vs.shape}')
+    if not (all(np.isfinite(o).all() for o in os_) and np.isfinite(vs).all() and (vs > 0).all()):
+        raise ValueError(f'{names} must be finite and voxel_size finite and > 0, got {", ".join(str(o.tolist()) for o in os_)} and {vs.tolist()}')
+    return os_, vs
+
+
+def _check_forget(forget_below):
+    if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float)) or not (math.isfinite(forget_below) and forget_below >= 0):
+        raise ValueError(f'forget_below must be a finite number >= 0, got {forget_below!r}')
+
+
 def volume_warp(vol_sum, wsum, count, rows, transforms, new_origin, voxel_size, out, out_rows=None, forget_below=0.0):
     """Scenes that turn with their platform: resample rows of the state pools vol_sum [R,X,Y,Z,C] fp32 / wsum [R,X,Y,Z] fp32 / count [R,X,Y,Z]
     int32 under rigid transforms into the pools out = (sum, wsum, count) of the same X, Y, Z, C (ivx_volume_warp_fwd; include/imvoxel.h has the
@@ -1590,31 +1631,9 @@ def volume_warp(vol_sum, wsum, count, rows, transforms, new_origin, voxel_size, 
         raise ValueError('rows must name at least one row')
     B = len(rows)
     out_rows = list(rows) if out_rows is None else _host_ints(out_rows, 'out_rows', B)
-    if isinstance(transforms, (str, bytes)) or not hasattr(transforms, '__len__'):
-        raise TypeError('transforms must be a host list of 4x4 or 3x4 matrices')
-    if B == 1 and (transforms.dim() == 2 if isinstance(transforms, torch.Tensor) else
-                   len(transforms) in (3, 4) and all(hasattr(r, '__len__') and len(r) == 4 and not any(hasattr(v, '__len__') for v in r) for r in transforms)):
-        transforms = [transforms]                               # one matrix alone for one row
-    if len(transforms) != B:
-        raise ValueError(f'transforms must hold one matrix per row: {B} rows, got {len(transforms)}')
-    M = [check_rigid(T, f'transforms[{b}]') for b, T in enumerate(transforms)]
-    if isinstance(new_origin, torch.Tensor):
-        if new_origin.is_cuda:
-            raise TypeError('new_origin must be host floats [B,3] (it is checked and passed by value), got a device tensor')
-        new_origin = new_origin.detach().numpy()
-    try:
-        o = np.asarray(new_origin, np.float32)
-        vs = np.asarray([float(v) for v in voxel_size], np.float32)
-    except (TypeError, ValueError):
-        raise TypeError('new_origin must be host floats [B,3] and voxel_size three numbers') from None
-    if o.shape == (3,):
-        o = np.broadcast_to(o, (B, 3))
-    if o.shape != (B, 3) or vs.shape != (3,):
-        raise ValueError(f'new_origin must be [B,3] (or [3]) for {B} rows and voxel_size three numbers, got {o.shape} and {vs.shape}')
-    if not (np.isfinite(o).all() and np.isfinite(vs).all() and (vs > 0).all()):
-        raise ValueError(f'new_origin must be finite and voxel_size finite and > 0, got {o.tolist()} and {vs.tolist()}')
-    if isinstance(forget_below, bool) or not isinstance(forget_below, (int, float)) or not (math.isfinite(forget_below) and forget_below >= 0):
-        raise ValueError(f'forget_below must be a finite number >= 0, got {forget_below!r}')
+    M = _rigid_list(transforms, B)
+    (o,), vs = _grid_floats(B, voxel_size, new_origin=new_origin)
+    _check_forget(forget_below)
     if any(not 0 <= r < R for r in rows):
         raise ValueError(f'rows must be in [0, {R}), got {rows}')
     if osum.dim() != 5 or tuple(osum.shape[1:]) != (X, Y, Z, Cn):
@@ -1646,6 +1665,85 @@ def volume_warp(vol_sum, wsum, count, rows, transforms, new_origin, voxel_size, 
     check(fn(B, (C.c_int32 * B)(*rows), (C.c_int32 * B)(*out_rows), flat(np.stack(M)), flat(o), flat(vs), float(forget_below), R, Ro, X, Y, Z, Cn,
              _ptr(vol_sum), _ptr(wsum), _ptr(count), _ptr(osum), _ptr(owsum), _ptr(ocount), _stream()), 'ivx_volume_warp_fwd')
     return out
+
+
+def volume_merge_(vol_sum, wsum, count, rows, src, src_rows, transforms, new_origin, src_origin, voxel_size, alpha=1.0, forget_below=0.0):
+    """Scenes that become one: add rows of the state pools src = (sum, wsum, count) into rows of the pools vol_sum [R,X,Y,Z,C] fp32 / wsum [R,X,Y,Z]
+    fp32 / count [R,X,Y,Z] int32 of the same X, Y, Z, C under rigid transforms, in place (ivx_volume_merge_fwd; include/imvoxel.h has the
+    definition).  For sample b, row rows[b] takes  S += alpha * S_s, W += alpha * W_s, count += count_s  where (S_s, W_s, count_s) is the trilinear
+    read of row src_rows[b] of `src` at x_src = T x_dst, T = transforms[b] a host 4x4 or 3x4 matrix (check_rigid; one matrix alone for one row)
+    that maps a point of the destination grid's frame to the source grid's -- at the voxels where the source holds evidence (inside its grid,
+    W_s > 0); no other voxel is written.  new_origin / src_origin: the two grids' corner terms, host floats [B,3] (or [3] for all), which may
+    differ (a scrolled scene); voxel_size is common.  alpha: one float or B floats, finite and > 0.  forget_below > 0: a merged voxel whose new
+    weight sum is below it becomes unseen.  rows: B distinct host integers in [0, R); src_rows: B host integers (a source row may repeat).  `src`
+    may be the same pools (rows of one batch) as long as no row is both a source and a destination; any other shared memory raises.  Rows not
+    named are neither read nor written, and the source pools are read only.  Every check comes before the one C call, so a call that raises
+    changes nothing.  Returns (vol_sum, wsum, count)."""
+    import numpy as np
+    for t, name in ((vol_sum, 'vol_sum'), (wsum, 'wsum'), (count, 'count')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch.Tensor')
+    if not isinstance(src, (tuple, list)) or len(src) != 3 or any(not isinstance(t, torch.Tensor) for t in src):
+        raise TypeError('src must be a (sum, wsum, count) triple of torch.Tensors')
+    ssum, swsum, scount = src
+    if vol_sum.dim() != 5:
+        raise ValueError(f'vol_sum must be [R,X,Y,Z,C], got {tuple(vol_sum.shape)}')
+    R, X, Y, Z, Cn = (int(v) for v in vol_sum.shape)
+    rows = _host_ints(rows, 'rows')
+    if not rows:
+        raise ValueError('rows must name at least one row')
+    B = len(rows)
+    src_rows = _host_ints(src_rows, 'src_rows', B)
+    M = _rigid_list(transforms, B)
+    (o, so), vs = _grid_floats(B, voxel_size, new_origin=new_origin, src_origin=src_origin)
+    try:
+        al = np.asarray(alpha.tolist() if isinstance(alpha, torch.Tensor) else alpha, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        raise TypeError(f'alpha must be one number or {B} numbers, got {alpha!r}') from None
+    if isinstance(alpha, bool) or al.shape not in ((1,), (B,)) or (al.shape == (1,) and hasattr(alpha, '__len__') and B != 1):
+        raise ValueError(f'alpha must be one number or {B} numbers (one per row), got {alpha!r}')
+    al = np.broadcast_to(al, (B,)).astype(np.float32)
+    if not (np.isfinite(al).all() and (al > 0).all()):
+        raise ValueError(f'alpha must be finite and > 0 (after rounding to float32), got {al.tolist()}')
+    _check_forget(forget_below)
+    if len(set(rows)) != B:
+        raise ValueError(f'rows must be distinct (two samples on one destination row race), got {rows}')
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}')
+    if ssum.dim() != 5 or tuple(ssum.shape[1:]) != (X, Y, Z, Cn):
+        raise ValueError(f'src[0] must be [R_src,{X},{Y},{Z},{Cn}] like vol_sum, got {tuple(ssum.shape)}')
+    Rs = int(ssum.shape[0])
+    if any(not 0 <= r < Rs for r in src_rows):
+        raise ValueError(f'src_rows must be in [0, {Rs}), got {src_rows}')
+    if Cn % 4:
+        raise ValueError(f'vol_sum must have C % 4 == 0, got C = {Cn}')
+    for t, name, shape in ((wsum, 'wsum', (R, X, Y, Z)), (count, 'count', (R, X, Y, Z)), (swsum, 'src[1]', (Rs, X, Y, Z)), (scount, 'src[2]', (Rs, X, Y, Z))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'{name} must be {list(shape)} beside its sums, got {tuple(t.shape)}')
+    for t, name, dt in ((vol_sum, 'vol_sum', torch.float32), (wsum, 'wsum', torch.float32), (count, 'count', torch.int32), (ssum, 'src[0]', torch.float32),
+                        (swsum, 'src[1]', torch.float32), (scount, 'src[2]', torch.int32)):
+        _chk(t, name, dt)
+        if t.device != vol_sum.device:
+            raise ValueError(f'{name} must be on the device of vol_sum')
+    dst = (vol_sum, wsum, count)
+    same = all(a.data_ptr() == t.data_ptr() for a, t in zip(dst, src)) and Rs == R
+    if same:
+        both = sorted(set(rows) & set(src_rows))
+        if both:
+            raise ValueError(f'with the same pools as source and destination, rows {both} are named both as a source and as a destination')
+    else:
+        for a, an in zip(dst, ('vol_sum', 'wsum', 'count')):
+            for t, tn in zip(src, ('src[0]', 'src[1]', 'src[2]')):
+                a0, t0 = a.data_ptr(), t.data_ptr()
+                if a0 < t0 + t.numel() * 4 and t0 < a0 + a.numel() * 4:
+                    raise ValueError(f'{tn} shares memory with {an} without src being the same pools: a merge reads its source while it writes')
+    fn = getattr(_lib.lib(), 'ivx_volume_merge_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_merge_fwd (needs version 0.5.5)')
+    flat = lambda a: (C.c_float * a.size)(*np.ascontiguousarray(a, np.float32).reshape(-1).tolist())     # noqa: E731
+    check(fn(B, (C.c_int32 * B)(*src_rows), (C.c_int32 * B)(*rows), flat(np.stack(M)), flat(o), flat(so), flat(al), flat(vs), float(forget_below), Rs, R,
+             X, Y, Z, Cn, _ptr(ssum), _ptr(swsum), _ptr(scount), _ptr(vol_sum), _ptr(wsum), _ptr(count), _stream()), 'ivx_volume_merge_fwd')
+    return vol_sum, wsum, count
 
 
 _STATE_KIND = {torch.int32: _lib.STATE_COUNT, torch.float32: _lib.STATE_WSUM, torch.uint8: _lib.STATE_MASK, torch.bool: _lib.STATE_MASK}

@@ -69,6 +69,19 @@ opening one: x_opening = frame @ x_grid.  A warp is not a tick: nothing fades, b
 A plain scene raises NotImplementedError -- integer view counts cannot be resampled; decay=1.0 fades nothing and can.  The identity launches
 nothing; a session that never warps runs the code it ran before.  scroll keeps its behaviour, its refusal for anchor heads included.
 
+Merging scenes (SceneSession.merge(other, T=None, weight=1.0) / SceneBatch.merge(scenes, sources, Ts=None, weights=None)).  Every operation above acts
+on one scene; two scenes could not become one except by pushing every frame through the trunk again.  But a fading scene's (sum, weight sum, count)
+state is linear: two such states named in one frame add.  merge adds the other scene's state to this one's under a rigid T with x_other = T x_self
+(None: the two were opened in one common frame, T = inv(other.frame) @ self.frame) -- two robots or two passes that fused the same rooms, a
+relocalisation against a map built earlier, two rows of a batch that turn out to be one flat.  One launch (ops.volume_merge_, ivx_volume_merge_fwd,
+the MERGE instantiation of the resample kernel of csrc/volume_warp.hip; include/imvoxel.h has the definition) reads the other state by the warp's
+trilinear rule, in the OTHER grid -- the two grids keep their own origins, so a scrolled scene merges -- and adds it in place, scaled by `weight`, at
+the voxels where the other scene holds evidence; no other voxel is written, no scratch row exists, and this scene's forget_below applies to what was
+merged.  The host record follows the warp's rule: the other's extrinsics arrive as warped_extrinsic(E, T) behind this scene's own, n_views adds, the
+mean is recomputed when next asked for, and frame, origin and scrolled stay.  A merge is not a tick: nothing fades.  The other scene is unchanged.
+Evidence both scenes hold of the same views counts twice.  A batch merges rows of its own pools, all pairs of a call in one launch.  Plain and
+windowed scenes refuse.  A scene that never merges runs the code it ran before.
+
 Pixel maps (add_views(..., pixel_weights=..., depths=...); open_scene(meta, ..., depth_gate=(behind, front))).  A weight per view scales a whole
 frame, but a person walking through the scan, the robot's own arm, lens dirt and the black border after undistortion are properties of pixels, and
 an RGB-D camera knows which voxels on a pixel's ray lie behind the surface it shows.  Sessions that take weights (decay= or window=) take two
@@ -119,7 +132,10 @@ choosing which kept view of a window to evict; decay on windowed scenes; confide
 sessions and for simple_test; warping a plain session (integer view counts cannot be resampled: open it with decay=1.0); non-rigid transforms
 (a scale or a shear would not keep the voxel size; ops.check_rigid refuses them); scrolling by a fraction of a voxel (warp resamples instead);
 scrolling a model with an Anchor3DHead (its boxes would have to be translated; warp keeps the origin and needs no translation); scene batches across ranks; a model-level C handle for sessions
-(the state lives here, over the op-level ABI and the handle's sub-range calls).
+(the state lives here, over the op-level ABI and the handle's sub-range calls); merging windowed scenes (adopting the other's kept views into the
+ring); merging plain scenes (their integer counts cannot be resampled: open them with decay=1.0); merges between a session and a batch row, or
+across batches (ops.volume_merge_ takes any pools); several sources into one destination in one launch; de-duplicating views both scenes saw;
+estimating T (registration); saving a scene to disk; merging scenes on different devices or ranks.
 """
 import math
 
@@ -424,6 +440,41 @@ _PLAIN_WARP = ('warp: a plain {what} keeps integer view counts, which cannot be 
                'nothing fades) or with window=W')
 
 
+# ------------------------------------------------------------------ merging: the host rules
+_PLAIN_MERGE = ('merge: a plain {what} keeps integer view counts, which cannot be resampled; open it with decay=1.0 (a weight sum beside the sums, '
+                'nothing fades)')
+_WINDOW_MERGE = ('merge: a windowed {what} (window=W) keeps views, not a running state; adopting the kept views of another scene into the ring is '
+                 'out of scope: open it with decay=')
+
+
+def _check_merge_kind(window, fading, what):
+    """Only fading scenes merge: a windowed or a plain one (what: 'session' / 'batch', as it was opened) refuses."""
+    if window is not None:
+        raise NotImplementedError(_WINDOW_MERGE.format(what=what))
+    if not fading:
+        raise NotImplementedError(_PLAIN_MERGE.format(what=what))
+
+
+def _check_merge_weight(weight):
+    """weight of a merge -> float: one finite number > 0 (as float32 too: it reaches the kernel as alpha)."""
+    if isinstance(weight, bool) or not isinstance(weight, (int, float, np.integer, np.floating)):
+        raise TypeError(f'weight must be a number > 0, got {weight!r}')
+    weight = float(weight)
+    if not (math.isfinite(weight) and np.float32(weight) > 0 and np.isfinite(np.float32(weight))):
+        raise ValueError(f'weight must be finite and > 0, got {weight}')
+    return weight
+
+
+def _merge_transform(dst, src, T):
+    """T of a merge of the record src into the record dst (x_src = T x_dst) -> float64 [4,4]: the caller's, by the _check_warp rule, or for None
+    inv(src.frame) @ dst.frame in float64 -- the two scenes were opened in one common frame."""
+    if T is not None:
+        return _check_warp(T)
+    T = np.linalg.inv(src._frame) @ dst._frame
+    T[3] = (0, 0, 0, 1)
+    return T
+
+
 # ------------------------------------------------------------------ the two model calls around the lift
 def _trunk(m, img):
     """[V,3,H,W] -> FPN level 0 of these views.  The native handle's trunk sub-range is the same kernels with the same plans as
@@ -527,6 +578,19 @@ class _SceneRecord:
         self.meta['lidar2img']['extrinsic'], self._views = extrinsics, views
         self._frame = self._frame @ T
         self._stale = self._stale or self.n_views > 0
+
+    def _merged(self, other, T):
+        """A merge of the record `other` under T (x_other = T x_self) is in: the other's extrinsics, each by warped_extrinsic, count behind this
+        scene's own, in the other's order; the view counts add; an empty scene takes the other's image size and the shapes its meta lacks; the
+        mean is behind.  frame, origin and scrolled stay."""
+        self.meta['lidar2img']['extrinsic'] = self.meta['lidar2img']['extrinsic'] + [warped_extrinsic(e, T) for e in other.meta['lidar2img']['extrinsic']]
+        self.n_views += other.n_views
+        if self._hw is None:
+            self._hw = other._hw
+        for k in ('img_shape', 'ori_shape', 'pad_shape'):
+            if k not in self.meta and k in other.meta:
+                self.meta[k] = other.meta[k]
+        self._stale = True
 
     @property
     def scrolled(self):
@@ -932,6 +996,54 @@ class SceneSession(_SceneRecord):
         self._warp(T, extrinsics, views)
         return self
 
+    # ------------------------------------------------------------------ merging
+    def merge(self, other, T=None, weight=1.0):
+        """Add the fused state of another session to this one's: T is a host float 4x4 with x_other = T x_self -- it takes a point of this scene's
+        grid frame to the other's (two robots that fused the same rooms, a relocalisation against an earlier map).  T=None: the two scenes were
+        opened in one common frame, and T = inv(other.frame) @ self.frame in float64.  weight > 0 scales the other's evidence (alpha).
+        Both sessions must be fading (decay=; decay=1.0 fades nothing), open, on one device and of the same prepared model.  ONE
+        ops.volume_merge_ (ivx_volume_merge_fwd) reads the other's (sum, weight sum, count) trilinearly at T x and adds it in place where the other
+        holds evidence; each scene's grid keeps its own origin (a scrolled scene's differs), this session's forget_below applies to the merged
+        voxels, and nothing fades: a merge is not a tick.  The host record follows: meta['lidar2img']['extrinsic'] grows by
+        warped_extrinsic(E, T) of the other's extrinsics, in the other's order after this scene's own, n_views adds, and the mean is recomputed
+        when next asked for; frame, origin and scrolled stay.  `other` is unchanged and stays usable.  An empty `other` changes nothing and
+        launches nothing; an empty `self` starts its state from zero as its first add would, on the other's device, and takes the other's image
+        size; when both hold views their image sizes must agree.
+        Evidence that both scenes hold of the same views counts twice: the merge adds states and cannot know which views they share.
+        A plain session on either side raises NotImplementedError (open it with decay=1.0), so does a windowed one; `other is self` raises
+        ValueError.  A call that raises leaves both scenes as they were.  Returns self."""
+        self._check_open()
+        if not isinstance(other, SceneSession):
+            raise TypeError(f'merge takes another SceneSession, got {type(other).__name__}')
+        other._check_open()
+        if other is self:
+            raise ValueError('merge: other is self (a scene cannot be added to itself: the kernel reads its source while it writes)')
+        _check_merge_kind(self._window if self._window is not None else other._window, self._decay is not None and other._decay is not None, 'session')
+        if other._model is not self._model:
+            raise ValueError('merge: the two sessions must be of the same prepared model')
+        T = _merge_transform(self, other, T)
+        weight = _check_merge_weight(weight)
+        if self.n_views and other.n_views:
+            _check_size(other._hw, self._hw, 'scene')
+            if other._sum.device != self._sum.device:
+                raise ValueError(f'merge: the two scenes must be on one device, got {self._sum.device} and {other._sum.device}')
+        if other.n_views == 0:
+            return self
+        m = self._model
+        mine, fresh = (self._sum, self._wsum, self._count, self._mean, self._valid), False
+        if self.n_views == 0:                     # the state as the first add would start it: from zero, on the other's device
+            theirs = (other._sum, other._wsum, other._count, other._mean, other._valid)
+            fits = self._sum is not None and all(a.shape == b.shape and a.dtype == b.dtype and a.device == b.device for a, b in zip(mine, theirs))
+            mine = tuple(t.zero_() for t in mine) if fits else tuple(torch.zeros_like(t) for t in theirs)
+            fresh = not fits
+        ops.volume_merge_(*mine[:3], [0], (other._sum, other._wsum, other._count), [0], [T], m._new_origin(self.meta['lidar2img']['origin']).numpy()[None],
+                          m._new_origin(other.meta['lidar2img']['origin']).numpy()[None], m.voxel_size, alpha=weight, forget_below=self._forget)
+        self._sum, self._wsum, self._count, self._mean, self._valid = mine
+        if fresh:                                 # new buffers, perhaps on another device: what belonged to the old ones goes (each is made again when next needed)
+            self._twin = self._origin = self._crop = None
+        self._merged(other, T)
+        return self
+
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None,
                      lens=None, depth_frames=None, depth_scale=0.001, format=None, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
@@ -1199,6 +1311,55 @@ class SceneBatch:
                 pool.index_copy_(0, idx, part)
         for s, T, ext, views in moves:
             self._scenes[s]._warp(T, ext, views)
+        return self
+
+    def merge(self, scenes, sources, Ts=None, weights=None):
+        """SceneSession.merge between scenes of the batch: one destination index with one source index, or two lists of one length; scene
+        scenes[i] takes the state of scene sources[i] under Ts[i] (x_source = T x_destination; None: inv(frame(source)) @ frame(destination))
+        with weights[i] (None: 1).  Destinations are distinct, no index is both a destination and a source, a source may repeat.  All pairs go in
+        ONE ops.volume_merge_ in place on the pools, with no scratch: the pools are their own source, on disjoint rows.  The records follow the
+        session rule.  A source without views is skipped; a destination without views has its rows zeroed first.  Scenes not named are neither
+        read nor written.  Evidence two scenes hold of the same views counts twice.  A plain batch and a windowed batch raise
+        NotImplementedError.  A call that raises leaves every scene as it was."""
+        self._check_open()
+        one = isinstance(scenes, (int, np.integer)) and not isinstance(scenes, bool)
+        if one:
+            scenes, sources, Ts, weights = [scenes], [sources], (None if Ts is None else [Ts]), (None if weights is None else [weights])
+        if isinstance(scenes, torch.Tensor) or not hasattr(scenes, '__len__') or isinstance(sources, torch.Tensor) or not hasattr(sources, '__len__') \
+                or len(scenes) != len(sources) or not len(scenes):
+            raise ValueError(f'merge takes one destination index with one source index, or lists of both of one length, got {scenes!r} and {sources!r}')
+        P = len(scenes)
+        scenes, sources = [self._scene_index(s) for s in scenes], [self._scene_index(s) for s in sources]
+        if len(set(scenes)) != P:
+            raise ValueError(f'a scene can be the destination of one merge per call, got {scenes}')
+        both = sorted(set(scenes) & set(sources))
+        if both:
+            raise ValueError(f'scenes {both} are named both as a destination and as a source of one call')
+        for arg, name in ((Ts, 'Ts'), (weights, 'weights')):
+            if arg is not None and (isinstance(arg, (str, bytes)) or (isinstance(arg, torch.Tensor) and arg.is_cuda) or not hasattr(arg, '__len__') or len(arg) != P):
+                raise ValueError(f'{name} must be None or hold one entry per pair: {P} pairs, got {len(arg) if hasattr(arg, "__len__") else arg!r}')
+        _check_merge_kind(self._window, self._fading, 'batch')
+        Ts = [_merge_transform(self._scenes[d], self._scenes[s], None if Ts is None else Ts[i]) for i, (d, s) in enumerate(zip(scenes, sources))]
+        weights = [1.0] * P if weights is None else [_check_merge_weight(w) for w in weights]
+        pairs = [(d, s, T, w) for d, s, T, w in zip(scenes, sources, Ts, weights) if self._scenes[s].n_views]
+        if not pairs:
+            return self
+        m = self._model
+        origin = lambda s: (self._cam[s][0] if self._cam[s] is not None else m._new_origin(self._scenes[s].meta['lidar2img']['origin'])).float().numpy()      # noqa: E731
+        fresh = [d for d, _, _, _ in pairs if not self._scenes[d].n_views]
+        if fresh:                                 # what a `first` add would do to these rows (they hold nothing: no scene changes)
+            idx = torch.tensor(fresh, dtype=torch.int64).to(self._sum.device)
+            for pool in (self._sum, self._wsum, self._count):
+                pool.index_fill_(0, idx, 0)
+        state = (self._sum, self._wsum, self._count)
+        ops.volume_merge_(*state, [d for d, _, _, _ in pairs], state, [s for _, s, _, _ in pairs], [T for _, _, T, _ in pairs],
+                          np.stack([origin(d) for d, _, _, _ in pairs]), np.stack([origin(s) for _, s, _, _ in pairs]), m.voxel_size,
+                          alpha=[w for _, _, _, w in pairs], forget_below=self._forget)
+        for d, s, T, _ in pairs:
+            self._scenes[d]._merged(self._scenes[s], T)
+            if self._cam[d] is None:              # a scene with views has its host camera record (warp, scroll and the refresh read it): what its first add
+                meta = self._scenes[d].meta       # would have stored, by _camera_setup's rules at the lifts' stride of 4
+                self._cam[d] = (m._new_origin(meta['lidar2img']['origin']), torch.tensor([meta['img_shape'][0] // 4, meta['img_shape'][1] // 4], dtype=torch.int32))
         return self
 
     # ------------------------------------------------------------------ adding views

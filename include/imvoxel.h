@@ -48,7 +48,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * for yet, before its trunk runs; 502 = 0.5.2: ivx_image_prep_lens_u8 / ivx_map_prep_lens, the image pipeline through a lens model (undistortion
  * in the prep launch) and the cover / depth maps of the same geometry at feature resolution; 503 = 0.5.3: ivx_image_prep_fmt_u8 / ivx_yuv_matrix, the image pipeline on decoder pixel
  * formats (RGB, BGRA / RGBA, gray, NV12, YUYV) converted in the fetch of the prep launch; 540 = 0.5.4: ivx_volume_warp_fwd, the rigid out-of-place
- * resample of rows of the state pools, for scenes that turn with their platform) and the message of the last failing call on this
+ * resample of rows of the state pools, for scenes that turn with their platform; 550 = 0.5.5: ivx_volume_merge_fwd, the rigid in-place merge of
+ * rows of the state pools, for scenes that become one) and the message of the last failing call on this
  * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -981,6 +982,66 @@ int ivx_volume_warp_fwd(int32_t B, const int32_t *row_src /*host [B]*/, const in
                         const float *new_origin /*host [B,3]*/, const float *voxel_size /*host [3]*/, float forget_below, int32_t R_src, int32_t R_dst,
                         int32_t X, int32_t Y, int32_t Z, int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src,
                         float *sum_dst, float *wsum_dst, int32_t *count_dst, ivx_stream_t stream);
+
+/* (0.5.5) Rigid merge of rows of the state pools: the fused state of one scene is ADDED to another's under a rigid transform that relates their
+ * frames (two robots or two passes that fused the same rooms, a relocalisation against an earlier map, two rows of a batch that turn out to be one
+ * flat: scene.py, SceneSession.merge / SceneBatch.merge).  A fading state (sum, weight sum, count) is linear, so two states named in one frame add;
+ * the source is read by the trilinear rule of ivx_volume_warp_fwd -- the same kernel, a second instantiation of csrc/volume_warp.hip -- and added in
+ * place: no scratch row, voxels the source never saw are not rewritten, and the two grids may have different origins (a scrolled scene).  Like the
+ * warp it lies outside the reference-parity claims and is pinned to an fp64 reference written from the definition below (tests/ref_volume_merge.py).
+ *
+ * Definition.  Every operation is fp32, round-to-nearest, no contraction.  M = xform[b] [3,4] maps a point of the DESTINATION grid's frame to the
+ * SOURCE grid's frame: x_src = R x_dst + t.  For sample b and voxel (i,j,k) of destination row row_dst[b], reading source row row_src[b]:
+ *   1. centre   p_a = float(idx_a) * voxel_size_a + origin_dst[b]_a                           (warp step 1: the lift's voxel centre)
+ *   2. source   q_a = fma(M_a3, 1, fma(M_a2, p_z, fma(M_a1, p_y, M_a0 * p_x)))                (warp step 2: the same fma chain)
+ *   3. grid     g_a = (q_a - origin_src[b]_a) / voxel_size_a: the grid coordinate in the SOURCE grid.  The inside test !(g_a > -1 && g_a < N_a),
+ *               i0_a = floor(g_a) and f_a = g_a - i0_a are exactly warp step 3, taken against the source origin.
+ *   4. sample   S_s[c], W_s and cnt_s exactly as warp step 4: the same corner order and weights (w_x * w_y) * w_z; a corner outside the grid or
+ *               with w == 0 is not read; the fma chains start from +0; cnt_s is the maximum over the corners read.
+ *   5. merged?  The voxel is merged iff it is inside and W_s > 0 (the state's own "seen" rule).  Otherwise the destination voxel is NOT WRITTEN:
+ *               source evidence that is unseen, outside or NaN changes no bit of the destination.
+ *   6. add      S'[c] = fma(alpha_b, S_s[c], S_d[c]),   W' = fma(alpha_b, W_s, W_d),   cnt' = min(cnt_d + cnt_s, 2^31 - 1), formed in 64 bits.
+ *   7. forget   if forget_below > 0 && !(W' >= forget_below):  S' = +0, W' = +0, cnt' = 0     (the weighted lift's rule; it can only fire where
+ *               W_d was below the threshold, that is 0 in a session's state, and alpha * W_s is small: the session's invariant is kept)
+ *   8. store    S', W', cnt' into the destination voxel.  In place on the destination: a voxel reads only itself there, so there is no race.
+ *
+ * B            samples of this call
+ * row_src      HOST [B] int32: sample b reads row row_src[b] of the source pools (two samples may read one row)
+ * row_dst      HOST [B] int32: ... and adds into row row_dst[b] of the destination pools; distinct
+ * xform        HOST [B,3,4] fp32, finite; rigidity is NOT required here (ops.volume_merge_ checks it)
+ * origin_dst   HOST [B,3] fp32, finite: the corner term (the new_origin of the lifts) of the destination grid
+ * origin_src   HOST [B,3] fp32, finite: ... and of the source grid
+ * alpha        HOST [B] fp32, finite and > 0: the weight of the source's evidence
+ * voxel_size   HOST [3] fp32, finite and > 0, common to both grids
+ * forget_below >= 0, finite
+ * R_src, R_dst, X, Y, Z, C   the source / destination pools have R_src / R_dst rows of X*Y*Z voxels; C % 4 == 0
+ * sum_src, wsum_src, count_src   DEVICE [R_src,X,Y,Z,C] fp32 (16-byte aligned), [R_src,X,Y,Z] fp32, [R_src,X,Y,Z] int32, read only
+ * sum_dst, wsum_dst, count_dst   DEVICE the same with R_dst rows, read and written.  They may BE the source pools (the same base and R_src ==
+ *              R_dst: rows of one batch) as long as no row is named both as a source and as a destination; any other overlap is refused.
+ * The lists are host lists, as for ivx_volume_warp_fwd: everything is checked before any launch and nothing is uploaded (32 samples per launch).
+ *
+ * Properties.
+ *   Untouched.   Rows that no sample names are neither read nor written.  Unmerged voxels of named rows are not written and their sums are not
+ *                read (the weight sum and count of a voxel whose source point lies inside the grid are loaded beside the corners, before the
+ *                decision).  The source pools are read only.
+ *   Empty destination.  On an all-zero destination row, with alpha = 1 and origin_src == origin_dst, the row after the call equals bit for bit
+ *                what ivx_volume_warp_fwd writes for the same source, transform and forget_below -- on valid states (W = 0 implies S = 0, cnt = 0).
+ *   Identity.    M = I and equal origins on a grid where the chain is exact (dyadic voxel sizes, the origin on their lattice): every merged voxel
+ *                has one corner of weight 1, so S' = fma(alpha, S_s, S_d) -- with alpha = 1 the correctly rounded S_d + S_s, with alpha = 0.5
+ *                S_d + 0.5 * S_s, bit for bit -- W' by the same rule, and the counts add.
+ *   Error.       Against the exact value of steps 4 and 6 on the same i0 and f:
+ *                    |S' - exact| <= |alpha| * 11 * 2^-24 * sum_corners |w S_corner| + 2^-24 * |exact| + 2^-126
+ *                (the warp's derived K = 11 on the sample, one rounding of the final fma; tests/ref_volume_merge.py); the same for W'.  Counts are equal.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names this entry: everything ivx_volume_warp_fwd rejects (a null pointer; a
+ * non-positive B, R_src, R_dst, X, Y, Z or C; C % 4 != 0; X*Y*Z at or beyond 2^31; a row outside its pool; two samples on one destination row; sum
+ * pools that are not 16-byte aligned; a non-finite xform, origin or voxel_size; voxel_size <= 0; a negative or non-finite forget_below) with its
+ * memory rule replaced by: source and destination sum pools that overlap without being the same pool; with the same pool, a row named both as a
+ * source and as a destination.  And an alpha[b] that is not finite or not > 0.                                                                    */
+int ivx_volume_merge_fwd(int32_t B, const int32_t *row_src /*host [B]*/, const int32_t *row_dst /*host [B]*/, const float *xform /*host [B,3,4]*/,
+                         const float *origin_dst /*host [B,3]*/, const float *origin_src /*host [B,3]*/, const float *alpha /*host [B]*/,
+                         const float *voxel_size /*host [3]*/, float forget_below, int32_t R_src, int32_t R_dst, int32_t X, int32_t Y, int32_t Z,
+                         int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src, float *sum_dst, float *wsum_dst,
+                         int32_t *count_dst, ivx_stream_t stream);
 
 /* (0.5.1) View coverage: what would a candidate view add to a scene?  Every frame that reaches a streaming scene pays for the 2-D trunk, and
  * most frames of a 30 Hz camera look at voxels the scene has already fused.  Whether a pose adds anything depends only on the geometry and on
