@@ -25,6 +25,7 @@ SOURCES = [
     ('backproject.hip', ['-ffp-contract=off']),
     ('volume_scroll.hip', []),
     ('volume_warp.hip', ['-ffp-contract=off']),
+    ('volume_pack.hip', ['-ffp-contract=off']),
     ('view_coverage.hip', ['-ffp-contract=off']),
     ('anchor_tail.hip', ['-ffp-contract=off']),
     ('image_prep.hip', ['-ffp-contract=off']),

@@ -194,7 +194,7 @@ EXPORTS = ['ivx_conv_plan_query', 'ivx_conv_tile_info', 'ivx_model_plan_info', '
            'ivx_maxpool2d_fwd', 'ivx_maxpool2d_fwd_bf16', 'ivx_maxpool2d_fwd_fp8', 'ivx_global_avgpool_fwd', 'ivx_global_avgpool_fwd_bf16', 'ivx_upsample_trilinear2x_fwd', 'ivx_dcn_im2col_fwd', 'ivx_dcn_im2col_fwd_bf16', 'ivx_dcn_im2col_fwd_pair', 'ivx_nchw_to_nhwc', 'ivx_image_s2d_bf16', 'ivx_nhwc_to_nchw', 'ivx_backproject_mean_fwd', 'ivx_backproject_mean_fwd_amax', 'ivx_backproject_amax_blocks', 'ivx_backproject_mean_fwd_bf16', 'ivx_upsample_trilinear2x_fwd_bf16', 'ivx_backproject_sum_fwd', 'ivx_volume_normalize_fwd',
            'ivx_backproject_accum_fwd', 'ivx_backproject_accum_fwd_bf16', 'ivx_volume_mean_fwd', 'ivx_backproject_fwd_ex', 'ivx_backproject_gather_fwd',
            'ivx_backproject_lists_fwd', 'ivx_backproject_weighted_fwd', 'ivx_volume_wmean_fwd', 'ivx_volume_scroll_fwd', 'ivx_backproject_mapped_fwd',
-           'ivx_view_coverage_fwd', 'ivx_volume_warp_fwd', 'ivx_volume_merge_fwd',
+           'ivx_view_coverage_fwd', 'ivx_volume_warp_fwd', 'ivx_volume_merge_fwd', 'ivx_volume_pack_scratch_bytes', 'ivx_volume_pack_fwd', 'ivx_volume_unpack_fwd',
            'ivx_anchor_head_workspace_bytes', 'ivx_anchor_head_get_bboxes', 'ivx_fcos_head_workspace_bytes',
            'ivx_fcos_head_level_candidates', 'ivx_nms_workspace_bytes',
            'ivx_nms_bev', 'ivx_boxes_overlap_bev', 'ivx_aligned_3d_nms', 'ivx_aligned_3d_nms_workspace_bytes', 'ivx_aligned_3d_nms_ws', 'ivx_multiclass_nms_workspace_bytes', 'ivx_multiclass_nms_bev',
@@ -333,6 +333,11 @@ def lib():
         L.ivx_volume_warp_fwd.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(f32), C.POINTER(f32), C.POINTER(f32), f32] + [i32] * 6 + [vp] * 7
     if hasattr(L, 'ivx_volume_merge_fwd'):         # (0.5.5; an older build still loads: ops.volume_merge_ and the scenes' merge() then refuse)
         L.ivx_volume_merge_fwd.argtypes = [i32, C.POINTER(i32), C.POINTER(i32)] + [C.POINTER(f32)] * 5 + [f32] + [i32] * 6 + [vp] * 7
+    if hasattr(L, 'ivx_volume_pack_fwd'):          # (0.5.6; an older build still loads: ops.volume_pack / volume_unpack_ and the scenes' snapshot() / restore then refuse)
+        L.ivx_volume_pack_scratch_bytes.argtypes = [i32] * 4
+        L.ivx_volume_pack_scratch_bytes.restype = i64
+        L.ivx_volume_pack_fwd.argtypes = [i32, C.POINTER(i32)] + [i32] * 5 + [vp] * 3 + [i32, i32] + [vp] * 7
+        L.ivx_volume_unpack_fwd.argtypes = [i32, C.POINTER(i32), C.POINTER(i32), i32] + [vp] * 4 + [i32] * 6 + [vp] * 4
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -381,6 +381,21 @@ class ImVoxelNet(nn.Module):
         from .scene import SceneSession
         return SceneSession(self, meta, window=window, decay=decay, forget_below=forget_below, depth_gate=depth_gate)
 
+    def restore_scene(self, snapshot, device=None):
+        """A SceneSession opened as a scene.SceneSnapshot was taken (scene.snapshot(), batch.snapshot(scene), SceneSnapshot.load(path)): kind, decay,
+        forget_below, depth_gate, meta (intrinsic, origin, extrinsics, shapes, box type), scrolled, frame, n_views and image size are the
+        snapshot's, the (sum, weight sum, count) state is unpacked by ONE ops.volume_unpack_ (ivx_volume_unpack_fwd) on `device` (None: the
+        model's, else the current HIP device), and the mean is marked stale: the next volume() / detect() computes it.  A float32 snapshot
+        restores every bit of the state, so the session goes on -- add_views, scroll, warp, merge, detect -- exactly as the one it was taken
+        from.  ValueError when this model's grid, voxel size, channel count or sampling rule differs from the snapshot's.  Nothing checks that
+        this model's weights are those that fused the state.  Out of scope: windowed scenes, turning a plain snapshot into a fading scene."""
+        from .scene import SceneSession, _check_restore, _restored_meta
+        _check_restore(self, snapshot)
+        if snapshot.n_views and self._prepared_device is None:
+            self.prepare(torch.device(device) if device is not None else torch.device('cuda', torch.cuda.current_device()))
+        s = SceneSession(self, _restored_meta(snapshot), decay=snapshot.decay, forget_below=snapshot.forget_below, depth_gate=snapshot.depth_gate)
+        return s._restore(snapshot, device)
+
     def open_scenes(self, metas, window=None, decay=None, forget_below=0.0, depth_gate=None):
         """N streaming scenes that share their launches (scene.SceneBatch): per tick one trunk call over the new views of any subset of
         the scenes, one listed lift into the touched scenes' rows of the state pools, and detect() as one batched neck + head + NMS.

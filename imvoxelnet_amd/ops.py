@@ -1746,6 +1746,163 @@ def volume_merge_(vol_sum, wsum, count, rows, src, src_rows, transforms, new_ori
     return vol_sum, wsum, count
 
 
+_PACK_DT = {torch.float32: 0, torch.bfloat16: 1}      # the payload of a packed state: IVX_F32 (the sums, as words) | IVX_BF16 (the mean)
+
+
+def _pack_pools(vol_sum, count, rows, wsum):
+    """The checks the pack and the unpack share: pools vol_sum [R,X,Y,Z,C] fp32 / count [R,X,Y,Z] int32 (/ wsum [R,X,Y,Z] fp32) on one device, rows a
+    non-empty host list of distinct integers in [0, R) -> (rows, (R, X, Y, Z, C))."""
+    for t, name in ((vol_sum, 'vol_sum'), (count, 'count')) + (((wsum, 'wsum'),) if wsum is not None else ()):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch.Tensor')
+    if vol_sum.dim() != 5:
+        raise ValueError(f'vol_sum must be [R,X,Y,Z,C], got {tuple(vol_sum.shape)}')
+    R, X, Y, Z, Cn = (int(v) for v in vol_sum.shape)
+    rows = _host_ints(rows, 'rows')
+    if not rows:
+        raise ValueError('rows must name at least one row')
+    if len(set(rows)) != len(rows):
+        raise ValueError(f'rows must be distinct, got {rows}')
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}')
+    if Cn % 4:
+        raise ValueError(f'vol_sum must have C % 4 == 0, got C = {Cn}')
+    if X * Y * Z >= 2 ** 31:
+        raise ValueError(f'X*Y*Z must be below 2^31, got {X * Y * Z}')
+    if tuple(count.shape) != (R, X, Y, Z):
+        raise ValueError('count must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
+    if wsum is not None and tuple(wsum.shape) != (R, X, Y, Z):
+        raise ValueError('wsum must be [R,X,Y,Z] for vol_sum [R,X,Y,Z,C]')
+    return rows, (R, X, Y, Z, Cn)
+
+
+def _pack_on_device(vol_sum, count, wsum):
+    """... and the checks that end them: fp32 / int32, contiguous, on one HIP device."""
+    _chk(vol_sum, 'vol_sum')
+    _chk(count, 'count', torch.int32)
+    if count.device != vol_sum.device:
+        raise ValueError('count must be on the device of vol_sum')
+    if wsum is not None:
+        _chk(wsum, 'wsum')
+        if wsum.device != vol_sum.device:
+            raise ValueError('wsum must be on the device of vol_sum')
+
+
+def _pack_call(vol_sum, count, rows, wsum, dims, dt, cap, outs):
+    """One ivx_volume_pack_fwd; outs: (index, payload, wsum, count) device tensors or four Nones (cap == 0, the count-only form) -> n per row,
+    read back (the one host sync of a pack)."""
+    L = _lib.lib()
+    fn = getattr(L, 'ivx_volume_pack_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_pack_fwd (needs version 0.5.6)')
+    R, X, Y, Z, Cn = dims
+    B, dev = len(rows), vol_sum.device
+    nbytes = L.ivx_volume_pack_scratch_bytes(B, X, Y, Z)
+    if nbytes < 0:
+        raise ValueError(f'ivx_volume_pack_scratch_bytes refuses B = {B}, grid {X} x {Y} x {Z}')
+    scratch = torch.empty((nbytes // 4,), device=dev, dtype=torch.int32)
+    n_out = torch.empty((B,), device=dev, dtype=torch.int32)
+    check(fn(B, (C.c_int32 * B)(*rows), R, X, Y, Z, Cn, _ptr(vol_sum), _ptr(count), _ptr(wsum), dt, cap, *(_ptr(t) for t in outs), _ptr(n_out), _ptr(scratch),
+             _stream()), 'ivx_volume_pack_fwd')
+    return [int(v) for v in n_out.tolist()]
+
+
+def volume_pack_count(vol_sum, count, rows, wsum=None):
+    """Scene snapshots: how many voxels of rows of the state pools hold evidence (the count-only form of ivx_volume_pack_fwd; include/imvoxel.h has
+    the definition).  A voxel is kept iff its count word or its wsum word is non-zero, as raw 32-bit words.  rows: distinct host integers in [0, R).
+    Only the two counting launches run; the pools are read only.  -> list of ints, one per row."""
+    rows, dims = _pack_pools(vol_sum, count, rows, wsum)
+    _pack_on_device(vol_sum, count, wsum)
+    return _pack_call(vol_sum, count, rows, wsum, dims, 0, 0, (None,) * 4)
+
+
+def volume_pack(vol_sum, count, rows, wsum=None, dtype=torch.float32):
+    """Scene snapshots: the kept voxels of rows of the state pools vol_sum [R,X,Y,Z,C] fp32 / count [R,X,Y,Z] int32 (/ wsum [R,X,Y,Z] fp32) as
+    records in ascending flat voxel index (ivx_volume_pack_fwd; include/imvoxel.h has the definition).  It counts, reads the counts back (the one
+    host sync), allocates exactly max(n) records per row and packs.  dtype=torch.float32: the payload is the C sums, moved as words -- every bit
+    pattern survives; torch.bfloat16: the payload is the mean S / den (den the weight sum, or the count without wsum), rounded once.  rows:
+    distinct host integers in [0, R); rows not named are not read and the pools are read only.  -> per row (index int32 [n], payload [n,C], wsum
+    fp32 [n] or None, count int32 [n]) as device tensors (views of the call's buffers); a call whose rows are all unseen returns empty tensors
+    without a second call.  Every check comes before the C calls, so a call that raises changes nothing."""
+    rows, dims = _pack_pools(vol_sum, count, rows, wsum)
+    if dtype not in _PACK_DT:
+        raise TypeError(f'dtype must be torch.float32 (the sums as words) or torch.bfloat16 (the mean), got {dtype!r}')
+    _pack_on_device(vol_sum, count, wsum)
+    n = _pack_call(vol_sum, count, rows, wsum, dims, _PACK_DT[dtype], 0, (None,) * 4)
+    B, Cn, dev, cap = len(rows), dims[4], vol_sum.device, max(n)
+    outs = (torch.empty((B, cap), device=dev, dtype=torch.int32), torch.empty((B, cap, Cn), device=dev, dtype=dtype),
+            torch.empty((B, cap), device=dev, dtype=torch.float32) if wsum is not None else None, torch.empty((B, cap), device=dev, dtype=torch.int32))
+    if cap:
+        n2 = _pack_call(vol_sum, count, rows, wsum, dims, _PACK_DT[dtype], cap, outs)
+        if n2 != n:
+            raise _lib.IvxError(f'ivx_volume_pack_fwd: the pools changed between the count and the pack ({n} then {n2} kept voxels)')
+    return [tuple(None if t is None else t[b, :n[b]] for t in outs) for b in range(B)]
+
+
+def volume_unpack_(vol_sum, count, rows, records, wsum=None):
+    """Scene snapshots: write rows of the state pools from packed records (ivx_volume_unpack_fwd; include/imvoxel.h has the definition): for sample b,
+    voxel index[q] of row rows[b] takes record q of records[b] = (index int32 [n], payload [n,C] fp32 or bf16, wsum fp32 [n] or None, count int32
+    [n]) -- what volume_pack returns, as device tensors or host tensors / numpy arrays (a bf16 payload on the host may be its uint16 words) -- and
+    every other voxel of that row becomes unseen, all bits zero.  A bf16 payload restores S = float(m) * den.  The records carry a weight sum iff
+    the pools have one.  Checked on the host before the one C call: each index list is strictly ascending and inside [0, X*Y*Z) (device lists are
+    read back for it), dtypes, shapes and devices agree; a call that raises changes nothing.  Rows not named are neither read nor written.
+    Returns (vol_sum, count) or (vol_sum, wsum, count)."""
+    import numpy as np
+    rows, (R, X, Y, Z, Cn) = _pack_pools(vol_sum, count, rows, wsum)
+    if isinstance(records, torch.Tensor) or not hasattr(records, '__len__') or len(records) != len(rows):
+        raise ValueError(f'records must hold one (index, payload, wsum, count) per row: {len(rows)} rows')
+    B, dev, nvox = len(rows), vol_sum.device, X * Y * Z
+    recs, dtype = [], None
+    for b, rec in enumerate(records):
+        if isinstance(rec, torch.Tensor) or not hasattr(rec, '__len__') or len(rec) != 4:
+            raise ValueError(f'records[{b}] must be (index, payload, wsum or None, count)')
+        idx, pay, ws, cnt = (None if t is None else t if isinstance(t, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(t)) for t in rec)
+        if idx is None or pay is None or cnt is None:
+            raise ValueError(f'records[{b}]: index, payload and count are required')
+        if pay.dtype == torch.uint16:
+            pay = pay.view(torch.bfloat16)
+        if idx.dtype != torch.int32 or cnt.dtype != torch.int32 or pay.dtype not in _PACK_DT or (ws is not None and ws.dtype != torch.float32):
+            raise TypeError(f'records[{b}] must be (int32, float32 or bfloat16, float32 or None, int32), got ({idx.dtype}, {pay.dtype}, '
+                            f'{None if ws is None else ws.dtype}, {cnt.dtype})')
+        if dtype is not None and pay.dtype != dtype:
+            raise TypeError(f'the payloads of one call must share a dtype, got {dtype} and {pay.dtype}')
+        dtype = pay.dtype
+        n = int(idx.shape[0]) if idx.dim() == 1 else -1
+        if n < 0 or tuple(pay.shape) != (n, Cn) or tuple(cnt.shape) != (n,) or (ws is not None and tuple(ws.shape) != (n,)):
+            raise ValueError(f'records[{b}] must be index [n], payload [n,{Cn}], wsum [n] or None, count [n], got {tuple(idx.shape)}, {tuple(pay.shape)}, '
+                             f'{None if ws is None else tuple(ws.shape)}, {tuple(cnt.shape)}')
+        if (ws is None) != (wsum is None):
+            raise ValueError(f'records[{b}]: the records must carry a weight sum iff the pools have one (wsum=)')
+        for t in (idx, pay, ws, cnt):
+            if t is not None and t.is_cuda and t.device != dev:
+                raise ValueError(f'records[{b}] lies on {t.device}, the pools on {dev}')
+        if n:
+            host = idx.cpu().numpy().astype(np.int64)
+            if host[0] < 0 or host[-1] >= nvox or (np.diff(host) <= 0).any():
+                raise ValueError(f'records[{b}]: the indices must be strictly ascending inside [0, {nvox})')
+        recs.append((idx, pay, ws, cnt, n))
+    _pack_on_device(vol_sum, count, wsum)
+    fn = getattr(_lib.lib(), 'ivx_volume_unpack_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_unpack_fwd (needs version 0.5.6)')
+    ns = [r[4] for r in recs]
+    cap = max(ns)
+    bufs = (None,) * 4
+    if cap:
+        if B == 1 and all(t is None or (t.is_cuda and t.is_contiguous()) for t in recs[0][:4]):
+            bufs = recs[0][:4]                    # one row whose records are on the device already: they are the call's lists
+        else:                                     # [B,cap] lists, filled per row (host records: one upload each)
+            bufs = (torch.empty((B, cap), device=dev, dtype=torch.int32), torch.empty((B, cap, Cn), device=dev, dtype=dtype),
+                    torch.empty((B, cap), device=dev, dtype=torch.float32) if wsum is not None else None, torch.empty((B, cap), device=dev, dtype=torch.int32))
+            for b, rec in enumerate(recs):
+                for buf, t in zip(bufs, rec[:4]):
+                    if buf is not None and rec[4]:
+                        buf[b, :rec[4]].copy_(t)
+    check(fn(B, (C.c_int32 * B)(*rows), (C.c_int32 * B)(*ns), cap, _ptr(bufs[0]), _ptr(bufs[1]), _ptr(bufs[2]), _ptr(bufs[3]), _PACK_DT[dtype or torch.float32],
+             R, X, Y, Z, Cn, _ptr(vol_sum), _ptr(count), _ptr(wsum), _stream()), 'ivx_volume_unpack_fwd')
+    return (vol_sum, count) if wsum is None else (vol_sum, wsum, count)
+
+
 _STATE_KIND = {torch.int32: _lib.STATE_COUNT, torch.float32: _lib.STATE_WSUM, torch.uint8: _lib.STATE_MASK, torch.bool: _lib.STATE_MASK}
 MAX_COVERAGE_VIEWS = 256      # candidates per sample of one view_coverage call (the kernel's counters live in LDS)
 

@@ -82,6 +82,18 @@ mean is recomputed when next asked for, and frame, origin and scrolled stay.  A 
 Evidence both scenes hold of the same views counts twice.  A batch merges rows of its own pools, all pairs of a call in one launch.  Plain and
 windowed scenes refuse.  A scene that never merges runs the code it ran before.
 
+Scene snapshots (SceneSession.snapshot(dtype) / model.restore_scene(snapshot) / SceneBatch.snapshot(scene) / SceneBatch.restore(scene, snapshot);
+SceneSnapshot.save / load).  Everything above happens inside one process, on one device, in one kind of container.  A snapshot is the fused state of a
+plain or fading scene as HOST data: a state row is large (26 / 54 / 170 MB of fp32 at the ScanNet-fast / ScanNet-v1 / KITTI grids) and partly unseen --
+a single frustum, a scrolled grid and a faded scene leave all-zero voxels -- so ONE ordered stream compaction (ops.volume_pack, ivx_volume_pack_fwd,
+csrc/volume_pack.hip; include/imvoxel.h has the definition) keeps the voxels whose count or weight-sum word is non-zero, in ascending voxel order, and
+only those records cross the link, beside the scene's host record (kind, decay, threshold, gate, grid, meta, views, scrolled, frame).  restore unpacks
+them into a whole row in one launch (ops.volume_unpack_).  The float32 payload is the sums as words: the restored (sum, weight sum, count) are the
+original's bit for bit -- the state's invariant that unseen voxels hold all-zero sums is what makes dropping them exact -- so a restored scene goes on
+exactly as the original would.  The bfloat16 payload is the mean, half the bytes, sums within (2^-8 + 2^-22) |S|.  A snapshot does not remember its
+container: a session's opens as a batch row and a batch row's as a session, on any device, after a restart (.npz, loaded with allow_pickle=False and
+validated before it is believed).  A scene that never snapshots runs the code it ran before.
+
 Pixel maps (add_views(..., pixel_weights=..., depths=...); open_scene(meta, ..., depth_gate=(behind, front))).  A weight per view scales a whole
 frame, but a person walking through the scan, the robot's own arm, lens dirt and the black border after undistortion are properties of pixels, and
 an RGB-D camera knows which voxels on a pixel's ray lie behind the surface it shows.  Sessions that take weights (decay= or window=) take two
@@ -135,7 +147,10 @@ scrolling a model with an Anchor3DHead (its boxes would have to be translated; w
 (the state lives here, over the op-level ABI and the handle's sub-range calls); merging windowed scenes (adopting the other's kept views into the
 ring); merging plain scenes (their integer counts cannot be resampled: open them with decay=1.0); merges between a session and a batch row, or
 across batches (ops.volume_merge_ takes any pools); several sources into one destination in one launch; de-duplicating views both scenes saw;
-estimating T (registration); saving a scene to disk; merging scenes on different devices or ranks.
+estimating T (registration); saving a scene to disk other than through a snapshot; merging scenes on different devices or ranks directly (snapshot
+one and restore it beside the other); snapshots of windowed scenes (the state is the feature ring, a plain copy); merge taking a snapshot directly
+(restore it, then merge); turning a plain snapshot into a fading scene; compression of a snapshot beyond the bf16 mean; any check that the weights of
+the restoring model are those that fused the state.
 """
 import math
 
@@ -473,6 +488,242 @@ def _merge_transform(dst, src, T):
     T = np.linalg.inv(src._frame) @ dst._frame
     T[3] = (0, 0, 0, 1)
     return T
+
+
+# ------------------------------------------------------------------ snapshots: a scene's fused state as host data
+SNAPSHOT_FORMAT = 1
+LIBRARY_VERSION = 560                             # the library version that wrote a snapshot (ivx_version() of the 0.5.6 entries)
+_WINDOW_SNAPSHOT = ('snapshot: a windowed {what} (window=W) keeps views, not a running state; its state is the feature ring, a plain copy with no kernel, '
+                    'which is out of scope: open it with decay= or plain')
+_SNAP_SCALARS = ('format', 'version', 'kind', 'decay', 'forget_below', 'channels', 'sampling', 'n_views', 'box_type', 'payload_dtype')
+_SNAP_ARRAYS = ('index', 'payload', 'count', 'wsum', 'depth_gate', 'grid', 'voxel_size', 'intrinsic', 'origin', 'extrinsics', 'img_shape', 'ori_shape', 'pad_shape',
+                'hw', 'scrolled', 'frame')
+
+
+class SceneSnapshot:
+    """The fused state of one plain or fading scene as HOST data: the packed records of the voxels that hold evidence (ops.volume_pack) and the
+    scene's host record.  No device buffer, no model reference: a snapshot outlives the process, the device and the container (a SceneSession or a
+    row of a SceneBatch) it was taken from.  scene.snapshot() / batch.snapshot(scene) make one, model.restore_scene(snapshot) / batch.restore(scene,
+    snapshot) open a scene from one, save(path) / SceneSnapshot.load(path) move it through an .npz file.
+
+    Records (numpy, n_seen of them, in ascending flat voxel index n = (i*Y + j)*Z + k): index int32 [n]; payload [n,C] -- float32, the sums, every
+    bit as it was, or uint16, the bf16 words of the mean S / den (dtype=torch.bfloat16: half the bytes; restored sums lie within (2^-8 + 2^-22) |S|);
+    count int32 [n]; wsum float32 [n] (a fading scene; None for a plain one).
+    The scene: kind ('plain' / 'fading'), decay, forget_below, depth_gate (None or (behind, front)); grid (X, Y, Z), channels C, voxel_size and the
+    sampling rule of the model that fused it; the meta's lidar2img intrinsic, origin and extrinsics [V,4,4]; img_shape / ori_shape / pad_shape when
+    the meta had them; hw, the padded image size of the views; n_views, scrolled, frame; box_type, the name of the meta's box_type_3d class (None:
+    the head's default); payload_dtype, version (the library's) and format.  Other keys of the meta are not kept.
+    nbytes: the bytes of the records; n_seen; seen_fraction = n_seen / (X*Y*Z).
+
+    A snapshot built from arrays -- by hand, or by load -- is validated before it is believed: ValueError names what is wrong.  load reads with
+    allow_pickle=False, so nothing in a file is executed.
+    Out of scope: windowed scenes; merge taking a snapshot directly (restore it, then merge); turning a plain snapshot into a fading scene;
+    compression beyond the bf16 mean; any check that the weights of the restoring model are those that fused the state."""
+
+    def __init__(self, index, payload, count, wsum=None, *, kind, grid, channels, voxel_size, sampling, intrinsic, origin, extrinsics=None, decay=None,
+                 forget_below=0.0, depth_gate=None, img_shape=None, ori_shape=None, pad_shape=None, hw=None, n_views=0, scrolled=(0, 0, 0), frame=None,
+                 box_type=None, version=LIBRARY_VERSION, format=SNAPSHOT_FORMAT):
+        opt = lambda a, dt: None if a is None else np.ascontiguousarray(a, dt)      # noqa: E731
+        self.index, self.payload, self.count, self.wsum = np.ascontiguousarray(index), np.ascontiguousarray(payload), np.ascontiguousarray(count), opt(wsum, None)
+        self.kind, self.decay, self.forget_below = kind, (None if decay is None else float(decay)), float(forget_below)
+        self.depth_gate = None if depth_gate is None else tuple(float(v) for v in depth_gate)
+        self.grid, self.channels = tuple(int(v) for v in grid), int(channels)
+        self.voxel_size, self.sampling = tuple(float(v) for v in voxel_size), sampling
+        self.intrinsic, self.origin = np.ascontiguousarray(intrinsic), np.ascontiguousarray(origin)
+        self.extrinsics = np.zeros((0, 4, 4), np.float32) if extrinsics is None or len(extrinsics) == 0 else np.ascontiguousarray(extrinsics)
+        self.img_shape, self.ori_shape, self.pad_shape, self.hw = (None if v is None else tuple(int(x) for x in v) for v in (img_shape, ori_shape, pad_shape, hw))
+        self.n_views, self.scrolled = int(n_views), tuple(int(v) for v in scrolled)
+        self.frame = np.eye(4) if frame is None else np.ascontiguousarray(frame, np.float64)
+        self.box_type, self.version, self.format = box_type, int(version), int(format)
+        self._validate()
+
+    def _validate(self):
+        """ValueError that names what is wrong with this snapshot; nothing of it is used before this has passed."""
+        if self.format != SNAPSHOT_FORMAT:
+            raise ValueError(f'snapshot: format {self.format} is not the format {SNAPSHOT_FORMAT} this version reads')
+        if self.kind not in ('plain', 'fading'):
+            raise ValueError(f"snapshot: kind must be 'plain' or 'fading', got {self.kind!r}")
+        if self.sampling not in ('nearest', 'bilinear'):
+            raise ValueError(f"snapshot: sampling must be 'nearest' or 'bilinear', got {self.sampling!r}")
+        if len(self.grid) != 3 or any(v < 1 for v in self.grid) or self.grid[0] * self.grid[1] * self.grid[2] >= 2 ** 31:
+            raise ValueError(f'snapshot: grid must be three positive sizes with X*Y*Z below 2^31, got {self.grid}')
+        if self.channels < 4 or self.channels % 4:
+            raise ValueError(f'snapshot: channels must be a positive multiple of 4, got {self.channels}')
+        if len(self.voxel_size) != 3 or not all(math.isfinite(v) and v > 0 for v in self.voxel_size):
+            raise ValueError(f'snapshot: voxel_size must be three finite numbers > 0, got {self.voxel_size}')
+        if (self.kind == 'fading') != (self.decay is not None) or (self.decay is not None and not 0 < self.decay <= 1):
+            raise ValueError(f'snapshot: a fading scene has a decay in (0, 1] and a plain one has none, got kind {self.kind!r} with decay {self.decay!r}')
+        if not (math.isfinite(self.forget_below) and self.forget_below >= 0) or (self.kind == 'plain' and self.forget_below != 0):
+            raise ValueError(f'snapshot: forget_below must be finite and >= 0 (0 on a plain scene), got {self.forget_below}')
+        if self.depth_gate is not None and (len(self.depth_gate) != 2 or self.kind == 'plain' or not all(v >= 0 for v in self.depth_gate)):
+            raise ValueError(f'snapshot: depth_gate must be None or (behind, front), both >= 0, on a fading scene, got {self.depth_gate}')
+        n, nvox = (int(self.index.shape[0]) if self.index.ndim == 1 else -1), self.grid[0] * self.grid[1] * self.grid[2]
+        if n < 0 or self.index.dtype != np.int32:
+            raise ValueError(f'snapshot: index must be int32 [n], got {self.index.dtype} {self.index.shape}')
+        if self.payload.dtype not in (np.float32, np.uint16):
+            raise ValueError(f'snapshot: payload must be float32 (the sums) or uint16 (bf16 words of the mean), got {self.payload.dtype}')
+        if self.payload.shape != (n, self.channels):
+            raise ValueError(f'snapshot: payload must be [{n},{self.channels}] (one row of C = {self.channels} channels per index), got {self.payload.shape}')
+        if self.count.dtype != np.int32 or self.count.shape != (n,):
+            raise ValueError(f'snapshot: count must be int32 [{n}], got {self.count.dtype} {self.count.shape}')
+        if (self.wsum is not None) != (self.kind == 'fading'):
+            raise ValueError(f'snapshot: a fading scene has a weight sum per record and a plain one has none (kind {self.kind!r})')
+        if self.wsum is not None and (self.wsum.dtype != np.float32 or self.wsum.shape != (n,)):
+            raise ValueError(f'snapshot: wsum must be float32 [{n}], got {self.wsum.dtype} {self.wsum.shape}')
+        if n and (self.index[0] < 0 or self.index[-1] >= nvox or (np.diff(self.index.astype(np.int64)) <= 0).any()):
+            raise ValueError(f'snapshot: index must be strictly ascending inside [0, {nvox})')
+        if self.intrinsic.dtype != np.float32 or self.intrinsic.ndim != 2 or min(self.intrinsic.shape) < 3 or not np.isfinite(self.intrinsic).all():
+            raise ValueError(f'snapshot: intrinsic must be a finite float32 matrix of at least 3x3, got {self.intrinsic.dtype} {self.intrinsic.shape}')
+        if self.origin.shape != (3,) or not np.isfinite(np.asarray(self.origin, np.float64)).all():
+            raise ValueError(f'snapshot: origin must be three finite numbers, got shape {self.origin.shape}')
+        if self.extrinsics.dtype != np.float32 or self.extrinsics.ndim != 3 or self.extrinsics.shape[1:] != (4, 4) or not np.isfinite(self.extrinsics).all():
+            raise ValueError(f'snapshot: extrinsics must be finite float32 [V,4,4], got {self.extrinsics.dtype} {self.extrinsics.shape}')
+        if self.n_views < 0 or self.extrinsics.shape[0] != self.n_views:
+            raise ValueError(f'snapshot: {self.extrinsics.shape[0]} extrinsics for n_views = {self.n_views}')
+        if (n != 0 or self.hw is not None) if self.n_views == 0 else self.hw is None:
+            raise ValueError(f'snapshot: a scene without views has no records and no image size, one with views has an image size (n_views {self.n_views}, '
+                             f'{n} records, hw {self.hw})')
+        if self.n_views and (self.img_shape is None or self.ori_shape is None):
+            raise ValueError('snapshot: a scene with views knows its img_shape and ori_shape')
+        if self.frame.shape != (4, 4) or not np.isfinite(self.frame).all():
+            raise ValueError(f'snapshot: frame must be a finite 4x4 matrix, got shape {self.frame.shape}')
+        if len(self.scrolled) != 3:
+            raise ValueError(f'snapshot: scrolled must be three integers, got {self.scrolled}')
+        for name in ('img_shape', 'ori_shape', 'pad_shape', 'hw'):
+            v = getattr(self, name)
+            if v is not None and (len(v) not in ((2,) if name == 'hw' else (2, 3)) or any(x < 1 for x in v)):
+                raise ValueError(f'snapshot: {name} must be None or positive sizes, got {v}')
+        if self.box_type is not None and not isinstance(self.box_type, str):
+            raise ValueError(f'snapshot: box_type must be None or the name of a box class, got {self.box_type!r}')
+
+    @property
+    def payload_dtype(self):
+        """'float32' (the sums, as words) or 'bfloat16' (the mean)."""
+        return 'float32' if self.payload.dtype == np.float32 else 'bfloat16'
+
+    @property
+    def n_seen(self):
+        return int(self.index.shape[0])
+
+    @property
+    def seen_fraction(self):
+        return self.n_seen / float(self.grid[0] * self.grid[1] * self.grid[2])
+
+    @property
+    def nbytes(self):
+        """The bytes of the packed records."""
+        return int(sum(a.nbytes for a in (self.index, self.payload, self.count, self.wsum) if a is not None))
+
+    def records(self):
+        """(index, payload, wsum or None, count): the record tuple of ops.volume_unpack_."""
+        return self.index, self.payload, self.wsum, self.count
+
+    def save(self, path):
+        """Write the snapshot to `path` as an uncompressed .npz of plain arrays (no pickled object).  A field that is None is left out.  Returns path."""
+        out = {k: np.asarray(getattr(self, k)) for k in _SNAP_SCALARS + _SNAP_ARRAYS if getattr(self, k) is not None}
+        with open(path, 'wb') as f:
+            np.savez(f, **out)
+        return path
+
+    @classmethod
+    def load(cls, path):
+        """Read a snapshot written by save.  allow_pickle=False: a file that holds a pickled object raises ValueError and nothing in it is executed;
+        the result is validated like any snapshot built from arrays."""
+        try:
+            z = np.load(path, allow_pickle=False)
+        except ValueError as e:                   # (a bare pickle instead of an archive)
+            raise ValueError(f'snapshot {path}: not an .npz archive of plain arrays ({e})') from None
+        if not hasattr(z, 'files'):
+            raise ValueError(f'snapshot {path}: not an .npz archive')
+        with z:
+            unknown = sorted(set(z.files) - set(_SNAP_SCALARS + _SNAP_ARRAYS))
+            missing = sorted({'format', 'kind', 'index', 'payload', 'count', 'grid', 'channels', 'voxel_size', 'sampling', 'intrinsic', 'origin'} - set(z.files))
+            if unknown or missing:
+                raise ValueError(f'snapshot {path}: not a scene snapshot (missing fields {missing}, unknown fields {unknown})')
+            try:
+                d = {k: z[k] for k in z.files}
+            except ValueError as e:               # numpy's refusal of an object array
+                raise ValueError(f'snapshot {path}: a field holds a pickled object, which is never loaded ({e})') from None
+        if int(d['format']) != SNAPSHOT_FORMAT:
+            raise ValueError(f'snapshot {path}: format {int(d["format"])} is not the format {SNAPSHOT_FORMAT} this version reads')
+        for k in _SNAP_SCALARS:
+            if k in d:
+                if d[k].ndim != 0:
+                    raise ValueError(f'snapshot {path}: {k} must be a scalar, got shape {d[k].shape}')
+                d[k] = d[k].item()
+        d.pop('payload_dtype', None)              # (told by the payload's own dtype)
+        return cls(d.pop('index'), d.pop('payload'), d.pop('count'), d.pop('wsum', None), **d)
+
+
+_BOX_TYPES = ('LiDARInstance3DBoxes', 'DepthInstance3DBoxes')
+
+
+def _snapshot_of(rec, model, records, channels):
+    """The SceneSnapshot of the record `rec` of a plain or fading scene of `model` with the host records (index, payload, wsum, count) as numpy."""
+    l2i, bt = rec.meta['lidar2img'], rec.meta.get('box_type_3d')
+    index, payload, wsum, count = records
+    return SceneSnapshot(index, payload, count, wsum, kind='plain' if rec._decay is None else 'fading', decay=rec._decay, forget_below=rec._forget,
+                         depth_gate=rec._gate, grid=model.n_voxels, channels=channels, voxel_size=model.voxel_size, sampling=getattr(model, 'sampling', 'nearest'),
+                         intrinsic=np.array(l2i['intrinsic']), origin=np.array(l2i['origin']), extrinsics=[np.asarray(e) for e in l2i['extrinsic']],
+                         img_shape=rec.meta.get('img_shape'), ori_shape=rec.meta.get('ori_shape'), pad_shape=rec.meta.get('pad_shape'), hw=rec._hw,
+                         n_views=rec.n_views, scrolled=rec._scrolled, frame=rec._frame.copy(), box_type=None if bt is None else getattr(bt, '__name__', str(bt)),
+                         version=ops._lib.lib().ivx_version())
+
+
+def _host_records(recs, channels, dtype, fading):
+    """The device records of ops.volume_pack (None: an empty scene) -> numpy (index, payload, wsum, count): the copy to the host of n records only."""
+    if recs is None:
+        pay = np.zeros((0, channels), np.float32 if dtype == torch.float32 else np.uint16)
+        return np.zeros((0,), np.int32), pay, (np.zeros((0,), np.float32) if fading else None), np.zeros((0,), np.int32)
+    index, payload, wsum, count = recs
+    payload = payload.cpu().numpy() if payload.dtype == torch.float32 else payload.view(torch.int16).cpu().numpy().view(np.uint16)
+    return index.cpu().numpy(), payload, (None if wsum is None else wsum.cpu().numpy()), count.cpu().numpy()
+
+
+def _check_snapshot_dtype(dtype):
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise TypeError(f'dtype must be torch.float32 (the sums, every bit) or torch.bfloat16 (the mean), got {dtype!r}')
+
+
+def _check_restore(model, snap, fading=None, what='model'):
+    """A snapshot against the model that is to restore it (and, fading not None, against the kind of the batch): ValueError names the difference."""
+    if not isinstance(snap, SceneSnapshot):
+        raise TypeError(f'restore takes a SceneSnapshot, got {type(snap).__name__}')
+    snap._validate()
+    if tuple(model.n_voxels) != snap.grid or tuple(np.float32(model.voxel_size)) != tuple(np.float32(snap.voxel_size)):
+        raise ValueError(f'restore: the {what} has grid {tuple(model.n_voxels)} with voxel size {tuple(model.voxel_size)}, the snapshot {snap.grid} with {snap.voxel_size}')
+    if int(model.neck.out_channels) != snap.channels:
+        raise ValueError(f'restore: the {what} lifts {int(model.neck.out_channels)} channels per voxel, the snapshot holds {snap.channels}')
+    if getattr(model, 'sampling', 'nearest') != snap.sampling:
+        raise ValueError(f"restore: the model samples by the {getattr(model, 'sampling', 'nearest')!r} rule, the snapshot was fused by the {snap.sampling!r} rule")
+    if fading is not None and fading != (snap.kind == 'fading'):
+        raise ValueError(f"restore: a {snap.kind} snapshot into a {'fading' if fading else 'plain'} batch (the kind must match; turning one into the other is out of scope)")
+
+
+def _restored_meta(snap):
+    """The scene meta a snapshot describes (without extrinsics: open_scene's form)."""
+    from . import boxes
+    meta = dict(lidar2img=dict(intrinsic=snap.intrinsic.copy(), origin=snap.origin.copy()))
+    for k in ('img_shape', 'ori_shape', 'pad_shape'):
+        if getattr(snap, k) is not None:
+            meta[k] = getattr(snap, k)
+    if snap.box_type is not None:
+        if snap.box_type not in _BOX_TYPES:
+            raise ValueError(f'restore: unknown box type {snap.box_type!r} (known: {_BOX_TYPES})')
+        meta['box_type_3d'] = getattr(boxes, snap.box_type)
+    return meta
+
+
+def _adopt(rec, snap):
+    """The record takes the host fields of a snapshot: extrinsics, view count, image size, scrolled, frame, origin and shapes; the mean is behind."""
+    meta = _restored_meta(snap)
+    rec.meta['lidar2img'] = dict(meta['lidar2img'], extrinsic=[e.copy() for e in snap.extrinsics])
+    for k in ('img_shape', 'ori_shape', 'pad_shape', 'box_type_3d'):
+        if k in meta:
+            rec.meta[k] = meta[k]
+    rec.n_views, rec._hw, rec._stale = snap.n_views, snap.hw, snap.n_views > 0
+    rec._views, rec._next_id = [], snap.n_views
+    rec._scrolled, rec._frame = snap.scrolled, snap.frame.copy()
 
 
 # ------------------------------------------------------------------ the two model calls around the lift
@@ -1044,6 +1295,42 @@ class SceneSession(_SceneRecord):
         self._merged(other, T)
         return self
 
+    # ------------------------------------------------------------------ snapshots
+    def snapshot(self, dtype=torch.float32):
+        """The scene as host data (SceneSnapshot): ONE ops.volume_pack (ivx_volume_pack_fwd) compacts the voxels that hold evidence, in ascending
+        voxel order, and only those n records are copied to the host, beside the scene's host record.  dtype=torch.float32 keeps every bit of the
+        state: model.restore_scene(snapshot) holds the (sum, weight sum, count) this session holds, bit for bit.  dtype=torch.bfloat16 keeps the
+        mean in bf16 instead of the sums (half the payload; count and weight sum stay exact, restored sums lie within (2^-8 + 2^-22) |S|).  Plain
+        and fading sessions; the session is unchanged.  An empty scene gives a snapshot with no records and launches nothing.  A windowed session
+        raises NotImplementedError (its state is the feature ring: out of scope), a closed one RuntimeError."""
+        self._check_open()
+        _check_snapshot_dtype(dtype)
+        if self._window is not None:
+            raise NotImplementedError(_WINDOW_SNAPSHOT.format(what='session'))
+        m = self._model
+        if self.n_views == 0:
+            Cn = int(m.neck.out_channels)         # (the channels of FPN level 0: what the state of this model's scenes holds per voxel)
+            return _snapshot_of(self, m, _host_records(None, Cn, dtype, self._decay is not None), Cn)
+        recs = ops.volume_pack(self._sum, self._count, [0], self._wsum, dtype)[0]
+        return _snapshot_of(self, m, _host_records(recs, int(self._sum.shape[-1]), dtype, self._decay is not None), int(self._sum.shape[-1]))
+
+    def _restore(self, snap, device):
+        """This freshly opened session takes the state and the host fields of a checked snapshot (model.restore_scene)."""
+        m = self._model
+        if snap.n_views:
+            X, Y, Z = m.n_voxels
+            Cn, dev = snap.channels, torch.device(device) if device is not None else _scene_device(m)
+            store = m.storage_dtype if m.storage_dtype in (torch.float32, torch.bfloat16) else torch.float32
+            state = (torch.empty((1, X, Y, Z, Cn), device=dev, dtype=torch.float32), torch.empty((1, X, Y, Z), device=dev, dtype=torch.int32),
+                     torch.empty((1, X, Y, Z), device=dev, dtype=torch.float32) if self._decay is not None else None)
+            with torch.cuda.device(dev):
+                ops.volume_unpack_(state[0], state[1], [0], [snap.records()], state[2])
+            self._sum, self._count, self._wsum = state
+            self._mean = torch.empty((1, X, Y, Z, Cn), device=dev, dtype=store)
+            self._valid = torch.empty((1, X, Y, Z), device=dev, dtype=torch.uint8)
+        _adopt(self, snap)
+        return self
+
     def add_views_u8(self, frames, extrinsics, img_scale, emit=True, weights=None, pixel_weights=None, depths=None, min_novelty=None, fresh_below=None,
                      lens=None, depth_frames=None, depth_scale=0.001, format=None, **pipeline_kw):
         """add_views from uint8 camera frames ((H,W,3) BGR arrays / tensors, or one [V,H,W,3]): the test pipeline runs on the device
@@ -1360,6 +1647,88 @@ class SceneBatch:
             if self._cam[d] is None:              # a scene with views has its host camera record (warp, scroll and the refresh read it): what its first add
                 meta = self._scenes[d].meta       # would have stored, by _camera_setup's rules at the lifts' stride of 4
                 self._cam[d] = (m._new_origin(meta['lidar2img']['origin']), torch.tensor([meta['img_shape'][0] // 4, meta['img_shape'][1] // 4], dtype=torch.int32))
+        return self
+
+    # ------------------------------------------------------------------ snapshots
+    def _scene_list(self, scenes, others=None, what='snapshot'):
+        """One scene index (with one entry of `others`) or a list of distinct indices (with a list of as many) -> (one, indices, others)."""
+        one = isinstance(scenes, (int, np.integer)) and not isinstance(scenes, bool)
+        if one:
+            scenes, others = [scenes], [others]
+        if isinstance(scenes, torch.Tensor) or not hasattr(scenes, '__len__') or not len(scenes) or \
+                (others is not None and (not isinstance(others, (list, tuple)) or len(others) != len(scenes))):
+            raise ValueError(f'{what} takes one scene index, or a list of distinct indices (with one snapshot each), got {scenes!r}')
+        scenes = [self._scene_index(s) for s in scenes]
+        if len(set(scenes)) != len(scenes):
+            raise ValueError(f'a scene can be named once per {what} call, got {scenes}')
+        return one, scenes, others
+
+    def snapshot(self, scene, dtype=torch.float32):
+        """SceneSession.snapshot for scenes of a plain or fading batch: one scene index -> a SceneSnapshot, a list of distinct indices -> a list.
+        The rows of all named scenes that have views go in ONE ops.volume_pack; a scene without views gives a snapshot with no records.  The
+        batch is unchanged.  A snapshot does not remember its container: model.restore_scene opens it as a SceneSession, restore puts it into a
+        row of any batch of the same kind.  A windowed batch raises NotImplementedError."""
+        self._check_open()
+        _check_snapshot_dtype(dtype)
+        one, scenes, _ = self._scene_list(scene)
+        if self._window is not None:
+            raise NotImplementedError(_WINDOW_SNAPSHOT.format(what='batch'))
+        m = self._model
+        rows = [s for s in scenes if self._scenes[s].n_views]
+        Cn = int(self._sum.shape[-1]) if self._sum is not None else int(m.neck.out_channels)
+        recs = dict(zip(rows, ops.volume_pack(self._sum, self._count, rows, self._wsum, dtype))) if rows else {}
+        out = [_snapshot_of(self._scenes[s], m, _host_records(recs.get(s), Cn, dtype, self._fading), Cn) for s in scenes]
+        return out[0] if one else out
+
+    def restore(self, scene, snapshot, device=None):
+        """Put snapshots into rows of a plain or fading batch: one scene index with one SceneSnapshot, or a list of distinct indices with one
+        snapshot each.  Each named row takes its snapshot's state -- ONE ops.volume_unpack_ for all rows of the call: every voxel of the row is
+        written, so what the scene held before is gone -- and its record takes the snapshot's host fields: extrinsics, n_views, origin, shapes,
+        scrolled, frame; the decay of a fading scene becomes the snapshot's.  The mean is recomputed when next asked for.  The snapshot's kind
+        must be the batch's, forget_below and depth_gate the batch's own, grid / voxel size / channels / sampling rule the model's, and the image
+        size of a snapshot with views what the batch already holds (an empty batch takes it).  A batch that has not allocated its pools
+        allocates them as its first add would (on `device`, else the model's).  A snapshot without views resets the scene to it.  A windowed
+        batch raises NotImplementedError.  A call that raises leaves every scene as it was."""
+        self._check_open()
+        one, scenes, snaps = self._scene_list(scene, snapshot, 'restore')
+        if self._window is not None:
+            raise NotImplementedError(_WINDOW_SNAPSHOT.format(what='batch').replace('snapshot:', 'restore:'))
+        m = self._model
+        hw = self._hw
+        for s, snap in zip(scenes, snaps):
+            _check_restore(m, snap, self._fading, 'batch')
+            _restored_meta(snap)
+            if snap.forget_below != self._forget or snap.depth_gate != self._scenes[s]._gate:
+                raise ValueError(f'restore: the snapshot was fused with forget_below {snap.forget_below} and depth_gate {snap.depth_gate}, the batch with '
+                                 f'{self._forget} and {self._scenes[s]._gate}')
+            if snap.n_views:
+                _check_size(snap.hw, hw, 'batch')
+                hw = snap.hw
+        full = [(s, snap) for s, snap in zip(scenes, snaps) if snap.n_views]
+        if full:
+            X, Y, Z = m.n_voxels
+            Cn = full[0][1].channels
+            if self._sum is None:                 # the state pools, as the first add allocates them
+                dev, N = torch.device(device) if device is not None else _scene_device(m), self._N
+                store = m.storage_dtype if m.storage_dtype in (torch.float32, torch.bfloat16) else torch.float32
+                pools = (torch.empty((N, X, Y, Z, Cn), device=dev, dtype=torch.float32), torch.empty((N, X, Y, Z), device=dev, dtype=torch.int32),
+                         torch.empty((N, X, Y, Z), device=dev, dtype=torch.float32) if self._fading else None,
+                         torch.empty((N, X, Y, Z, Cn), device=dev, dtype=store), torch.empty((N, X, Y, Z), device=dev, dtype=torch.uint8))
+            else:
+                pools = (self._sum, self._count, self._wsum, self._mean, self._valid)
+            with torch.cuda.device(pools[0].device):
+                ops.volume_unpack_(pools[0], pools[1], [s for s, _ in full], [snap.records() for _, snap in full], pools[2])
+            self._sum, self._count, self._wsum, self._mean, self._valid = pools
+            self._hw = hw
+        for s, snap in zip(scenes, snaps):
+            r = self._scenes[s]
+            _adopt(r, snap)
+            r._decay = snap.decay
+            self._cam[s] = None
+            if snap.n_views:                      # the host camera record its first add would have stored (warp, scroll and the refresh read it)
+                self._cam[s] = (m._new_origin(r.meta['lidar2img']['origin']), torch.tensor([r.meta['img_shape'][0] // 4, r.meta['img_shape'][1] // 4], dtype=torch.int32))
+        if not any(self.n_views):
+            self._hw = None
         return self
 
     # ------------------------------------------------------------------ adding views

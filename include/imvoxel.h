@@ -49,7 +49,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * in the prep launch) and the cover / depth maps of the same geometry at feature resolution; 503 = 0.5.3: ivx_image_prep_fmt_u8 / ivx_yuv_matrix, the image pipeline on decoder pixel
  * formats (RGB, BGRA / RGBA, gray, NV12, YUYV) converted in the fetch of the prep launch; 540 = 0.5.4: ivx_volume_warp_fwd, the rigid out-of-place
  * resample of rows of the state pools, for scenes that turn with their platform; 550 = 0.5.5: ivx_volume_merge_fwd, the rigid in-place merge of
- * rows of the state pools, for scenes that become one) and the message of the last failing call on this
+ * rows of the state pools, for scenes that become one; 560 = 0.5.6: ivx_volume_pack_fwd / ivx_volume_unpack_fwd / ivx_volume_pack_scratch_bytes, the
+ * ordered compaction of the seen voxels of rows of the state pools and its inverse, for scene snapshots) and the message of the last failing call on this
  * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -1042,6 +1043,68 @@ int ivx_volume_merge_fwd(int32_t B, const int32_t *row_src /*host [B]*/, const i
                          const float *voxel_size /*host [3]*/, float forget_below, int32_t R_src, int32_t R_dst, int32_t X, int32_t Y, int32_t Z,
                          int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src, float *sum_dst, float *wsum_dst,
                          int32_t *count_dst, ivx_stream_t stream);
+
+/* (0.5.6) Ordered compaction of the seen voxels of rows of the state pools, and its inverse: a scene's fused state leaves the process it was fused in
+ * (scene snapshots: scene.py, SceneSession.snapshot / ImVoxelNet.restore_scene / SceneBatch.snapshot / SceneBatch.restore).  A single frustum, a
+ * scrolled grid or a faded scene leaves much of a row unseen, all bits zero; the pack moves only the voxels that hold evidence, in ascending voxel
+ * order, and the unpack writes a whole row from such a list.  Like ivx_volume_scroll_fwd the F32 form is a pure move of bits, pinned with == to a
+ * numpy restatement (tests/ref_volume_pack.py), and both entries lie outside the reference-parity claims.
+ *
+ * Definition.  Voxel n = (i*Y + j)*Z + k of a row is KEPT iff its count word or its wsum word is non-zero, compared as raw 32-bit words: a -0 or
+ * NaN weight sum is kept and no float rule enters.  A voxel that is not kept is an unseen voxel.
+ *   pack    For sample b with r = row[b]: n_out[b] = the number of kept voxels of row r -- the true number, also when it exceeds cap.  For
+ *           q < min(n_out[b], cap), record q is the q-th kept voxel in ascending n:  index_out[b,q] = n,  count_out[b,q] and wsum_out[b,q] its two
+ *           words,  payload_out[b,q,:] its payload.  Nothing at or beyond [b, min(n_out[b], cap)) of any output is touched.
+ *   unpack  For sample b with r = row[b] and its n[b] records: voxel index[b,q] of row r takes record q; every other voxel of row r becomes unseen,
+ *           sums +0, count 0, weight sum +0.  Every voxel of a named row is written once.
+ *   payload IVX_F32:  the C sums as raw 16-byte words; every bit pattern survives (NaN payloads, -0, denormals).
+ *           IVX_BF16: the mean.  den = the weight sum, or (float)count without a wsum pool;  m = den > 0 ? S / den : +0, one IEEE division, rounded
+ *           once to bf16, round to nearest even.  Unpack restores S = float(m) * den, one rounded product, with den from the record (wsum_rec, or
+ *           (float)count_rec).  For |S / den| in bf16's normal range:  |S' - S| <= (2^-8 + 2^-22) |S|  (tests/ref_volume_pack.py derives it).
+ *
+ * ivx_volume_pack_fwd
+ * B            samples of this call
+ * row          HOST [B] int32: sample b reads row row[b] of the pools; distinct
+ * R, X, Y, Z, C  the pools have R rows of X*Y*Z voxels; C % 4 == 0
+ * volume_sum   DEVICE [R,X,Y,Z,C] fp32, 16-byte aligned, read only;  count  DEVICE [R,X,Y,Z] int32;  wsum  DEVICE [R,X,Y,Z] fp32 or NULL
+ * payload_dtype  IVX_F32 | IVX_BF16
+ * cap          records per sample the outputs have room for, >= 0.  cap == 0 is the count-only form: only n_out is written, by the counting
+ *              launches alone, and the four outputs may be NULL.
+ * index_out    DEVICE [B,cap] int32;  payload_out  DEVICE [B,cap,C] fp32 (16-byte aligned) or bf16 (8-byte aligned);  wsum_out  DEVICE [B,cap] fp32,
+ *              given iff wsum is;  count_out  DEVICE [B,cap] int32
+ * n_out        DEVICE [B] int32
+ * scratch      DEVICE, ivx_volume_pack_scratch_bytes(B, X, Y, Z) bytes (-1 for non-positive arguments or X*Y*Z at or beyond 2^31)
+ * ivx_volume_unpack_fwd
+ * row, n       HOST [B] int32: sample b writes row row[b] (distinct) from its first n[b] records, 0 <= n[b] <= cap
+ * cap          the record lists have cap entries per sample; with cap == 0 every n[b] is 0, the lists may be NULL and the named rows become unseen
+ * index, payload, wsum_rec, count_rec   DEVICE, as the pack wrote them: [B,cap] int32 strictly ascending in [0, X*Y*Z), [B,cap,C], [B,cap] fp32 given
+ *              iff the wsum pool is, [B,cap] int32
+ * volume_sum, count, wsum   the pools as above, written
+ * row (and n) are host lists, as for ivx_volume_scroll_fwd: everything is checked before any launch and nothing is uploaded (32 samples per launch).
+ *
+ * Properties.
+ *   Order.         Deterministic: three launches per 32 samples (count per chunk of 256 voxels, an exclusive scan of the chunk counts by one
+ *                  workgroup per sample, write) with no atomics, no spinning and no dependence between the workgroups of a launch; the unpack is
+ *                  one launch.  csrc/volume_pack.hip has the schedule.
+ *   Untouched.     The source pools of a pack are read only; rows that no sample names are neither read (pack) nor read or written (unpack).
+ *   Round trip.    F32: unpack(pack(row)) equals the row bit for bit IF every unseen voxel of the row has all-zero sums.  That is the state's own
+ *                  invariant: a `first` lift, the forgetting rule, scroll, warp and merge all store +0 sums wherever they leave count and weight sum
+ *                  zero, and nothing else writes a state (tests/test_gpu_scene_snapshot.py checks it on a state that went through all of them).
+ *                  Sums at unseen voxels that are not zero are dropped.
+ *   Checked data.  No address of the unpack depends on unchecked data: the index list is searched at positions inside [0, n[b]) and an index that
+ *                  does not fall into the chunk of voxels being written -- so any index outside [0, X*Y*Z) -- is skipped.  A list that is not strictly
+ *                  ascending loses records but writes nothing out of place; ops.volume_unpack_ refuses it on the host.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names the entry: a null required pointer (pack: a null scratch too); a non-positive B,
+ * R, X, Y, Z or C; C % 4 != 0; sums or payload not 16-byte aligned (the bf16 payload: 8-byte); X*Y*Z at or beyond 2^31; a negative cap; cap > 0
+ * with a null output or record list; n[b] outside [0, cap]; a row outside [0, R); two samples on one row; an unknown payload_dtype; wsum / wsum_out
+ * (pack) or wsum / wsum_rec (unpack) given on one side only.                                                                                     */
+int64_t ivx_volume_pack_scratch_bytes(int32_t B, int32_t X, int32_t Y, int32_t Z);
+int ivx_volume_pack_fwd(int32_t B, const int32_t *row /*host [B]*/, int32_t R, int32_t X, int32_t Y, int32_t Z, int32_t C, const float *volume_sum,
+                        const int32_t *count, const float *wsum /*or NULL*/, int32_t payload_dtype, int32_t cap, int32_t *index_out, void *payload_out,
+                        float *wsum_out /*or NULL*/, int32_t *count_out, int32_t *n_out, void *scratch, ivx_stream_t stream);
+int ivx_volume_unpack_fwd(int32_t B, const int32_t *row /*host [B]*/, const int32_t *n /*host [B]*/, int32_t cap, const int32_t *index, const void *payload,
+                          const float *wsum_rec /*or NULL*/, const int32_t *count_rec, int32_t payload_dtype, int32_t R, int32_t X, int32_t Y, int32_t Z,
+                          int32_t C, float *volume_sum, int32_t *count, float *wsum /*or NULL*/, ivx_stream_t stream);
 
 /* (0.5.1) View coverage: what would a candidate view add to a scene?  Every frame that reaches a streaming scene pays for the 2-D trunk, and
  * most frames of a 30 Hz camera look at voxels the scene has already fused.  Whether a pose adds anything depends only on the geometry and on
