@@ -20,7 +20,8 @@ from .boxes import (LiDARInstance3DBoxes, DepthInstance3DBoxes, limit_period, xy
 from .nms import nms_gpu, nms_normal_gpu, box3d_multiclass_nms, aligned_3d_nms, boxes_iou_bev  # noqa: F401
 from .evaluation import indoor_eval, average_precision, eval_det_cls, eval_map_recall  # noqa: F401
 from .kitti_ap import kitti_eval, kitti_eval_coco_style, bbox2result_kitti  # noqa: F401
-from .scene import SceneSession, SceneBatch, SceneSnapshot, scrolled_origin, warped_extrinsic             # noqa: F401
+from .scene import (SceneSession, SceneBatch, SceneSnapshot, MatchResult, scrolled_origin, warped_extrinsic,  # noqa: F401
+                    pose_candidates)
 from .params import randomize_                                              # noqa: F401
 
 from .data import (load_checkpoint, prepare_image, MultiViewPipeline, KittiSetOrigin, SunRgbdSetOrigin,  # noqa: F401

@@ -26,6 +26,7 @@ SOURCES = [
     ('volume_scroll.hip', []),
     ('volume_warp.hip', ['-ffp-contract=off']),
     ('volume_pack.hip', ['-ffp-contract=off']),
+    ('volume_match.hip', ['-ffp-contract=off']),
     ('view_coverage.hip', ['-ffp-contract=off']),
     ('anchor_tail.hip', ['-ffp-contract=off']),
     ('image_prep.hip', ['-ffp-contract=off']),
@@ -54,7 +55,7 @@ def _stale(target, deps):
 
 def build(force=False, verbose=False):
     hipcc = _hipcc()
-    headers = [os.path.join(CSRC, h) for h in ('ivx_common.h', 'lift_geometry.h', 'pixel_fetch.h', 'conv_shared.h', 'conv_tiles.h', 'conv_plan.h')] + \
+    headers = [os.path.join(CSRC, h) for h in ('ivx_common.h', 'lift_geometry.h', 'warp_geometry.h', 'pixel_fetch.h', 'conv_shared.h', 'conv_tiles.h', 'conv_plan.h')] + \
               [os.path.join(os.path.dirname(os.path.dirname(CSRC)), 'include', h) for h in ('imvoxel.h', 'imvoxel_lab.h')]
     objs, jobs = [], []
     for entry in SOURCES:

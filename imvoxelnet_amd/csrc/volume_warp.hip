@@ -51,6 +51,7 @@
 
 #include "ivx_common.h"
 #include "lift_geometry.h"
+#include "warp_geometry.h"
 
 #ifndef IVX_WARP_WG
 #define IVX_WARP_WG 256
@@ -86,21 +87,7 @@ static_assert(sizeof(WarpArgs) <= 4096, "the samples travel by value: the argume
 // corner bits: the sample is added to the destination's sums.  STORE | FORGOT (no corner bits): forgotten, zeros are stored and nothing is read.
 constexpr int MASK_STORE = 1 << 8, MASK_FORGOT = 1 << 9;
 
-// One axis of step 3: the grid coordinate g of the source point's coordinate q.  -> inside; i0 = floor(g), f = g - i0 (one rounded difference).
-__device__ __forceinline__ bool warp_axis(const float q, const float origin, const float vs, const int N, int &i0, float &f) {
-  const float g = __fdiv_rn(__fsub_rn(q, origin), vs);
-  if (!(g > -1.0f && g < (float)N)) return false;      // NaN and inf fail as well
-  const float fl = floorf(g);
-  i0 = (int)fl;
-  f = __fsub_rn(g, fl);
-  return true;
-}
-
-// The weight of corner c = dx * 4 + dy * 2 + dz from the three fractions: (w_x * w_y) * w_z with w_a = 1 - f_a (d = 0) or f_a (d = 1).
-__device__ __forceinline__ float warp_weight(const int c, const float fx, const float fy, const float fz) {
-  const float wx = c & 4 ? fx : __fsub_rn(1.0f, fx), wy = c & 2 ? fy : __fsub_rn(1.0f, fy), wz = c & 1 ? fz : __fsub_rn(1.0f, fz);
-  return __fmul_rn(__fmul_rn(wx, wy), wz);
-}
+// (One axis of step 3, warp_axis, and the weight of a corner, warp_weight, are csrc/warp_geometry.h: the match kernel shares them.)
 
 // MERGE = false: ivx_volume_warp_fwd, the destination row is written whole.  MERGE = true: ivx_volume_merge_fwd, the sample is added in place to
 // the destination voxels that are merged (inside, W_s > 0) and no other voxel is written.

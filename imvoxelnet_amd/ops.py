@@ -1746,7 +1746,91 @@ def volume_merge_(vol_sum, wsum, count, rows, src, src_rows, transforms, new_ori
     return vol_sum, wsum, count
 
 
-_PACK_DT = {torch.float32: 0, torch.bfloat16: 1}      # the payload of a packed state: IVX_F32 (the sums, as words) | IVX_BF16 (the mean)
+def _match_step(step):
+    """The lattice step of a match: one integer for all axes or three -> [px, py, pz], each >= 1 and an int32."""
+    if hasattr(step, '__index__') and not isinstance(step, (bool, torch.Tensor)) and not hasattr(step, '__len__'):
+        step = (step,) * 3
+    try:
+        p = _host_ints(step, 'step')
+    except TypeError:
+        raise ValueError(f'step must be one integer >= 1 or three (px, py, pz), got {step!r}') from None
+    if len(p) != 3 or any(not 1 <= v < 2 ** 31 for v in p):
+        raise ValueError(f'step must be one integer >= 1 or three (px, py, pz), each >= 1, got {step!r}')
+    return p
+
+
+def volume_match(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src_origin, voxel_size, step=(1, 1, 1)):
+    """Matching scenes: score candidate rigid transforms between rows of the state pools vol_sum [R,X,Y,Z,C] fp32 / wsum [R,X,Y,Z] fp32 and rows of
+    the pools src = (sum, wsum) of the same X, Y, Z, C (ivx_volume_match_fwd; include/imvoxel.h has the definition).  For sample b, row rows[b]
+    (the destination: its voxels are visited) is compared with the trilinear read of row src_rows[b] of `src` at x_src = T x_dst for each of the
+    K candidates T of transforms[b] -- a host list of K 4x4 or 3x4 matrices per sample (check_rigid each), the same K for every sample.  Over the
+    voxels both hold evidence for ("paired": own W_d > 0, inside the source grid, sampled W_s > 0) and all channels, with the means a = S_d / W_d
+    and b = S_s / W_s:  dot = sum a b, na = sum a a, nb = sum b b.  new_origin / src_origin: the two grids' corner terms, host floats [B,3] (or [3]
+    for all); voxel_size is common.  step: the lattice step, one integer or (px, py, pz), each >= 1: only voxels with i % px == j % py == k % pz
+    == 0 are visited.  rows and src_rows: B host integers each; rows may repeat, `src` may be the same pools and a row may be matched against
+    itself: everything is read only.  Every check comes before the one C call.  The sums are deterministic: the same two states give the same
+    bits in any rows of any pools.
+    -> (pairs [B,K] int64, own [B] int64, stats [B,K,3] float64 = (dot, na, nb)) as device tensors; the score is the caller's:
+    ncc = dot / sqrt(na * nb), overlap = pairs / own."""
+    import numpy as np
+    for t, name in ((vol_sum, 'vol_sum'), (wsum, 'wsum')):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch.Tensor')
+    if not isinstance(src, (tuple, list)) or len(src) not in (2, 3) or any(not isinstance(t, torch.Tensor) for t in src):
+        raise TypeError('src must be a (sum, wsum) pair of torch.Tensors (a (sum, wsum, count) triple is taken too; the count is not read)')
+    ssum, swsum = src[:2]
+    if vol_sum.dim() != 5:
+        raise ValueError(f'vol_sum must be [R,X,Y,Z,C], got {tuple(vol_sum.shape)}')
+    R, X, Y, Z, Cn = (int(v) for v in vol_sum.shape)
+    rows = _host_ints(rows, 'rows')
+    if not rows:
+        raise ValueError('rows must name at least one row')
+    B = len(rows)
+    src_rows = _host_ints(src_rows, 'src_rows', B)
+    if isinstance(transforms, (str, bytes, torch.Tensor)) or not hasattr(transforms, '__len__') or len(transforms) != B or \
+            any(isinstance(c, (str, bytes)) or not hasattr(c, '__len__') for c in transforms):
+        raise TypeError(f'transforms must be a host list of {B} lists (one per row) of 4x4 or 3x4 matrices')
+    K = len(transforms[0])
+    if K == 0 or any(len(c) != K for c in transforms):
+        raise ValueError(f'transforms must hold the same number K >= 1 of candidates for every row, got {[len(c) for c in transforms]}')
+    M = [check_rigid(T, f'transforms[{b}][{k}]') for b, cands in enumerate(transforms) for k, T in enumerate(cands)]
+    (o, so), vs = _grid_floats(B, voxel_size, new_origin=new_origin, src_origin=src_origin)
+    step = _match_step(step)
+    if any(not 0 <= r < R for r in rows):
+        raise ValueError(f'rows must be in [0, {R}), got {rows}')
+    if ssum.dim() != 5 or tuple(ssum.shape[1:]) != (X, Y, Z, Cn):
+        raise ValueError(f'src[0] must be [R_src,{X},{Y},{Z},{Cn}] like vol_sum, got {tuple(ssum.shape)}')
+    Rs = int(ssum.shape[0])
+    if any(not 0 <= r < Rs for r in src_rows):
+        raise ValueError(f'src_rows must be in [0, {Rs}), got {src_rows}')
+    if Cn % 4:
+        raise ValueError(f'vol_sum must have C % 4 == 0, got C = {Cn}')
+    for t, name, shape in ((wsum, 'wsum', (R, X, Y, Z)), (swsum, 'src[1]', (Rs, X, Y, Z))):
+        if tuple(t.shape) != shape:
+            raise ValueError(f'{name} must be {list(shape)} beside its sums, got {tuple(t.shape)}')
+    for t, name in ((vol_sum, 'vol_sum'), (wsum, 'wsum'), (ssum, 'src[0]'), (swsum, 'src[1]')):
+        _chk(t, name)
+        if t.device != vol_sum.device:
+            raise ValueError(f'{name} must be on the device of vol_sum')
+    L = _lib.lib()
+    fn = getattr(L, 'ivx_volume_match_fwd', None)
+    if fn is None:
+        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_match_fwd (needs version 0.5.7)')
+    nbytes = L.ivx_volume_match_scratch_bytes(B, K, X, Y, Z, Cn)
+    if nbytes < 0:
+        raise ValueError(f'ivx_volume_match_scratch_bytes refuses B = {B}, K = {K}, grid {X} x {Y} x {Z}, C = {Cn}')
+    dev = vol_sum.device
+    scratch = torch.empty((nbytes // 8,), device=dev, dtype=torch.int64)
+    pairs, own = torch.empty((B, K), device=dev, dtype=torch.int64), torch.empty((B,), device=dev, dtype=torch.int64)
+    stats = torch.empty((B, K, 3), device=dev, dtype=torch.float64)
+    flat = lambda a: (C.c_float * a.size)(*np.ascontiguousarray(a, np.float32).reshape(-1).tolist())     # noqa: E731
+    check(fn(B, K, (C.c_int32 * B)(*src_rows), (C.c_int32 * B)(*rows), flat(np.stack(M)), flat(o), flat(so), flat(vs), (C.c_int32 * 3)(*step), Rs, R,
+             X, Y, Z, Cn, _ptr(ssum), _ptr(swsum), _ptr(vol_sum), _ptr(wsum), _ptr(pairs), _ptr(own), _ptr(stats), _ptr(scratch), _stream()),
+          'ivx_volume_match_fwd')
+    return pairs, own, stats
+
+
+_PACK_DT = {torch.float32: 0, torch.bfloat16: 1}     # the payload of a packed state: IVX_F32 (the sums, as words) | IVX_BF16 (the mean)
 
 
 def _pack_pools(vol_sum, count, rows, wsum):

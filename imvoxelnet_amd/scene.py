@@ -82,6 +82,19 @@ mean is recomputed when next asked for, and frame, origin and scrolled stay.  A 
 Evidence both scenes hold of the same views counts twice.  A batch merges rows of its own pools, all pairs of a call in one launch.  Plain and
 windowed scenes refuse.  A scene that never merges runs the code it ran before.
 
+Matching scenes (SceneSession.match(other, Ts=None, step=1, min_overlap=0.3) / register(other, T0=None, yaw, shift, levels, step, min_overlap);
+SceneBatch.match(scenes, sources, Ts) / register(scene, source, ...); pose_candidates; MatchResult).  scroll, warp, merge and restore all take the
+transform between two frames as given, and a pose that is off by a voxel smears a merge without a warning.  But the state holds what judges a pose:
+two fading states are per-voxel mean feature vectors with weights, and for a candidate T (x_other = T x_self, the merge's convention) the
+correlation of the two means over the voxels both scenes have seen says how well they agree.  match scores K candidates in one call
+(ops.volume_match, ivx_volume_match_fwd, csrc/volume_match.hip; include/imvoxel.h has the definition): the other state is read by the merge's
+trilinear rule, each grid with its own origin, nothing is written, and per candidate come back pairs (voxels both hold evidence for), own, and the
+fp64 sums (dot, na, nb) of the means' products -- deterministic, with no atomics, so a batch's answer equals a session's bit for bit.  The host
+forms ncc = dot / sqrt(na * nb) and overlap = pairs / own; a candidate below min_overlap is not eligible.  register is a thin LOCAL search on top:
+per level the 81 candidates of pose_candidates around the current pose (yaw and three shifts, each offset in {-h, 0, +h}, about the grid's
+centre), move to the best eligible one, halve the offsets.  Plain and windowed scenes refuse, as for merge.  A scene that never matches runs the
+code it ran before.
+
 Scene snapshots (SceneSession.snapshot(dtype) / model.restore_scene(snapshot) / SceneBatch.snapshot(scene) / SceneBatch.restore(scene, snapshot);
 SceneSnapshot.save / load).  Everything above happens inside one process, on one device, in one kind of container.  A snapshot is the fused state of a
 plain or fading scene as HOST data: a state row is large (26 / 54 / 170 MB of fp32 at the ScanNet-fast / ScanNet-v1 / KITTI grids) and partly unseen --
@@ -147,7 +160,8 @@ scrolling a model with an Anchor3DHead (its boxes would have to be translated; w
 (the state lives here, over the op-level ABI and the handle's sub-range calls); merging windowed scenes (adopting the other's kept views into the
 ring); merging plain scenes (their integer counts cannot be resampled: open them with decay=1.0); merges between a session and a batch row, or
 across batches (ops.volume_merge_ takes any pools); several sources into one destination in one launch; de-duplicating views both scenes saw;
-estimating T (registration); saving a scene to disk other than through a snapshot; merging scenes on different devices or ranks directly (snapshot
+estimating T without a start (a global search, no T0), pitch and roll in register, weighting pairs by evidence, zero-mean (Pearson)
+correlation, gradient-based refinement of a pose, matching plain or windowed scenes; saving a scene to disk other than through a snapshot; merging scenes on different devices or ranks directly (snapshot
 one and restore it beside the other); snapshots of windowed scenes (the state is the feature ring, a plain copy); merge taking a snapshot directly
 (restore it, then merge); turning a plain snapshot into a fading scene; compression of a snapshot beyond the bf16 mean; any check that the weights of
 the restoring model are those that fused the state.
@@ -488,6 +502,127 @@ def _merge_transform(dst, src, T):
     T = np.linalg.inv(src._frame) @ dst._frame
     T[3] = (0, 0, 0, 1)
     return T
+
+
+# ------------------------------------------------------------------ matching: the host rules
+_PLAIN_MATCH = ('{op}: a plain {what} keeps integer view counts and no weight sum, so it has no mean field to sample; open it with decay=1.0 (a weight '
+                'sum beside the sums, nothing fades)')
+_WINDOW_MATCH = ('{op}: a windowed {what} (window=W) keeps views, not a running state; matching it is out of scope: open it with decay=')
+
+
+def _check_match_kind(window, fading, what, op='match'):
+    """Only fading scenes match: a windowed or a plain one (what: 'session' / 'batch', as it was opened) refuses."""
+    if window is not None:
+        raise NotImplementedError(_WINDOW_MATCH.format(what=what, op=op))
+    if not fading:
+        raise NotImplementedError(_PLAIN_MATCH.format(what=what, op=op))
+
+
+def _check_min_overlap(min_overlap):
+    if isinstance(min_overlap, bool) or not isinstance(min_overlap, (int, float, np.integer, np.floating)) or not 0 <= float(min_overlap) <= 1:
+        raise ValueError(f'min_overlap must be a number in [0, 1], got {min_overlap!r}')
+    return float(min_overlap)
+
+
+def _rigid_yaw(yaw, t, about):
+    """float64 [4,4]: the turn by `yaw` about the vertical through the point `about`, then the translation t."""
+    c, s = math.cos(yaw), math.sin(yaw)
+    T = np.eye(4)
+    T[:3, :3] = [[c, -s, 0], [s, c, 0], [0, 0, 1]]
+    about = np.asarray(about, np.float64)
+    T[:3, 3] = about - T[:3, :3] @ about + np.asarray(t, np.float64)
+    return T
+
+
+def pose_candidates(T_c, yaw, shift, about=(0, 0, 0)):
+    """The 81 candidates of one level of register around T_c (a 4x4 with x_other = T x_self):  T_c @ rigid(yaw=a, t=(x, y, z), about=about)  with
+    a in (-yaw, 0, +yaw) and x, y, z in (-h, 0, +h) of shift = (h_x, h_y, h_z), in the order a, x, y, z with z fastest -- so candidate 40 is T_c
+    itself, bit for bit, and candidates i and 80 - i carry opposite offsets.  yaw in radians, shift in metres, both >= 0; `about` is the point the
+    turn goes through (register: the grid's centre).  Needs no device.  -> list of 81 float64 [4,4]."""
+    T_c = _check_warp(T_c)
+    sh = np.asarray(shift, np.float64).reshape(-1)
+    ab = np.asarray(about, np.float64).reshape(-1)
+    if isinstance(yaw, bool) or not isinstance(yaw, (int, float, np.integer, np.floating)) or not (math.isfinite(yaw) and yaw >= 0):
+        raise ValueError(f'yaw must be a finite number >= 0 (radians), got {yaw!r}')
+    if sh.shape != (3,) or not (np.isfinite(sh).all() and (sh >= 0).all()):
+        raise ValueError(f'shift must be three finite numbers >= 0 (h_x, h_y, h_z), got {shift!r}')
+    if ab.shape != (3,) or not np.isfinite(ab).all():
+        raise ValueError(f'about must be three finite coordinates, got {about!r}')
+    out = []
+    for a in (-1, 0, 1):
+        for x in (-1, 0, 1):
+            for y in (-1, 0, 1):
+                for z in (-1, 0, 1):
+                    out.append(T_c.copy() if (a, x, y, z) == (0, 0, 0, 0) else T_c @ _rigid_yaw(a * float(yaw), (x * sh[0], y * sh[1], z * sh[2]), ab))
+    return out
+
+
+class MatchResult:
+    """What a match says about K candidate transforms, as host numpy arrays:
+      pairs   [K] int64    the voxels of this scene that hold evidence and whose sample of the other scene does too
+      own     int          the voxels of this scene that hold evidence (of those visited)
+      overlap [K] float64  pairs / own (0 where own is 0)
+      score   [K] float64  ncc = dot / sqrt(na * nb), the cosine of the two mean fields over the paired voxels; -inf where a candidate is not
+                           eligible: pairs == 0, overlap < min_overlap, or a norm that is not positive
+      stats   [K,3] float64  (dot, na, nb) as the device summed them
+      best    int or None  the eligible candidate of the highest score (the first of equals); None when none is eligible
+      T       float64 [4,4] or None  that candidate
+      Ts      the candidates."""
+
+    def __init__(self, pairs, own, stats, Ts, min_overlap=0.3):
+        self.pairs, self.own, self.stats = np.asarray(pairs, np.int64).reshape(-1), int(own), np.asarray(stats, np.float64).reshape(-1, 3)
+        self.Ts, self.min_overlap = [np.asarray(T, np.float64) for T in Ts], _check_min_overlap(min_overlap)
+        if not (len(self.pairs) == len(self.stats) == len(self.Ts)):
+            raise ValueError(f'{len(self.pairs)} pair counts, {len(self.stats)} statistics and {len(self.Ts)} candidates')
+        self.overlap = self.pairs / self.own if self.own > 0 else np.zeros(len(self.pairs))
+        dot, den = self.stats[:, 0], self.stats[:, 1] * self.stats[:, 2]
+        ok = (self.pairs > 0) & (self.overlap >= self.min_overlap) & (den > 0)
+        with np.errstate(invalid='ignore', divide='ignore'):
+            self.score = np.where(ok, dot / np.sqrt(np.where(ok, den, 1.0)), -np.inf)
+        self.best = int(np.argmax(self.score)) if ok.any() else None
+        self.T = None if self.best is None else self.Ts[self.best].copy()
+
+    def __repr__(self):
+        return f'MatchResult(K={len(self.pairs)}, best={self.best}, score={None if self.best is None else float(self.score[self.best]):}, own={self.own})'
+
+
+def _match_candidates(dst, src, Ts):
+    """Ts of a match of the record dst against the record src -> list of float64 [4,4] with x_src = T x_dst: the caller's host list, each by the
+    _check_warp rule, or for None the one candidate a merge would default to."""
+    if Ts is None:
+        return [_merge_transform(dst, src, None)]
+    if isinstance(Ts, (str, bytes, torch.Tensor, np.ndarray)) or not hasattr(Ts, '__len__') or not len(Ts):
+        raise ValueError('Ts must be None or a non-empty host list of 4x4 matrices with x_other = T x_self')
+    return [_check_warp(T) for T in Ts]
+
+
+def _match_results(pairs, own, stats, cands, min_overlap):
+    """The device outputs of one ops.volume_match over P pairs -> P MatchResults (the one host sync of a match)."""
+    pairs, own, stats = pairs.cpu().numpy(), own.cpu().numpy(), stats.cpu().numpy()
+    return [MatchResult(pairs[p], own[p], stats[p], cands[p], min_overlap) for p in range(len(cands))]
+
+
+def _register(match, T0, yaw, shift, levels, step, min_overlap, about, voxel_size):
+    """The coarse-to-fine search of register, shared by sessions and batches: match(Ts, step) -> MatchResult scores one level's candidates.
+    -> (T float64 [4,4], the MatchResult of the last level)."""
+    if isinstance(levels, bool) or not isinstance(levels, (int, np.integer)) or levels < 1:
+        raise ValueError(f'levels must be an integer >= 1, got {levels!r}')
+    steps = list(step) if hasattr(step, '__len__') and not isinstance(step, (str, bytes, torch.Tensor)) else [step] * levels
+    if len(steps) != levels:
+        raise ValueError(f'step must be one integer for every level or a list of one lattice step per level: {levels} levels, got {step!r}')
+    steps = [ops._match_step(s) for s in steps]
+    vs = np.asarray(voxel_size, np.float64)
+    shift = np.array([2 * vs[0], 2 * vs[1], vs[2]]) if shift is None else np.asarray(shift, np.float64).reshape(-1)
+    min_overlap = _check_min_overlap(min_overlap)
+    T = T0
+    pose_candidates(T, yaw, shift, about)                                    # (every argument is checked before the first launch)
+    res = None
+    for lv in range(levels):
+        res = match(pose_candidates(T, yaw, shift, about), steps[lv])
+        if res.best is not None:
+            T = res.T
+        yaw, shift = yaw / 2, shift / 2
+    return T, res
 
 
 # ------------------------------------------------------------------ snapshots: a scene's fused state as host data
@@ -1295,6 +1430,60 @@ class SceneSession(_SceneRecord):
         self._merged(other, T)
         return self
 
+    # ------------------------------------------------------------------ matching
+    def _check_match(self, other, op):
+        """The refusals of match / register against another session: both open, fading, of one prepared model, holding views, on one device and of
+        one grid and channel count."""
+        self._check_open()
+        if not isinstance(other, SceneSession):
+            raise TypeError(f'{op} takes another SceneSession, got {type(other).__name__}')
+        other._check_open()
+        _check_match_kind(self._window if self._window is not None else other._window, self._decay is not None and other._decay is not None, 'session', op)
+        if other._model is not self._model:
+            raise ValueError(f'{op}: the two sessions must be of the same prepared model')
+        if self.n_views == 0 or other.n_views == 0:
+            raise ValueError(f'{op}: {"this" if self.n_views == 0 else "the other"} scene is empty (it holds no views, so there is no state to compare)')
+        if other._sum.device != self._sum.device:
+            raise ValueError(f'{op}: the two scenes must be on one device, got {self._sum.device} and {other._sum.device}')
+        if other._sum.shape != self._sum.shape:
+            raise ValueError(f'{op}: the two scenes must have one grid and channel count, got {tuple(self._sum.shape[1:])} and {tuple(other._sum.shape[1:])}')
+
+    def _match(self, other, Ts, step, min_overlap):
+        m = self._model
+        pairs, own, stats = ops.volume_match(self._sum, self._wsum, [0], (other._sum, other._wsum), [0], [Ts],
+                                             m._new_origin(self.meta['lidar2img']['origin']).numpy()[None],
+                                             m._new_origin(other.meta['lidar2img']['origin']).numpy()[None], m.voxel_size, step)
+        return _match_results(pairs, own, stats, [Ts], min_overlap)[0]
+
+    def match(self, other, Ts=None, step=1, min_overlap=0.3):
+        """How well does this scene agree with another under candidate transforms?  Ts: a host list of K float 4x4 with x_other = T x_self, the
+        merge's convention (None: the one candidate a merge would default to, inv(other.frame) @ self.frame).  ONE ops.volume_match
+        (ivx_volume_match_fwd) visits this scene's voxels, reads the other's state trilinearly at T x -- each scene's grid keeps its own origin, so
+        scrolled scenes match -- and sums, over the voxels both hold evidence for, the correlation of the two mean feature fields; the score of a
+        candidate is ncc = dot / sqrt(na * nb) and its overlap pairs / own.  step: the lattice step, one integer or (px, py, pz): only every
+        step-th voxel per axis is visited (a coarse look).  A candidate is eligible iff pairs > 0 and overlap >= min_overlap.
+        Both sessions must be fading (decay=; decay=1.0 fades nothing), open, hold views, be on one device and of the same prepared model; both are
+        left bit-unchanged, records included.  A plain session on either side raises NotImplementedError, so does a windowed one; an empty scene
+        raises ValueError.  -> MatchResult (host arrays: score, overlap, pairs, own, stats, best, T)."""
+        self._check_match(other, 'match')
+        Ts = _match_candidates(self, other, Ts)
+        return self._match(other, Ts, ops._match_step(step), _check_min_overlap(min_overlap))
+
+    def register(self, other, T0=None, yaw=math.radians(8), shift=None, levels=6, step=1, min_overlap=0.3):
+        """Refine a transform between this scene and another (x_other = T x_self) by a coarse-to-fine search over yaw and translation, built on
+        match.  This is a LOCAL search around T0 (None: inv(other.frame) @ self.frame): it finds the best pose within about twice the first
+        level's offsets of T0 and does not look further.  Each of `levels` levels scores the 81 candidates pose_candidates(T_c, yaw, shift,
+        about=the grid's centre) -- T_c @ rigid(yaw=a, t=(x, y, z)) with each offset in {-h, 0, +h} -- in one match, moves T_c to the best eligible
+        candidate (keeps it when none is eligible), then halves yaw and shift.  shift (h_x, h_y, h_z) in metres defaults to (2 vs_x, 2 vs_y,
+        vs_z); yaw is in radians.  step: one integer for every level or a list of one lattice step per level (a coarse level may pass 2).
+        Pitch and roll are not searched.  Refusals are match's.  Both scenes are unchanged.
+        -> (T float64 [4,4], the MatchResult of the last level)."""
+        self._check_match(other, 'register')
+        T0 = _merge_transform(self, other, T0)
+        min_overlap = _check_min_overlap(min_overlap)
+        return _register(lambda Ts, p: self._match(other, Ts, p, min_overlap), T0, yaw, shift, levels, step, min_overlap,
+                         np.asarray(self.meta['lidar2img']['origin'], np.float64), self._model.voxel_size)
+
     # ------------------------------------------------------------------ snapshots
     def snapshot(self, dtype=torch.float32):
         """The scene as host data (SceneSnapshot): ONE ops.volume_pack (ivx_volume_pack_fwd) compacts the voxels that hold evidence, in ascending
@@ -1648,6 +1837,58 @@ class SceneBatch:
                 meta = self._scenes[d].meta       # would have stored, by _camera_setup's rules at the lifts' stride of 4
                 self._cam[d] = (m._new_origin(meta['lidar2img']['origin']), torch.tensor([meta['img_shape'][0] // 4, meta['img_shape'][1] // 4], dtype=torch.int32))
         return self
+
+    # ------------------------------------------------------------------ matching
+    def _check_match(self, scenes, sources, op):
+        """Scene indices of a match -> (scenes, sources) as int lists; the batch is open and fading and every named scene holds views."""
+        self._check_open()
+        scenes, sources = [self._scene_index(s) for s in scenes], [self._scene_index(s) for s in sources]
+        _check_match_kind(self._window, self._fading, 'batch', op)
+        empty = sorted({s for s in scenes + sources if not self._scenes[s].n_views})
+        if empty:
+            raise ValueError(f'{op}: scenes {empty} are empty (they hold no views, so there is no state to compare)')
+        return scenes, sources
+
+    def _origin_of(self, s):
+        m = self._model
+        return (self._cam[s][0] if self._cam[s] is not None else m._new_origin(self._scenes[s].meta['lidar2img']['origin'])).float().numpy()
+
+    def _match(self, scenes, sources, cands, step, min_overlap):
+        state = (self._sum, self._wsum)
+        pairs, own, stats = ops.volume_match(*state, scenes, state, sources, cands, np.stack([self._origin_of(d) for d in scenes]),
+                                             np.stack([self._origin_of(s) for s in sources]), self._model.voxel_size, step)
+        return _match_results(pairs, own, stats, cands, min_overlap)
+
+    def match(self, scenes, sources, Ts=None, step=1, min_overlap=0.3):
+        """SceneSession.match between scenes of the batch: one scene index with one source index and one candidate list (-> one MatchResult), or
+        two lists of one length with one candidate list per pair (-> a list).  Pair i scores Ts[i], K host 4x4 with x_source = T x_scene -- the
+        same K for every pair -- or, with Ts None, the one candidate inv(frame(source)) @ frame(scene).  All pairs go in ONE ops.volume_match on
+        the pools, which are read only: a scene may appear in any number of pairs, on either side.  A plain batch and a windowed batch raise
+        NotImplementedError, a scene without views ValueError.  Every scene is unchanged."""
+        one = isinstance(scenes, (int, np.integer)) and not isinstance(scenes, bool)
+        if one:
+            scenes, sources, Ts = [scenes], [sources], (None if Ts is None else [Ts])
+        if isinstance(scenes, torch.Tensor) or not hasattr(scenes, '__len__') or isinstance(sources, torch.Tensor) or not hasattr(sources, '__len__') \
+                or len(scenes) != len(sources) or not len(scenes):
+            raise ValueError(f'match takes one scene index with one source index, or lists of both of one length, got {scenes!r} and {sources!r}')
+        P = len(scenes)
+        if Ts is not None and (isinstance(Ts, (str, bytes, torch.Tensor)) or not hasattr(Ts, '__len__') or len(Ts) != P):
+            raise ValueError(f'Ts must be None or hold one candidate list per pair: {P} pairs, got {len(Ts) if hasattr(Ts, "__len__") else Ts!r}')
+        scenes, sources = self._check_match(scenes, sources, 'match')
+        cands = [_match_candidates(self._scenes[d], self._scenes[s], None if Ts is None else Ts[i]) for i, (d, s) in enumerate(zip(scenes, sources))]
+        if len({len(c) for c in cands}) != 1:
+            raise ValueError(f'every pair of a call takes the same number of candidates, got {[len(c) for c in cands]}')
+        res = self._match(scenes, sources, cands, ops._match_step(step), _check_min_overlap(min_overlap))
+        return res[0] if one else res
+
+    def register(self, scene, source, T0=None, yaw=math.radians(8), shift=None, levels=6, step=1, min_overlap=0.3):
+        """SceneSession.register between two scenes of the batch (x_source = T x_scene): the same local coarse-to-fine search around T0 over yaw
+        and translation, one ops.volume_match per level.  -> (T float64 [4,4], the MatchResult of the last level)."""
+        (d,), (s,) = self._check_match([scene], [source], 'register')
+        T0 = _merge_transform(self._scenes[d], self._scenes[s], T0)
+        min_overlap = _check_min_overlap(min_overlap)
+        return _register(lambda Ts, p: self._match([d], [s], [Ts], p, min_overlap)[0], T0, yaw, shift, levels, step, min_overlap,
+                         np.asarray(self._scenes[d].meta['lidar2img']['origin'], np.float64), self._model.voxel_size)
 
     # ------------------------------------------------------------------ snapshots
     def _scene_list(self, scenes, others=None, what='snapshot'):

@@ -50,7 +50,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * formats (RGB, BGRA / RGBA, gray, NV12, YUYV) converted in the fetch of the prep launch; 540 = 0.5.4: ivx_volume_warp_fwd, the rigid out-of-place
  * resample of rows of the state pools, for scenes that turn with their platform; 550 = 0.5.5: ivx_volume_merge_fwd, the rigid in-place merge of
  * rows of the state pools, for scenes that become one; 560 = 0.5.6: ivx_volume_pack_fwd / ivx_volume_unpack_fwd / ivx_volume_pack_scratch_bytes, the
- * ordered compaction of the seen voxels of rows of the state pools and its inverse, for scene snapshots) and the message of the last failing call on this
+ * ordered compaction of the seen voxels of rows of the state pools and its inverse, for scene snapshots; 570 = 0.5.7: ivx_volume_match_fwd /
+ * ivx_volume_match_scratch_bytes, the read-only scoring of candidate poses between two rows of the state pools, for matching scenes) and the message of the last failing call on this
  * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -1043,6 +1044,78 @@ int ivx_volume_merge_fwd(int32_t B, const int32_t *row_src /*host [B]*/, const i
                          const float *voxel_size /*host [3]*/, float forget_below, int32_t R_src, int32_t R_dst, int32_t X, int32_t Y, int32_t Z,
                          int32_t C, const float *sum_src, const float *wsum_src, const int32_t *count_src, float *sum_dst, float *wsum_dst,
                          int32_t *count_dst, ivx_stream_t stream);
+
+/* (0.5.7) Scoring candidate poses between two rows of the state pools: how well do two fused scenes agree under a rigid transform?  scroll, warp,
+ * merge and restore all take the transform between two frames as given; this entry judges one (scene.py, SceneSession.match / register,
+ * SceneBatch.match / register).  Two fading states are per-voxel mean feature vectors with weights: for a candidate M the correlation of the two
+ * means over the voxels both scenes have seen says how well they agree, and the trilinear read of the source is the merge's.  A read-only
+ * reduction: it writes its outputs and its scratch, nothing else.  Like the merge it lies outside the reference-parity claims and is pinned to an
+ * fp64 reference written from the definition below (tests/ref_volume_match.py).
+ *
+ * Definition.  Sample b names a destination row row_dst[b], a source row row_src[b] and the two grids' origins, as in ivx_volume_merge_fwd, and
+ * carries K candidates M = xform[b,k] [3,4] that map the DESTINATION grid's frame to the SOURCE grid's: x_src = R x_dst + t.  The lattice step
+ * (px, py, pz) >= 1 (NULL: 1, 1, 1) visits the destination voxels (i,j,k) with i % px == 0 && j % py == 0 && k % pz == 0, in ascending order of
+ * (i, j, k) with k fastest.  For every visited voxel n of the row and every candidate k, in fp32, round-to-nearest, no contraction:
+ *   1. own      W_d = wsum_dst[n]; the voxel is OWN iff W_d > 0 (a NaN is not).  own_out[b] counts the own voxels; it does not depend on k.
+ *               Nothing further happens at a voxel that is not own.
+ *   2. sample   steps 1 - 4 of ivx_volume_merge_fwd give inside, S_s[c] and W_s: the centre from origin_dst[b], the fma chain of M, the grid
+ *               coordinate against origin_src[b] with the same inside test, floor and fraction, the same corner order and weights
+ *               (w_x * w_y) * w_z, the fma chains from +0 over the corners read.  A corner outside the grid or of weight exactly 0 is not read.
+ *               Counts are not read.
+ *   3. paired   the voxel is PAIRED iff it is own, inside and W_s > 0.  Of an unpaired voxel only W_d and, where it is own and inside, the corner
+ *               words of wsum_src are read: neither S_d nor any source sum.
+ *   4. terms    r_d = 1 / W_d and r_s = 1 / W_s, one IEEE division each;  a_c = S_d[c] * r_d  and  b_c = S_s[c] * r_s, one rounded product
+ *               each.  The channels of a voxel are taken in words of four, c = 4 w .. 4 w + 3.  Per word and per statistic, four rounded
+ *               products and three rounded sums in channel order:
+ *                   d_w = ((a_0 b_0 + a_1 b_1) + a_2 b_2) + a_3 b_3,   and the same with a a for na and b b for nb.
+ *               An fp32 chain is never longer than these four terms: each d_w is widened to fp64 at once, and everything after it is fp64.
+ *   5. sums     dot = sum d_w over the paired voxels and their words, na and nb likewise, in fp64, in an order that is a function of
+ *               (X, Y, Z, C, step) alone: a lane's ascending walk, a fixed tree over the lanes of a wave, the waves of a workgroup in order, one
+ *               partial per workgroup in the scratch slab, and a second launch that adds the partials of a candidate in a fixed order
+ *               (csrc/volume_match.hip has the schedule).  pairs counts the paired voxels.
+ *   6. outputs  pairs_out [B,K] int64 and own_out [B] int64, exact; stats_out [B,K,3] fp64 = (dot, na, nb).
+ * The host forms the score: ncc = dot / sqrt(na * nb), the cosine of the two mean fields over the overlap, and overlap = pairs / own.
+ *
+ * B, K         samples of this call; candidates per sample
+ * row_src      HOST [B] int32: sample b reads row row_src[b] of the source pools
+ * row_dst      HOST [B] int32: ... and row row_dst[b] of the destination pools (rows may repeat: nothing is written)
+ * xform        HOST [B,K,3,4] fp32, finite; rigidity is NOT required here (ops.volume_match checks it)
+ * origin_dst, origin_src   HOST [B,3] fp32, finite: the corner terms (the new_origin of the lifts) of the two grids
+ * voxel_size   HOST [3] fp32, finite and > 0, common to both grids
+ * step         HOST [3] int32, each >= 1, or NULL for (1, 1, 1)
+ * R_src, R_dst, X, Y, Z, C   the source / destination pools have R_src / R_dst rows of X*Y*Z voxels; C % 4 == 0
+ * sum_src, wsum_src   DEVICE [R_src,X,Y,Z,C] fp32 (16-byte aligned), [R_src,X,Y,Z] fp32, read only
+ * sum_dst, wsum_dst   DEVICE the same with R_dst rows, read only.  They may be the source pools, and a row may be matched against itself:
+ *              there is no memory rule beyond the alignment.
+ * pairs_out, own_out, stats_out   DEVICE [B,K] int64, [B] int64, [B,K,3] fp64, written
+ * scratch      DEVICE, ivx_volume_match_scratch_bytes(B, K, X, Y, Z, C) bytes (-1 for non-positive arguments, C % 4 != 0 or X*Y*Z at or beyond
+ *              2^31), 8-byte aligned; it serves every step
+ * The lists are host lists, as for ivx_volume_merge_fwd: everything is checked before any launch and nothing is uploaded (the candidates reach
+ * the kernel by value, 32 per launch, one sample per launch: B * ceil(K / 32) launches and one that sums).
+ *
+ * Properties.
+ *   Read only.      The pools keep every bit; rows that no sample names are not read.
+ *   Zero weights.   A corner of weight 0 is never read, and the sums of an unpaired voxel are never read: a NaN there cannot reach the statistics.
+ *   Deterministic.  No float atomics, no spinning, no dependence between the workgroups of a launch.  The same two states give the same bits in
+ *                   any row of any pool, alone or beside other samples and candidates.
+ *   Identity.       M = I and equal origins on a grid where the chain is exact (dyadic voxel sizes, the origin on their lattice), source and
+ *                   destination the same state: every paired voxel has one corner of weight 1, b_c == a_c bit for bit, so dot == na == nb bit
+ *                   for bit and ncc == 1.
+ *   Error.          Against the exact value of steps 2 - 5 on the same i0 and f, to first order, with A_c = |a_c| and
+ *                   B_c = sum_corners |w S_corner[c]| / W_s (>= |b_c|):
+ *                       |dot - exact| <= 31 * 2^-24 * sum A_c B_c,   |na - exact| <= 9 * 2^-24 * sum A_c^2,   |nb - exact| <= 53 * 2^-24 * sum B_c^2
+ *                   (+ 2^-126 per term): the sample's 11 on S_s and on W_s, a reciprocal and a product (2) per factor, the product of the two
+ *                   factors (1), three sums of the four-term chain (3), and 1 for every fp64 sum together (below 2^29 terms);
+ *                   tests/ref_volume_match.py derives it.  pairs and own are exact.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names this entry: a null pointer (a null scratch too; step may be NULL); a
+ * non-positive B, K, R_src, R_dst, X, Y, Z or C; C % 4 != 0; X*Y*Z at or beyond 2^31; a row outside its pool; sum pools that are not 16-byte
+ * aligned; a scratch that is not 8-byte aligned; a non-finite xform, origin or voxel_size; voxel_size <= 0; a step below 1.                         */
+int64_t ivx_volume_match_scratch_bytes(int32_t B, int32_t K, int32_t X, int32_t Y, int32_t Z, int32_t C);
+int ivx_volume_match_fwd(int32_t B, int32_t K, const int32_t *row_src /*host [B]*/, const int32_t *row_dst /*host [B]*/,
+                         const float *xform /*host [B,K,3,4]*/, const float *origin_dst /*host [B,3]*/, const float *origin_src /*host [B,3]*/,
+                         const float *voxel_size /*host [3]*/, const int32_t *step /*host [3] or NULL*/, int32_t R_src, int32_t R_dst, int32_t X,
+                         int32_t Y, int32_t Z, int32_t C, const float *sum_src, const float *wsum_src, const float *sum_dst, const float *wsum_dst,
+                         int64_t *pairs_out, int64_t *own_out, double *stats_out, void *scratch, ivx_stream_t stream);
 
 /* (0.5.6) Ordered compaction of the seen voxels of rows of the state pools, and its inverse: a scene's fused state leaves the process it was fused in
  * (scene snapshots: scene.py, SceneSession.snapshot / ImVoxelNet.restore_scene / SceneBatch.snapshot / SceneBatch.restore).  A single frustum, a
