@@ -21,7 +21,7 @@ from .nms import nms_gpu, nms_normal_gpu, box3d_multiclass_nms, aligned_3d_nms, 
 from .evaluation import indoor_eval, average_precision, eval_det_cls, eval_map_recall  # noqa: F401
 from .kitti_ap import kitti_eval, kitti_eval_coco_style, bbox2result_kitti  # noqa: F401
 from .scene import (SceneSession, SceneBatch, SceneSnapshot, MatchResult, scrolled_origin, warped_extrinsic,  # noqa: F401
-                    pose_candidates)
+                    pose_candidates, AlignResult, rigid_increment, solve_align)
 from .params import randomize_                                              # noqa: F401
 
 from .data import (load_checkpoint, prepare_image, MultiViewPipeline, KittiSetOrigin, SunRgbdSetOrigin,  # noqa: F401

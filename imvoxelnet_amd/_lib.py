@@ -195,7 +195,7 @@ EXPORTS = ['ivx_conv_plan_query', 'ivx_conv_tile_info', 'ivx_model_plan_info', '
            'ivx_backproject_accum_fwd', 'ivx_backproject_accum_fwd_bf16', 'ivx_volume_mean_fwd', 'ivx_backproject_fwd_ex', 'ivx_backproject_gather_fwd',
            'ivx_backproject_lists_fwd', 'ivx_backproject_weighted_fwd', 'ivx_volume_wmean_fwd', 'ivx_volume_scroll_fwd', 'ivx_backproject_mapped_fwd',
            'ivx_view_coverage_fwd', 'ivx_volume_warp_fwd', 'ivx_volume_merge_fwd', 'ivx_volume_pack_scratch_bytes', 'ivx_volume_pack_fwd', 'ivx_volume_unpack_fwd',
-           'ivx_volume_match_scratch_bytes', 'ivx_volume_match_fwd',
+           'ivx_volume_match_scratch_bytes', 'ivx_volume_match_fwd', 'ivx_volume_align_scratch_bytes', 'ivx_volume_align_fwd',
            'ivx_anchor_head_workspace_bytes', 'ivx_anchor_head_get_bboxes', 'ivx_fcos_head_workspace_bytes',
            'ivx_fcos_head_level_candidates', 'ivx_nms_workspace_bytes',
            'ivx_nms_bev', 'ivx_boxes_overlap_bev', 'ivx_aligned_3d_nms', 'ivx_aligned_3d_nms_workspace_bytes', 'ivx_aligned_3d_nms_ws', 'ivx_multiclass_nms_workspace_bytes', 'ivx_multiclass_nms_bev',
@@ -343,6 +343,10 @@ def lib():
         L.ivx_volume_match_scratch_bytes.argtypes = [i32] * 6
         L.ivx_volume_match_scratch_bytes.restype = i64
         L.ivx_volume_match_fwd.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)] + [C.POINTER(f32)] * 4 + [C.POINTER(i32)] + [i32] * 6 + [vp] * 9
+    if hasattr(L, 'ivx_volume_align_fwd'):         # (0.5.8; an older build still loads: ops.volume_align and the scenes' refine() then refuse)
+        L.ivx_volume_align_scratch_bytes.argtypes = [i32] * 6
+        L.ivx_volume_align_scratch_bytes.restype = i64
+        L.ivx_volume_align_fwd.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32)] + [C.POINTER(f32)] * 5 + [C.POINTER(i32)] + [i32] * 6 + [vp] * 10
     L.ivx_anchor_head_workspace_bytes.argtypes = [C.POINTER(AnchorHeadDesc)]
     L.ivx_anchor_head_workspace_bytes.restype = i64
     L.ivx_anchor_head_get_bboxes.argtypes = [C.POINTER(AnchorHeadDesc), vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -15,7 +15,7 @@ void ivx_set_error(const char *fmt, ...) {
   va_end(ap);
 }
 
-extern "C" int ivx_version(void) { return 570; /* 0.5.7: the read-only scoring of candidate poses between two rows of the scene state pools (csrc/volume_match.hip; include/imvoxel.h has the entry and its definition), for matching scenes; 0.5.6: the ordered compaction of the seen voxels of rows of the scene state pools and its inverse (csrc/volume_pack.hip; include/imvoxel.h has the entries and their definition), for scene snapshots; 0.5.5: the rigid in-place merge of rows of the scene state pools, a second instantiation of the resample kernel (csrc/volume_warp.hip; include/imvoxel.h has the entry and its definition), for scenes that become one; 0.5.4: the rigid out-of-place resample of rows of the scene state pools (csrc/volume_warp.hip; include/imvoxel.h has the entry and its definition), for scenes that turn with their platform; 0.5.3: ivx_image_prep_fmt_u8, ivx_yuv_matrix (csrc/pixel_fetch.h: the image pipeline on decoder pixel formats -- RGB, BGRA / RGBA, gray, NV12, YUYV -- converted in the fetch of the prep launch by a stated integer rule; include/imvoxel.h); 0.5.2: ivx_image_prep_lens_u8, ivx_map_prep_lens (csrc/image_prep.hip: the image pipeline through a Brown / fisheye lens model, one interpolation, and the cover / depth maps of the same geometry at feature resolution; include/imvoxel.h); 0.5.1: the view coverage counts of csrc/view_coverage.hip (the voxels a candidate view would see and those the scene has no evidence for, before its trunk runs; include/imvoxel.h); 0.5.0: pixel maps for the weighted listed lift of csrc/backproject.hip (a per-pixel confidence and a gated depth map per view; include/imvoxel.h); 0.4.9: the in-place voxel shift of rows of the state pools of csrc/volume_scroll.hip (scrolling scenes; include/imvoxel.h); 0.4.8: the weighted listed lift of csrc/backproject.hip (per-view weights, per-sample decay, a forgetting threshold: fading scenes; include/imvoxel.h); 0.4.7: the listed lift with per-sample rows and first flags of csrc/backproject.hip (batches of scenes, ragged batches; include/imvoxel.h); 0.4.6: the gathered mean lift of csrc/backproject.hip (views listed by slot; include/imvoxel.h); 0.4.5: ivx_conv_route, ivx_bf16_pair_pack_filters (the routing rule and the split-operand filter packer as host functions of the library); 0.4.4: ivx_backproject_fwd_ex, ivx_model_cfg.sampling (csrc/backproject.hip: the optional bilinear sampling rule of the unprojection); 0.4.3: ivx_image_prep_u8, ivx_rescale_size (csrc/image_prep.hip: uint8 frames -> normalised, padded fp32 input); 0.4.2: ivx_dcn_im2col_fwd_bf16, ivx_global_avgpool_fwd_bf16 (bf16 storage with DCNv2 stages / the LayoutHead); 0.4.1: ivx_bottleneck_fwd_pio, ivx_stem_pool_fwd_pair, the SURVEY 8(b) export names, include/imvoxel_lab.h; 0.4.0: ivx_pair_io / ivx_conv_fwd_pio (chained fp16-pair activations), ivx_model_cfg.trunk_operands; 0.3.1: ivx_conv_desc.wino_operands, IVX_BF16_PAIR / IVX_F16_PAIR, ivx_model_cfg.wino_operands (0.3.0: head / DCNv2 / LayoutHead fields, ivx_model_detect) */ }
+extern "C" int ivx_version(void) { return 580; /* 0.5.8: the Gauss-Newton normal equations of a six-DoF pose between two rows of the scene state pools (the ALIGN instantiation of csrc/volume_match.hip; include/imvoxel.h has the entry and its definition), for aligning scenes; 0.5.7:the read-only scoring of candidate poses between two rows of the scene state pools (csrc/volume_match.hip; include/imvoxel.h has the entry and its definition), for matching scenes; 0.5.6: the ordered compaction of the seen voxels of rows of the scene state pools and its inverse (csrc/volume_pack.hip; include/imvoxel.h has the entries and their definition), for scene snapshots; 0.5.5: the rigid in-place merge of rows of the scene state pools, a second instantiation of the resample kernel (csrc/volume_warp.hip; include/imvoxel.h has the entry and its definition), for scenes that become one; 0.5.4: the rigid out-of-place resample of rows of the scene state pools (csrc/volume_warp.hip; include/imvoxel.h has the entry and its definition), for scenes that turn with their platform; 0.5.3: ivx_image_prep_fmt_u8, ivx_yuv_matrix (csrc/pixel_fetch.h: the image pipeline on decoder pixel formats -- RGB, BGRA / RGBA, gray, NV12, YUYV -- converted in the fetch of the prep launch by a stated integer rule; include/imvoxel.h); 0.5.2: ivx_image_prep_lens_u8, ivx_map_prep_lens (csrc/image_prep.hip: the image pipeline through a Brown / fisheye lens model, one interpolation, and the cover / depth maps of the same geometry at feature resolution; include/imvoxel.h); 0.5.1: the view coverage counts of csrc/view_coverage.hip (the voxels a candidate view would see and those the scene has no evidence for, before its trunk runs; include/imvoxel.h); 0.5.0: pixel maps for the weighted listed lift of csrc/backproject.hip (a per-pixel confidence and a gated depth map per view; include/imvoxel.h); 0.4.9: the in-place voxel shift of rows of the state pools of csrc/volume_scroll.hip (scrolling scenes; include/imvoxel.h); 0.4.8: the weighted listed lift of csrc/backproject.hip (per-view weights, per-sample decay, a forgetting threshold: fading scenes; include/imvoxel.h); 0.4.7: the listed lift with per-sample rows and first flags of csrc/backproject.hip (batches of scenes, ragged batches; include/imvoxel.h); 0.4.6: the gathered mean lift of csrc/backproject.hip (views listed by slot; include/imvoxel.h); 0.4.5: ivx_conv_route, ivx_bf16_pair_pack_filters (the routing rule and the split-operand filter packer as host functions of the library); 0.4.4: ivx_backproject_fwd_ex, ivx_model_cfg.sampling (csrc/backproject.hip: the optional bilinear sampling rule of the unprojection); 0.4.3: ivx_image_prep_u8, ivx_rescale_size (csrc/image_prep.hip: uint8 frames -> normalised, padded fp32 input); 0.4.2: ivx_dcn_im2col_fwd_bf16, ivx_global_avgpool_fwd_bf16 (bf16 storage with DCNv2 stages / the LayoutHead); 0.4.1: ivx_bottleneck_fwd_pio, ivx_stem_pool_fwd_pair, the SURVEY 8(b) export names, include/imvoxel_lab.h; 0.4.0: ivx_pair_io / ivx_conv_fwd_pio (chained fp16-pair activations), ivx_model_cfg.trunk_operands; 0.3.1: ivx_conv_desc.wino_operands, IVX_BF16_PAIR / IVX_F16_PAIR, ivx_model_cfg.wino_operands (0.3.0: head / DCNv2 / LayoutHead fields, ivx_model_detect) */ }
 extern "C" const char *ivx_last_error(void) { return g_err; }
 
 // bf16 entry points that model.cpp calls on a bf16 handle with DCNv2 stages / a LayoutHead.  The product library defines them in dcn.hip and

@@ -1772,6 +1772,11 @@ def volume_match(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src
     bits in any rows of any pools.
     -> (pairs [B,K] int64, own [B] int64, stats [B,K,3] float64 = (dot, na, nb)) as device tensors; the score is the caller's:
     ncc = dot / sqrt(na * nb), overlap = pairs / own."""
+    return _match_call(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src_origin, voxel_size, step)
+
+
+def _match_call(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src_origin, voxel_size, step, about=None):
+    """The one path of volume_match (about None) and volume_align: every host check, the scratch, the outputs and the one C call."""
     import numpy as np
     for t, name in ((vol_sum, 'vol_sum'), (wsum, 'wsum')):
         if not isinstance(t, torch.Tensor):
@@ -1794,7 +1799,8 @@ def volume_match(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src
     if K == 0 or any(len(c) != K for c in transforms):
         raise ValueError(f'transforms must hold the same number K >= 1 of candidates for every row, got {[len(c) for c in transforms]}')
     M = [check_rigid(T, f'transforms[{b}][{k}]') for b, cands in enumerate(transforms) for k, T in enumerate(cands)]
-    (o, so), vs = _grid_floats(B, voxel_size, new_origin=new_origin, src_origin=src_origin)
+    origins, vs = _grid_floats(B, voxel_size, new_origin=new_origin, src_origin=src_origin, **({} if about is None else {'about': about}))
+    o, so = origins[:2]
     step = _match_step(step)
     if any(not 0 <= r < R for r in rows):
         raise ValueError(f'rows must be in [0, {R}), got {rows}')
@@ -1813,21 +1819,42 @@ def volume_match(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src
         if t.device != vol_sum.device:
             raise ValueError(f'{name} must be on the device of vol_sum')
     L = _lib.lib()
-    fn = getattr(L, 'ivx_volume_match_fwd', None)
+    align = about is not None
+    entry, version = ('ivx_volume_align', '0.5.8') if align else ('ivx_volume_match', '0.5.7')
+    fn = getattr(L, entry + '_fwd', None)
     if fn is None:
-        raise _lib.IvxError('this build of libimvoxel_hip.so has no ivx_volume_match_fwd (needs version 0.5.7)')
-    nbytes = L.ivx_volume_match_scratch_bytes(B, K, X, Y, Z, Cn)
+        raise _lib.IvxError(f'this build of libimvoxel_hip.so has no {entry}_fwd (needs version {version})')
+    nbytes = getattr(L, entry + '_scratch_bytes')(B, K, X, Y, Z, Cn)
     if nbytes < 0:
-        raise ValueError(f'ivx_volume_match_scratch_bytes refuses B = {B}, K = {K}, grid {X} x {Y} x {Z}, C = {Cn}')
+        raise ValueError(f'{entry}_scratch_bytes refuses B = {B}, K = {K}, grid {X} x {Y} x {Z}, C = {Cn}')
     dev = vol_sum.device
     scratch = torch.empty((nbytes // 8,), device=dev, dtype=torch.int64)
     pairs, own = torch.empty((B, K), device=dev, dtype=torch.int64), torch.empty((B,), device=dev, dtype=torch.int64)
-    stats = torch.empty((B, K, 3), device=dev, dtype=torch.float64)
+    stats = torch.empty((B, K, 31 if align else 3), device=dev, dtype=torch.float64)
     flat = lambda a: (C.c_float * a.size)(*np.ascontiguousarray(a, np.float32).reshape(-1).tolist())     # noqa: E731
-    check(fn(B, K, (C.c_int32 * B)(*src_rows), (C.c_int32 * B)(*rows), flat(np.stack(M)), flat(o), flat(so), flat(vs), (C.c_int32 * 3)(*step), Rs, R,
-             X, Y, Z, Cn, _ptr(ssum), _ptr(swsum), _ptr(vol_sum), _ptr(wsum), _ptr(pairs), _ptr(own), _ptr(stats), _ptr(scratch), _stream()),
-          'ivx_volume_match_fwd')
+    lists = (B, K, (C.c_int32 * B)(*src_rows), (C.c_int32 * B)(*rows), flat(np.stack(M))) + ((flat(origins[2]),) if align else ()) + \
+        (flat(o), flat(so), flat(vs), (C.c_int32 * 3)(*step), Rs, R, X, Y, Z, Cn, _ptr(ssum), _ptr(swsum), _ptr(vol_sum), _ptr(wsum))
+    if align:
+        used = torch.empty((B, K), device=dev, dtype=torch.int64)
+        check(fn(*lists, _ptr(pairs), _ptr(used), _ptr(own), _ptr(stats), _ptr(scratch), _stream()), entry + '_fwd')
+        return pairs, used, own, stats
+    check(fn(*lists, _ptr(pairs), _ptr(own), _ptr(stats), _ptr(scratch), _stream()), entry + '_fwd')
     return pairs, own, stats
+
+
+def volume_align(vol_sum, wsum, rows, src, src_rows, transforms, about, new_origin, src_origin, voxel_size, step=(1, 1, 1)):
+    """Aligning scenes: the Gauss-Newton normal equations of the six degrees of freedom of a pose between rows of the state pools
+    (ivx_volume_align_fwd, the ALIGN instantiation of the match kernel; include/imvoxel.h has the definition).  The arguments are volume_match's
+    and go through the same checks; `about`, host floats [B,3] (or [3] for all), finite, is the point the rotation increments go through.  For
+    sample b and candidate T (x_src = T x_dst), over the USED voxels -- paired, all eight corners of the sample inside the source grid and of
+    positive weight sum -- and all channels, with r = b - a and J the derivative of b by a small motion (v, w) of the destination point,
+    p -> p + v + w x (p - about):  e = sum r^2,  g = sum J r,  H = sum J J^T.
+    -> (pairs [B,K] int64, used [B,K] int64, own [B] int64, stats [B,K,31] float64 = (dot, na, nb, e, g[6], H upper triangle row-major [21])) as
+    device tensors; pairs, own, dot, na, nb are volume_match's bit for bit.  The step is the caller's (scene.solve_align):
+    (H + damping diag H) delta = -g, the trial pose T @ scene.rigid_increment(delta, about)."""
+    if about is None:
+        raise TypeError('about must be host floats [B,3] (or [3] for all): the point the rotation increments go through')
+    return _match_call(vol_sum, wsum, rows, src, src_rows, transforms, new_origin, src_origin, voxel_size, step, about)
 
 
 _PACK_DT = {torch.float32: 0, torch.bfloat16: 1}     # the payload of a packed state: IVX_F32 (the sums, as words) | IVX_BF16 (the mean)

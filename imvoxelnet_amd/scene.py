@@ -95,6 +95,21 @@ per level the 81 candidates of pose_candidates around the current pose (yaw and 
 centre), move to the best eligible one, halve the offsets.  Plain and windowed scenes refuse, as for merge.  A scene that never matches runs the
 code it ran before.
 
+Aligning scenes (SceneSession.refine(other, T0=None, iters=12, dof, step, min_overlap, damping, tol_shift, tol_rot) / SceneBatch.refine(scenes,
+sources, T0s); register(..., refine=True); rigid_increment; solve_align; AlignResult).  register scores 486 candidates for six levels, resolves the
+pose to its last lattice step and searches yaw and translation only; a hand-held camera, a robot on a ramp and a vehicle that pitches under braking
+need pitch and roll too.  The state already holds what a direct method needs: the mean field b(x) = S(x) / W(x) is read trilinearly, so its spatial
+gradient comes from the same eight corners the match loads.  One evaluation (ops.volume_align, ivx_volume_align_fwd, the ALIGN instantiation of the
+match kernel in csrc/volume_match.hip; include/imvoxel.h has the definition) returns, beside the match's own numbers bit for bit, the cost
+e = sum |b - a|^2 over the USED voxels (paired, all eight corners of the read inside the other grid and seen), g = sum J r and H = sum J J^T for the
+six degrees of freedom (three translations, three rotation-vector components about the grid's centre) as 31 fp64 sums -- deterministic, no atomics,
+so a batch's answer equals a session's bit for bit.  The host solves (H + damping diag H) delta = -g (solve_align), tries
+T @ rigid_increment(delta, about) and keeps it iff it is eligible (used > 0, used / own >= min_overlap) and its cost e / (used * C) is strictly
+lower: Levenberg-Marquardt with one stated rule (_refine), 31 doubles read back per evaluation.  refine is LOCAL: the gradient is that of a
+trilinear read, so its basin is about a voxel and a few degrees on real features -- run register with coarse levels first, then refine, or
+register(..., refine=True), which refines the degrees the lattice searched unless told otherwise.  A scene that never refines runs the code it ran
+before.
+
 Scene snapshots (SceneSession.snapshot(dtype) / model.restore_scene(snapshot) / SceneBatch.snapshot(scene) / SceneBatch.restore(scene, snapshot);
 SceneSnapshot.save / load).  Everything above happens inside one process, on one device, in one kind of container.  A snapshot is the fused state of a
 plain or fading scene as HOST data: a state row is large (26 / 54 / 170 MB of fp32 at the ScanNet-fast / ScanNet-v1 / KITTI grids) and partly unseen --
@@ -160,8 +175,10 @@ scrolling a model with an Anchor3DHead (its boxes would have to be translated; w
 (the state lives here, over the op-level ABI and the handle's sub-range calls); merging windowed scenes (adopting the other's kept views into the
 ring); merging plain scenes (their integer counts cannot be resampled: open them with decay=1.0); merges between a session and a batch row, or
 across batches (ops.volume_merge_ takes any pools); several sources into one destination in one launch; de-duplicating views both scenes saw;
-estimating T without a start (a global search, no T0), pitch and roll in register, weighting pairs by evidence, zero-mean (Pearson)
-correlation, gradient-based refinement of a pose, matching plain or windowed scenes; saving a scene to disk other than through a snapshot; merging scenes on different devices or ranks directly (snapshot
+estimating T without a start (a global search, no T0), pitch and roll in register's candidate lattice (refine moves them),
+weighting pairs by evidence in match or refine, zero-mean (Pearson) correlation, gradient-based refinement with a robust loss (refine's loss is the plain sum of
+squares), refining against a snapshot directly (restore it, then refine), solving the normal equations on the device (six unknowns: the host
+solves them after a read-back of 31 doubles), matching plain or windowed scenes; saving a scene to disk other than through a snapshot; merging scenes on different devices or ranks directly (snapshot
 one and restore it beside the other); snapshots of windowed scenes (the state is the feature ring, a plain copy); merge taking a snapshot directly
 (restore it, then merge); turning a plain snapshot into a fading scene; compression of a snapshot beyond the bf16 mean; any check that the weights of
 the restoring model are those that fused the state.
@@ -623,6 +640,193 @@ def _register(match, T0, yaw, shift, levels, step, min_overlap, about, voxel_siz
             T = res.T
         yaw, shift = yaw / 2, shift / 2
     return T, res
+
+
+# ------------------------------------------------------------------ aligning: the host rules
+ALIGN_DOF = ('x', 'y', 'z', 'rx', 'ry', 'rz')     # the order of g and of the rows of H: three translations, three rotation-vector components
+REGISTER_DOF = ('x', 'y', 'z', 'rz')              # what register(refine=True) refines unless told otherwise: the degrees its lattice searches
+DAMPING_FLOOR, DAMPING_CAP = 1e-9, 1e6            # Levenberg-Marquardt: accepted steps divide the damping by 10 down to the floor; beyond the cap it stops
+_TRIU = tuple((i, j) for i in range(6) for j in range(i, 6))
+
+
+def _check_dof(dof):
+    """dof: a non-empty host sequence of names out of ALIGN_DOF, each once -> the sorted list of their indices."""
+    if isinstance(dof, (str, bytes)) or not hasattr(dof, '__len__') or not len(dof) or any(d not in ALIGN_DOF for d in dof) or len(set(dof)) != len(dof):
+        raise ValueError(f'dof must be a non-empty sequence of distinct names out of {ALIGN_DOF}, got {dof!r}')
+    return sorted(ALIGN_DOF.index(d) for d in dof)
+
+
+def rigid_increment(xi, about=(0, 0, 0)):
+    """float64 [4,4]: the rotation by the rotation vector xi[3:] (radians, Rodrigues' formula) about the point `about`, then the translation
+    xi[:3] -- the small motion of a destination point that ivx_volume_align_fwd differentiates by:  p -> about + R (p - about) + xi[:3].
+    Needs no device."""
+    xi, about = np.asarray(xi, np.float64).reshape(-1), np.asarray(about, np.float64).reshape(-1)
+    if xi.shape != (6,) or not np.isfinite(xi).all():
+        raise ValueError(f'xi must be six finite numbers (x, y, z, rx, ry, rz), got {xi!r}')
+    if about.shape != (3,) or not np.isfinite(about).all():
+        raise ValueError(f'about must be three finite coordinates, got {about!r}')
+    w = xi[3:]
+    th = float(np.linalg.norm(w))
+    K = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
+    s, c = (1.0 - th * th / 6, 0.5 - th * th / 24) if th < 1e-8 else (math.sin(th) / th, (1 - math.cos(th)) / (th * th))
+    T = np.eye(4)
+    T[:3, :3] = np.eye(3) + s * K + c * (K @ K)
+    T[:3, 3] = about - T[:3, :3] @ about + xi[:3]
+    return T
+
+
+def solve_align(H, g, damping=0.0, dof=ALIGN_DOF):
+    """The Levenberg-Marquardt step of the normal equations H [6,6], g [6] of ivx_volume_align_fwd:  (H + damping * diag(H)) delta = -g  on the
+    degrees of freedom `dof` (names out of ALIGN_DOF), zeros elsewhere.  -> delta float64 [6]; NaN on the selected degrees where the system is
+    singular or not finite.  Needs no device."""
+    H, g = np.asarray(H, np.float64), np.asarray(g, np.float64).reshape(-1)
+    if H.shape != (6, 6) or g.shape != (6,):
+        raise ValueError(f'H must be [6,6] and g [6], got {H.shape} and {g.shape}')
+    if isinstance(damping, bool) or not isinstance(damping, (int, float, np.integer, np.floating)) or not (math.isfinite(damping) and damping >= 0):
+        raise ValueError(f'damping must be a finite number >= 0, got {damping!r}')
+    sel = _check_dof(dof)
+    A, delta = H[np.ix_(sel, sel)], np.zeros(6)
+    A = A + float(damping) * np.diag(np.diag(A))
+    try:
+        if not (np.isfinite(A).all() and np.isfinite(g).all()):
+            raise np.linalg.LinAlgError
+        delta[sel] = np.linalg.solve(A, -g[sel])
+    except np.linalg.LinAlgError:
+        delta[sel] = np.nan
+    return delta
+
+
+class AlignResult:
+    """What a refinement says, as host data: the pose it ends at and the normal equations there.
+      T        float64 [4,4]  the pose (x_other = T x_self)
+      cost     float          e / (used * C), the mean squared difference of the two mean fields over the used voxels (inf where used == 0)
+      used, pairs, own  int   the voxels that carry the gradient / that both scenes hold evidence for / that this scene holds evidence for
+      overlap  float          used / own (0 where own is 0)
+      ncc      float          dot / sqrt(na * nb) over the paired voxels, match's score (-inf where a norm is not positive)
+      g, H     float64 [6], [6,6]   sum J r and sum J J^T in the order ALIGN_DOF
+      stats    float64 [31]   as the device summed them
+      evaluations, accepted  int   launches of the refinement; steps that lowered the cost
+      converged  bool         the last step was below both tolerances
+      history  list of float  the cost at the start and after every accepted step, strictly decreasing
+      ok       bool           the start was eligible: used > 0 and overlap >= min_overlap."""
+
+    def __init__(self, T, pairs, used, own, stats, channels, min_overlap=0.3):
+        self.T, self.stats = np.array(T, np.float64), np.asarray(stats, np.float64).reshape(-1)
+        if self.T.shape != (4, 4) or self.stats.shape != (31,):
+            raise ValueError(f'T must be [4,4] and stats [31], got {self.T.shape} and {self.stats.shape}')
+        self.pairs, self.used, self.own, self.channels = int(pairs), int(used), int(own), int(channels)
+        self.min_overlap = _check_min_overlap(min_overlap)
+        self.overlap = self.used / self.own if self.own > 0 else 0.0
+        dot, na, nb, e = (float(v) for v in self.stats[:4])
+        self.e, self.cost = e, (e / (self.used * self.channels) if self.used > 0 else math.inf)
+        self.ncc = dot / math.sqrt(na * nb) if na * nb > 0 else -math.inf
+        self.g = self.stats[4:10].copy()
+        self.H = np.zeros((6, 6))
+        for n, (i, j) in enumerate(_TRIU):
+            self.H[i, j] = self.H[j, i] = self.stats[10 + n]
+        self.ok = self.eligible
+        self.evaluations, self.accepted, self.converged, self.history = 1, 0, False, [self.cost]
+
+    @property
+    def eligible(self):
+        return self.used > 0 and self.overlap >= self.min_overlap and math.isfinite(self.cost)
+
+    def __repr__(self):
+        return (f'AlignResult(ok={self.ok}, cost={self.cost:.6g}, used={self.used}, overlap={self.overlap:.3f}, evaluations={self.evaluations}, '
+                f'accepted={self.accepted}, converged={self.converged})')
+
+
+def _check_refine(iters, dof, min_overlap, damping, tol_shift, tol_rot, voxel_size):
+    """The host arguments of a refinement -> (iters, dof indices as names, min_overlap, damping, tol_shift, tol_rot)."""
+    if isinstance(iters, bool) or not isinstance(iters, (int, np.integer)) or iters < 1:
+        raise ValueError(f'iters must be an integer >= 1 (the evaluations a refinement may spend), got {iters!r}')
+    sel = _check_dof(dof)
+    min_overlap = _check_min_overlap(min_overlap)
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float, np.integer, np.floating)) and math.isfinite(v)      # noqa: E731
+    if not num(damping) or not 0 < damping <= DAMPING_CAP:
+        raise ValueError(f'damping must be a finite number in (0, {DAMPING_CAP:g}], got {damping!r}')
+    if tol_shift is None:
+        tol_shift = 1e-3 * float(np.min(np.asarray(voxel_size, np.float64)))
+    if not num(tol_shift) or tol_shift < 0 or not num(tol_rot) or tol_rot < 0:
+        raise ValueError(f'tol_shift (metres) and tol_rot (radians) must be finite numbers >= 0, got {tol_shift!r} and {tol_rot!r}')
+    return int(iters), tuple(ALIGN_DOF[i] for i in sel), min_overlap, float(damping), float(tol_shift), float(tol_rot)
+
+
+def _refine(align, T0s, abouts, channels, iters, dof, min_overlap, damping, tol_shift, tol_rot):
+    """The Levenberg-Marquardt loop of refine, shared by sessions and batches, over P pairs in lockstep: align(idx, Ts) evaluates the poses Ts of
+    the pairs idx (two lists of one length) in ONE call and returns one (pairs, used, own, stats [31]) of host numbers per pose.  The arguments
+    have passed _check_refine.  One rule, per pair:
+      evaluate at T (the first evaluation is T0; a T0 that is not eligible -- used > 0 and used / own >= min_overlap -- ends the pair, ok False);
+      delta = solve_align(H, g, damping, dof); a non-finite delta ends the pair; a delta below tol_shift (|delta[:3]|) AND tol_rot (|delta[3:]|)
+      ends it converged; `iters` evaluations end it;
+      the trial T @ rigid_increment(delta, about) is evaluated and ACCEPTED iff it is eligible and its cost is strictly lower: then T is the trial
+      and damping = max(damping / 10, DAMPING_FLOOR); otherwise damping *= 10, and a damping above DAMPING_CAP ends the pair.
+    A pair's numbers do not depend on which other pairs run beside it.  -> list of P (T float64 [4,4], AlignResult at T)."""
+    P = len(T0s)
+    first = align(list(range(P)), [np.array(T, np.float64) for T in T0s])
+    cur = [AlignResult(T0s[p], *first[p], channels, min_overlap) for p in range(P)]
+    lam, running = [damping] * P, [p for p in range(P) if cur[p].ok]
+    while running:
+        idx, trials = [], []
+        for p in running:
+            c = cur[p]
+            delta = solve_align(c.H, c.g, lam[p], dof)
+            if not np.isfinite(delta).all():
+                continue                                                     # a non-finite solve
+            if np.linalg.norm(delta[:3]) < tol_shift and np.linalg.norm(delta[3:]) < tol_rot:
+                c.converged = True
+                continue
+            if c.evaluations >= iters:
+                continue
+            idx.append(p)
+            trials.append(c.T @ rigid_increment(delta, abouts[p]))
+        if not idx:
+            break
+        res, running = align(idx, trials), []
+        for p, T, out in zip(idx, trials, res):
+            c, t = cur[p], AlignResult(T, *out, channels, min_overlap)
+            if t.eligible and t.cost < c.cost:
+                t.evaluations, t.accepted, t.history = c.evaluations + 1, c.accepted + 1, c.history + [t.cost]
+                cur[p], lam[p] = t, max(lam[p] / 10, DAMPING_FLOOR)
+            else:
+                c.evaluations += 1
+                lam[p] *= 10
+            if lam[p] <= DAMPING_CAP:
+                running.append(p)
+    return [(c.T.copy(), c) for c in cur]
+
+
+def _refine_T0s(pairs, T0s):
+    """T0s of a refinement over the record pairs [(dst, src)] -> list of float64 [4,4]: None (every pair starts where a merge would default to),
+    or one 4x4 or None per pair."""
+    if T0s is None:
+        T0s = [None] * len(pairs)
+    if isinstance(T0s, (str, bytes, torch.Tensor, np.ndarray)) or not hasattr(T0s, '__len__') or len(T0s) != len(pairs):
+        raise ValueError(f'T0s must be None or a host list of one 4x4 (or None) per pair: {len(pairs)} pairs, got {T0s!r}')
+    return [_merge_transform(d, s, T) for (d, s), T in zip(pairs, T0s)]
+
+
+def _align_host(outs, n):
+    """The device outputs of one ops.volume_align over n pairs with K = 1 -> n (pairs, used, own, stats [31]) of host numbers: the one host sync of
+    an iteration, 31 doubles and three counts per pair."""
+    pairs, used, own, stats = (t.cpu().numpy() for t in outs)
+    return [(int(pairs[p, 0]), int(used[p, 0]), int(own[p]), stats[p, 0]) for p in range(n)]
+
+
+def _check_register_refine(refine, dof):
+    """refine / dof of a register -> the dof names its refinement moves (None without refine): checked before the first launch."""
+    if not isinstance(refine, (bool, np.bool_)):
+        raise ValueError(f'refine must be True or False, got {refine!r}')
+    if not refine:
+        if dof is not None:
+            raise ValueError('dof names what refine=True moves; without refine= it has no meaning')
+        return None
+    return tuple(ALIGN_DOF[i] for i in _check_dof(REGISTER_DOF if dof is None else dof))
+
+
+def _last_step(step):
+    """The lattice step of the last level of a register: `step` itself, or the last of a list of one step per level."""
+    return step[-1] if hasattr(step, '__len__') and not isinstance(step, (str, bytes, torch.Tensor)) and len(step) else step
 
 
 # ------------------------------------------------------------------ snapshots: a scene's fused state as host data
@@ -1469,7 +1673,36 @@ class SceneSession(_SceneRecord):
         Ts = _match_candidates(self, other, Ts)
         return self._match(other, Ts, ops._match_step(step), _check_min_overlap(min_overlap))
 
-    def register(self, other, T0=None, yaw=math.radians(8), shift=None, levels=6, step=1, min_overlap=0.3):
+    def _align(self, other, Ts, step):
+        m = self._model
+        about = np.asarray(self.meta['lidar2img']['origin'], np.float64)
+        outs = ops.volume_align(self._sum, self._wsum, [0] * len(Ts), (other._sum, other._wsum), [0] * len(Ts), [[T] for T in Ts], about,
+                                m._new_origin(self.meta['lidar2img']['origin']).numpy(), m._new_origin(other.meta['lidar2img']['origin']).numpy(),
+                                m.voxel_size, step)
+        return _align_host(outs, len(Ts))
+
+    def refine(self, other, T0=None, iters=12, dof=ALIGN_DOF, step=1, min_overlap=0.3, damping=1e-3, tol_shift=None, tol_rot=1e-5):
+        """Refine a transform between this scene and another (x_other = T x_self) in all six degrees of freedom by a direct method: each
+        evaluation is ONE ops.volume_align (ivx_volume_align_fwd), which returns the cost e = sum |b - a|^2 of the two mean feature fields over
+        the used voxels with its Gauss-Newton normal equations, and the host takes a Levenberg-Marquardt step
+        T <- T @ rigid_increment(delta, about), (H + damping diag H) delta = -g, with `about` the grid's centre (the point register turns about).
+        This is a LOCAL method: its basin is about a voxel and a few degrees on real features, because the gradient is that of a trilinear read.
+        For anything wider run register with coarse levels first, then refine (or register(..., refine=True)).
+        T0: the start (None: inv(other.frame) @ self.frame).  iters: the evaluations it may spend.  dof: the degrees of freedom that move, names
+        out of ('x', 'y', 'z', 'rx', 'ry', 'rz').  step: the lattice step.  A pose is eligible iff used > 0 and used / own >= min_overlap; a
+        trial is accepted iff it is eligible and its cost e / (used * C) is strictly lower; accepted steps divide the damping by 10, rejected
+        ones multiply it by 10.  It stops after `iters` evaluations, on a step below tol_shift (metres; None: 1e-3 of the smallest voxel edge)
+        and tol_rot (radians), on a damping above 1e6 or on a solve that is not finite.  A T0 that is not eligible comes back as it is with
+        ok False: no exception.  Each evaluation reads 31 doubles and three counts back.  Refusals are match's.  Both scenes are unchanged.
+        -> (T float64 [4,4], AlignResult at T)."""
+        self._check_match(other, 'refine')
+        T0 = _merge_transform(self, other, T0)
+        args = _check_refine(iters, dof, min_overlap, damping, tol_shift, tol_rot, self._model.voxel_size)
+        step = ops._match_step(step)
+        about = np.asarray(self.meta['lidar2img']['origin'], np.float64)
+        return _refine(lambda idx, Ts: self._align(other, Ts, step), [T0], [about], int(self._sum.shape[-1]), *args)[0]
+
+    def register(self, other, T0=None, yaw=math.radians(8), shift=None, levels=6, step=1, min_overlap=0.3, refine=False, dof=None):
         """Refine a transform between this scene and another (x_other = T x_self) by a coarse-to-fine search over yaw and translation, built on
         match.  This is a LOCAL search around T0 (None: inv(other.frame) @ self.frame): it finds the best pose within about twice the first
         level's offsets of T0 and does not look further.  Each of `levels` levels scores the 81 candidates pose_candidates(T_c, yaw, shift,
@@ -1477,12 +1710,21 @@ class SceneSession(_SceneRecord):
         candidate (keeps it when none is eligible), then halves yaw and shift.  shift (h_x, h_y, h_z) in metres defaults to (2 vs_x, 2 vs_y,
         vs_z); yaw is in radians.  step: one integer for every level or a list of one lattice step per level (a coarse level may pass 2).
         Pitch and roll are not searched.  Refusals are match's.  Both scenes are unchanged.
-        -> (T float64 [4,4], the MatchResult of the last level)."""
+        refine=True then runs refine (its defaults, the same min_overlap, the last level's lattice step) from the last level's pose over
+        dof = ('x', 'y', 'z', 'rz') -- the degrees the lattice searches -- unless a `dof` is given, and returns refine's answer with the last
+        level's MatchResult as its .match; the default changes nothing, launch for launch.
+        -> (T float64 [4,4], the MatchResult of the last level);  refine=True: (T float64 [4,4], AlignResult)."""
         self._check_match(other, 'register')
         T0 = _merge_transform(self, other, T0)
         min_overlap = _check_min_overlap(min_overlap)
-        return _register(lambda Ts, p: self._match(other, Ts, p, min_overlap), T0, yaw, shift, levels, step, min_overlap,
-                         np.asarray(self.meta['lidar2img']['origin'], np.float64), self._model.voxel_size)
+        dof = _check_register_refine(refine, dof)
+        T, res = _register(lambda Ts, p: self._match(other, Ts, p, min_overlap), T0, yaw, shift, levels, step, min_overlap,
+                           np.asarray(self.meta['lidar2img']['origin'], np.float64), self._model.voxel_size)
+        if not refine:
+            return T, res
+        T, out = self.refine(other, T, dof=dof, step=_last_step(step), min_overlap=min_overlap)
+        out.match = res
+        return T, out
 
     # ------------------------------------------------------------------ snapshots
     def snapshot(self, dtype=torch.float32):
@@ -1881,14 +2123,49 @@ class SceneBatch:
         res = self._match(scenes, sources, cands, ops._match_step(step), _check_min_overlap(min_overlap))
         return res[0] if one else res
 
-    def register(self, scene, source, T0=None, yaw=math.radians(8), shift=None, levels=6, step=1, min_overlap=0.3):
+    def register(self, scene, source, T0=None, yaw=math.radians(8), shift=None, levels=6, step=1, min_overlap=0.3, refine=False, dof=None):
         """SceneSession.register between two scenes of the batch (x_source = T x_scene): the same local coarse-to-fine search around T0 over yaw
-        and translation, one ops.volume_match per level.  -> (T float64 [4,4], the MatchResult of the last level)."""
+        and translation, one ops.volume_match per level; refine=True then refines the last level's pose as SceneSession.register does.
+        -> (T float64 [4,4], the MatchResult of the last level);  refine=True: (T float64 [4,4], AlignResult)."""
         (d,), (s,) = self._check_match([scene], [source], 'register')
         T0 = _merge_transform(self._scenes[d], self._scenes[s], T0)
         min_overlap = _check_min_overlap(min_overlap)
-        return _register(lambda Ts, p: self._match([d], [s], [Ts], p, min_overlap)[0], T0, yaw, shift, levels, step, min_overlap,
-                         np.asarray(self._scenes[d].meta['lidar2img']['origin'], np.float64), self._model.voxel_size)
+        dof = _check_register_refine(refine, dof)
+        T, res = _register(lambda Ts, p: self._match([d], [s], [Ts], p, min_overlap)[0], T0, yaw, shift, levels, step, min_overlap,
+                           np.asarray(self._scenes[d].meta['lidar2img']['origin'], np.float64), self._model.voxel_size)
+        if not refine:
+            return T, res
+        T, out = self.refine(d, s, T, dof=dof, step=_last_step(step), min_overlap=min_overlap)
+        out.match = res
+        return T, out
+
+    def _align(self, scenes, sources, Ts, abouts, step):
+        state = (self._sum, self._wsum)
+        outs = ops.volume_align(*state, scenes, state, sources, [[T] for T in Ts], np.stack(abouts), np.stack([self._origin_of(d) for d in scenes]),
+                                np.stack([self._origin_of(s) for s in sources]), self._model.voxel_size, step)
+        return _align_host(outs, len(Ts))
+
+    def refine(self, scenes, sources, T0s=None, iters=12, dof=ALIGN_DOF, step=1, min_overlap=0.3, damping=1e-3, tol_shift=None, tol_rot=1e-5):
+        """SceneSession.refine between scenes of the batch: one scene index with one source index and one T0 (-> (T, AlignResult)), or two
+        lists of one length with one T0 (or None) per pair (-> a list of (T, AlignResult)); x_source = T x_scene, T0s None: every pair starts
+        at inv(frame(source)) @ frame(scene).  Every iteration makes ONE ops.volume_align over all the pairs that are still running (B = those
+        pairs, K = 1) and reads 31 doubles and three counts per pair back; a pair's answer does not depend on the pairs beside it and equals a
+        session's on the same two states bit for bit.  LOCAL like the session's: run register first for anything wider than about a voxel and
+        a few degrees.  The pools are read only: a scene may appear in any number of pairs, on either side.  Refusals are match's."""
+        one = isinstance(scenes, (int, np.integer)) and not isinstance(scenes, bool)
+        if one:
+            scenes, sources, T0s = [scenes], [sources], [T0s]
+        if isinstance(scenes, torch.Tensor) or not hasattr(scenes, '__len__') or isinstance(sources, torch.Tensor) or not hasattr(sources, '__len__') \
+                or len(scenes) != len(sources) or not len(scenes):
+            raise ValueError(f'refine takes one scene index with one source index, or lists of both of one length, got {scenes!r} and {sources!r}')
+        scenes, sources = self._check_match(scenes, sources, 'refine')
+        T0s = _refine_T0s([(self._scenes[d], self._scenes[s]) for d, s in zip(scenes, sources)], T0s)
+        args = _check_refine(iters, dof, min_overlap, damping, tol_shift, tol_rot, self._model.voxel_size)
+        step = ops._match_step(step)
+        abouts = [np.asarray(self._scenes[d].meta['lidar2img']['origin'], np.float64) for d in scenes]
+        res = _refine(lambda idx, Ts: self._align([scenes[p] for p in idx], [sources[p] for p in idx], Ts, [abouts[p] for p in idx], step),
+                      T0s, abouts, int(self._sum.shape[-1]), *args)
+        return res[0] if one else res
 
     # ------------------------------------------------------------------ snapshots
     def _scene_list(self, scenes, others=None, what='snapshot'):

@@ -51,7 +51,8 @@ typedef void *ivx_stream_t; /* hipStream_t */
  * resample of rows of the state pools, for scenes that turn with their platform; 550 = 0.5.5: ivx_volume_merge_fwd, the rigid in-place merge of
  * rows of the state pools, for scenes that become one; 560 = 0.5.6: ivx_volume_pack_fwd / ivx_volume_unpack_fwd / ivx_volume_pack_scratch_bytes, the
  * ordered compaction of the seen voxels of rows of the state pools and its inverse, for scene snapshots; 570 = 0.5.7: ivx_volume_match_fwd /
- * ivx_volume_match_scratch_bytes, the read-only scoring of candidate poses between two rows of the state pools, for matching scenes) and the message of the last failing call on this
+ * ivx_volume_match_scratch_bytes, the read-only scoring of candidate poses between two rows of the state pools, for matching scenes; 580 = 0.5.8: ivx_volume_align_fwd / ivx_volume_align_scratch_bytes, the Gauss-Newton
+ * normal equations of a six-DoF pose between two rows of the state pools, for aligning scenes) and the message of the last failing call on this
  * thread (never NULL). */
 int ivx_version(void);
 const char *ivx_last_error(void);
@@ -1116,6 +1117,79 @@ int ivx_volume_match_fwd(int32_t B, int32_t K, const int32_t *row_src /*host [B]
                          const float *voxel_size /*host [3]*/, const int32_t *step /*host [3] or NULL*/, int32_t R_src, int32_t R_dst, int32_t X,
                          int32_t Y, int32_t Z, int32_t C, const float *sum_src, const float *wsum_src, const float *sum_dst, const float *wsum_dst,
                          int64_t *pairs_out, int64_t *own_out, double *stats_out, void *scratch, ivx_stream_t stream);
+
+/* (0.5.8) The Gauss-Newton normal equations of a six-DoF pose between two rows of the state pools: which small rigid motion makes two fused scenes
+ * agree better?  ivx_volume_match_fwd judges a candidate; this entry also says where to go from it (scene.py, SceneSession.refine,
+ * SceneBatch.refine, register(refine=True)).  The mean field b(x) = S_s(x) / W_s(x) is read trilinearly, so its spatial gradient comes from the
+ * eight corners the match already loads, and one launch returns the cost e = sum r^2 of the residual r = b - a, its half gradient g = sum J r
+ * and the Gauss-Newton matrix H = sum J J^T over all six degrees of freedom.  The kernel is the match kernel's ALIGN instantiation
+ * (csrc/volume_match.hip); a read-only reduction pinned to an fp64 reference written from the definition below (tests/ref_volume_align.py).
+ *
+ * Definition.  Samples, rows, origins, candidates M = xform[b,k] (x_src = R x_dst + t), the lattice step and the visiting order are
+ * ivx_volume_match_fwd's; about[b] is the point the rotation increments go through.  The increment xi = (v, w) -- a translation v, then a
+ * rotation vector w about `about`, both in the DESTINATION frame -- moves a destination point p to  p + v + w x (p - about)  to first order, and
+ * the candidate after it is  M o increment.  For every visited voxel n and every candidate, in fp32, round-to-nearest, no contraction:
+ *   1. own, sample, paired   exactly steps 1 - 4 of ivx_volume_match_fwd.  pairs, own, dot, na and nb are the match's, over the PAIRED voxels,
+ *               bit for bit what ivx_volume_match_fwd returns for the same inputs: the sample folds the corners the match folds (inside the
+ *               grid, weight != 0), and the tile walk and the order of the fp64 sums are the match's.
+ *   2. used     a paired voxel is USED iff all eight corners i0 + (dx, dy, dz) lie inside the source grid and wsum_src > 0 at every one of them
+ *               (a NaN is not), the corners of weight exactly 0 included: the wsum words of all corners inside the grid are read here, although
+ *               the match does not read those of weight 0.  used_out counts the used voxels.  Only used voxels contribute to e, g and H, by
+ *               selection, never by a product with zero: the source sums of a corner with W <= 0 cannot reach e, g, H.  At a used voxel all
+ *               eight corner words of sum_src are read.
+ *   3. gradient With V[c'] the eight corner values of one quantity (c' = dx * 4 + dy * 2 + dz), f the three fractions, w_a0 = 1 - f_a (one
+ *               rounded difference) and w_a1 = f_a, the corner derivative along axis A with (p, q) the other two axes in x, y, z order is
+ *                   D_A V = fma(w_p1 * w_q1, V[1,1,+] - V[1,1,0], fma(w_p1 * w_q0, .., fma(w_p0 * w_q1, .., fma(w_p0 * w_q0, V[0,0,+] - V[0,0,0], +0))))
+ *               -- one rounded product per pair weight, one rounded difference (the corner at +1 along A minus the corner at 0) per pair, the
+ *               chain from +0 with q fastest.  dD_A = D_A wsum_src, and per channel dN_A = D_A sum_src[.., c].  With b_c and r_s of step 4 of
+ *               the match:
+ *                   grad_c[A] = (((dN_A - b_c * dD_A) * r_s) / voxel_size[A])        a product, a difference, a product, an IEEE division
+ *                   u_c[j]    = fma(R[2][j], grad_c[2], fma(R[1][j], grad_c[1], R[0][j] * grad_c[0]))          (u_c = R^T grad_c, R = M[:, :3])
+ *                   d         = p - about[b], one rounded difference per axis, p the voxel centre of step 1
+ *                   J_c       = (u_c[0], u_c[1], u_c[2],  d[1] u_c[2] - d[2] u_c[1],  d[2] u_c[0] - d[0] u_c[2],  d[0] u_c[1] - d[1] u_c[0])
+ *               -- two rounded products and one rounded difference per component of d x u_c: three translations, then three rotations.
+ *   4. terms    r_c = b_c - a_c, one rounded difference.  Per word of four channels and per sum, four rounded products and three rounded sums
+ *               in channel order, as for dot:  e_w = ((r_0 r_0 + r_1 r_1) + r_2 r_2) + r_3 r_3;  g_w[i] the same with J_c[i] r_c (6 sums);
+ *               H_w[i][j], i <= j, the same with J_c[i] J_c[j] (21 sums).  Each of the 28 is widened to fp64 at once; everything after is fp64,
+ *               in the order of step 5 of the match: a function of (X, Y, Z, C, step) alone, no float atomics, no spinning, partials in the
+ *               scratch slab, a second launch that adds them in a fixed order.
+ *   5. outputs  pairs_out [B,K], used_out [B,K], own_out [B] int64, exact;  stats_out [B,K,31] fp64 = (dot, na, nb, e, g[0..5], H upper
+ *               triangle row-major: H00 H01 .. H05 H11 .. H55).
+ * The host forms the step: cost = e / (used * C); (H + damping * diag H) delta = -g; the trial pose is M o increment(delta) (scene.py).
+ *
+ * Arguments: ivx_volume_match_fwd's, and
+ * about        HOST [B,3] fp32, finite
+ * used_out     DEVICE [B,K] int64, written;  stats_out is [B,K,31]
+ * scratch      DEVICE, ivx_volume_align_scratch_bytes(B, K, X, Y, Z, C) bytes (-1 as for the match's), 8-byte aligned
+ * A sums lane keeps 31 fp64 accumulators (the direct arrangement); launches as for the match.
+ *
+ * Properties.
+ *   Read only, Deterministic   as for ivx_volume_match_fwd.
+ *   Match parity.   pairs, own, dot, na, nb == ivx_volume_match_fwd's, bit for bit.
+ *   Zero weights.   A NaN in sum_src wherever wsum_src == 0 leaves e, g, H unchanged bit for bit (such a corner makes its voxel unused).
+ *   Identity.       M = I, equal origins, a grid where the chain is exact, source and destination the same state: b_c == a_c bit for bit at every
+ *                   paired voxel, so r_c == +0 and e == 0, g == 0 exactly.
+ *   Error.          Against the exact value on the same i0, f and d, to first order, with u = 2^-24, A_c and B_c of the match,
+ *                   Rm_c = A_c + B_c,  MN = sum_pairs |w_p w_q| (|V[+]| + |V[0]|) over sum_src,  MD the same over wsum_src,
+ *                   Gm_c[A] = (MN + B_c MD) / (W_s voxel_size[A]),  Um_c[j] = sum_i |R[i][j]| Gm_c[i],
+ *                   Jm_c = (Um_c, |d[1]| Um_c[2] + |d[2]| Um_c[1], ..):
+ *                     r_c  25 u Rm_c: b's 24, a's 2 <= 25 (A + B) with the difference's 1
+ *                     dN, dD  8 u: two axis weights (2), their product (1), the corner difference (1), the chain of four (4)
+ *                     grad  48 u Gm: b dD 24 + 8 + 1 = 33, the difference + 1 = 34, r_s 12 and the product 1 = 47, the division 1
+ *                     u  51 u Um (a product and two fma: 3);   d x u  53 u (a product 1, the difference 1)
+ *                     |e - exact| <= 55 u sum Rm^2  (25 + 25 + 1, the chain 3, every fp64 sum together 1)
+ *                     |g[i] - exact| <= (81 | 83) u sum Jm[i] Rm   (translation | rotation: K_J + 25 + 1 + 3 + 1)
+ *                     |H[i][j] - exact| <= (107 | 109 | 111) u sum Jm[i] Jm[j]   (both translations | one of each | both rotations)
+ *                   (+ 2^-126 per term); dot, na, nb as for the match.  tests/ref_volume_align.py derives it.  The counts are exact.
+ * IVX_ERR_INVALID_ARG before any launch, with a message that names this entry: the errors of ivx_volume_match_fwd (used_out and about are
+ * required too), and an about that is not finite.                                                                                                */
+int64_t ivx_volume_align_scratch_bytes(int32_t B, int32_t K, int32_t X, int32_t Y, int32_t Z, int32_t C);
+int ivx_volume_align_fwd(int32_t B, int32_t K, const int32_t *row_src /*host [B]*/, const int32_t *row_dst /*host [B]*/,
+                         const float *xform /*host [B,K,3,4]*/, const float *about /*host [B,3]*/, const float *origin_dst /*host [B,3]*/,
+                         const float *origin_src /*host [B,3]*/, const float *voxel_size /*host [3]*/, const int32_t *step /*host [3] or NULL*/,
+                         int32_t R_src, int32_t R_dst, int32_t X, int32_t Y, int32_t Z, int32_t C, const float *sum_src, const float *wsum_src,
+                         const float *sum_dst, const float *wsum_dst, int64_t *pairs_out, int64_t *used_out, int64_t *own_out, double *stats_out,
+                         void *scratch, ivx_stream_t stream);
 
 /* (0.5.6) Ordered compaction of the seen voxels of rows of the state pools, and its inverse: a scene's fused state leaves the process it was fused in
  * (scene snapshots: scene.py, SceneSession.snapshot / ImVoxelNet.restore_scene / SceneBatch.snapshot / SceneBatch.restore).  A single frustum, a
